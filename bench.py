@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- image-pairs/sec of the extract + NMS + brute-force-match hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs-per-step B] [--sparse]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs-per-step B] [--sparse] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): ALIKE-t extract + NMS(nms_dist 6, border 8, top_k 1000) + brute-force
@@ -10,11 +10,19 @@ inputs resident in HBM before the timed region.  One step = one pass of the whol
 B pairs per GPU; pairs shard across ranks with no data-path collective (weak scaling); the only exchange
 is the end-of-run RCCL all-gather of per-pair metric rows, outside the timed region.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it; with --full the line
+also carries (each from runs of its own, outside the timed region; null otherwise)
   roofline     -- the kernel that takes the most time in the step, timed live with HIP events on the
                   launch stream (kpb_prof_*), against its algorithmic FLOPs/bytes
   cpu_baseline -- the CPU oracle (oracle/, a port of the reference algorithm) on a bounded sample of the
                   same pairs, one single-threaded worker per host core, rank 0 at N=1 only
+  variant, variant_fp32 -- the keypoint-only descriptors and the strict-fp32 kernels on the same pairs
+                  (--no-cpu-baseline / --no-variants leave those legs out of a --full run)
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's pairs) as DIR/<name>.npy, float32 / float64,
+64 MB at most: rows past each image's keypoint count or each pair's match count are zeroed, and an array larger than
+its share of the budget is replaced by a fixed, seeded sample of its elements.  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -98,7 +106,7 @@ def fp32_companion(args):
     """The same command with the strict-fp32 kernels (KPB_FP32_MATRIX=1: fp32 MFMA / fp32 vector ALUs, no half-precision
     operand anywhere), run in a CHILD process before this one touches the GPU: what the split-f16 matrix arithmetic buys."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(max(3, args.steps // 2)), "--warmup", str(args.warmup), "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(max(3, args.steps // 2)), "--warmup", str(args.warmup), "--full", "--no-cpu-baseline",
            "--no-variants", "--model", args.model, "--matcher", args.matcher, "--lg-attention", args.lg_attention]
     if args.pairs_per_step:
         cmd += ["--pairs-per-step", str(args.pairs_per_step)]
@@ -349,6 +357,44 @@ def workload_label(model, matcher):
     return "%s extract + NMS(nms_dist=6, border=8, top_k=1000) + %s, 640x480 pairs [%s]" % (net, m, tag)
 
 
+DUMP_BUDGET = 64 << 20
+
+
+def dump_outputs(pipe, out_dir):
+    """The arrays a caller of PairPipeline.run receives after the last step, as out_dir/<name>.npy (see the module docstring).
+    Rows past the valid counts are zeroed: the library leaves them unwritten, so they would differ from run to run."""
+    import numpy as np
+    import torch
+    B, K = pipe.B, pipe.top_k
+    dev = pipe.n.device
+    slot = torch.arange(K, device=dev)
+    kp_ok = slot[None, :] < pipe.n[:, None].long()          # [2B, K]
+    m_ok = slot[None, :] < pipe.k[:, None].long()            # [B, K]
+
+    def rows(t, ok):
+        return torch.where(ok.view(ok.shape + (1,) * (t.dim() - 2)), t, torch.zeros((), dtype=t.dtype, device=dev))
+
+    arrays = {"num_keypoints": pipe.n, "keypoints": rows(pipe.kps, kp_ok), "num_matches": pipe.k, "matches": rows(pipe.pairs, m_ok),
+              "matched_keypoints0": rows(pipe.m0, m_ok), "matched_keypoints1": rows(pipe.m1, m_ok), "score_map": pipe.score}
+    if pipe.lg is not None:
+        arrays["match_scores"] = rows(pipe.lg_scores, m_ok)
+    else:
+        arrays["match_distance"] = rows(pipe.dist, m_ok)
+        arrays["keypoint_descriptors"] = rows(pipe.sdesc, kp_ok)
+    if pipe.desc is not None:
+        arrays["descriptor_map"] = pipe.desc
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET // len(arrays)
+    for i, (name, t) in enumerate(sorted(arrays.items())):
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.double()                                   # integer outputs: exact in float64
+        if t.numel() * t.element_size() > share:             # a fixed, seeded sample of the elements, in index order
+            pick = np.sort(np.random.default_rng(1000 + i).integers(0, t.numel(), share // t.element_size()))
+            t = t.reshape(-1)[torch.from_numpy(pick).to(dev)]
+            name += "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -356,8 +402,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=20, help="untimed steps before them (SURVEY 8d: 20)")
     ap.add_argument("--pairs-per-step", type=int, default=None, help="pairs per GPU per step (default: 256 ALIKE and XFeat [SURVEY 8d], 16 SuperPoint and DISK)")
     ap.add_argument("--sparse", action="store_true", help="keypoint-only descriptors (no dense 78.6 MB/img map)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the keypoint-only and strict-fp32 companion figures")
+    ap.add_argument("--full", action="store_true", help="also measure the CPU baseline, the keypoint-only and strict-fp32 variants, the per-kernel "
+                                                           "roofline and the per-rank figures (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the keypoint-only and strict-fp32 companion figures")
     ap.add_argument("--spawn", action="store_true", help="take the multi-GPU launch path (a child torchrun, one rank per GPU over RCCL) even at --gpus 1")
     ap.add_argument("--distinct", type=int, default=None, help="distinct synthetic pairs generated (default: one per pair of the batch; fewer are cycled)")
     ap.add_argument("--matcher", default="brute_force", choices=["brute_force", "lightglue"],
@@ -368,6 +417,8 @@ def main():
     ap.add_argument("--model", default="alike", choices=["alike", "superpoint", "xfeat", "disk"],
                     help="alike = BASELINE configs[1] (the headline); superpoint = configs[2] with seeded random weights")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if (args.gpus > 1 or args.spawn) and "RANK" not in os.environ:
         # a bare `python bench.py --gpus N` (or --spawn at N = 1): start the N ranks as a CHILD torchrun (nothing in this process has touched the
@@ -393,10 +444,10 @@ def main():
         print("warning: WORLD_SIZE=%d but --gpus %d" % (world, args.gpus), file=sys.stderr)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()          # before anything touches the GPU (spawned workers, CPU only)
     fp32 = None
-    if rank == 0 and world == 1 and "RANK" not in os.environ and not args.no_variants and not strict_fp32():
+    if args.full and rank == 0 and world == 1 and "RANK" not in os.environ and not args.no_variants and not strict_fp32():
         fp32 = fp32_companion(args)   # a child process with KPB_FP32_MATRIX=1 (the library reads the knob once per process)
 
     import numpy as np
@@ -459,6 +510,8 @@ def main():
     elapsed, tail, own = timed_steps(lambda: pipe.run(images), args.steps, args.warmup, dev, use_dist, dist)
     value = world * B * args.steps / elapsed
     value_sustained = (world * B * (args.steps - args.steps // 2) / tail) if tail else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pipe, args.dump_outputs)
 
     # end-of-run exchange: fixed-width per-pair rows [n0, n1, matches], one RCCL all-gather
     rows = torch.stack([pipe.n[:B].float(), pipe.n[B:].float(), pipe.k.float()], dim=1).contiguous()
@@ -468,7 +521,7 @@ def main():
     # the same pairs with keypoint-only descriptors (ALNet(dense_descriptors=False): same keypoints and matches, the
     # 78.6 MB/image descriptor map is never written; SURVEY 8d asks to say which was run): timed like the main loop
     variant = None
-    if args.model == "alike" and not args.sparse and args.matcher == "brute_force" and not args.no_variants:
+    if args.full and args.model == "alike" and not args.sparse and args.matcher == "brute_force" and not args.no_variants:
         pipe2 = PairPipeline(alike_t(dense_descriptors=False).eval(), EXTRACTOR, BRUTE_FORCE, B, H, W, device=dev)
         e2, _, _ = timed_steps(lambda: pipe2.run(images), args.steps, args.warmup, dev, use_dist, dist)
         same = bool(torch.equal(pipe2.k, pipe.k) and torch.equal(pipe2.pairs[:, :16], pipe.pairs[:, :16]))
@@ -477,22 +530,23 @@ def main():
         del pipe2
 
     # roofline leg: per-kernel durations from HIP events on the launch stream, same workload
-    roof = None
-    ctx = pipe.ctx
-    # r06: two untimed steps first, then ten profiled ones.  The first step after the host-side pause that precedes this leg (row exchange, the
-    # variant's set-up) runs its big kernels 5-7 % slower (kernel trace: the head 9.89 ms, then 9.21, 9.24) -- with r05's three profiled steps and no
-    # warm-up that one launch put `avg_ms` 2.4 % above the kernel-trace average of the same process (profiles/r06_head_modes.txt)
-    for _ in range(2):
-        pipe.run(images)
-    ctx.prof_enable(True)
-    prof_steps = 10
-    for _ in range(prof_steps):
-        pipe.run(images)
-    prof = ctx.prof_report()
-    ctx.prof_enable(False)
-    # every rank's own step time and the average of ITS dominant kernel: gathered, reported under quality.per_rank
-    dom = max(prof, key=lambda k: prof[k][1]) if prof else None
-    per_rank = per_rank_figures(1e3 * own / args.steps, (prof[dom][1] / prof[dom][0]) if dom else None, world, use_dist, dist, dev)
+    roof, prof, per_rank = None, None, None
+    if args.full:
+        ctx = pipe.ctx
+        # r06: two untimed steps first, then ten profiled ones.  The first step after the host-side pause that precedes this leg (row exchange, the
+        # variant's set-up) runs its big kernels 5-7 % slower (kernel trace: the head 9.89 ms, then 9.21, 9.24) -- with r05's three profiled steps and no
+        # warm-up that one launch put `avg_ms` 2.4 % above the kernel-trace average of the same process (profiles/r06_head_modes.txt)
+        for _ in range(2):
+            pipe.run(images)
+        ctx.prof_enable(True)
+        prof_steps = 10
+        for _ in range(prof_steps):
+            pipe.run(images)
+        prof = ctx.prof_report()
+        ctx.prof_enable(False)
+        # every rank's own step time and the average of ITS dominant kernel: gathered, reported under quality.per_rank
+        dom = max(prof, key=lambda k: prof[k][1]) if prof else None
+        per_rank = per_rank_figures(1e3 * own / args.steps, (prof[dom][1] / prof[dom][0]) if dom else None, world, use_dist, dist, dev)
     if rank == 0 and prof:
         sweeps = prof.get("nms_sweep", (1, 0))[0] / prof_steps
         costs = kernel_costs(2 * B, B, EXTRACTOR["top_k"], net.dim, not args.sparse, sweeps)

@@ -28,10 +28,10 @@ n=$((n + 1))
     2> $out/hm3_$(printf %02d $n)_plain_rocprof.err | tee -a $out/head_modes3.txt ) || { echo "rocprof arm failed"; tail -5 $out/hm3_$(printf %02d $n)_plain_rocprof.err; exit 1; }
 arm plain post_prof
 for r in 1 2; do
-  python3 bench.py --no-cpu-baseline --no-variants > $out/hm3_bench_plain_$r.json 2> $out/hm3_bench_plain_$r.err || { echo plain bench failed; tail -5 $out/hm3_bench_plain_$r.err; exit 1; }
-  python3 bench.py --spawn --no-cpu-baseline --no-variants > $out/hm3_bench_spawn_$r.json 2> $out/hm3_bench_spawn_$r.err || { echo spawn bench failed; tail -5 $out/hm3_bench_spawn_$r.err; exit 1; }
+  python3 bench.py --full --no-cpu-baseline --no-variants > $out/hm3_bench_plain_$r.json 2> $out/hm3_bench_plain_$r.err || { echo plain bench failed; tail -5 $out/hm3_bench_plain_$r.err; exit 1; }
+  python3 bench.py --spawn --full --no-cpu-baseline --no-variants > $out/hm3_bench_spawn_$r.json 2> $out/hm3_bench_spawn_$r.err || { echo spawn bench failed; tail -5 $out/hm3_bench_spawn_$r.err; exit 1; }
 done
-( export TMPDIR=/tmp; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/hm3_bench_prof -- python3 bench.py --no-cpu-baseline --no-variants > $out/hm3_bench_profiled.json 2> $out/hm3_bench_profiled.err ) || { echo profiled bench failed; tail -5 $out/hm3_bench_profiled.err; exit 1; }
+( export TMPDIR=/tmp; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/hm3_bench_prof -- python3 bench.py --full --no-cpu-baseline --no-variants > $out/hm3_bench_profiled.json 2> $out/hm3_bench_profiled.err ) || { echo profiled bench failed; tail -5 $out/hm3_bench_profiled.err; exit 1; }
 python3 - <<'PY' | tee -a gpurun_out/head_modes3.txt
 import json, glob
 for f in sorted(glob.glob("gpurun_out/hm3_bench_*.json")):

@@ -6,7 +6,7 @@ sub=$1; bargs=$2; shift 2
 for lib in "$@"; do
   d=gpurun_out/kt_$(basename $lib .so)
   rm -rf $d
-  KPB_LIB_PATH=$(realpath $lib) timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $d -- python3 bench.py $bargs --steps 6 --warmup 2 --no-cpu-baseline --no-variants --distinct 32 > $d.log 2>&1
+  KPB_LIB_PATH=$(realpath $lib) timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $d -- python3 bench.py $bargs --steps 6 --warmup 2 --full --no-cpu-baseline --no-variants --distinct 32 > $d.log 2>&1
   python3 - "$lib" $d "$sub" <<'PY'
 import csv, glob, sys, statistics as st
 f = glob.glob(sys.argv[2] + "/*/*kernel_trace.csv")

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 for lib in "$@"; do
   d=gpurun_out/nmsko_$(basename $lib .so)
   rm -rf $d
-  KPB_LIB_PATH=$(realpath $lib) timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $d -- python3 bench.py --sparse --steps 6 --warmup 2 --no-cpu-baseline --no-variants --distinct 32 > $d.log 2>&1
+  KPB_LIB_PATH=$(realpath $lib) timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $d -- python3 bench.py --sparse --steps 6 --warmup 2 --full --no-cpu-baseline --no-variants --distinct 32 > $d.log 2>&1
   python3 - "$lib" $d <<'PY'
 import csv, glob, sys, statistics as st
 f = glob.glob(sys.argv[2] + "/*/*kernel_trace.csv")

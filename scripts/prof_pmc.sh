@@ -6,10 +6,11 @@
 # kernels issue (the _F32 counter of pass 2 reads 0 for them).
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-OUT=gpurun_out/pmc_$1
+RESULTS=${RESULTS:-results}   # where the records go (a directory under the repository root, git-ignored)
+OUT=$RESULTS/pmc_$1
 shift
 mkdir -p $OUT
-ARGS="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-variants $@"
+ARGS="bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-variants $@"
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SMEM" \
            "SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_SCA SQ_INSTS_VALU_MFMA_MOPS_F32" \

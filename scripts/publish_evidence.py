@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Copy the summaries of scripts/collect_evidence.sh from gpurun_out/ into profiles/ (tracked).  Usage: publish_evidence.py r01"""
+"""Copy the summaries of scripts/collect_evidence.sh from $RESULTS (default results/) into profiles/ (tracked).  Usage: publish_evidence.py r01"""
 import glob, json, os, shutil, sys
 R = sys.argv[1] if len(sys.argv) > 1 else "r01"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src, dst = os.path.join(root, "gpurun_out"), os.path.join(root, "profiles")
+src, dst = os.path.join(root, os.environ.get("RESULTS", "results")), os.path.join(root, "profiles")
 b = json.load(open(os.path.join(src, R, "bench_default.json")))
 B = b["config"]["pairs_per_step_per_gpu"]
 shutil.copy(max(glob.glob(os.path.join(src, R, "stats", "*", "*_kernel_stats.csv")), key=os.path.getmtime), os.path.join(dst, "%s_bench_default_kernel_stats.csv" % R))

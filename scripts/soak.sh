@@ -1,7 +1,8 @@
 #!/bin/bash
 # Longer validation of ONE build than the test suite runs (r05): run-to-run determinism at three shapes, the metric bar on 64 pairs each
-# (repeatability / MHA and pose AUC), a 2000-step bench line.  scripts/soak.sh <round>  ->  gpurun_out/<round>/soak_*.txt|json
-R=${1:-r05}; O=gpurun_out/$R; mkdir -p $O
+# (repeatability / MHA and pose AUC), a 2000-step bench line.  scripts/soak.sh <round>  ->  $RESULTS/<round>/soak_*.txt|json
+RESULTS=${RESULTS:-results}   # where the records go (a directory under the repository root, git-ignored)
+R=${1:-r05}; O=$RESULTS/$R; mkdir -p $O
 sha256sum keypoint_bench_amd/libkpb.so | cut -c1-12 > $O/soak_build.txt
 { python scripts/determinism_probe.py 1216 1600 300 dense 4 | tail -1
   python scripts/determinism_probe.py 800 1216 200 dense 8 | tail -1

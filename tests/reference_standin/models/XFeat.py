@@ -1,0 +1,3 @@
+class XFeatModel(object):
+    def __init__(self, *a, **k):
+        raise NotImplementedError("the stand-in has no XFeatModel")

@@ -1,0 +1,1 @@
+"""Stand-in package (see ../README.md)."""

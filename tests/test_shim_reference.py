@@ -1,9 +1,10 @@
-"""keypoint_bench_amd.shim.install() against the REAL reference modules (build container only: /root/reference is not on the
-GPU box).  cv2 / skimage / torchvision / utils.export are absent from this image; they are supplied blank, exactly as
-tests/golden/make_golden*.py do (none is touched on the paths exercised here).
+"""keypoint_bench_amd.shim.install() against a reference checkout's module layout: tests/reference_standin/ holds the names
+install() swaps, imported the way the reference's task modules import them (its README says what it is).  The ALIKE-t
+state_dict is the reference checkpoint's, stored as tests/golden/alike_t_state_dict.npz.  cv2 / skimage / torchvision are
+supplied blank, as tests/golden/make_golden*.py do (none is touched on the paths exercised here).
 
 What is checked: every listed name is swapped and re-bound in the task modules that imported it earlier; the
-reference's ORIGINAL callables (taken from the checkout, not from oracle/) are kept and reached for inputs outside the
+reference's ORIGINAL callables (taken from the checkout's modules) are kept and reached for inputs outside the
 library's contract -- host tensors and negative score maps (BASELINE configs[0]: models/Harris.py returns signed
 cv2.cornerHarris responses); uninstall() restores everything."""
 import os
@@ -15,8 +16,8 @@ import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (build container only)")
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_standin")
+STATE_DICT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "alike_t_state_dict.npz")
 
 _STUBBED = ["cv2", "skimage", "skimage.feature", "torchvision", "torchvision.models", "torchvision.models.resnet", "openvino", "tensorrt"]
 
@@ -149,7 +150,7 @@ def test_model_constructors_fall_back(reference_on_path):
     assert isinstance(big, ref_cls)
     # ALIKE-t: HIP net for device images, the reference module (same state_dict) for host images
     net = ref_alike.ALNet({"c1": 8, "c2": 16, "c3": 32, "c4": 64, "dim": 64})
-    sd = torch.load(os.path.join(REF, "weights", "alike-t.pth"), map_location="cpu")
+    sd = {k: torch.from_numpy(v) for k, v in np.load(STATE_DICT).items()}
     net.load_state_dict(sd)
     net.eval()
     img = torch.rand(1, 3, 64, 96)
