@@ -29,7 +29,7 @@ SOURCES = ["api.hip", "detect.hip", "match.hip", "net_api.hip", "alike.hip", "co
 # them in lg_flash_h (192 -> 145 registers without), 24 in alike_block2, 8 in alike_block1_h (r03, found in the ISA).
 # -ffile-prefix-map: the objects record the sources as ./keypoint_bench_amd/csrc/..., not by absolute path -- the library's hash (config.build.lib_sha256
 # of every bench line) is then the same wherever the commit is checked out and built (r05)
-FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-ffp-contract=off",
+FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++20", "-ffp-contract=off",
          "-Wall", "-Wno-unused-result", "-fvisibility=hidden", "-mllvm", "-amdgpu-mfma-vgpr-form=1",
          "-ffile-prefix-map=%s=." % os.path.dirname(HERE)]
 ARCH = "gfx950"

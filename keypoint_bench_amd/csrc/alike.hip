@@ -1963,6 +1963,13 @@ float max_abs(const float* b, int n)
     return m;
 }
 
+// The conv_mfma_h forms of blocks 3 and 4 (block_h in AlikeNet::forward): C16 / C32 for 16 / 32 input channels, 1T one n-tile per workgroup, P4 block 4's conv1
+// max-pooling x3 4 x 4 while it stages it, LAT the latency forms (CmForm::wpre) for fewer than 16 images
+constexpr CmForm CM_C16{.ks = 3, .s = 1, .cc = 16, .ntb = 1, .mt = 2, .wn = 2}, CM_C32{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
+                 CM_C32_1T{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CM_P4{.ks = 3, .s = 1, .cc = 32, .pool_in = true, .ntb = 1, .mt = 4, .pf = 4, .wn = 2},
+                 CM_C16_LAT{.ks = 3, .s = 1, .cc = 16, .wpre = true}, CM_C32_LAT{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .wpre = true},
+                 CM_P4_LAT{.ks = 3, .s = 1, .cc = 32, .pool_in = true, .ntb = 1, .pf = 4, .wpre = true};
+
 template <int CIN, int COUT, int POOL, bool RES, int CDS, int RPOOL, bool DSOUT = false, int TW = 32>
 void launch_conv(kpb_ctx* ctx, const char* name, hipStream_t st, const ConvArgs& a, int B)
 {
@@ -2057,39 +2064,39 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
             m.CIN = cin; m.COUT = 2 * cout; m.NCH = 1; m.relu = 2; m.relu_nt = cout / 32;
             m.nblk = cout / 32; m.istride = cin; m.ostride = 2 * cout; m.ooff = 0;
             m.unscale = 1.0f / wscale.at(k1);
-            const std::string tag1 = std::string("conv3x3_") + n1, tag2 = std::string("conv3x3_") + n2;
-            // small layers are bound by per-workgroup latency: 8-row tiles (r02: b3c1 0.36 -> 0.32 ms, b3c2 0.58 -> 0.49 ms)
-            if (prepooled && batch < 16) KPB_LAUNCH(ctx, tag1.c_str(), (conv_mfma_h<3, 1, 16, false, false, false, 2, 1, false, 2, true>), dim3(cdiv(m.W, 16), cdiv(m.H, 8), batch * m.nblk), dim3(256), 0, st, m);
-            else if (prepooled && cin == 32) KPB_LAUNCH(ctx, tag1.c_str(), (conv_mfma_h<3, 1, 32, false, false, false, 1, 4, false, 2, false, false, 2>), dim3(cdiv(m.W, 16), cdiv(m.H, 16), batch * m.nblk), dim3(256), 0, st, m);
-            else if (prepooled) KPB_LAUNCH(ctx, tag1.c_str(), (conv_mfma_h<3, 1, 16, false, false, false, 1, 2, false, 2, false, false, 2>), dim3(cdiv(m.W, 16), cdiv(m.H, 8), batch * m.nblk), dim3(256), 0, st, m);
-            else if (batch >= 16) KPB_LAUNCH(ctx, tag1.c_str(), (conv_mfma_h<3, 1, 32, true, false, false, 1, 4, false, 4, false, false, 2>), dim3(cdiv(m.W, 16), cdiv(m.H, 16), batch * m.nblk), dim3(256), 0, st, m);
-            else {      // a handful of images (the drop-in path runs ONE): a 15 x 20 map in 16 x 16 tiles with two n-tiles each is 4 workgroups of
-                        // pure latency (41 us); 8-row tiles with one n-tile each are 16 (same weights, same arithmetic per output)
-                m.nblk = 2 * cout / 32;
-                KPB_LAUNCH(ctx, tag1.c_str(), (conv_mfma_h<3, 1, 32, true, false, false, 1, 1, false, 4, true>), dim3(cdiv(m.W, 16), cdiv(m.H, 8), batch * m.nblk), dim3(256), 0, st, m);
-            }
+            auto launch = [&](const char* n, const CmForm& f, const ConvM& cm) {     // profiled as conv3x3_<n>
+                return launch_conv_mfma_h<CM_C16, CM_C32, CM_C32_1T, CM_P4, CM_C16_LAT, CM_C32_LAT, CM_P4_LAT>(ctx, ("conv3x3_" + std::string(n)).c_str(), f, cm, batch); };
+            // small layers are bound by per-workgroup latency: 8-row tiles (r02: b3c1 0.36 -> 0.32 ms, b3c2 0.58 -> 0.49 ms).  A handful of images (the drop-in
+            // path runs ONE): a 15 x 20 map in 16 x 16 tiles with two n-tiles each is 4 workgroups of pure latency (41 us); 8-row tiles with one n-tile each are 16
+            // (same weights, same arithmetic per output)
+            if (batch < 16 && !prepooled) m.nblk = 2 * cout / 32;
+            const CmForm f1 = !prepooled ? (batch < 16 ? CM_P4_LAT : CM_P4) : batch < 16 ? CM_C16_LAT : cin == 32 ? CM_C32 : CM_C16;
+            if (int rc = launch(n1, f1, m)) return rc;
             ConvM c2;
             c2.in = tr; c2.out = xo; c2.wp = wp(k2.c_str()); c2.bias = wp((std::string(n2) + ".bp").c_str()); c2.xf = nullptr; c2.active = nullptr;
             c2.res = tr + cout; c2.rstride = 2 * cout;
-            c2.Hi = Hi / 4; c2.Wi = Wi / 4; c2.H = Hi / 4; c2.W = Wi / 4; c2.CIN = cout; c2.COUT = cout; c2.NCH = cout / 32; c2.relu = 0; c2.nblk = 1;
+            c2.Hi = Hi / 4; c2.Wi = Wi / 4; c2.H = Hi / 4; c2.W = Wi / 4; c2.CIN = cout; c2.COUT = cout; c2.NCH = cout / 32; c2.relu = 0; c2.nblk = batch < 16 ? cout / 32 : 1;
             c2.istride = 2 * cout; c2.ostride = cout; c2.ooff = 0;
             c2.unscale = 1.0f / wscale.at(k2);
-            if (cout == 32 && batch < 16) KPB_LAUNCH(ctx, tag2.c_str(), (conv_mfma_h<3, 1, 32, false, false, false, 1, 1, false, 2, true>), dim3(cdiv(c2.W, 16), cdiv(c2.H, 8), batch), dim3(256), 0, st, c2);
-            else if (cout == 32) KPB_LAUNCH(ctx, tag2.c_str(), (conv_mfma_h<3, 1, 32, false, false, false, 1, 1>), dim3(cdiv(c2.W, 16), cdiv(c2.H, 8), batch), dim3(256), 0, st, c2);
-            else if (batch >= 16) KPB_LAUNCH(ctx, tag2.c_str(), (conv_mfma_h<3, 1, 32, false, false, false, 1, 4, false, 2, false, false, 2>), dim3(cdiv(c2.W, 16), cdiv(c2.H, 16), batch), dim3(256), 0, st, c2);
-            else {
-                c2.nblk = cout / 32;
-                KPB_LAUNCH(ctx, tag2.c_str(), (conv_mfma_h<3, 1, 32, false, false, false, 1, 1, false, 2, true>), dim3(cdiv(c2.W, 16), cdiv(c2.H, 8), batch * c2.nblk), dim3(256), 0, st, c2);
-            }
+            return launch(n2, batch < 16 ? CM_C32_LAT : cout == 32 ? CM_C32_1T : CM_C32, c2);
         };
-        block_h("b3c1", "b3c2", p2, t3r3, x3, 16, 32, H / 2, W / 2, true);
+        if (int rc = block_h("b3c1", "b3c2", p2, t3r3, x3, 16, 32, H / 2, W / 2, true)) return rc;
         if (batch >= 16) {      // block 4's input pooled once, by a kernel of its own (see maxpool4_nhwc); a handful of images keep the fused form (one launch fewer)
             KPB_LAUNCH(ctx, "maxpool4_x3", maxpool4_nhwc, dim3((unsigned)(((size_t)(H / 32) * (W / 32) * 8 + 255) / 256), batch), dim3(256), 0, st, x3, p3, H / 32, W / 32, 32);
-            block_h("b4c1", "b4c2", p3, t4r4, x4, 32, 64, H / 8, W / 8, true);
-        } else
-            block_h("b4c1", "b4c2", x3, t4r4, x4, 32, 64, H / 8, W / 8, false);
+            if (int rc = block_h("b4c1", "b4c2", p3, t4r4, x4, 32, 64, H / 8, W / 8, true)) return rc;
+        } else if (int rc = block_h("b4c1", "b4c2", x3, t4r4, x4, 32, 64, H / 8, W / 8, false))
+            return rc;
     } else {
         // strict fp32: block 1 and the 3x3 convolutions on the fp32 vector ALUs, conv2 of blocks 3 / 4 on the fp32 MFMA
+        auto conv2 = [&](const char* n, const float* in, float* out, const float* res, int h, int w, int c) {    // identity branch precomputed (ALike.py:72-80)
+            const std::string k = n;
+            ConvM m;
+            m.in = in; m.out = out; m.wp = wp((k + ".wp").c_str()); m.bias = wp((k + ".bp").c_str()); m.xf = nullptr; m.active = nullptr; m.res = res;
+            m.Hi = h; m.Wi = w; m.H = h; m.W = w; m.CIN = c; m.COUT = c; m.NCH = c / 32; m.relu = 0; m.nblk = 1;
+            m.istride = c; m.ostride = c; m.ooff = 0;
+            return launch_conv_mfma<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32}>(
+                ctx, ("conv3x3_" + k).c_str(), CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = c / 32}, m, batch);
+        };
         KPB_LAUNCH(ctx, "alike_block1", alike_block1, dim3(cdiv(W, B1_TW), cdiv(H, B1_TH), batch), dim3(256), 0, st, b1);
         c = ConvArgs{p1, t2, wp("b2c1.w"), wp("b2c1.b"), nullptr, nullptr, nullptr, nullptr, H / 2, W / 2};      // pooled by block1
         launch_conv<8, 16, 1, false, 4, 1>(ctx, "conv3x3_b2c1", st, c, batch);
@@ -2098,23 +2105,11 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
         // block3 @ H/8 (141-142): pool4
         c = ConvArgs{x2, t3, wp("b3c1.w"), wp("b3c1.b"), nullptr, wp("b3ds.w"), wp("b3ds.b"), r3, H / 8, W / 8};
         launch_conv<16, 32, 4, false, 4, 1, true, 16>(ctx, "conv3x3_b3c1", st, c, batch);        // 80 columns at 480x640: 16-wide tiles divide them
-        {   // conv2 of block3 on the MFMA kernel, identity branch precomputed (ALike.py:72-80)
-            ConvM m;
-            m.in = t3; m.out = x3; m.wp = wp("b3c2.wp"); m.bias = wp("b3c2.bp"); m.xf = nullptr; m.active = nullptr; m.res = r3;
-            m.Hi = H / 8; m.Wi = W / 8; m.H = H / 8; m.W = W / 8; m.CIN = 32; m.COUT = 32; m.NCH = 1; m.relu = 0; m.nblk = 1;
-            m.istride = 32; m.ostride = 32; m.ooff = 0;
-            KPB_LAUNCH(ctx, "conv3x3_b3c2", (conv_mfma<3, 1, 32, false, false, false, 1>), dim3(cdiv(m.W, 16), cdiv(m.H, 8), batch), dim3(256), 0, st, m);
-        }
+        if (int rc = conv2("b3c2", t3, x3, r3, H / 8, W / 8, 32)) return rc;
         // block4 @ H/32 (143-144): pool4
         c = ConvArgs{x3, t4, wp("b4c1.w"), wp("b4c1.b"), nullptr, wp("b4ds.w"), wp("b4ds.b"), r4, H / 32, W / 32};
         launch_conv<32, 64, 4, false, 4, 1, true, 16>(ctx, "conv3x3_b4c1", st, c, batch);
-        {
-            ConvM m;
-            m.in = t4; m.out = x4; m.wp = wp("b4c2.wp"); m.bias = wp("b4c2.bp"); m.xf = nullptr; m.active = nullptr; m.res = r4;
-            m.Hi = H / 32; m.Wi = W / 32; m.H = H / 32; m.W = W / 32; m.CIN = 64; m.COUT = 64; m.NCH = 2; m.relu = 0; m.nblk = 1;
-            m.istride = 64; m.ostride = 64; m.ooff = 0;
-            KPB_LAUNCH(ctx, "conv3x3_b4c2", (conv_mfma<3, 1, 32, false, false, false, 2>), dim3(cdiv(m.W, 16), cdiv(m.H, 8), batch), dim3(256), 0, st, m);
-        }
+        if (int rc = conv2("b4c2", t4, x4, r4, H / 32, W / 32, 64)) return rc;
         // aggregation 1x1 + ReLU of block 2 (147-148); agg1 is fused into the head
         KPB_LAUNCH(ctx, "conv1x1_agg2", conv1x1_relu<16>, dim3((unsigned)((B * P / 4 + 255) / 256)), dim3(256), 0, st, x2, a2, wp("agg2.w"), wp("head.ws") + 16, S2, B * P / 4, nullptr, nullptr);
     }

@@ -30,7 +30,7 @@ struct ConvM {
     const float* xw = nullptr;    // conv_mfma_h<XC>: weights of ONE extra output channel (index xco) taken on the VALU: [tap][CIN / 2] x (hi pair, lo pair) of
                                   // halves (pack_xc_pairs), scaled by 1 / xun
     float xun = 1.0f;
-    // conv_mfma_h<.., PRE, .., GEN> (r05): the input is GENERATED while the tile is staged -- `in` is a one-channel image and the slab's 32 channels are
+    // conv_mfma_h<GEN> (r05): the input is GENERATED while the tile is staged -- `in` is a one-channel image and the slab's 32 channels are
     // relu(3 x 3 convolution + bias) of it (SuperPoint conv1a: gen_w [9][64] tap-major, gen_b [64]), scaled and split as the pre-split hand-off would be
     const float* gen_w = nullptr; const float* gen_b = nullptr;
     float xb = 0.0f;              // its bias
@@ -42,13 +42,13 @@ struct ConvM {
     const float* aux1 = nullptr;
     float* out1 = nullptr;
     float* out2 = nullptr;
-    // conv_mfma_h<.., PRE, .., GEN>: the tile holds the generated activations ALREADY SPLIT -- per pixel and 32-channel slab 128 bytes = [4 x 16 B of hi
+    // conv_mfma_h<PRE>: the tile holds the generated activations ALREADY SPLIT -- per pixel and 32-channel slab 128 bytes = [4 x 16 B of hi
     // halves | 4 x 16 B of lo halves], taken at the per-image power-of-two scale of cm_exp_of(amax_in l1 + bmax), a rigorous bound of the generated
     // layer's output (amax_in: the maximum of ITS input, measured; l1 / bmax: its largest row L1 norm / |bias|): no maximum pass over the slab, one
     // barrier per slab.  (r05 also had the producer as its own kernel writing this format to HBM and the consumer landing it by LDS-DMA: 2.10 -> 2.07 ms,
     // profiles/r05_presplit_conv1b_ab.txt -- superseded by GEN and removed in r06, together with KPB_PRESPLIT.)
     const unsigned* pre_amax = nullptr; float pre_l1 = 0.0f, pre_bmax = 0.0f;
-    // conv_mfma_h<.., UP> (r06, DISK's decoder): the first up_c input channels are NOT in `in` -- they are the 2 x bilinear upsampling (align_corners = False,
+    // conv_mfma_h<UP> (r06, DISK's decoder): the first up_c input channels are NOT in `in` -- they are the 2 x bilinear upsampling (align_corners = False,
     // disk.py:126-127) of up_src [B][Hi / 2][Wi / 2][up_c], evaluated while the tile is staged; `in` holds the remaining CIN - up_c channels (istride floats
     // per pixel).  The concatenated map [up(bottom) | horizontal] is never written.
     const float* up_src = nullptr; int up_c = 0;
@@ -64,9 +64,47 @@ struct ConvM {
 // GE_L2NORM: COUT = 64 = the workgroup's two tiles, so a wave holds whole rows: out = v / max(||v||_2, xb) (F.normalize, XFeat.py:136).
 enum { GE_PLAIN = 0, GE_RESIDUAL = 1, GE_ROTARY = 2, GE_SPLIT2 = 3, GE_L2NORM = 4 };
 
-template <int KS, int S, int CC, bool POOL_IN, bool POOL_OUT, bool XF, int NTB = 2>
+// A form of conv_mfma_h, named field by field: conv_mfma_h<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2}>.  The strict-fp32 conv_mfma has the
+// first seven fields; the others stay at their defaults.  launch_conv_mfma(_h) (below the kernels) launch a form on the grid its 16 x tile_h() tile needs.
+struct CmForm {
+    int ks, s, cc;          // kernel size, stride, input channels per LDS slab
+    bool pool_in, pool_out; // the input max-pooled pf x pf while it is staged (ALike.py:139-143), the output max-pooled 2 x 2 in the epilogue
+    bool xf;                // InstanceNorm (scale, shift) + PReLU of the pre-activation Conv block on the input while it is staged (ConvM::xf, disk.py:76-97)
+    int ntb = 2;            // 32-wide output tiles (n-tiles) per wave; a workgroup owns wn ntb of them
+    int mt = 1;             // conv_mfma_h: 32-pixel M tiles (two output rows each) per wave; it reuses every weight fragment it loads (1 KB, L2-resident) mt times
+    // one more output channel than the tiles hold (DISK's 129 = 4 x 32 + 1) is accumulated on the VALU from the same LDS tile (ConvM::xw), one output pixel per
+    // thread of a 16 x 16 tile, by the workgroup that owns the first n-tiles, instead of spending a 32-wide MFMA tile on it
+    bool xc = false;
+    int pf = 2;             // the pooling window of pool_in (2 or 4)
+    // (r04) the latency form for grids that cannot fill the chip (one image on the drop-in path: 2-16 workgroups per layer, each a chain of dependent round
+    // trips -- per tap a weight fetch, then LDS reads, then the products).  The weight fragments of ALL taps of a slab are requested before the slab's input is
+    // even loaded and land while it is staged: one round trip per slab instead of ten.  Costs T x 4 NTB NKB registers (144 for a 3 x 3 kernel, one n-tile),
+    // irrelevant at one wave per SIMD; the arithmetic and its order are those of the throughput form.
+    bool wpre = false;
+    bool pre = false;       // the tile holds the input already split (ConvM::pre_amax); exists as the generated form (gen) only
+    // (r05) the four waves as 4 / wn row groups x wn column groups.  wn = 1: every wave multiplies its mt row tiles by ALL ntb n-tiles of the workgroup -- the
+    // four waves request the same weight fragments, 4 x the bytes through the CU's vector L1 (64 B/clk), and a knock-out put 18 % of SuperPoint's conv1b there
+    // (profiles/r05_presplit_conv1b_ab.txt).  wn = 2: a wave takes twice the rows and half the n-tiles: the same 64 accumulator registers and products, half
+    // the weight bytes, twice the activation reads -- which come from LDS.
+    int wn = 1;
+    bool gen = false;       // the input is generated while the tile is staged (ConvM::gen_w)
+    // (r06) see ConvM::up_src.  DISK's up_3 read an 80-channel map [up(u2) | f1] that a kernel of its own had written (3.1 GB per 32 images, read once more
+    // for the InstanceNorm statistics and then here with a 5 x 5 halo by both workgroups of a tile).  Here a slab of upsampled channels is staged from the
+    // HALF-resolution source: its (IH / 2 + 2)^2 pixels land raw in 9 KB of LDS and every staged float4 is the four-tap mix of that -- the direct form (four
+    // global taps per staged float4, r05) spilled 95 registers and lost 3 ms.  The staging has the room: a slab's taps are 750 MFMAs per wave.
+    bool up = false;
+    constexpr bool operator==(const CmForm&) const = default;
+    constexpr int tile_h() const { return 8 * mt / wn; }       // output rows of a workgroup tile
+    // conv_mfma_h: waves per SIMD the register allocation is held to: what r02's code reached without being told (accumulators 16 mt ntb) -- left alone, the
+    // allocator keeps a second copy of the accumulators in VGPRs for the rare rescale (+64 registers, a wave per SIMD lost on every two-tile layer)
+    constexpr int waves() const { return wpre ? 1 : mt * ntb >= 4 ? ((ks == 5 && cc == 32) || pool_in ? 2 : 3) : (mt * ntb == 2 ? (ks == 3 && cc == 16 ? 3 : 4) : 5); }
+};
+
+template <CmForm F>
 __global__ __launch_bounds__(256) void conv_mfma(ConvM a)
 {
+    constexpr int KS = F.ks, S = F.s, CC = F.cc, NTB = F.ntb; constexpr bool POOL_IN = F.pool_in, POOL_OUT = F.pool_out, XF = F.xf;
+    static_assert(F == CmForm{KS, S, CC, POOL_IN, POOL_OUT, XF, NTB}, "conv_mfma: the strict-fp32 kernel has no mt, xc, pf, wpre, pre, wn, gen or up");
     constexpr int KC = CC / 2, PITCH = CC + 4, T = KS * KS, PAD = KS / 2;
     constexpr int IH = 7 * S + KS, IW = 15 * S + KS, Q = CC / 4;
     constexpr int NLD = (IH * IW * Q + 255) / 256;
@@ -209,8 +247,6 @@ __global__ __launch_bounds__(256) void conv_mfma(ConvM a)
 // 20-27} and so on); with lane = (pixel row p >> 4, column p & 15) those are 8 pixels of one row and 8 of the next, and with
 // an odd pixel pitch and a row pitch of 0 mod 256 bytes their sixteen 16-byte slots are distinct (stride 1).  The first
 // r02 layout (two planes, pitch 2*CC + 16, rows unpadded) measured SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 50 %.
-// A wave owns MT 32-pixel M tiles (two output rows each) and reuses every weight fragment it loads (1 KB per wave-load,
-// L2-resident) MT times.
 typedef _Float16 cm_h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 cm_h2 __attribute__((ext_vector_type(2)));
 
@@ -283,51 +319,6 @@ __device__ __forceinline__ float cm_wave_max(float v)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-// XC: one more output channel than the tiles hold (DISK's 129 = 4 x 32 + 1) is accumulated on the VALU from the same LDS
-// tile, one output pixel per thread (MT = 2: 256 pixels) of the workgroup that owns the first NTB tiles, instead of spending a
-// 32-wide MFMA tile on it.
-// (Tried, r02: requesting the weight fragments of tap t + 1 before the MFMAs of tap t in a second register set -- 12-15 %
-// slower on every layer; the extra 32-64 VGPRs cost a wave per SIMD and the other waves already cover the L2 latency.
-// The same for the one-tile layer b3c2 alone, where the second set is 16 registers: 0.58 -> 0.71 ms.  Fetching a tap's fragments
-// once per workgroup, a tap ahead, through a double-buffered LDS strip (one barrier per tap, 4-8 registers): +1-3 % -- the
-// weight round trip is not what keeps the matrix pipe at 46 %.  Nor is the slab staging: a persistent form that fetches the next
-// slab (or the next tile's first slab) into registers before the taps of the current one ran 2 % faster on conv1b at two
-// waves per SIMD and 20 % slower on DISK's up_3 (the 44 registers of the slab in flight cost the third wave).)
-// (Tried, r04: the next slab's input requested into registers right after this slab's split, its round trip flying under the nine taps,
-// with the fragments taken one 16-deep k-block at a time so that the 44 staging registers fit beside the accumulators at three waves per
-// SIMD (no spill in the loops): every SuperPoint layer 10-14 % SLOWER (conv1b 2.10 -> 2.38 ms), DISK's 5 x 5 layers 0-8 % slower -- the
-// half-size fragment sets cost the tap loop more than the hidden load gives back.)
-// (Tried, r04: the workgroups sharing a CU start together and take the same time per phase, so their load / split / store phases
-// might coincide and idle the matrix pipe together; delaying the first generation's slot k by k x 8-48 k cycles changed no layer of
-// SuperPoint by more than 1 % -- the phases are not in lockstep.)
-// PF: with POOL_IN the input is max-pooled PF x PF (2 or 4) while it is staged (ALike.py:139-143).
-// waves per SIMD the register allocation is held to: what r02's code reached without being told (accumulators 16 MT NTB) --
-// left alone, the allocator keeps a second copy of the accumulators in VGPRs for the rare rescale below (+64 registers, a wave
-// per SIMD lost on every two-tile layer)
-// 16 bytes per lane from global memory to LDS at lds_wave_base + 16 * lane (wave-uniform base), no register in between (the head of
-// ALIKE has the story: alike.hip hp_dma16).  M0 belongs to the compiler: saved and restored around the one instruction that reads it.
-__device__ __forceinline__ void cm_dma16(const void* gsrc, const void* lds_wave_base)
-{
-    const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<uintptr_t>(lds_wave_base));
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(m0v), "v"(gsrc) : "memory");
-}
-
-constexpr int conv_mfma_h_waves(int KS, int CC, bool POOL_IN, int NTB, int MT)
-{
-    return MT * NTB >= 4 ? ((KS == 5 && CC == 32) || POOL_IN ? 2 : 3) : (MT * NTB == 2 ? (KS == 3 && CC == 16 ? 3 : 4) : 5);
-}
-
-// WPRE (r04): the latency form for grids that cannot fill the chip (one image on the drop-in path: 2-16 workgroups per layer, each a
-// chain of dependent round trips -- per tap a weight fetch, then LDS reads, then the products).  The weight fragments of ALL taps of a
-// slab are requested before the slab's input is even loaded and land while it is staged: one round trip per slab instead of ten.
-// Costs T x 4 NTB NKB registers (144 for a 3 x 3 kernel, one n-tile), irrelevant at one wave per SIMD; the arithmetic and its order
-// are those of the throughput form.
-// WN (r05): the four waves as 4 / WN row groups x WN column groups.  WN = 1: every wave multiplies its MT row tiles by ALL NTB n-tiles of the
-// workgroup -- the four waves request the same weight fragments, 4 x the bytes through the CU's vector L1 (64 B/clk), and a knock-out
-// put 18 % of SuperPoint's conv1b there (profiles/r05_presplit_conv1b_ab.txt).  WN = 2: a wave takes twice the rows and half the
-// n-tiles: the same 64 accumulator registers and products, half the weight bytes, twice the activation reads -- which come from LDS.
 // The taps of the 2 x bilinear upsampling torch's F.interpolate(scale_factor = 2, mode = 'bilinear', align_corners = False) reads for output coordinate o of
 // a source of n samples: source indices i0 <= i1, weight l of i1 (1 - l of i0).  Shared by upsample2_concat (the materialised form the strict-fp32 path keeps),
 // up_chan_sums (its statistics) and conv_mfma_h<UP> (the staging that evaluates it in place): the three compute the same floats.
@@ -345,20 +336,28 @@ __device__ __forceinline__ float4 cm_up2_mix(const float4 p00, const float4 p01,
                        hy * (hx * p00.z + lx * p01.z) + ly * (hx * p10.z + lx * p11.z), hy * (hx * p00.w + lx * p01.w) + ly * (hx * p10.w + lx * p11.w));
 }
 
-// UP (r06): see ConvM::up_src.  DISK's up_3 read an 80-channel map [up(u2) | f1] that a kernel of its own had written (3.1 GB per 32 images, read once more
-// for the InstanceNorm statistics and then here with a 5 x 5 halo by both workgroups of a tile).  Here a slab of upsampled channels is staged from the
-// HALF-resolution source: its (IH / 2 + 2)^2 pixels land raw in 9 KB of LDS and every staged float4 is the four-tap mix of that -- the direct form (four global
-// taps per staged float4, r05) spilled 95 registers and lost 3 ms.  The staging has the room: a slab's taps are 750 MFMAs per wave.
-template <int KS, int S, int CC, bool POOL_IN, bool POOL_OUT, bool XF, int NTB = 2, int MT = 1, bool XC = false, int PF = 2, bool WPRE = false, bool PRE = false, int WN = 1, bool GEN = false,
-          bool UP = false>
-__global__ __launch_bounds__(256, WPRE ? 1 : conv_mfma_h_waves(KS, CC, POOL_IN, NTB, MT)) void conv_mfma_h(ConvM a)
+// (Tried, r02: requesting the weight fragments of tap t + 1 before the MFMAs of tap t in a second register set -- 12-15 % slower on every layer; the extra 32-64 VGPRs
+// cost a wave per SIMD and the other waves already cover the L2 latency.  The same for the one-tile layer b3c2 alone, where the second set is 16 registers:
+// 0.58 -> 0.71 ms.  Fetching a tap's fragments once per workgroup, a tap ahead, through a double-buffered LDS strip (one barrier per tap, 4-8 registers): +1-3 % --
+// the weight round trip is not what keeps the matrix pipe at 46 %.  Nor is the slab staging: a persistent form that fetches the next slab (or the next tile's first
+// slab) into registers before the taps of the current one ran 2 % faster on conv1b at two waves per SIMD and 20 % slower on DISK's up_3 (the 44 registers of the slab
+// in flight cost the third wave).)
+// (Tried, r04: the next slab's input requested into registers right after this slab's split, its round trip flying under the nine taps, with the fragments taken one
+// 16-deep k-block at a time so that the 44 staging registers fit beside the accumulators at three waves per SIMD (no spill in the loops): every SuperPoint layer
+// 10-14 % SLOWER (conv1b 2.10 -> 2.38 ms), DISK's 5 x 5 layers 0-8 % slower -- the half-size fragment sets cost the tap loop more than the hidden load gives back.)
+// (Tried, r04: the workgroups sharing a CU start together and take the same time per phase, so their load / split / store phases might coincide and idle the matrix
+// pipe together; delaying the first generation's slot k by k x 8-48 k cycles changed no layer of SuperPoint by more than 1 % -- the phases are not in lockstep.)
+template <CmForm F>
+__global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
 {
-    static_assert(!UP || (S == 1 && !POOL_IN && !PRE && !WPRE && (((8 * MT / WN - 1) * S + KS) % 2 == 0) && ((15 * S + KS) % 2 == 0) && KS / 2 % 2 == 0),
+    constexpr int KS = F.ks, S = F.s, CC = F.cc, NTB = F.ntb, MT = F.mt, PF = F.pf, WN = F.wn;
+    constexpr bool POOL_IN = F.pool_in, POOL_OUT = F.pool_out, XF = F.xf, XC = F.xc, WPRE = F.wpre, PRE = F.pre, GEN = F.gen, UP = F.up;
+    static_assert(!UP || (S == 1 && !POOL_IN && !PRE && !WPRE && (((F.tile_h() - 1) * S + KS) % 2 == 0) && ((15 * S + KS) % 2 == 0) && KS / 2 % 2 == 0),
                   "conv_mfma_h<UP>: stride-1 layers whose input tile starts on an even row and column");
     static_assert(WN == 1 || (WN == 2 && MT % 2 == 0 && !WPRE), "conv_mfma_h: waves split the n-tiles two ways at most");
     static_assert(PRE == GEN && (!GEN || KS == 3), "conv_mfma_h: the pre-split tile exists as the generated one (a 3 x 3 one-channel layer computed while staging); r05's DMA-landed form was measured, superseded and removed in r06");
     static_assert(!PRE || (CC == 32 && S == 1 && !POOL_IN && !XF && !XC && !WPRE), "conv_mfma_h: the pre-split input form exists for plain stride-1 32-channel slabs");
-    constexpr int KC = CC / 2, NKB = CC / 16, T = KS * KS, PAD = KS / 2, TH = 8 * MT / WN;
+    constexpr int KC = CC / 2, NKB = CC / 16, T = KS * KS, PAD = KS / 2, TH = F.tile_h();
     // r06: a tap's weight fragments (L2 round trips: NTB NKB 2 loads of 16 bytes per lane) are requested ONE TAP AHEAD and the order is pinned with a scheduling
     // barrier -- left alone the scheduler puts every request next to its first use, the round trip exposed nine (25) times per slab.  The 3 x 3 forms unroll their
     // tap loop (the two fragment sets are then plain registers: ALIKE's b3c2 0.444 -> 0.372 ms per 512 images, SuperPoint's conv2a .. conv4b -4 .. 5 %, no spills);
@@ -839,6 +838,23 @@ __global__ __launch_bounds__(256, WPRE ? 1 : conv_mfma_h_waves(KS, CC, POOL_IN, 
         }
     }
 }
+
+// Launches the instance among FS (the forms a translation unit compiles) whose form is f, on cdiv(W, 16) x cdiv(H, f.tile_h()) x B nblk workgroups of 256
+// threads; KPB_E_INVALID if FS has no such form.  H: conv_mfma_h, else conv_mfma.
+template <bool H, CmForm... FS>
+int cm_launch(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B)
+{
+    const bool found = ((f == FS && [&] {
+        const dim3 grid(cdiv(a.W, 16), cdiv(a.H, FS.tile_h()), B * a.nblk);
+        if constexpr (H) KPB_LAUNCH(ctx, tag, conv_mfma_h<FS>, grid, dim3(256), 0, ctx->stream, a);
+        else KPB_LAUNCH(ctx, tag, conv_mfma<FS>, grid, dim3(256), 0, ctx->stream, a);
+        return true;
+    }()) || ...);
+    return found ? KPB_OK : kpb_fail(ctx, KPB_E_INVALID, "%s: no instance for %s: ks=%d s=%d cc=%d pool_in=%d pool_out=%d xf=%d ntb=%d mt=%d xc=%d pf=%d wpre=%d pre=%d wn=%d gen=%d up=%d",
+        H ? "conv_mfma_h" : "conv_mfma", tag, f.ks, f.s, f.cc, f.pool_in, f.pool_out, f.xf, f.ntb, f.mt, f.xc, f.pf, f.wpre, f.pre, f.wn, f.gen, f.up);
+}
+template <CmForm... FS> int launch_conv_mfma_h(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B) { return cm_launch<true, FS...>(ctx, tag, f, a, B); }
+template <CmForm... FS> int launch_conv_mfma(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B) { return cm_launch<false, FS...>(ctx, tag, f, a, B); }
 
 // ---------------------------------------------------------------------------------------------- 1x1 / Linear
 // A 1x1 convolution has no taps to amortise the staging of conv_mfma_h over: per 32-channel slab it pays a global-load

@@ -440,7 +440,7 @@ std::vector<float> pack_xf_s2(const float* w, int cout, float scale)
 
 // SuperPoint conv1a (1 -> 64, 3x3, ReLU; SuperPoint.py:44): 16 lanes share a pixel, each lane keeps the 9 taps of its
 // 4 output channels in registers and walks down a column of pixels, so a wave store is 4 whole 256-byte pixels.
-// (The split-f16 path never launches it: conv1b generates these channels while it stages its tile, conv_mfma_h<.., GEN>; this kernel is the
+// (The split-f16 path never launches it: conv1b generates these channels while it stages its tile, conv_mfma_h<GEN>; this kernel is the
 // strict-fp32 path's conv1a.)
 __global__ __launch_bounds__(256) void conv1a_c64(const float* gray, float* out, const float* w /*[9][64]*/, const float* bias, int H, int W, int rows_per_block)
 {
@@ -727,67 +727,55 @@ int launch_mfma(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, co
     a.CIN = L.cin; a.COUT = L.cout; a.NCH = L.cin / CC; a.relu = relu_ ? 1 : 0; a.nblk = (L.cout + 32 * L.ntb - 1) / (32 * L.ntb);
     hipStream_t st = ctx->stream;
     const bool x = xf != nullptr;
-    const dim3 block(256);
-    if (conv_mfma_use_h16()) {     // split-f16 form: stride-1 layers on 16-row workgroup tiles; with two n-tiles per workgroup the waves
-                                   // form 2 row groups x 2 n-tiles (conv_mfma_h<.., WN = 2>: four M tiles and one n-tile per wave)
+    if (conv_mfma_use_h16()) {
         a.unscale = 1.0f / (net->wscale.at(L.name + ".w"));
-        const dim3 g2(cdiv(a.W, 16), cdiv(a.H, 16), B * a.nblk), g1(cdiv(a.W, 16), cdiv(a.H, 8), B * a.nblk);
-        // one-tile layers (cout <= 32) are bound by per-workgroup latency: 8-row tiles (one M tile per wave, 28 KB of LDS, five
-        // workgroups per CU) measured 8-16 % faster; layers with two output tiles lose the fragment reuse that way (+8 % time)
-        if (pre) {      // the input arrives already split (ConvM::pre_amax): raw bytes land in the tile by LDS-DMA
-            a.pre_amax = pre->amax; a.pre_l1 = pre->l1; a.pre_bmax = pre->bmax;
-            if (pre->gen_w && L.ks == 3 && S == 1 && CC == 32 && !pool_in && pool_out && !x && L.ntb == 2) {
-                a.gen_w = pre->gen_w; a.gen_b = pre->gen_b; a.istride = 1;         // `in` is the one-channel image the layer in front reads
-                KPB_LAUNCH(ctx, name, (conv_mfma_h<3, 1, 32, false, true, false, 1, 4, false, 2, false, true, 2, true>), g2, block, 0, st, a);
+        if (L.ks == 1 && S == 1 && CC == 32 && !pool_in && !pool_out && !x && !pre) {     // 1x1: gemm_h
+            const dim3 grid(cdiv(a.H * a.W, 128), 1, B * a.nblk), block(256);
+            if (l2_eps > 0.0f) {
+                if (L.cout != 64 || L.ntb != 2) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: the fused L2 norm needs a 64-channel layer");
+                a.xb = l2_eps;
+                KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_L2NORM>), grid, block, 0, st, a);
             }
-            else return kpb_fail(ctx, KPB_E_INVALID, "conv_mfma_h: no generated-input instance for %s", L.name.c_str());
+            else if (unfold_w) KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_PLAIN, true>), grid, block, 0, st, a);
+            else KPB_LAUNCH(ctx, name, (gemm_h<2, 1>), grid, block, 0, st, a);
             return KPB_OK;
         }
-        if (L.ks == 3 && S == 1 && CC == 32 && !pool_in && !pool_out && !x && L.ntb == 1) KPB_LAUNCH(ctx, name, (conv_mfma_h<3, 1, 32, false, false, false, 1, 1>), g1, block, 0, st, a);
-        else if (L.ks == 3 && S == 1 && CC == 32 && !pool_in && !pool_out && !x) KPB_LAUNCH(ctx, name, (conv_mfma_h<3, 1, 32, false, false, false, 1, 4, false, 2, false, false, 2>), g2, block, 0, st, a);
-        else if (L.ks == 3 && S == 1 && CC == 32 && !pool_in && pool_out && !x) KPB_LAUNCH(ctx, name, (conv_mfma_h<3, 1, 32, false, true, false, 1, 4, false, 2, false, false, 2>), g2, block, 0, st, a);
-        else if (L.ks == 3 && S == 1 && CC == 32 && pool_in && !pool_out && !x) KPB_LAUNCH(ctx, name, (conv_mfma_h<3, 1, 32, true, false, false, 1, 4, false, 2, false, false, 2>), g2, block, 0, st, a);
-        else if (L.ks == 5 && S == 1 && CC == 32 && !pool_in && !pool_out && x && up) {     // [up(bottom) | horizontal] evaluated while staging (ConvM::up_src)
+        // split-f16 form: stride-1 layers on 16-row workgroup tiles; with two n-tiles per workgroup the waves form 2 row groups x 2 n-tiles
+        // (four M tiles and one n-tile per wave)
+        CmForm f{.ks = L.ks, .s = S, .cc = CC, .pool_in = pool_in, .pool_out = pool_out, .xf = x, .ntb = 1, .mt = 4, .wn = 2};
+        // one-tile layers (cout <= 32) are bound by per-workgroup latency: 8-row tiles (one M tile per wave, 28 KB of LDS, five
+        // workgroups per CU) measured 8-16 % faster; layers with two output tiles lose the fragment reuse that way (+8 % time)
+        if (L.ntb == 1) f.mt = f.wn = 1;
+        if (S == 2) f.mt = 2;           // stride 2: 8-row tiles
+        if (pre) {      // the input arrives already split (ConvM::pre_amax), generated while the tile is staged from the one-channel image the layer in front reads
+            if (!pre->gen_w) return kpb_fail(ctx, KPB_E_INVALID, "conv_mfma_h: no generated-input instance for %s", L.name.c_str());
+            a.pre_amax = pre->amax; a.pre_l1 = pre->l1; a.pre_bmax = pre->bmax; a.gen_w = pre->gen_w; a.gen_b = pre->gen_b; a.istride = 1;
+            f.pre = f.gen = true;
+        }
+        if (up) {       // [up(bottom) | horizontal] evaluated while staging (ConvM::up_src); `in` holds the channels behind the upsampled ones
             if (up->c % CC || up->c >= L.cin || (Hi % 2) || (Wi % 2)) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: bad upsampled-input split for %s", L.name.c_str());
             a.up_src = up->src; a.up_c = up->c; a.istride = L.cin - up->c;
-            KPB_LAUNCH(ctx, name, (conv_mfma_h<5, 1, 32, false, false, true, 1, 4, false, 2, false, false, 2, false, true>), g2, block, 0, st, a);
+            f.up = true;
         }
-        else if (L.ks == 5 && S == 1 && CC == 32 && !pool_in && !pool_out && x) KPB_LAUNCH(ctx, name, (conv_mfma_h<5, 1, 32, false, false, true, 1, 4, false, 2, false, false, 2>), g2, block, 0, st, a);
-        else if (L.ks == 5 && S == 1 && CC == 16 && !pool_in && !pool_out && x && L.ntb == 2) KPB_LAUNCH(ctx, name, (conv_mfma_h<5, 1, 16, false, false, true, 1, 4, false, 2, false, false, 2>), g2, block, 0, st, a);
-        else if (L.ks == 5 && S == 1 && CC == 16 && !pool_in && !pool_out && x && L.ntb == 5) {
+        if (L.ntb == 5) {
             // 129 = 4 x 32 + 1 (DISK up_3): four MFMA tiles (two workgroups of two: 64 accumulator registers, three waves per SIMD)
             // and the score channel on the VALU of the first workgroup
             a.nblk = 2; a.xw = net->wp((L.name + ".xw").c_str()); a.xb = net->wscale.at(L.name + ".xb"); a.xun = 1.0f / net->wscale.at(L.name + ".xs"); a.xco = L.cout - 1;
-            if (up) {       // `in` holds the channels behind the upsampled ones: cin - up->c floats per pixel
-                if (up->c % CC || up->c >= L.cin || (Hi % 2) || (Wi % 2)) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: bad upsampled-input split for %s", L.name.c_str());
-                a.up_src = up->src; a.up_c = up->c; a.istride = L.cin - up->c;
-                KPB_LAUNCH(ctx, name, (conv_mfma_h<5, 1, 16, false, false, true, 1, 4, true, 2, false, false, 2, false, true>), dim3(cdiv(a.W, 16), cdiv(a.H, 16), B * 2), block, 0, st, a);
-            } else
-            KPB_LAUNCH(ctx, name, (conv_mfma_h<5, 1, 16, false, false, true, 1, 4, true, 2, false, false, 2>), dim3(cdiv(a.W, 16), cdiv(a.H, 16), B * 2), block, 0, st, a);
+            f.xc = true;
         }
-        else if (L.ks == 1 && S == 1 && CC == 32 && !pool_in && !pool_out && !x && l2_eps > 0.0f) {
-            if (L.cout != 64 || L.ntb != 2) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: the fused L2 norm needs a 64-channel layer");
-            a.xb = l2_eps;
-            KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_L2NORM>), dim3(cdiv(a.H * a.W, 128), 1, B * a.nblk), block, 0, st, a);
-        }
-        else if (L.ks == 1 && S == 1 && CC == 32 && !pool_in && !pool_out && !x && unfold_w) KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_PLAIN, true>), dim3(cdiv(a.H * a.W, 128), 1, B * a.nblk), block, 0, st, a);
-        else if (L.ks == 1 && S == 1 && CC == 32 && !pool_in && !pool_out && !x) KPB_LAUNCH(ctx, name, (gemm_h<2, 1>), dim3(cdiv(a.H * a.W, 128), 1, B * a.nblk), block, 0, st, a);
-        else if (L.ks == 3 && S == 2 && CC == 16 && !pool_in && !pool_out && !x) KPB_LAUNCH(ctx, name, (conv_mfma_h<3, 2, 16, false, false, false, 1, 2, false, 2, false, false, 2>), g1, block, 0, st, a);
-        else return kpb_fail(ctx, KPB_E_INVALID, "conv_mfma_h: no instance for ks=%d stride=%d cc=%d pool_in=%d pool_out=%d xf=%d", L.ks, S, CC, pool_in, pool_out, x);
-        return KPB_OK;
+        return launch_conv_mfma_h<
+            CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
+            CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_in = true, .ntb = 1, .mt = 4, .wn = 2},
+            CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .pre = true, .wn = 2, .gen = true}, CmForm{.ks = 3, .s = 2, .cc = 16, .ntb = 1, .mt = 2, .wn = 2},
+            CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2, .up = true},
+            CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .xc = true, .wn = 2},
+            CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .xc = true, .wn = 2, .up = true}>(ctx, name, f, a, B);
     }
-    const dim3 grid(cdiv(a.W, 16), cdiv(a.H, 8), B * a.nblk);
-    if (L.ks == 3 && S == 1 && CC == 32 && !pool_in && !pool_out && !x && L.ntb == 1) KPB_LAUNCH(ctx, name, (conv_mfma<3, 1, 32, false, false, false, 1>), grid, block, 0, st, a);
-    else if (L.ks == 3 && S == 1 && CC == 32 && !pool_in && !pool_out && !x) KPB_LAUNCH(ctx, name, (conv_mfma<3, 1, 32, false, false, false>), grid, block, 0, st, a);
-    else if (L.ks == 3 && S == 1 && CC == 32 && !pool_in && pool_out && !x) KPB_LAUNCH(ctx, name, (conv_mfma<3, 1, 32, false, true, false>), grid, block, 0, st, a);
-    else if (L.ks == 3 && S == 1 && CC == 32 && pool_in && !pool_out && !x) KPB_LAUNCH(ctx, name, (conv_mfma<3, 1, 32, true, false, false>), grid, block, 0, st, a);
-    else if (L.ks == 1 && S == 1 && CC == 32 && !pool_in && !pool_out && !x) KPB_LAUNCH(ctx, name, (conv_mfma<1, 1, 32, false, false, false>), grid, block, 0, st, a);
-    else if (L.ks == 3 && S == 2 && CC == 16 && !pool_in && !pool_out && !x) KPB_LAUNCH(ctx, name, (conv_mfma<3, 2, 16, false, false, false>), grid, block, 0, st, a);
-    else if (L.ks == 5 && S == 1 && CC == 32 && !pool_in && !pool_out && x) KPB_LAUNCH(ctx, name, (conv_mfma<5, 1, 32, false, false, true>), grid, block, 0, st, a);
-    else if (L.ks == 5 && S == 1 && CC == 16 && !pool_in && !pool_out && x && L.ntb == 2) KPB_LAUNCH(ctx, name, (conv_mfma<5, 1, 16, false, false, true>), grid, block, 0, st, a);
-    else if (L.ks == 5 && S == 1 && CC == 16 && !pool_in && !pool_out && x && L.ntb == 5) KPB_LAUNCH(ctx, name, (conv_mfma<5, 1, 16, false, false, true, 5>), grid, block, 0, st, a);
-    else return kpb_fail(ctx, KPB_E_INVALID, "conv_mfma: no instance for ks=%d stride=%d cc=%d pool_in=%d pool_out=%d xf=%d", L.ks, S, CC, pool_in, pool_out, x);
-    return KPB_OK;
+    return launch_conv_mfma<
+        CmForm{.ks = 1, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1},
+        CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true}, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_in = true}, CmForm{.ks = 3, .s = 2, .cc = 16},
+        CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 5}>(
+        ctx, name, CmForm{.ks = L.ks, .s = S, .cc = CC, .pool_in = pool_in, .pool_out = pool_out, .xf = x, .ntb = L.ntb}, a, B);
 }
 
 int launch_valu(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, const float* in, float* out, int B, int Hi, int Wi,
@@ -880,7 +868,7 @@ struct SuperPointNet : kpb_net {
         KPB_LAUNCH(ctx, "sp_rgb_sum", rgb_sum, dim3((unsigned)((P + 255) / 256), batch), dim3(256), 0, st, img, gray, P);
         int rc;
         // conv1a (:44) is not launched on the split-f16 path: conv1b computes its channels from the gray image while it stages its tile
-        // (conv_mfma_h<.., GEN>, r05), split at the scale of the bound amax(gray) l1 + bmax of conv1a's output.  r05's two earlier forms -- conv1a as
+        // (conv_mfma_h<GEN>, r05), split at the scale of the bound amax(gray) l1 + bmax of conv1a's output.  r05's two earlier forms -- conv1a as
         // its own kernel handing over fp32 or pre-split halves, KPB_PRESPLIT=0 / 1 -- were measured, superseded and removed (r06).
         const bool fused = conv_mfma_use_h16();
         PreSplit ps;

@@ -3,7 +3,7 @@
 // stopping (check_if_stop 670-681) and point pruning (get_pruning_mask 659-668) decided ON THE DEVICE, so a batch of
 // pairs runs through all nine layers without a host round trip; pairs that stopped are skipped by every later kernel.
 //
-//   Linear layers   = conv_mfma<1,...> over tokens laid out as a 16-wide "image" (weights pre-packed once)
+//   Linear layers   = 1 x 1 convolutions (gemm_h; strict fp32: conv_mfma) over tokens laid out as a 16-wide "image" (weights pre-packed once)
 //   attention       = lg_flash: per wave 32 queries, K tile as the MFMA A operand and Q as B (S^T = K.Q^T), so each
 //                     lane owns one query column and its softmax statistics; the probability tile then feeds the
 //                     P.V MFMA straight from its accumulator registers (k order permuted, V rows loaded to match)
@@ -870,7 +870,8 @@ struct LgNetShim : kpb_net {     // WeightStage::upload wants a kpb_net; only ct
 };
 
 // One Linear over the tokens of every sequence.  Split-f16 form: gemm_h, rows past cnt[s] neither read nor written; `epi` selects
-// the fused epilogue (conv_mfma.h GE_*) and `x` carries its operands.  Strict fp32 form: conv_mfma<1,...>, plain epilogue only.
+// the fused epilogue (conv_mfma.h GE_*) and `x` carries its operands.  Strict fp32 form: conv_mfma<LG_LINEAR_F32>, plain epilogue only.
+constexpr CmForm LG_LINEAR_F32{.ks = 1, .s = 1, .cc = 32};
 struct LgEpi {
     int epi = GE_PLAIN;
     const float* res = nullptr; int rstride = 0;          // GE_RESIDUAL
@@ -896,7 +897,7 @@ int lg_linear(kpb_ctx* ctx, kpb_lg* lg, const char* tag, const std::string& name
         else KPB_LAUNCH(ctx, tag, (gemm_h<2, 1>), grid, dim3(256), 0, ctx->stream, a);
     } else {
         if (x.epi != GE_PLAIN) return kpb_fail(ctx, KPB_E_INVALID, "lg_linear: fused epilogues exist in the split-f16 form only");
-        KPB_LAUNCH(ctx, tag, (conv_mfma<1, 1, 32, false, false, false, 2>), dim3(1, MP / 128, S * a.nblk), dim3(256), 0, ctx->stream, a);
+        return launch_conv_mfma<LG_LINEAR_F32>(ctx, tag, LG_LINEAR_F32, a, S);      // MP / 16 rows of 16 tokens: MP / 128 workgroup tiles (MP is a multiple of 128)
     }
     return KPB_OK;
 }
