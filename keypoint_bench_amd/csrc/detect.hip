@@ -906,7 +906,8 @@ __device__ __forceinline__ int scan_chunks(const SelArgs& a, const float* map, u
     return n;
 }
 
-// r06: the same list from the NMS's bitmap of confirmed maxima (signed map, threshold <= 0: every confirmed maximum is > 0 >= threshold): 38 KB of an image
+// r06: the same list from the NMS's bitmap of confirmed maxima (signed map, threshold 0 or -0: every confirmed maximum is > 0 = threshold, every other
+// pixel of the NMS's output is 0 and fails it; det_select sends a negative or NaN threshold to the map-reading form): 38 KB of an image
 // instead of its 1.2 MB map -- the map scan is 19 rounds at the HBM rate of the whole launch (629 MB).  Four 32-pixel words per thread and round, the
 // border masked per word, raster order kept by the block scan; the scores are gathered afterwards, every load independent.
 __device__ __forceinline__ int scan_bits(const SelArgs& a, const float* map, const unsigned* bits, unsigned long long* cand, unsigned long long* wsum)
@@ -1203,6 +1204,8 @@ int nms_plan(kpb_ctx* ctx, int batch, int H, int W, int r, NmsPlan& p, int prune
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
         KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(select_topk<false>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(select_topk<true>),     // kpad * 8 bytes: 64 KB for top_k 4097 .. KPB_MAX_TOPK
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
         ctx->lds_attr_done |= KPB_ATTR_NMS;
     }
     return KPB_OK;
@@ -1374,8 +1377,10 @@ int det_select(kpb_ctx* ctx, const DetState& d)
     }
     s.host_status = ctx->host_det;
     s.chunk_cnt = nullptr; s.nchunks = cdiv(d.H * d.W, SEL_CHUNK); s.lcap = 0;
-    // the bitmap of confirmed maxima stands for the map right after sweep 0 + tail only (later sweeps do not keep it), and only for thresholds every maximum passes
-    const bool bits = d.plan.cbits && d.sweeps_run == 1 && !(d.prm.threshold > 0.0f) && s.signed_map;
+    // the bitmap of confirmed maxima stands for the map right after sweep 0 + tail only (later sweeps do not keep it), and only at threshold 0 (or -0):
+    // every maximum passes it and no suppressed pixel does.  A negative threshold keeps the zeroed non-maxima as well (map > threshold after NMS), a
+    // NaN one keeps nothing: both read the map.
+    const bool bits = d.plan.cbits && d.sweeps_run == 1 && d.prm.threshold == 0.0f && s.signed_map;
     s.cbits = bits ? reinterpret_cast<const unsigned*>(d.plan.cbits) : nullptr; s.wb = d.plan.wb;
     size_t lds = (size_t)s.kpad * sizeof(unsigned long long);
     if (d.batch < 64 && s.nchunks > 1) {       // too few images to fill the chip with one workgroup each: scan in (chunks x batch) workgroups first

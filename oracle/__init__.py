@@ -110,6 +110,20 @@ def sample(desc_chw, pts):
     return out
 
 
+def sample_hwc(desc_hwc, pts):
+    """sample() on a channels-last [Hd, Wd, C] map (the pipelines' layout), read through its strides: no transposed copy."""
+    d = np.asarray(desc_hwc, dtype=np.float32)
+    if not d.flags.c_contiguous:
+        d = np.ascontiguousarray(d)
+    Hd, Wd, C = d.shape
+    p = _f32(pts)
+    n = p.shape[0]
+    out = np.empty((n, C), np.float32)
+    if n:
+        lib().kpbo_sample(_fp(d), C, Hd, Wd, 1, Wd * C, C, _fp(p), n, p.shape[1], _fp(out))
+    return out
+
+
 def match(d0, d1, max_distance=np.inf, cross_check=True):
     """skimage.feature.match_descriptors as called at utils/matcher.py:227-230 (restated, unpinned).
     Returns (pairs[K,2] int64, dist[K] float64)."""

@@ -254,8 +254,8 @@ def test_nms_tail_handoff_bitmap_and_histogram_edges(monkeypatch):
 @pytest.mark.parametrize("shape", [(480, 640), (237, 301), (96, 80)])
 def test_selection_from_the_bitmap_of_confirmed_maxima_equals_the_map_scan(shape, monkeypatch):
     """r06: right after sweep 0 + tail, select_topk<BITS> reads the NMS's bitmap of confirmed maxima (a byte per eight pixels from sweep 0's owner threads, bits set
-    by the tail for what it confirms) instead of the map.  It runs for batches of 64 images and more (or one-chunk maps) when the threshold is <= 0; a threshold
-    of 1e-37 -- below every score -- sends the same detection through the map-reading form.  Both must give the same rows, bit for bit: 64 images, three
+    by the tail for what it confirms) instead of the map.  It runs for batches of 64 images and more (or one-chunk maps) when the threshold is 0 (or -0; a negative or
+    NaN threshold reads the map: test_largest_top_k_and_non_positive_thresholds_on_the_large_batch_path); a threshold of 1e-37 -- below every score -- sends the same detection through the map-reading form.  Both must give the same rows, bit for bit: 64 images, three
     bitmap rounds per image at 480 x 640, a ragged width, a map smaller than one round; a few images also against the oracle."""
     from keypoint_bench_amd.utils.extracter import detection_batch
     monkeypatch.setenv("KPB_NMS_TILED", "0")            # (64 images are below the batch at which the tail is the default)
@@ -274,3 +274,52 @@ def test_selection_from_the_bitmap_of_confirmed_maxima_equals_the_map_scan(shape
         for b in (0, 5, 63):
             want, _ = oracle.detection(maps[b, 0], p)
             np.testing.assert_array_equal(k0[b, : n0[b]].view(np.uint32), want.view(np.uint32), err_msg="oracle, image %d %r" % (b, p))
+
+
+_LARGE_BATCH = []
+
+
+def _large_batch_maps():
+    """64 maps of 480 x 640.  Even: uniform -- at nms_dist 2 about 22 000 maxima inside an 8-pixel border, more than any top_k.  Odd: zero but for a
+    band of 60 uniform rows -- about 2 500 maxima, fewer than top_k (the suppressed and the zero pixels alike are 0 after NMS)."""
+    if not _LARGE_BATCH:
+        maps = np.stack([synthetic.score_uniform(800 + b, 480, 640) for b in range(64)])
+        maps[1::2, 60:] = 0.0
+        _LARGE_BATCH.append(maps)
+    return _LARGE_BATCH[0]
+
+
+@pytest.mark.parametrize("thr", [0.0, -0.0, -1e-30, -0.5, float("nan")], ids=["0", "-0", "-1e-30", "-0.5", "nan"])
+@pytest.mark.parametrize("top_k", [4097, 8192])
+def test_largest_top_k_and_non_positive_thresholds_on_the_large_batch_path(top_k, thr, monkeypatch):
+    """The large-batch path at its limits: 64 maps with the tail forced (the batch takes select_topk's one-workgroup-per-image form, which reads the
+    bitmap of confirmed maxima where it may).  From top_k 4097 to KPB_MAX_TOPK its selection slots take 64 KB of dynamic LDS, as the map-reading
+    form's do.  The bitmap stands for `map > threshold` after NMS only at threshold 0 (or -0): a negative threshold keeps the zeroed non-maxima as
+    well -- they fill up the banded maps, which have fewer maxima than top_k -- and a NaN threshold keeps nothing.  The same maps in calls of 32
+    (the two-phase form, which reads the map) must give the same rows bit for bit, and every image the oracle's under the tie rule."""
+    from concurrent.futures import ThreadPoolExecutor
+    from keypoint_bench_amd.utils.extracter import detection_batch
+    monkeypatch.setenv("KPB_NMS_TILED", "0")            # (64 images are below the batch at which the tail is the default)
+    maps = _large_batch_maps()
+    p = dict(nms_dist=2, threshold=thr, border_dist=8, top_k=top_k, min_score=0.0)
+    x = torch.from_numpy(maps)[:, None].to(_dev())
+    k1, i1, n1 = (t.cpu().numpy() for t in detection_batch(x, p))
+    parts = [[t.cpu().numpy() for t in detection_batch(x[h:h + 32], p)] for h in (0, 32)]
+    k2, i2, n2 = (np.concatenate([q[j] for q in parts]) for j in range(3))
+    with ThreadPoolExecutor(16) as ex:
+        wants = list(ex.map(lambda m: oracle.detection(m, p)[0], maps))
+    np.testing.assert_array_equal(n1, n2, err_msg=repr(p))
+    for b in range(64):
+        what = "image %d %r" % (b, p)
+        assert_kps_equal(k1[b, : n1[b]], wants[b], top_k, what)
+        np.testing.assert_array_equal(k1[b, : n1[b]].view(np.uint32), k2[b, : n2[b]].view(np.uint32), err_msg=what)
+        np.testing.assert_array_equal(i1[b, : n1[b]], i2[b, : n2[b]], err_msg=what)
+    # the cases test what they are meant to: top_k binds on the uniform maps; the banded ones fall short of it, or are filled up with zeros
+    if thr != thr:
+        assert not n1.any()
+    else:
+        assert (n1[0::2] == top_k).all(), n1
+        if thr < 0:
+            assert (n1[1::2] == top_k).all() and all((wants[b][:, 2] == 0).any() for b in range(1, 64, 2)), n1
+        else:
+            assert (n1[1::2] < top_k).all(), n1

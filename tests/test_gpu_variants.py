@@ -31,6 +31,8 @@ GOLDEN_TESTS = [
     "tests/test_gpu_disk.py",
     "tests/test_gpu_lightglue.py::test_lightglue_against_reference_golden",
     "tests/test_gpu_pipeline.py",
+    # bench.py's variant_fp32 figure: the ALIKE configuration at the benchmark's 256 pairs
+    "tests/test_gpu_bench_scale.py::test_bench_configuration_against_the_oracle_at_the_benchmark_batch[alike]",
 ]
 
 
