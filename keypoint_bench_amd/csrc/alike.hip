@@ -1963,12 +1963,11 @@ float max_abs(const float* b, int n)
     return m;
 }
 
-// The conv_mfma_h forms of blocks 3 and 4 (block_h in AlikeNet::forward): C16 / C32 for 16 / 32 input channels, 1T one n-tile per workgroup, P4 block 4's conv1
-// max-pooling x3 4 x 4 while it stages it, LAT the latency forms (CmForm::wpre) for fewer than 16 images
+// The conv_mfma_h forms of blocks 3 and 4 (block_h in AlikeNet::forward): C16 / C32 for 16 / 32 input channels, 1T one n-tile per workgroup, LAT the latency
+// forms (CmForm::wpre) for fewer than 16 images, P4_LAT block 4's conv1 max-pooling x3 4 x 4 while it stages it (fewer than 16 images: see maxpool4_nhwc)
 constexpr CmForm CM_C16{.ks = 3, .s = 1, .cc = 16, .ntb = 1, .mt = 2, .wn = 2}, CM_C32{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
-                 CM_C32_1T{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CM_P4{.ks = 3, .s = 1, .cc = 32, .pool_in = true, .ntb = 1, .mt = 4, .pf = 4, .wn = 2},
-                 CM_C16_LAT{.ks = 3, .s = 1, .cc = 16, .wpre = true}, CM_C32_LAT{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .wpre = true},
-                 CM_P4_LAT{.ks = 3, .s = 1, .cc = 32, .pool_in = true, .ntb = 1, .pf = 4, .wpre = true};
+                 CM_C32_1T{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CM_C16_LAT{.ks = 3, .s = 1, .cc = 16, .wpre = true},
+                 CM_C32_LAT{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .wpre = true}, CM_P4_LAT{.ks = 3, .s = 1, .cc = 32, .pool_in = true, .ntb = 1, .pf = 4, .wpre = true};
 
 template <int CIN, int COUT, int POOL, bool RES, int CDS, int RPOOL, bool DSOUT = false, int TW = 32>
 void launch_conv(kpb_ctx* ctx, const char* name, hipStream_t st, const ConvArgs& a, int B)
@@ -2058,26 +2057,20 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
         // buffer and adds the other half.  Block 4's conv1 max-pools x3 4 x 4 while it stages it.
         auto block_h = [&](const char* n1, const char* n2, const float* in, float* tr, float* xo, int cin, int cout, int Hi, int Wi, bool prepooled) {
             const std::string k1 = std::string(n1) + ".h", k2 = std::string(n2) + ".wp";
-            ConvM m;
-            m.in = in; m.out = tr; m.wp = wp(k1.c_str()); m.bias = wp((std::string(n1) + ".hb").c_str()); m.xf = nullptr; m.active = nullptr; m.res = nullptr;
-            m.Hi = prepooled ? Hi / 4 : Hi; m.Wi = prepooled ? Wi / 4 : Wi; m.H = Hi / 4; m.W = Wi / 4;
-            m.CIN = cin; m.COUT = 2 * cout; m.NCH = 1; m.relu = 2; m.relu_nt = cout / 32;
-            m.nblk = cout / 32; m.istride = cin; m.ostride = 2 * cout; m.ooff = 0;
-            m.unscale = 1.0f / wscale.at(k1);
+            ConvM m{.in = in, .out = tr, .wp = wp(k1.c_str()), .bias = wp((std::string(n1) + ".hb").c_str()), .Hi = prepooled ? Hi / 4 : Hi, .Wi = prepooled ? Wi / 4 : Wi,
+                    .H = Hi / 4, .W = Wi / 4, .CIN = cin, .COUT = 2 * cout, .NCH = 1, .relu = 2, .nblk = cout / 32, .istride = cin, .ostride = 2 * cout,
+                    .unscale = 1.0f / wscale.at(k1), .relu_nt = cout / 32};
             auto launch = [&](const char* n, const CmForm& f, const ConvM& cm) {     // profiled as conv3x3_<n>
-                return launch_conv_mfma_h<CM_C16, CM_C32, CM_C32_1T, CM_P4, CM_C16_LAT, CM_C32_LAT, CM_P4_LAT>(ctx, ("conv3x3_" + std::string(n)).c_str(), f, cm, batch); };
+                return launch_conv_mfma_h<CM_C16, CM_C32, CM_C32_1T, CM_C16_LAT, CM_C32_LAT, CM_P4_LAT>(ctx, ("conv3x3_" + std::string(n)).c_str(), f, cm, batch); };
             // small layers are bound by per-workgroup latency: 8-row tiles (r02: b3c1 0.36 -> 0.32 ms, b3c2 0.58 -> 0.49 ms).  A handful of images (the drop-in
             // path runs ONE): a 15 x 20 map in 16 x 16 tiles with two n-tiles each is 4 workgroups of pure latency (41 us); 8-row tiles with one n-tile each are 16
             // (same weights, same arithmetic per output)
             if (batch < 16 && !prepooled) m.nblk = 2 * cout / 32;
-            const CmForm f1 = !prepooled ? (batch < 16 ? CM_P4_LAT : CM_P4) : batch < 16 ? CM_C16_LAT : cin == 32 ? CM_C32 : CM_C16;
+            const CmForm f1 = !prepooled ? CM_P4_LAT : batch < 16 ? CM_C16_LAT : cin == 32 ? CM_C32 : CM_C16;     // (only a handful of images leave x3 unpooled)
             if (int rc = launch(n1, f1, m)) return rc;
-            ConvM c2;
-            c2.in = tr; c2.out = xo; c2.wp = wp(k2.c_str()); c2.bias = wp((std::string(n2) + ".bp").c_str()); c2.xf = nullptr; c2.active = nullptr;
-            c2.res = tr + cout; c2.rstride = 2 * cout;
-            c2.Hi = Hi / 4; c2.Wi = Wi / 4; c2.H = Hi / 4; c2.W = Wi / 4; c2.CIN = cout; c2.COUT = cout; c2.NCH = cout / 32; c2.relu = 0; c2.nblk = batch < 16 ? cout / 32 : 1;
-            c2.istride = 2 * cout; c2.ostride = cout; c2.ooff = 0;
-            c2.unscale = 1.0f / wscale.at(k2);
+            const ConvM c2{.in = tr, .out = xo, .wp = wp(k2.c_str()), .bias = wp((std::string(n2) + ".bp").c_str()), .res = tr + cout, .Hi = Hi / 4, .Wi = Wi / 4,
+                           .H = Hi / 4, .W = Wi / 4, .CIN = cout, .COUT = cout, .NCH = cout / 32, .nblk = batch < 16 ? cout / 32 : 1, .istride = 2 * cout,
+                           .ostride = cout, .unscale = 1.0f / wscale.at(k2), .rstride = 2 * cout};
             return launch(n2, batch < 16 ? CM_C32_LAT : cout == 32 ? CM_C32_1T : CM_C32, c2);
         };
         if (int rc = block_h("b3c1", "b3c2", p2, t3r3, x3, 16, 32, H / 2, W / 2, true)) return rc;
@@ -2090,10 +2083,8 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
         // strict fp32: block 1 and the 3x3 convolutions on the fp32 vector ALUs, conv2 of blocks 3 / 4 on the fp32 MFMA
         auto conv2 = [&](const char* n, const float* in, float* out, const float* res, int h, int w, int c) {    // identity branch precomputed (ALike.py:72-80)
             const std::string k = n;
-            ConvM m;
-            m.in = in; m.out = out; m.wp = wp((k + ".wp").c_str()); m.bias = wp((k + ".bp").c_str()); m.xf = nullptr; m.active = nullptr; m.res = res;
-            m.Hi = h; m.Wi = w; m.H = h; m.W = w; m.CIN = c; m.COUT = c; m.NCH = c / 32; m.relu = 0; m.nblk = 1;
-            m.istride = c; m.ostride = c; m.ooff = 0;
+            const ConvM m{.in = in, .out = out, .wp = wp((k + ".wp").c_str()), .bias = wp((k + ".bp").c_str()), .res = res, .Hi = h, .Wi = w, .H = h, .W = w,
+                          .CIN = c, .COUT = c, .NCH = c / 32, .nblk = 1, .istride = c, .ostride = c};
             return launch_conv_mfma<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32}>(
                 ctx, ("conv3x3_" + k).c_str(), CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = c / 32}, m, batch);
         };

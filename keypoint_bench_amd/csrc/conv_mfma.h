@@ -15,15 +15,15 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ float relu(float v) { return fmaxf(v, 0.0f); }
 
 struct ConvM {
-    const float* in;    // [B][Hi][Wi][CIN]
-    float* out;         // [B][Ho][Wo][COUT]   (Ho, Wo) = (H, W) or (H/2, W/2) with POOL_OUT
-    const float* wp;    // packed: [ntile][tap][chunk][h][32][KC]
-    const float* bias;  // [COUTP] (zero padded)
-    const float* xf;    // XF: [B][CIN][4] = (scale, shift, prelu slope, -) applied to the input before zero padding
-    const int* active;  // optional [B]: batch items with 0 are skipped (LightGlue pairs that stopped early)
-    const float* res;   // optional [B][H][W][COUT] added before the ReLU (ALIKE ResBlock identity branch, ALike.py:76-79)
-    int Hi, Wi, H, W, CIN, COUT, NCH, relu, nblk;
-    int istride, ostride, ooff;   // floats between consecutive input / output pixels, channel offset of the output
+    const float* in = nullptr;      // [B][Hi][Wi][CIN]
+    float* out = nullptr;           // [B][Ho][Wo][COUT]   (Ho, Wo) = (H, W) or (H/2, W/2) with POOL_OUT
+    const float* wp = nullptr;      // packed: [ntile][tap][chunk][h][32][KC]
+    const float* bias = nullptr;    // [COUTP] (zero padded)
+    const float* xf = nullptr;      // XF: [B][CIN][4] = (scale, shift, prelu slope, -) applied to the input before zero padding
+    const int* active = nullptr;    // optional [B]: batch items with 0 are skipped (LightGlue pairs that stopped early)
+    const float* res = nullptr;     // optional [B][H][W][COUT] added before the ReLU (ALIKE ResBlock identity branch, ALike.py:76-79)
+    int Hi = 0, Wi = 0, H = 0, W = 0, CIN = 0, COUT = 0, NCH = 0, relu = 0, nblk = 0;
+    int istride = 0, ostride = 0, ooff = 0;     // floats between consecutive input / output pixels, channel offset of the output
     float unscale = 1.0f;         // conv_mfma_h / gemm_h: 1 / (the layer's power-of-two weight scale)
     int relu_nt = 0;              // conv_mfma_h with relu == 2: only the first relu_nt 32-wide output tiles get the ReLU
     int rstride = 0;              // floats between consecutive pixels of `res` (0: COUT)

@@ -704,6 +704,8 @@ struct Layer {      // one convolution of a network plan
     std::string name;
     int cin, cout, ks, stride;
     bool mfma;
+    bool relu = true;           // ReLU on the output
+    bool pool_out = false;      // the output max-pooled 2 x 2 (SuperPoint's MaxPool2d after conv1b / 2b / 3b)
     int cc = 32;    // channels per LDS chunk of conv_mfma (32, or 16 for stride 2 / CIN not a multiple of 32)
     int ntb = 2;    // 32-wide output tiles per workgroup
 };
@@ -711,48 +713,53 @@ struct Layer {      // one convolution of a network plan
 struct UpSrc { const float* src; int c; };      // ConvM::up_src, up_c
 struct PreSplit { const unsigned* amax = nullptr; float l1 = 0.0f, bmax = 0.0f; const float* gen_w = nullptr; const float* gen_b = nullptr; };     // ConvM::pre_*, gen_*
 
-int launch_mfma(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, const float* in, float* out, int B, int Hi, int Wi,
-                bool pool_in, bool pool_out, bool relu_, const float* xf = nullptr, int unfold_w = 0, float l2_eps = 0.0f, const float2* unfold_mr = nullptr,
-                const PreSplit* pre = nullptr, const UpSrc* up = nullptr)
+// What one launch_mfma call adds to its layer, by designated initialisers: launch_mfma(..., {.xf = xf, .up = &up})
+struct MfmaOpt {
+    const float* xf = nullptr;          // ConvM::xf: DISK's InstanceNorm + PReLU of the input, applied while it is staged
+    const PreSplit* pre = nullptr;      // SuperPoint conv1b: its input generated from the grey image while the tile is staged
+    const UpSrc* up = nullptr;          // DISK up2 / up3: the upsampled input channels evaluated while the tile is staged
+    int unfold_w = 0;                   // XFeat keypoint_head.0: the 8 x 8 cells of a [B][8 H][unfold_w] image read in place (ConvM::unfold_w),
+    const float2* unfold_mr = nullptr;  // normalised by the per-image (mean, 1 / std) as they are read
+    float l2_eps = 0.0f;                // > 0: F.normalize(eps = l2_eps) of every output row in the epilogue (XFeat block_fusion.2, split-f16 form)
+};
+
+int launch_mfma(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const MfmaOpt& o = {})
 {
     const int S = L.stride, CC = L.cc, PAD = L.ks / 2;
-    const int Hc = pool_in ? Hi / 2 : Hi, Wc = pool_in ? Wi / 2 : Wi;
-    ConvM a;
-    a.in = in; a.out = out; a.wp = net->wp((L.name + ".w").c_str()); a.bias = net->wp((L.name + ".b").c_str()); a.xf = xf; a.res = nullptr;
-    a.active = nullptr; a.istride = L.cin; a.ostride = L.cout; a.ooff = 0;
-    a.Hi = Hi; a.Wi = Wi; a.unfold_w = unfold_w; a.aux0 = reinterpret_cast<const float*>(unfold_mr);
-    if (unfold_w && !(conv_mfma_use_h16() && L.ks == 1 && S == 1 && CC == 32 && !pool_in && !pool_out && !xf && L.cin == 64))
+    ConvM a{.in = in, .out = out, .wp = net->wp((L.name + ".w").c_str()), .bias = net->wp((L.name + ".b").c_str()), .xf = o.xf,
+            .Hi = Hi, .Wi = Wi, .H = (Hi + 2 * PAD - L.ks) / S + 1, .W = (Wi + 2 * PAD - L.ks) / S + 1, .CIN = L.cin, .COUT = L.cout, .NCH = L.cin / CC,
+            .relu = L.relu, .nblk = (L.cout + 32 * L.ntb - 1) / (32 * L.ntb), .istride = L.cin, .ostride = L.cout,
+            .aux0 = reinterpret_cast<const float*>(o.unfold_mr), .unfold_w = o.unfold_w};
+    if (o.unfold_w && !(conv_mfma_use_h16() && L.ks == 1 && S == 1 && CC == 32 && !L.pool_out && !o.xf && L.cin == 64))
         return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: the unfolded input exists for 64-channel 1x1 layers of the split-f16 form only");
-    a.H = (Hc + 2 * PAD - L.ks) / S + 1; a.W = (Wc + 2 * PAD - L.ks) / S + 1;
-    a.CIN = L.cin; a.COUT = L.cout; a.NCH = L.cin / CC; a.relu = relu_ ? 1 : 0; a.nblk = (L.cout + 32 * L.ntb - 1) / (32 * L.ntb);
     hipStream_t st = ctx->stream;
-    const bool x = xf != nullptr;
+    const bool x = o.xf != nullptr;
     if (conv_mfma_use_h16()) {
         a.unscale = 1.0f / (net->wscale.at(L.name + ".w"));
-        if (L.ks == 1 && S == 1 && CC == 32 && !pool_in && !pool_out && !x && !pre) {     // 1x1: gemm_h
+        if (L.ks == 1 && S == 1 && CC == 32 && !L.pool_out && !x && !o.pre) {     // 1x1: gemm_h
             const dim3 grid(cdiv(a.H * a.W, 128), 1, B * a.nblk), block(256);
-            if (l2_eps > 0.0f) {
+            if (o.l2_eps > 0.0f) {
                 if (L.cout != 64 || L.ntb != 2) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: the fused L2 norm needs a 64-channel layer");
-                a.xb = l2_eps;
+                a.xb = o.l2_eps;
                 KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_L2NORM>), grid, block, 0, st, a);
             }
-            else if (unfold_w) KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_PLAIN, true>), grid, block, 0, st, a);
+            else if (o.unfold_w) KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_PLAIN, true>), grid, block, 0, st, a);
             else KPB_LAUNCH(ctx, name, (gemm_h<2, 1>), grid, block, 0, st, a);
             return KPB_OK;
         }
         // split-f16 form: stride-1 layers on 16-row workgroup tiles; with two n-tiles per workgroup the waves form 2 row groups x 2 n-tiles
         // (four M tiles and one n-tile per wave)
-        CmForm f{.ks = L.ks, .s = S, .cc = CC, .pool_in = pool_in, .pool_out = pool_out, .xf = x, .ntb = 1, .mt = 4, .wn = 2};
+        CmForm f{.ks = L.ks, .s = S, .cc = CC, .pool_out = L.pool_out, .xf = x, .ntb = 1, .mt = 4, .wn = 2};
         // one-tile layers (cout <= 32) are bound by per-workgroup latency: 8-row tiles (one M tile per wave, 28 KB of LDS, five
         // workgroups per CU) measured 8-16 % faster; layers with two output tiles lose the fragment reuse that way (+8 % time)
         if (L.ntb == 1) f.mt = f.wn = 1;
         if (S == 2) f.mt = 2;           // stride 2: 8-row tiles
-        if (pre) {      // the input arrives already split (ConvM::pre_amax), generated while the tile is staged from the one-channel image the layer in front reads
+        if (const PreSplit* pre = o.pre) {      // the input arrives already split (ConvM::pre_amax), generated while the tile is staged from the one-channel image the layer in front reads
             if (!pre->gen_w) return kpb_fail(ctx, KPB_E_INVALID, "conv_mfma_h: no generated-input instance for %s", L.name.c_str());
             a.pre_amax = pre->amax; a.pre_l1 = pre->l1; a.pre_bmax = pre->bmax; a.gen_w = pre->gen_w; a.gen_b = pre->gen_b; a.istride = 1;
             f.pre = f.gen = true;
         }
-        if (up) {       // [up(bottom) | horizontal] evaluated while staging (ConvM::up_src); `in` holds the channels behind the upsampled ones
+        if (const UpSrc* up = o.up) {       // [up(bottom) | horizontal] evaluated while staging (ConvM::up_src); `in` holds the channels behind the upsampled ones
             if (up->c % CC || up->c >= L.cin || (Hi % 2) || (Wi % 2)) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: bad upsampled-input split for %s", L.name.c_str());
             a.up_src = up->src; a.up_c = up->c; a.istride = L.cin - up->c;
             f.up = true;
@@ -765,31 +772,31 @@ int launch_mfma(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, co
         }
         return launch_conv_mfma_h<
             CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
-            CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_in = true, .ntb = 1, .mt = 4, .wn = 2},
-            CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .pre = true, .wn = 2, .gen = true}, CmForm{.ks = 3, .s = 2, .cc = 16, .ntb = 1, .mt = 2, .wn = 2},
+            CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .pre = true, .wn = 2, .gen = true},
+            CmForm{.ks = 3, .s = 2, .cc = 16, .ntb = 1, .mt = 2, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .wn = 2},
             CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2, .up = true},
-            CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .xc = true, .wn = 2},
             CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .xc = true, .wn = 2, .up = true}>(ctx, name, f, a, B);
     }
     return launch_conv_mfma<
         CmForm{.ks = 1, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1},
-        CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true}, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_in = true}, CmForm{.ks = 3, .s = 2, .cc = 16},
+        CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true}, CmForm{.ks = 3, .s = 2, .cc = 16},
         CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 5}>(
-        ctx, name, CmForm{.ks = L.ks, .s = S, .cc = CC, .pool_in = pool_in, .pool_out = pool_out, .xf = x, .ntb = L.ntb}, a, B);
+        ctx, name, CmForm{.ks = L.ks, .s = S, .cc = CC, .pool_out = L.pool_out, .xf = x, .ntb = L.ntb}, a, B);
 }
 
-int launch_valu(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, const float* in, float* out, int B, int Hi, int Wi,
-                bool relu_, const float* xf = nullptr, const float* gray = nullptr, const float* skw = nullptr, const float* skb = nullptr, int skn = 0)
+struct ValuSkip { const float* gray = nullptr; const float* w = nullptr; const float* b = nullptr; int n = 0; };     // ConvV::gray, skw, skb, skn
+
+int launch_valu(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const ValuSkip& skip = {})
 {
     ConvV a;
-    a.gray = gray; a.skw = skw; a.skb = skb; a.skn = skn;
-    a.in = in; a.out = out; a.w = net->wp((L.name + ".w").c_str()); a.bias = net->wp((L.name + ".b").c_str()); a.xf = xf;
+    a.gray = skip.gray; a.skw = skip.w; a.skb = skip.b; a.skn = skip.n;
+    a.in = in; a.out = out; a.w = net->wp((L.name + ".w").c_str()); a.bias = net->wp((L.name + ".b").c_str()); a.xf = nullptr;
     a.Hi = Hi; a.Wi = Wi; a.KS = L.ks; a.S = L.stride; a.PAD = L.ks / 2;
     a.H = (Hi + 2 * a.PAD - L.ks) / L.stride + 1; a.W = (Wi + 2 * a.PAD - L.ks) / L.stride + 1;
-    a.CIN = L.cin; a.COUT = L.cout; a.COUT8 = ((L.cout + 7) / 8) * 8; a.relu = relu_ ? 1 : 0;
+    a.CIN = L.cin; a.COUT = L.cout; a.COUT8 = ((L.cout + 7) / 8) * 8; a.relu = L.relu;
     const dim3 grid(cdiv(a.H * a.W, 256), a.COUT8 / 8, B), block(256);
     hipStream_t st = ctx->stream;
-    const bool t3 = L.ks == 3 && !xf;
+    const bool t3 = L.ks == 3;
     if (t3 && L.cin == 1 && L.stride == 1 && L.cout == 4)      // XFeat block1.0: four output channels per thread, one 16-byte store (the 8-wide instance computed four padding channels and stored dword by dword)
         KPB_LAUNCH(ctx, name, (conv_valu_t<3, 1, 1, 4>), dim3(grid.x, 1, grid.z), block, 0, st, a);
     else if (t3 && L.cin == 1 && L.stride == 1) KPB_LAUNCH(ctx, name, (conv_valu_t<3, 1, 1>), grid, block, 0, st, a);
@@ -797,12 +804,12 @@ int launch_valu(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, co
     else if (t3 && L.cin == 8 && L.stride == 1) KPB_LAUNCH(ctx, name, (conv_valu_t<3, 8, 1>), grid, block, 0, st, a);
     else if (t3 && L.cin == 8 && L.stride == 2 && a.COUT8 == 32)
     {
-        if (skn == 24) KPB_LAUNCH(ctx, name, (conv_valu_t<3, 8, 2, 32, 24>), dim3(grid.x, 1, grid.z), block, 0, st, a);      // XFeat block1.3: channels 24..31 are padding
+        if (skip.n == 24) KPB_LAUNCH(ctx, name, (conv_valu_t<3, 8, 2, 32, 24>), dim3(grid.x, 1, grid.z), block, 0, st, a);      // XFeat block1.3: channels 24..31 are padding
         else KPB_LAUNCH(ctx, name, (conv_valu_t<3, 8, 2, 32>), dim3(grid.x, 1, grid.z), block, 0, st, a);
     }
     else if (t3 && L.cin == 8 && L.stride == 2) KPB_LAUNCH(ctx, name, (conv_valu_t<3, 8, 2>), grid, block, 0, st, a);
     else {
-        if (gray) return kpb_fail(ctx, KPB_E_INVALID, "conv_valu: the fused skip connection needs a templated instance");
+        if (skip.gray) return kpb_fail(ctx, KPB_E_INVALID, "conv_valu: the fused skip connection needs a templated instance");
         KPB_LAUNCH(ctx, name, conv_valu, grid, block, 0, st, a);
     }
     return KPB_OK;
@@ -880,17 +887,17 @@ struct SuperPointNet : kpb_net {
             ps.gen_w = wp("conv1a.w"); ps.gen_b = wp("conv1a.b");
         } else
             KPB_LAUNCH(ctx, "sp_conv1a", conv1a_c64, dim3(cdiv(W, 16), cdiv(H, 32), batch), dim3(256), 0, st, gray, x1a, wp("conv1a.w"), wp("conv1a.b"), H, W, 32);   // :44
-        if ((rc = launch_mfma(ctx, "sp_conv1b", this, L["conv1b"], fused ? gray : x1a, x1b, batch, H, W, false, true, true, nullptr, 0, 0.0f, nullptr, fused ? &ps : nullptr))) return rc;      // :45-46 (+pool)
-        if ((rc = launch_mfma(ctx, "sp_conv2a", this, L["conv2a"], x1b, x2a, batch, H / 2, W / 2, false, false, true))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_conv2b", this, L["conv2b"], x2a, x2b, batch, H / 2, W / 2, false, true, true))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_conv3a", this, L["conv3a"], x2b, x3a, batch, H / 4, W / 4, false, false, true))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_conv3b", this, L["conv3b"], x3a, x3b, batch, H / 4, W / 4, false, true, true))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_conv4a", this, L["conv4a"], x3b, x4a, batch, Hc, Wc, false, false, true))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_conv4b", this, L["conv4b"], x4a, x4b, batch, Hc, Wc, false, false, true))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_convPa", this, L["convPa"], x4b, cpa, batch, Hc, Wc, false, false, true))) return rc;    // :56
-        if ((rc = launch_mfma(ctx, "sp_convPb", this, L["convPb"], cpa, semi, batch, Hc, Wc, false, false, false))) return rc;  // :57
-        if ((rc = launch_mfma(ctx, "sp_convDa", this, L["convDa"], x4b, cda, batch, Hc, Wc, false, false, true))) return rc;    // :59
-        if ((rc = launch_mfma(ctx, "sp_convDb", this, L["convDb"], cda, desc_out, batch, Hc, Wc, false, false, false))) return rc; // :60
+        if ((rc = launch_mfma(ctx, "sp_conv1b", this, L.at("conv1b"), fused ? gray : x1a, x1b, batch, H, W, {.pre = fused ? &ps : nullptr}))) return rc;      // :45-46 (+pool)
+        if ((rc = launch_mfma(ctx, "sp_conv2a", this, L.at("conv2a"), x1b, x2a, batch, H / 2, W / 2))) return rc;
+        if ((rc = launch_mfma(ctx, "sp_conv2b", this, L.at("conv2b"), x2a, x2b, batch, H / 2, W / 2))) return rc;
+        if ((rc = launch_mfma(ctx, "sp_conv3a", this, L.at("conv3a"), x2b, x3a, batch, H / 4, W / 4))) return rc;
+        if ((rc = launch_mfma(ctx, "sp_conv3b", this, L.at("conv3b"), x3a, x3b, batch, H / 4, W / 4))) return rc;
+        if ((rc = launch_mfma(ctx, "sp_conv4a", this, L.at("conv4a"), x3b, x4a, batch, Hc, Wc))) return rc;
+        if ((rc = launch_mfma(ctx, "sp_conv4b", this, L.at("conv4b"), x4a, x4b, batch, Hc, Wc))) return rc;
+        if ((rc = launch_mfma(ctx, "sp_convPa", this, L.at("convPa"), x4b, cpa, batch, Hc, Wc))) return rc;    // :56
+        if ((rc = launch_mfma(ctx, "sp_convPb", this, L.at("convPb"), cpa, semi, batch, Hc, Wc))) return rc;  // :57
+        if ((rc = launch_mfma(ctx, "sp_convDa", this, L.at("convDa"), x4b, cda, batch, Hc, Wc))) return rc;    // :59
+        if ((rc = launch_mfma(ctx, "sp_convDb", this, L.at("convDb"), cda, desc_out, batch, Hc, Wc))) return rc; // :60
         KPB_LAUNCH(ctx, "sp_l2norm", l2norm_nhwc, dim3((unsigned)((B * Hc * Wc + 3) / 4)), dim3(256), 0, st, desc_out, 256, B * Hc * Wc, 0.0f);
         KPB_LAUNCH(ctx, "sp_softmax_d2s", softmax65_d2s, dim3(cdiv(Hc * Wc, 4 * PXW), batch), dim3(256), 0, st, semi, score_out, Hc, Wc, Hc * Wc);
         KPB_HIP(ctx, hipGetLastError());
@@ -902,10 +909,11 @@ struct SuperPointNet : kpb_net {
 
 int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
+    // name, cin, cout, ks, stride, mfma, relu, pool_out: conv1b, conv2b and conv3b are max-pooled 2 x 2; convPb and convDb have no ReLU
     const Layer plan[] = {
-        {"conv1a", 1, 64, 3, 1, false}, {"conv1b", 64, 64, 3, 1, true}, {"conv2a", 64, 64, 3, 1, true}, {"conv2b", 64, 64, 3, 1, true},
-        {"conv3a", 64, 128, 3, 1, true}, {"conv3b", 128, 128, 3, 1, true}, {"conv4a", 128, 128, 3, 1, true}, {"conv4b", 128, 128, 3, 1, true},
-        {"convPa", 128, 256, 3, 1, true}, {"convPb", 256, 65, 1, 1, true}, {"convDa", 128, 256, 3, 1, true}, {"convDb", 256, 256, 1, 1, true}};
+        {"conv1a", 1, 64, 3, 1, false}, {"conv1b", 64, 64, 3, 1, true, true, true}, {"conv2a", 64, 64, 3, 1, true}, {"conv2b", 64, 64, 3, 1, true, true, true},
+        {"conv3a", 64, 128, 3, 1, true}, {"conv3b", 128, 128, 3, 1, true, true, true}, {"conv4a", 128, 128, 3, 1, true}, {"conv4b", 128, 128, 3, 1, true},
+        {"convPa", 128, 256, 3, 1, true}, {"convPb", 256, 65, 1, 1, true, false}, {"convDa", 128, 256, 3, 1, true}, {"convDb", 256, 256, 1, 1, true, false}};
     SuperPointNet* net = new SuperPointNet();
     net->ctx = ctx; net->arch = KPB_ARCH_SUPERPOINT; net->dim = 256; net->desc_div = 8;
     WeightStage ws;
@@ -917,7 +925,7 @@ int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SuperPoint tensor %s.weight/.bias missing or mis-shaped", L.name.c_str());
         }
         stage_layer(ws, L, w, b);
-        net->L[L.name] = L;
+        net->L.emplace(L.name, L);
         if (L.name == "conv1a") {       // |conv1a output| <= amax(gray) l1 + bmax (its channels' largest L1 norm, its largest |bias|)
             float l1 = 0.0f, bmax = 0.0f;
             for (int co = 0; co < L.cout; ++co) {
@@ -951,13 +959,12 @@ const XFeatPlan XF[] = {
 
 struct XFeatNet : kpb_net {
     std::map<std::string, Layer> L;
-    std::map<std::string, bool> relu_of;
     int conv(const char* n, const float* in, float* out, int batch, int Hi, int Wi)
     {
         const Layer& l = L.at(n);
         const std::string tag = std::string("xf_") + n;
-        if (l.mfma) return launch_mfma(ctx, tag.c_str(), this, l, in, out, batch, Hi, Wi, false, false, relu_of.at(n));
-        return launch_valu(ctx, tag.c_str(), this, l, in, out, batch, Hi, Wi, relu_of.at(n));
+        if (l.mfma) return launch_mfma(ctx, tag.c_str(), this, l, in, out, batch, Hi, Wi);
+        return launch_valu(ctx, tag.c_str(), this, l, in, out, batch, Hi, Wi);
     }
     int forward(const float* img, int batch, int H_, int W_, float* score_out, float* desc_out) override
     {
@@ -997,7 +1004,7 @@ struct XFeatNet : kpb_net {
         {   // block1.0 + block1.1 fused: the 4-channel full-resolution map never reaches HBM (r04)
             const Layer &l0 = L.at("block1.0"), &l1 = L.at("block1.1");
             if (l0.mfma || l1.mfma || l0.cin != 1 || l0.cout != 4 || l0.ks != 3 || l0.stride != 1 || l1.cin != 4 || l1.cout != 8 || l1.ks != 3 || l1.stride != 2 ||
-                !relu_of.at("block1.0") || !relu_of.at("block1.1"))
+                !l0.relu || !l1.relu)
                 return kpb_fail(ctx, KPB_E_INVALID, "XFeat block1.0 / block1.1: unexpected layer plan");
             KPB_LAUNCH(ctx, "xf_block1.01", xfeat_block1_01, dim3(cdiv(W2, XB_TW), cdiv(H2, XB_TH), batch), dim3(256), 0, st, gray, b1,
                        wp("block1.0.w"), wp("block1.0.b"), wp("block1.1.w"), wp("block1.1.b"), H, W, mr);
@@ -1017,7 +1024,7 @@ struct XFeatNet : kpb_net {
             const Layer& l = L.at("block1.3");
             if (l.mfma || l.ks != 3 || l.cin != 8 || l.stride != 2 || ((l.cout + 7) / 8) * 8 != 32)
                 return kpb_fail(ctx, KPB_E_INVALID, "XFeat block1.3: unexpected layer plan");
-            if ((rc = launch_valu(ctx, "xf_block1.3", this, l, c1, x1, batch, H2, W2, relu_of.at("block1.3"), nullptr, gray, wp("skip1.w"), wp("skip1.b"), 24))) return rc;
+            if ((rc = launch_valu(ctx, "xf_block1.3", this, l, c1, x1, batch, H2, W2, {.gray = gray, .w = wp("skip1.w"), .b = wp("skip1.b"), .n = 24}))) return rc;
         }
         }
         if ((rc = conv("block2.0", x1, t2, batch, H4, W4))) return rc;
@@ -1038,7 +1045,7 @@ struct XFeatNet : kpb_net {
         if ((rc = conv("block_fusion.0", u8[3], u8[4], batch, H8, W8))) return rc;
         if ((rc = conv("block_fusion.1", u8[4], u8[5], batch, H8, W8))) return rc;
         if (conv_mfma_use_h16() && L.at("block_fusion.2").mfma) {     // F.normalize in the product's epilogue (a wave holds whole 64-channel rows)
-            if ((rc = launch_mfma(ctx, "xf_block_fusion.2", this, L.at("block_fusion.2"), u8[5], desc_out, batch, H8, W8, false, false, relu_of.at("block_fusion.2"), nullptr, 0, 1e-12f))) return rc;
+            if ((rc = launch_mfma(ctx, "xf_block_fusion.2", this, L.at("block_fusion.2"), u8[5], desc_out, batch, H8, W8, {.l2_eps = 1e-12f}))) return rc;
         } else {
         if ((rc = conv("block_fusion.2", u8[5], desc_out, batch, H8, W8))) return rc;
         KPB_LAUNCH(ctx, "xf_l2norm", l2norm_nhwc, dim3((unsigned)((B * H8 * W8 + 4 * PXW - 1) / (4 * PXW))), dim3(256), 0, st, desc_out, 64, B * H8 * W8, 1e-12f);   // F.normalize
@@ -1047,7 +1054,7 @@ struct XFeatNet : kpb_net {
         if (conv_mfma_use_h16() && L.at("keypoint_head.0").mfma && W % 8 == 0) {
             // the first layer reads the 8 x 8 cells straight from the normalised image (ConvM::unfold_w): as a kernel of its own the
             // unfolding wrote and re-read 0.63 GB per 512 images (xf_unfold8, 0.24 ms)
-            if ((rc = launch_mfma(ctx, "xf_keypoint_head.0", this, L.at("keypoint_head.0"), gray, u8[1], batch, H8, W8, false, false, relu_of.at("keypoint_head.0"), nullptr, W, 0.0f, mr))) return rc;
+            if ((rc = launch_mfma(ctx, "xf_keypoint_head.0", this, L.at("keypoint_head.0"), gray, u8[1], batch, H8, W8, {.unfold_w = W, .unfold_mr = mr}))) return rc;
         } else {
             KPB_LAUNCH(ctx, "xf_unfold8", unfold8, dim3(cdiv(H8 * W8 * 16, 256), batch), dim3(256), 0, st, gray, u8[0], H, W);
             if ((rc = conv("keypoint_head.0", u8[0], u8[1], batch, H8, W8))) return rc;
@@ -1085,19 +1092,18 @@ int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
                 for (int t = 0; t < T; ++t) wpad[((size_t)o * cin + c) * T + t] = w[((size_t)o * q.cin + c) * T + t];
         }
         w = wpad.data(); b = bpad.data();
-        Layer L{q.name, cin, cout, q.ks, q.stride, (cin % 32 == 0)};
+        Layer L{q.name, cin, cout, q.ks, q.stride, (cin % 32 == 0), q.relu};
         L.cc = q.stride == 2 ? 16 : 32;
         if (cout <= 32 && q.ks == 3 && q.stride == 1) L.ntb = 1;      // block2: one 32-wide output tile, not a half-empty pair
         stage_layer(ws, L, w, b);
-        net->L[L.name] = L;
-        net->relu_of[L.name] = q.relu;
+        net->L.emplace(L.name, L);
     }
     if (conv_mfma_use_h16()) {      // the fused matrix form of block1.2 + block1.3 (xfeat_block1_23)
         const float* wA = bl.get("block1.2.w", {8, 8, 3, 3});
         const float* bA = bl.get("block1.2.b", {8});
         const float* wB = bl.get("block1.3.w", {24, 8, 3, 3});
         const float* bB = bl.get("block1.3.b", {24});
-        if (!wA || !bA || !wB || !bB || !net->relu_of.at("block1.2") || !net->relu_of.at("block1.3")) {
+        if (!wA || !bA || !wB || !bB || !net->L.at("block1.2").relu || !net->L.at("block1.3").relu) {
             delete net;
             return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat block1.2 / block1.3: unexpected layer plan");
         }
@@ -1408,41 +1414,41 @@ struct DiskNet : kpb_net {
         if ((rc = launch_valu_planar(img, f1, batch, H, W))) return rc;
         pool(f1, p1, H, W, 16);
         if ((rc = stats_xf(p1, P / 4, 16, "down1.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_down1", this, L["down1"], p1, f2, batch, H / 2, W / 2, false, false, false, xf))) return rc;
+        if ((rc = launch_mfma(ctx, "disk_down1", this, L.at("down1"), p1, f2, batch, H / 2, W / 2, {.xf = xf}))) return rc;
         pool(f2, p2, H / 2, W / 2, 32);
         if ((rc = stats_xf(p2, P / 16, 32, "down2.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_down2", this, L["down2"], p2, f3, batch, H / 4, W / 4, false, false, false, xf))) return rc;
+        if ((rc = launch_mfma(ctx, "disk_down2", this, L.at("down2"), p2, f3, batch, H / 4, W / 4, {.xf = xf}))) return rc;
         pool(f3, p3, H / 4, W / 4, 64);
         if ((rc = stats_xf(p3, P / 64, 64, "down3.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_down3", this, L["down3"], p3, f4, batch, H / 8, W / 8, false, false, false, xf))) return rc;
+        if ((rc = launch_mfma(ctx, "disk_down3", this, L.at("down3"), p3, f4, batch, H / 8, W / 8, {.xf = xf}))) return rc;
         pool(f4, p4, H / 8, W / 8, 64);
         if ((rc = stats_xf(p4, P / 256, 64, "down4.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_down4", this, L["down4"], p4, f5, batch, H / 16, W / 16, false, false, false, xf))) return rc;
+        if ((rc = launch_mfma(ctx, "disk_down4", this, L.at("down4"), p4, f5, batch, H / 16, W / 16, {.xf = xf}))) return rc;
         // up path (disk.py:114-141, 284-288)
         upcat(f5, f4, c0, H / 16, W / 16, 64, 64);
         if ((rc = stats_xf(c0, P / 64, 128, "up0.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_up0", this, L["up0"], c0, u0, batch, H / 8, W / 8, false, false, false, xf))) return rc;
+        if ((rc = launch_mfma(ctx, "disk_up0", this, L.at("up0"), c0, u0, batch, H / 8, W / 8, {.xf = xf}))) return rc;
         upcat(u0, f3, c1, H / 8, W / 8, 64, 64);
         if ((rc = stats_xf(c1, P / 16, 128, "up1.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_up1", this, L["up1"], c1, u1, batch, H / 4, W / 4, false, false, false, xf))) return rc;
+        if ((rc = launch_mfma(ctx, "disk_up1", this, L.at("up1"), c1, u1, batch, H / 4, W / 4, {.xf = xf}))) return rc;
         const bool fuse_up = conv_mfma_use_h16();        // r06: the concatenated decoder inputs of up_2 and up_3 are not written (profiles/r06_disk_fused_upsample_ab.txt)
         if (fuse_up) {
             if ((rc = stats_xf_up(u1, f2, H / 4, W / 4, 64, 32, "up2.slope", sums, mm, xf, batch))) return rc;
             const UpSrc up{u1, 64};
-            if ((rc = launch_mfma(ctx, "disk_up2", this, L["up2"], f2, u2, batch, H / 2, W / 2, false, false, false, xf, 0, 0.0f, nullptr, nullptr, &up))) return rc;
+            if ((rc = launch_mfma(ctx, "disk_up2", this, L.at("up2"), f2, u2, batch, H / 2, W / 2, {.xf = xf, .up = &up}))) return rc;
         } else {
             upcat(u1, f2, c2, H / 4, W / 4, 64, 32);
             if ((rc = stats_xf(c2, P / 4, 96, "up2.slope", sums, xf, batch))) return rc;
-            if ((rc = launch_mfma(ctx, "disk_up2", this, L["up2"], c2, u2, batch, H / 2, W / 2, false, false, false, xf))) return rc;
+            if ((rc = launch_mfma(ctx, "disk_up2", this, L.at("up2"), c2, u2, batch, H / 2, W / 2, {.xf = xf}))) return rc;
         }
         if (fuse_up) {      // r06: [up(u2) | f1] is not written -- up_3 evaluates the upsampling while it stages, the statistics come from u2 and f1
             if ((rc = stats_xf_up(u2, f1, H / 2, W / 2, 64, 16, "up3.slope", sums, mm, xf, batch))) return rc;
             const UpSrc up{u2, 64};
-            if ((rc = launch_mfma(ctx, "disk_up3", this, L["up3"], f1, lg, batch, H, W, false, false, false, xf, 0, 0.0f, nullptr, nullptr, &up))) return rc;
+            if ((rc = launch_mfma(ctx, "disk_up3", this, L.at("up3"), f1, lg, batch, H, W, {.xf = xf, .up = &up}))) return rc;
         } else {
             upcat(u2, f1, c3, H / 2, W / 2, 64, 16);
             if ((rc = stats_xf(c3, P, 80, "up3.slope", sums, xf, batch))) return rc;
-            if ((rc = launch_mfma(ctx, "disk_up3", this, L["up3"], c3, lg, batch, H, W, false, false, false, xf))) return rc;
+            if ((rc = launch_mfma(ctx, "disk_up3", this, L.at("up3"), c3, lg, batch, H, W, {.xf = xf}))) return rc;
         }
         KPB_LAUNCH(ctx, "disk_head", disk_head, dim3((unsigned)((B * P + 15) / 16)), dim3(256), 0, st, lg, desc_out, score_out, B * P);
         KPB_HIP(ctx, hipGetLastError());
@@ -1505,7 +1511,7 @@ int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     struct { const char* n; int cin, cout; } plan[] = {{"down1", 16, 32}, {"down2", 32, 64}, {"down3", 64, 64}, {"down4", 64, 64},
                                                        {"up0", 128, 64}, {"up1", 128, 64}, {"up2", 96, 64}};
     for (auto& q : plan) {
-        Layer L{q.n, q.cin, q.cout, 5, 1, true};
+        Layer L{q.n, q.cin, q.cout, 5, 1, true, false};
         L.cc = (q.cin % 32 == 0) ? 32 : 16;
         const float* w = bl.get((L.name + ".w").c_str(), {(uint32_t)q.cout, (uint32_t)q.cin, 5, 5});
         const float* b = bl.get((L.name + ".b").c_str(), {(uint32_t)q.cout});
@@ -1513,17 +1519,17 @@ int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         if (!w || !b || !sl) return fail(q.n);
         stage_layer(ws, L, w, b);
         ws.put_raw(L.name + ".slope", sl, q.cin);
-        net->L[L.name] = L;
+        net->L.emplace(L.name, L);
     }
     {   // up_3: 80 -> 129 = 128 descriptor channels + the score logit, five 32-wide tiles in one workgroup
         const float* w = bl.get("up3.w", {129, 80, 5, 5});
         const float* b = bl.get("up3.b", {129});
         const float* sl = bl.get("up3.slope", {80});
         if (!w || !b || !sl) return fail("up3");
-        Layer L3{"up3", 80, 129, 5, 1, true}; L3.cc = 16; L3.ntb = 5;
+        Layer L3{"up3", 80, 129, 5, 1, true, false}; L3.cc = 16; L3.ntb = 5;
         stage_layer(ws, L3, w, b);
         ws.put_raw("up3.slope", sl, 80);
-        net->L["up3"] = L3;
+        net->L.emplace("up3", L3);
     }
     if (int rc = ws.upload(net)) { delete net; return rc; }
     *out = net;

@@ -881,11 +881,8 @@ struct LgEpi {
 int lg_linear(kpb_ctx* ctx, kpb_lg* lg, const char* tag, const std::string& name, int cin, int cout, const float* in, int istride,
               float* out, int ostride, int ooff, int S, int MP, const int* active, const int* cnt, const LgEpi& x = LgEpi())
 {
-    ConvM a;
-    a.in = in; a.out = out; a.wp = lg->wp(name + ".w"); a.bias = lg->wp(name + ".b"); a.xf = nullptr; a.res = nullptr; a.active = active;
-    a.Hi = MP / 16; a.Wi = 16; a.H = MP / 16; a.W = 16;
-    a.CIN = cin; a.COUT = cout; a.NCH = cin / 32; a.relu = 0; a.nblk = (cout + 63) / 64;
-    a.istride = istride; a.ostride = ostride; a.ooff = ooff;
+    ConvM a{.in = in, .out = out, .wp = lg->wp(name + ".w"), .bias = lg->wp(name + ".b"), .active = active, .Hi = MP / 16, .Wi = 16, .H = MP / 16, .W = 16,
+            .CIN = cin, .COUT = cout, .NCH = cin / 32, .nblk = (cout + 63) / 64, .istride = istride, .ostride = ostride, .ooff = ooff};
     if (conv_mfma_use_h16()) {
         a.unscale = 1.0f / (lg->wscale.at(name + ".w"));
         a.rowcnt = cnt; a.res = x.res; a.rstride = x.rstride; a.aux0 = x.cosb; a.aux1 = x.sinb; a.out1 = x.out1; a.out2 = x.out2;
