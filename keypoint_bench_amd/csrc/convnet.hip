@@ -1377,6 +1377,9 @@ struct DiskNet : kpb_net {
     int forward(const float* img, int batch, int H_, int W_, float* score_out, float* desc_out) override
     {
         if ((H_ % 16) || (W_ % 16)) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: DISK needs H and W multiples of 16 (got %dx%d)", H_, W_);
+        // a 16 x 16 image leaves down_4 a single pixel to normalise: the reference's InstanceNorm2d raises there ("Expected more than 1 spatial element"), so there
+        // is no value to compute -- refused before anything is launched (16 x 32 and 32 x 16, a two-pixel bottleneck, are the smallest images DISK runs)
+        if (H_ == 16 && W_ == 16) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: DISK cannot run a 16x16 image: its 1x1 bottleneck has no instance statistics (the reference's InstanceNorm2d raises on one spatial element)");
         if (!desc_out) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: DISK writes its 128 x H x W descriptor map; desc_out_dev is required");
         const int H = H_, W = W_;
         const size_t P = (size_t)H * W, B = batch;

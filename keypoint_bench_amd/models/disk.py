@@ -1,6 +1,7 @@
 """Drop-in for the reference's models/disk.py: ``DISK()`` with ``load_state_dict`` / ``eval`` /
 ``__call__(image) -> (score_map [B,1,H,W], desc_map [B,128,H,W])`` (disk.py:309-313), computed by
-csrc/convnet.hip through libkpb.so.  The descriptor map is stored channels-last."""
+csrc/convnet.hip through libkpb.so.  The descriptor map is stored channels-last.  H and W are multiples of
+16; 16 x 16 is refused, as the reference's InstanceNorm2d refuses its 1 x 1 bottleneck."""
 from .. import weights as _weights
 from ._base import HipNet
 

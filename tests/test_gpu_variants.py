@@ -33,6 +33,8 @@ GOLDEN_TESTS = [
     "tests/test_gpu_pipeline.py",
     # bench.py's variant_fp32 figure: the ALIKE configuration at the benchmark's 256 pairs
     "tests/test_gpu_bench_scale.py::test_bench_configuration_against_the_oracle_at_the_benchmark_batch[alike]",
+    # the strict-fp32 conv_mfma / conv_valu / materialised-upsampling forms at every accepted shape class and batch, and the refusals
+    "tests/test_gpu_net_shapes.py",
 ]
 
 
