@@ -54,6 +54,7 @@ struct ConvM {
     const float* up_src = nullptr; int up_c = 0;
     int unfold_w = 0;             // gemm_h<.., UNFOLD>: `in` is a single-channel [B][8 H][unfold_w] image and row r, channel c stand for pixel
                                   // (8 (r / W) + c / 8, 8 (r % W) + c % 8): XFeat's _unfold2d(x, 8) read in place (XFeat.py:96-103, 138)
+    int tap_dil = 0;              // gemm_h<.., TAPK>: the dilation of the gathered taps (see there)
 };
 
 // gemm_h epilogues.  GE_RESIDUAL: out = res + (W x + b), rows of `res` rstride floats apart (lightglue.py:185 / 242, x + ffn(...)).
@@ -93,20 +94,27 @@ struct CmForm {
     // HALF-resolution source: its (IH / 2 + 2)^2 pixels land raw in 9 KB of LDS and every staged float4 is the four-tap mix of that -- the direct form (four
     // global taps per staged float4, r05) spilled 95 registers and lost 3 ms.  The staging has the room: a slab's taps are 750 MFMAs per wave.
     bool up = false;
+    // dilation: tap (ky, kx) reads input pixel (y s + ky dil - pad, x s + kx dil - pad), pad = (ks - 1) dil / 2 -- torch's Conv2d(dilation = dil, padding = pad), output
+    // = input extent at stride 1 for odd AND even ks (an even kernel's two taps sit at -dil / 2 and +dil / 2: R2D2's 2 x 2 layers).  The halo of the input tile grows
+    // to (ks - 1) dil pixels: a 16 x 16 output tile of a 3 x 3 layer stages 20 x 20 pixels at dil = 2 (61 KB with the row padding) -- two workgroups per CU, see waves().
+    int dil = 1;
     constexpr bool operator==(const CmForm&) const = default;
     constexpr int tile_h() const { return 8 * mt / wn; }       // output rows of a workgroup tile
     // conv_mfma_h: waves per SIMD the register allocation is held to: what r02's code reached without being told (accumulators 16 mt ntb) -- left alone, the
     // allocator keeps a second copy of the accumulators in VGPRs for the rare rescale (+64 registers, a wave per SIMD lost on every two-tile layer)
-    constexpr int waves() const { return wpre ? 1 : mt * ntb >= 4 ? ((ks == 5 && cc == 32) || pool_in ? 2 : 3) : (mt * ntb == 2 ? (ks == 3 && cc == 16 ? 3 : 4) : 5); }
+    constexpr int waves() const { return wpre ? 1 : dil > 1 ? 2 /* the dilated tiles are 56-61 KB of LDS: two workgroups per CU is all that fits */ : mt * ntb >= 4 ? ((ks == 5 && cc == 32) || pool_in ? 2 : 3) : (mt * ntb == 2 ? (ks == 3 && cc == 16 ? 3 : 4) : 5); }
 };
 
 template <CmForm F>
 __global__ __launch_bounds__(256) void conv_mfma(ConvM a)
 {
     constexpr int KS = F.ks, S = F.s, CC = F.cc, NTB = F.ntb; constexpr bool POOL_IN = F.pool_in, POOL_OUT = F.pool_out, XF = F.xf;
-    static_assert(F == CmForm{KS, S, CC, POOL_IN, POOL_OUT, XF, NTB}, "conv_mfma: the strict-fp32 kernel has no mt, xc, pf, wpre, pre, wn, gen or up");
-    constexpr int KC = CC / 2, PITCH = CC + 4, T = KS * KS, PAD = KS / 2;
-    constexpr int IH = 7 * S + KS, IW = 15 * S + KS, Q = CC / 4;
+    constexpr int DIL = F.dil;
+    static_assert(F == CmForm{.ks = KS, .s = S, .cc = CC, .pool_in = POOL_IN, .pool_out = POOL_OUT, .xf = XF, .ntb = NTB, .dil = DIL},
+                  "conv_mfma: the strict-fp32 kernel has no mt, xc, pf, wpre, pre, wn, gen or up");
+    constexpr int KC = CC / 2, PITCH = CC + 4, T = KS * KS, PAD = (KS - 1) * DIL / 2;
+    constexpr int IH = 7 * S + (KS - 1) * DIL + 1, IW = 15 * S + (KS - 1) * DIL + 1, Q = CC / 4;
+    static_assert(IH * IW * PITCH * 4 <= 65536, "conv_mfma: input tile exceeds the static LDS window");
     constexpr int NLD = (IH * IW * Q + 255) / 256;
     __shared__ __attribute__((aligned(16))) float tile[IH * IW * PITCH];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, p = lane & 31, h = lane >> 5;
@@ -168,7 +176,7 @@ __global__ __launch_bounds__(256) void conv_mfma(ConvM a)
 #pragma unroll 1
         for (int tap = 0; tap < T; ++tap) {
             const int ky = tap / KS, kx = tap - ky * KS;
-            const float* ap = &tile[((orow * S + ky) * IW + ocol * S + kx) * PITCH + h * KC];
+            const float* ap = &tile[((orow * S + ky * DIL) * IW + ocol * S + kx * DIL) * PITCH + h * KC];
             const float* bp = a.wp + ((((size_t)nt0 * T + tap) * a.NCH + ch) * 2 + h) * 32 * KC + p * KC;
             float A[KC], Bw[NTB][KC];
 #pragma unroll
@@ -350,14 +358,15 @@ __device__ __forceinline__ float4 cm_up2_mix(const float4 p00, const float4 p01,
 template <CmForm F>
 __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
 {
-    constexpr int KS = F.ks, S = F.s, CC = F.cc, NTB = F.ntb, MT = F.mt, PF = F.pf, WN = F.wn;
+    constexpr int KS = F.ks, S = F.s, CC = F.cc, NTB = F.ntb, MT = F.mt, PF = F.pf, WN = F.wn, DIL = F.dil;
     constexpr bool POOL_IN = F.pool_in, POOL_OUT = F.pool_out, XF = F.xf, XC = F.xc, WPRE = F.wpre, PRE = F.pre, GEN = F.gen, UP = F.up;
+    static_assert(DIL == 1 || (DIL >= 2 && S == 1 && !WPRE && !PRE && !UP && !XC && !POOL_IN && MT >= 2 && NTB == 1), "conv_mfma_h: the dilated form exists for plain stride-1 layers (R2D2)");
     static_assert(!UP || (S == 1 && !POOL_IN && !PRE && !WPRE && (((F.tile_h() - 1) * S + KS) % 2 == 0) && ((15 * S + KS) % 2 == 0) && KS / 2 % 2 == 0),
                   "conv_mfma_h<UP>: stride-1 layers whose input tile starts on an even row and column");
     static_assert(WN == 1 || (WN == 2 && MT % 2 == 0 && !WPRE), "conv_mfma_h: waves split the n-tiles two ways at most");
     static_assert(PRE == GEN && (!GEN || KS == 3), "conv_mfma_h: the pre-split tile exists as the generated one (a 3 x 3 one-channel layer computed while staging); r05's DMA-landed form was measured, superseded and removed in r06");
     static_assert(!PRE || (CC == 32 && S == 1 && !POOL_IN && !XF && !XC && !WPRE), "conv_mfma_h: the pre-split input form exists for plain stride-1 32-channel slabs");
-    constexpr int KC = CC / 2, NKB = CC / 16, T = KS * KS, PAD = KS / 2, TH = F.tile_h();
+    constexpr int KC = CC / 2, NKB = CC / 16, T = KS * KS, PAD = (KS - 1) * DIL / 2, TH = F.tile_h();
     // r06: a tap's weight fragments (L2 round trips: NTB NKB 2 loads of 16 bytes per lane) are requested ONE TAP AHEAD and the order is pinned with a scheduling
     // barrier -- left alone the scheduler puts every request next to its first use, the round trip exposed nine (25) times per slab.  The 3 x 3 forms unroll their
     // tap loop (the two fragment sets are then plain registers: ALIKE's b3c2 0.444 -> 0.372 ms per 512 images, SuperPoint's conv2a .. conv4b -4 .. 5 %, no spills);
@@ -366,7 +375,7 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
     // own order.  (r02 lost 12 % with "weights a tap ahead" written in the source alone: the scheduler undid it.  profiles/r06_weights_a_tap_ahead_ab.txt)
     constexpr int TAPU = (KS == 3 && !WPRE && !PRE) ? 9 : 1;
     constexpr bool ROW_AHEAD = TAPU == 1 && !WPRE && !PRE;
-    constexpr int IH = (TH - 1) * S + KS, IW = 15 * S + KS, Q = CC / 4;
+    constexpr int IH = (TH - 1) * S + (KS - 1) * DIL + 1, IW = 15 * S + (KS - 1) * DIL + 1, Q = CC / 4;
     constexpr int PITCH = 4 * CC + 16, LO = 2 * CC;                 // bytes per pixel, offset of its lo halves
     constexpr int ROWP = (IW * PITCH + 255) / 256 * 256;            // bytes per tile row
     constexpr int NLD = (IH * IW * Q + 255) / 256;
@@ -709,7 +718,7 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
                         Al[m][kb] = __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap + 16 * ((4 + 2 * h + kb) ^ key)));
                     }
                 } else {
-                const unsigned char* ap = &tile[(orow * S + ky) * ROWP + (ocol * S + kx) * PITCH + h * KC * 2];
+                const unsigned char* ap = &tile[(orow * S + ky * DIL) * ROWP + (ocol * S + kx * DIL) * PITCH + h * KC * 2];
 #pragma unroll
                 for (int kb = 0; kb < NKB; ++kb) {
                     Ah[m][kb] = __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap + 16 * kb));
@@ -724,7 +733,7 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
                 // DISK +1.1 %, SuperPoint +0.8 % (profiles/r06_weights_a_tap_ahead_ab.txt, 6.).  (Not the extra-channel form without the fused upsampling: 4 registers spilled.)
                 auto apiece = [&](int m, int kb, bool lo) {
                     const int orow = 2 * (wm * MT + m) + (p >> 4);
-                    const unsigned char* ap = &tile[(orow * S + ky) * ROWP + (ocol * S + kx) * PITCH + h * KC * 2];
+                    const unsigned char* ap = &tile[(orow * S + ky * DIL) * ROWP + (ocol * S + kx * DIL) * PITCH + h * KC * 2];
                     return __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap + (lo ? LO : 0) + 16 * kb));
                 };
 #pragma unroll
@@ -850,8 +859,8 @@ int cm_launch(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, in
         else KPB_LAUNCH(ctx, tag, conv_mfma<FS>, grid, dim3(256), 0, ctx->stream, a);
         return true;
     }()) || ...);
-    return found ? KPB_OK : kpb_fail(ctx, KPB_E_INVALID, "%s: no instance for %s: ks=%d s=%d cc=%d pool_in=%d pool_out=%d xf=%d ntb=%d mt=%d xc=%d pf=%d wpre=%d pre=%d wn=%d gen=%d up=%d",
-        H ? "conv_mfma_h" : "conv_mfma", tag, f.ks, f.s, f.cc, f.pool_in, f.pool_out, f.xf, f.ntb, f.mt, f.xc, f.pf, f.wpre, f.pre, f.wn, f.gen, f.up);
+    return found ? KPB_OK : kpb_fail(ctx, KPB_E_INVALID, "%s: no instance for %s: ks=%d s=%d cc=%d pool_in=%d pool_out=%d xf=%d ntb=%d mt=%d xc=%d pf=%d wpre=%d pre=%d wn=%d gen=%d up=%d dil=%d",
+        H ? "conv_mfma_h" : "conv_mfma", tag, f.ks, f.s, f.cc, f.pool_in, f.pool_out, f.xf, f.ntb, f.mt, f.xc, f.pf, f.wpre, f.pre, f.wn, f.gen, f.up, f.dil);
 }
 template <CmForm... FS> int launch_conv_mfma_h(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B) { return cm_launch<true, FS...>(ctx, tag, f, a, B); }
 template <CmForm... FS> int launch_conv_mfma(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B) { return cm_launch<false, FS...>(ctx, tag, f, a, B); }
@@ -863,7 +872,11 @@ template <CmForm... FS> int launch_conv_mfma(kpb_ctx* ctx, const char* tag, cons
 // of slab c) and go into the OTHER of two LDS buffers behind them, so there is one barrier per slab and the loads fly
 // under the matrix work.  Workgroup = 256 rows x 32 NTB columns; wave = 64 rows (two M tiles); weights in pack_mfma_h's
 // KS = 1 order; LDS rows as in conv_mfma_h (hi | lo | pad, 144 bytes: nine 16-byte slots, conflict-free).
-template <int NTB, int MT = 2, int EPI = GE_PLAIN, bool UNFOLD = false>
+// TAPK > 0 (R2D2's dilated layers): a TAPK x TAPK convolution of dilation ConvM::tap_dil as a TAP-GATHERED product, K = TAPK^2 taps x CIN.  Slab s = tap NCHI + c
+// (NCHI = CIN / 32; ConvM::NCH = TAPK^2 NCHI, pack_mfma_h's tap-major order as it stands) is the 1 x 1 row staging read at the pixel offset of its tap,
+// (ky, kx) tap_dil - (TAPK - 1) tap_dil / 2; a row whose tap falls outside the image is staged as zeros, like a row past rowcnt.  Nothing but the wave's own rows is
+// ever in LDS -- a halo tile of the 2 x 2, dilation-16 layer would be 32 x 32 x 144 B = 147 KB per slab -- and the operand scale is measured per wave and slab as in the 1 x 1 form.
+template <int NTB, int MT = 2, int EPI = GE_PLAIN, bool UNFOLD = false, int TAPK = 0>
 // (at four waves per SIMD the one-tile GE_RESIDUAL / GE_ROTARY forms spill 2 / 11 registers to scratch -- their epilogue operands
 // xv sit beside the accumulators in the last slab.  r05 measured the alternative it named, three waves per SIMD for those two (132 / 144
 // registers, no scratch): ffn3 + residual 0.915 -> 1.09 ms per 18 launches, three interleaved runs -- the spill is the cheaper evil; loading
@@ -872,7 +885,8 @@ template <int NTB, int MT = 2, int EPI = GE_PLAIN, bool UNFOLD = false>
 //  takes them; the RESIDUAL form stays at four.  The weight fragments through LDS, once per workgroup by LDS-DMA a slab ahead with one barrier per slab (53 KB: three
 //  workgroups per CU), help only that same form and by the same amount (it is the spills, not the bytes): ffn3 +18 %, to_out / out_proj +14 %, ffn0 +3 %.
 //  profiles/r06_gemm_forms_ab.txt)
-__global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY ? 3 : 4) : 2) void gemm_h(ConvM a)
+// (TAPK: the pixel coordinates of the staged rows are eight more registers; at four waves per SIMD two registers spill, at three none do.)
+__global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY || TAPK ? 3 : 4) : 2) void gemm_h(ConvM a)
 {
     // r03: a wave stages exactly the 32 MT rows it multiplies, so its slice of the LDS buffers is private to it (a wave's LDS
     // operations execute in order: no barrier anywhere in the kernel) and the activation scale is chosen PER WAVE from the
@@ -905,11 +919,31 @@ __global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY ? 3 : 4) : 2) void
 
     float4 buf[NLD];
     int e_cur = 24;
+    static_assert(TAPK == 0 || (!UNFOLD && EPI == GE_PLAIN), "gemm_h: the tap-gathered form is a plain convolution");
+    int gyx[TAPK ? NLD : 1];        // TAPK: (y << 16 | x) of the pixel each of the lane's staged rows stands for (H, W < 32768: checked by the caller)
+    if constexpr (TAPK > 0) {
+#pragma unroll
+        for (int k = 0; k < NLD; ++k) {
+            const int r = min(r0 + (lane + k * 64) / Q, nrows - 1), y = r / a.W;
+            gyx[k] = (y << 16) | (r - y * a.W);
+        }
+    }
+    const int nchi = TAPK ? a.CIN / CC : 1;
     auto fetch = [&](int ch) {
+        int dy = 0, dx = 0, chi = ch;        // TAPK: this slab's tap offset and its channel slab (wave-uniform)
+        if constexpr (TAPK > 0) {
+            const int tap = ch / nchi, ky = tap / TAPK, pad = (TAPK - 1) * a.tap_dil / 2;
+            chi = ch - tap * nchi; dy = ky * a.tap_dil - pad; dx = (tap - ky * TAPK) * a.tap_dil - pad;
+        }
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
             const int idx = lane + k * 64, row = idx / Q, q = idx - row * Q;
             buf[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (TAPK > 0) {
+                const int sy = (gyx[k] >> 16) + dy, sx = (gyx[k] & 0xFFFF) + dx;
+                if (r0 + row < nrows && sy >= 0 && sy < a.H && sx >= 0 && sx < a.W)
+                    buf[k] = *reinterpret_cast<const float4*>(in + ((size_t)sy * a.W + sx) * a.istride + chi * CC + 4 * q);
+            } else
             if (r0 + row < nrows) {
                 if constexpr (UNFOLD) {       // channels 32 ch + 4 q .. + 3 of cell (Y, X) = four adjacent pixels of cell row 4 ch + q / 2
                     const int r = r0 + row, Y = r / a.W, X = r - Y * a.W;

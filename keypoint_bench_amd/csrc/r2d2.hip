@@ -1,0 +1,179 @@
+// r2d2.hip -- N6 R2D2 (models/r2d2.py:101-141, Quad_L2Net_ConfCFS) on gfx950.  Nine convolutions at FULL resolution: the reference replaces every
+// stride by a dilation (1, 1, 1, 2, 2, 4 for the 3 x 3 layers, 4, 8, 16 for the closing 2 x 2 ones), BatchNorm(affine = False) folded at pack time
+// (weights.py fold_r2d2), then the confidence head on x^2 and the L2-normalised descriptor -- 483 168 MAC per pixel.
+//   conv0          3 -> 32 on the vector ALU from the planar image (0.2 % of the work)
+//   conv1, conv2   conv_mfma_h, the forms SuperPoint uses
+//   conv3 .. 5     conv_mfma_h with CmForm::dil = 2, 2, 4: the halo tile grows by (ks - 1) dil
+//   conv6 .. 8     gemm_h<.., TAPK = 2>: four taps x 128 channels gathered at (+-d / 2, +-d / 2) -- no halo in LDS
+//   r2d2_head      one pass over the 128-channel map: score and the normalised descriptor row
+// KPB_FP32_MATRIX=1: conv1 .. 8 on conv_mfma (fp32 MFMA) with the same dilation field.
+#include "conv_mfma.h"
+
+namespace {
+
+// conv0 + ReLU: one pixel x 8 output channels per thread, the 27 x 8 weights wave-uniform; reads [B][3][H][W], writes [B][H][W][32]
+__global__ __launch_bounds__(256) void r2d2_conv0(const float* __restrict__ img, float* __restrict__ out, const float* __restrict__ w /*[27][32]*/,
+                                                  const float* __restrict__ bias, int H, int W)
+{
+    const int b = blockIdx.z, cg = blockIdx.y, pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= H * W) return;
+    const int oy = pix / W, ox = pix - oy * W;
+    const float* im = img + (size_t)b * 3 * H * W;
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = bias[cg * 8 + j];
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int iy = oy + ky - 1, ix = ox + kx - 1;
+            const bool in = iy >= 0 && iy < H && ix >= 0 && ix < W;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float v = in ? im[((size_t)c * H + iy) * W + ix] : 0.0f;
+                const float* wt = w + ((ky * 3 + kx) * 3 + c) * 32 + cg * 8;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] = fmaf(v, wt[j], acc[j]);
+            }
+        }
+    float4* o = reinterpret_cast<float4*>(out + ((size_t)b * H * W + pix) * 32 + cg * 8);
+    o[0] = make_float4(relu(acc[0]), relu(acc[1]), relu(acc[2]), relu(acc[3]));
+    o[1] = make_float4(relu(acc[4]), relu(acc[5]), relu(acc[6]), relu(acc[7]));
+}
+
+// r2d2.py:136-141 on x = conv8's row of 128, IN PLACE on the descriptor map: reliability = softmax(clf(x^2))[1], repeatability = softplus(sal(x^2)) / (1 + softplus),
+// score = their product, desc = x / max(||x||_2, 1e-12).  One wave per pixel, RHW pixels per wave with their loads in flight together; lane l holds channels
+// 2 l and 2 l + 1, so a row is read and written as one 512-byte access.  The four sums are butterflies in a fixed order.  hw: [3][128] = clf row 0, clf row 1, sal; hb: [3].
+__global__ __launch_bounds__(256) void r2d2_head(float* __restrict__ desc, float* __restrict__ score, const float* __restrict__ hw, const float* __restrict__ hb, size_t npix)
+{
+    constexpr int RHW = 4;
+    const int lane = threadIdx.x & 63;
+    const size_t pix0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * RHW;
+    if (pix0 >= npix) return;
+    const float2 w0 = reinterpret_cast<const float2*>(hw)[lane], w1 = reinterpret_cast<const float2*>(hw + 128)[lane], ws = reinterpret_cast<const float2*>(hw + 256)[lane];
+    const float b0 = hb[0], b1 = hb[1], bs = hb[2];
+    float2 x[RHW];
+#pragma unroll
+    for (int i = 0; i < RHW; ++i) x[i] = reinterpret_cast<const float2*>(desc + min(pix0 + i, npix - 1) * 128)[lane];
+#pragma unroll
+    for (int i = 0; i < RHW; ++i) {
+        const size_t pix = pix0 + i;
+        const float q0 = x[i].x * x[i].x, q1 = x[i].y * x[i].y;
+        const float ss = kpb_wave_sum(q0 + q1);
+        const float u0 = kpb_wave_sum(fmaf(q0, w0.x, q1 * w0.y)) + b0;
+        const float u1 = kpb_wave_sum(fmaf(q0, w1.x, q1 * w1.y)) + b1;
+        const float us = kpb_wave_sum(fmaf(q0, ws.x, q1 * ws.y)) + bs;
+        const float n = fmaxf(sqrtf(ss), 1e-12f);
+        if (pix < npix) {
+            reinterpret_cast<float2*>(desc + pix * 128)[lane] = make_float2(__fdiv_rn(x[i].x, n), __fdiv_rn(x[i].y, n));
+            if (lane == 0) {
+                const float m = fmaxf(u0, u1), e0 = expf(u0 - m), e1 = expf(u1 - m);
+                const float rel = __fdiv_rn(e1, e0 + e1);
+                const float sp = us > 20.0f ? us : log1pf(expf(us));      // torch's softplus (beta 1, threshold 20)
+                score[pix] = __fdiv_rn(sp, 1.0f + sp) * rel;
+            }
+        }
+    }
+}
+
+struct R2Layer { const char* name; int cin, cout, ks, dil; bool relu; };
+// r2d2.py:105-117 with dilated = True: the strides of Quad_L2Net became the dilation of every layer behind them
+constexpr R2Layer R2D2_PLAN[9] = {{"conv0", 3, 32, 3, 1, true}, {"conv1", 32, 32, 3, 1, true}, {"conv2", 32, 64, 3, 1, true}, {"conv3", 64, 64, 3, 2, true},
+                                  {"conv4", 64, 128, 3, 2, true}, {"conv5", 128, 128, 3, 4, true}, {"conv6", 128, 128, 2, 4, false}, {"conv7", 128, 128, 2, 8, false},
+                                  {"conv8", 128, 128, 2, 16, false}};
+constexpr int r2_cc_fp32(const R2Layer& L) { return L.ks == 2 ? 16 : 32; }       // strict fp32: the 2 x 2, dilation-16 tile fits the LDS window in 16-channel slabs
+constexpr int r2_ntb_fp32(const R2Layer& L) { return L.cout == 32 ? 1 : 2; }
+
+struct R2d2Net : kpb_net {
+    int conv(const R2Layer& L, const float* in, float* out, int batch, int H, int W)
+    {
+        const std::string n = L.name;
+        ConvM a{.in = in, .out = out, .wp = wp((n + ".w").c_str()), .bias = wp((n + ".b").c_str()), .Hi = H, .Wi = W, .H = H, .W = W, .CIN = L.cin, .COUT = L.cout,
+                .NCH = L.cin / 32, .relu = L.relu, .nblk = cdiv(L.cout, 64), .istride = L.cin, .ostride = L.cout};
+        if (!conv_mfma_use_h16()) {
+            const int cc = r2_cc_fp32(L), ntb = r2_ntb_fp32(L);
+            a.NCH = L.cin / cc; a.nblk = cdiv(L.cout, 32 * ntb);
+            return launch_conv_mfma<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32, .dil = 2},
+                                    CmForm{.ks = 3, .s = 1, .cc = 32, .dil = 4}, CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 4}, CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 8},
+                                    CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 16}>(ctx, L.name, CmForm{.ks = L.ks, .s = 1, .cc = cc, .ntb = ntb, .dil = L.dil}, a, batch);
+        }
+        a.unscale = 1.0f / wscale.at(n + ".w");
+        if (L.ks == 2) {        // tap-gathered product: K = 4 taps x cin, 128 pixels x 64 output channels per workgroup
+            a.NCH = 4 * (L.cin / 32); a.tap_dil = L.dil;
+            KPB_LAUNCH(ctx, L.name, (gemm_h<2, 1, GE_PLAIN, false, 2>), dim3(cdiv(H * W, 128), 1, batch * a.nblk), dim3(256), 0, ctx->stream, a);
+            return KPB_OK;
+        }
+        // halo tiles: 16 x 16 outputs (8 x 16 for the one-tile layer and for dilation 4, whose 24-pixel-wide tile would not fit 16 rows into the LDS window)
+        CmForm f{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .dil = L.dil};
+        if (L.cout == 32) f.mt = f.wn = 1;
+        if (L.dil == 4) f.mt = 2;
+        return launch_conv_mfma_h<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
+                                  CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .dil = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 2, .wn = 2, .dil = 4}>(
+            ctx, L.name, f, a, batch);
+    }
+    int forward(const float* img, int batch, int H, int W, float* score_out, float* desc_out) override
+    {
+        if (!desc_out) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: R2D2 writes its 128 x H x W descriptor map; desc_out_dev is required");
+        if (H > 32767 || W > 32767 || (size_t)H * W > ((size_t)1 << 30)) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: R2D2 image %dx%d too large", H, W);
+        const size_t P = (size_t)H * W, B = batch;
+        // every layer runs at full resolution: two ping-pong maps of the widest layer (128 channels: 157 MB per 480 x 640 image each) carry the narrower early
+        // maps too; conv8 writes into the caller's descriptor map, which the head then normalises in place
+        if (int rc = kpb_reserve(ctx, act, 2 * B * P * 128 * sizeof(float))) return rc;
+        float* pp[2] = {static_cast<float*>(act.p), static_cast<float*>(act.p) + B * P * 128};
+        this->B = batch; this->H = H; this->W = W;
+        hipStream_t st = ctx->stream;
+        KPB_LAUNCH(ctx, "r2d2_conv0", r2d2_conv0, dim3((unsigned)((P + 255) / 256), 4, batch), dim3(256), 0, st, img, pp[0], wp("conv0.w"), wp("conv0.b"), H, W);
+        for (int i = 1; i < 9; ++i)
+            if (int rc = conv(R2D2_PLAN[i], pp[(i - 1) & 1], i == 8 ? desc_out : pp[i & 1], batch, H, W)) return rc;
+        KPB_LAUNCH(ctx, "r2d2_head", r2d2_head, dim3((unsigned)((B * P + 15) / 16)), dim3(256), 0, st, desc_out, score_out, wp("head.w"), wp("head.b"), B * P);
+        KPB_HIP(ctx, hipGetLastError());
+        return KPB_OK;
+    }
+};
+
+}  // namespace
+
+int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
+{
+    R2d2Net* net = new R2d2Net();
+    net->ctx = ctx; net->arch = KPB_ARCH_R2D2; net->dim = 128; net->desc_div = 1;
+    WeightStage ws;
+    auto bad = [&](const char* what) {
+        delete net;
+        return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: R2D2 tensor %s missing or mis-shaped", what);
+    };
+    for (const R2Layer& L : R2D2_PLAN) {
+        const std::string n = L.name;
+        const float* w = bl.get((n + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
+        const float* b = bl.get((n + ".b").c_str(), {(uint32_t)L.cout});
+        if (!w || !b) return bad(L.name);
+        if (L.cin == 3) {       // conv0: [tap][cin][32]
+            std::vector<float> p(27 * 32);
+            for (int o = 0; o < 32; ++o)
+                for (int c = 0; c < 3; ++c)
+                    for (int t = 0; t < 9; ++t) p[(t * 3 + c) * 32 + o] = w[(o * 3 + c) * 9 + t];
+            ws.put(n + ".w", p);
+            ws.put_raw(n + ".b", b, 32);
+        } else if (conv_mfma_use_h16()) {      // tap-major fragments, two n-tiles per workgroup: the same pack serves the halo form and the tap-gathered one
+            const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * L.ks * L.ks);
+            ws.put(n + ".w", pack_mfma_h(w, L.cout, L.cin, L.ks, 32, 2, sc));
+            ws.wscale[n + ".w"] = sc;
+            ws.put(n + ".b", pad_bias(b, L.cout, 64));
+        } else {
+            ws.put(n + ".w", pack_mfma(w, L.cout, L.cin, L.ks, r2_cc_fp32(L), r2_ntb_fp32(L)));
+            ws.put(n + ".b", pad_bias(b, L.cout, 64));
+        }
+    }
+    const float* cw = bl.get("clf.w", {2, 128});
+    const float* cb = bl.get("clf.b", {2});
+    const float* sw = bl.get("sal.w", {1, 128});
+    const float* sb = bl.get("sal.b", {1});
+    if (!cw || !cb || !sw || !sb) return bad("clf / sal");
+    std::vector<float> hw(cw, cw + 256), hb = {cb[0], cb[1], sb[0]};
+    hw.insert(hw.end(), sw, sw + 128);
+    ws.put("head.w", hw);
+    ws.put("head.b", hb);
+    if (int rc = ws.upload(net)) { delete net; return rc; }
+    *out = net;
+    return KPB_OK;
+}

@@ -65,7 +65,13 @@ def build_model(params, dense_descriptors=True):
         sd = torch.load(w, map_location="cpu")
         net.load_state_dict(sd[sub] if sub else sd)
         return net.eval()
-    raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK)" % (mt,))
+    if mt == "r2d2":     # model_interface.py:69-73: the checkpoint names its own constructor
+        from .models.r2d2 import from_checkpoint
+        w = (params.get("r2d2_params") or {}).get("weight")
+        if not (w and os.path.exists(w)):
+            raise FileNotFoundError("r2d2 checkpoint %r not found" % (w,))
+        return from_checkpoint(torch.load(w, map_location="cpu"))
+    raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2)" % (mt,))
 
 
 # ------------------------------------------------------------------------------------------ sharding

@@ -17,6 +17,7 @@ ARCH_SUPERPOINT = 2
 ARCH_XFEAT = 3
 ARCH_DISK = 4
 ARCH_LIGHTGLUE = 5
+ARCH_R2D2 = 6
 _REC = struct.Struct("<40sI4II")
 
 
@@ -199,6 +200,45 @@ def random_disk_state_dict(seed: int) -> dict:
         conv(key, cout, cin)
         sd[key + ".1.weight"] = rng.uniform(0.1, 0.4, size=(cin,)).astype(np.float32)
     return sd
+
+
+# Quad_L2Net_ConfCFS (models/r2d2.py:101-131, dilated = True): every layer at full resolution, the strides of L2-Net turned into the dilation of
+# the layers behind them.  (name, cin, cout, k, dilation, bn, relu); padding = (k - 1) dilation / 2, BatchNorm2d(affine=False, eps 1e-5); a 2 x 2
+# kernel's taps sit at -dilation / 2 and +dilation / 2.  `name` is the folded tensor's prefix, ops.N the state_dict's (conv N, then its BN).
+R2D2_PLAN = (("conv0", 3, 32, 3, 1, True, True), ("conv1", 32, 32, 3, 1, True, True), ("conv2", 32, 64, 3, 1, True, True),
+             ("conv3", 64, 64, 3, 2, True, True), ("conv4", 64, 128, 3, 2, True, True), ("conv5", 128, 128, 3, 4, True, True),
+             ("conv6", 128, 128, 2, 4, True, False), ("conv7", 128, 128, 2, 8, True, False), ("conv8", 128, 128, 2, 16, False, False))
+R2D2_NET = "Quad_L2Net_ConfCFS()"
+
+
+def fold_r2d2(sd, eps=1e-5) -> dict:
+    """state_dict of Quad_L2Net_ConfCFS (the checkpoint's keys carry a `module.` prefix, model_interface.py:71) -> folded tensors named as
+    csrc/r2d2.hip expects: w' = w / sqrt(var + eps), b' = (b - mean) / sqrt(var + eps) per output channel.  A state_dict whose tensors do not
+    have the shapes of R2D2_PLAN (another variant of r2d2.py, another `dim` or `mchan`) is refused."""
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+
+    def take(key, shape):
+        if key not in sd:
+            raise ValueError("R2D2 state_dict: %s is missing" % key)
+        a = _np(sd[key])
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("R2D2 state_dict: %s has shape %s, the Quad_L2Net_ConfCFS plan needs %s" % (key, tuple(a.shape), tuple(shape)))
+        return a
+
+    t, op = {}, 0
+    for name, cin, cout, k, dil, bn, relu in R2D2_PLAN:
+        w, b = take("ops.%d.weight" % op, (cout, cin, k, k)), take("ops.%d.bias" % op, (cout,))
+        op += 1
+        if bn:
+            mu, var = take("ops.%d.running_mean" % op, (cout,)), take("ops.%d.running_var" % op, (cout,))
+            op += 1
+            s = 1.0 / np.sqrt(var + eps)
+            w, b = w * s[:, None, None, None], (b - mu) * s
+        op += 1 if relu else 0
+        t[name + ".w"], t[name + ".b"] = w.astype(np.float32), b.astype(np.float32)
+    t["clf.w"], t["clf.b"] = take("clf.weight", (2, 128, 1, 1)).reshape(2, 128).astype(np.float32), take("clf.bias", (2,)).astype(np.float32)
+    t["sal.w"], t["sal.b"] = take("sal.weight", (1, 128, 1, 1)).reshape(1, 128).astype(np.float32), take("sal.bias", (1,)).astype(np.float32)
+    return t
 
 
 LG_LAYERS = 9
