@@ -1913,19 +1913,16 @@ __global__ __launch_bounds__(256) void alike_desc_at(DescAtArgs a)
 namespace {
 
 struct AlikeNet : kpb_net {
-    float *p1 = nullptr, *x1 = nullptr, *t2 = nullptr, *x2 = nullptr, *a2 = nullptr, *t3 = nullptr, *x3 = nullptr, *a3 = nullptr,
-          *t4 = nullptr, *x4 = nullptr, *a4 = nullptr, *S2 = nullptr, *S3 = nullptr, *S4 = nullptr, *E3 = nullptr, *E4 = nullptr;
-    // split-f16 form: reciprocal power-of-two weight scales of the custom packs, and the L1 norms / bias maxima behind the
-    // bounds the fused kernels scale their intermediate maps by (conv_mfma.h, cm_scale_of)
-    std::map<std::string, float> k;
-    HeadArgs head_args(float* score, float* desc)
-    {
-        HeadArgs h;
-        h.x1 = x1; h.a2 = a2; h.a3 = a3; h.a4 = a4;
-        h.agg1 = wp("agg1.w"); h.whT = wp("head.wT"); h.wsc = wp("head.ws");
-        h.score = score; h.desc = desc; h.H = H; h.W = W;
-        return h;
-    }
+    float *x1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr;      // the maps of the last forward that desc_at reads
+    // What forward needs of the staged weights, bound once at create: device pointers, and the host scalars of the split-f16 form -- reciprocal power-of-two
+    // weight scales of the custom packs, and the L1 norms / bias maxima behind the bounds the fused kernels scale their intermediate maps by (conv_mfma.h,
+    // cm_scale_of).  One struct per fused kernel; the members carry the names of the kernel arguments they fill.
+    struct { const float *w1, *b1, *w2, *b2; const uint4 *w1pk, *w2pk; float inv_ws1, inv_ws2, l1_c1, bmax_c1; } k1 = {};       // Block1Args, Block1HArgs
+    struct { const uint4 *w1pk, *w2pk, *wapk; const float *b1, *bsum; float inv_ws1, inv_ws2, inv_wsa, l1_c1, bmax_c1, l1_c2, l1_ds, bmax_sum; } k2 = {};   // Block2Args
+    // blocks 2 .. 4 as strict fp32 sees them (ConvArgs: w1 .. dsb).  Blocks 3 / 4 keep conv2 as an MFMA pack in both forms (w2p, b2p, un2) and, in the
+    // split-f16 form, conv1 + the identity branch as one pack (w1h, b1h, un1); prof1 / prof2 are the profile names of their conv1 / conv2
+    struct Res { const float *w1, *b1, *w2, *b2, *dsw, *dsb, *w1h, *b1h, *w2p, *b2p; float un1, un2; std::string prof1, prof2; } blk[5] = {};      // [2 .. 4]
+    struct { const float *agg[5], *whT, *wsc; const uint4 *wh16, *a1h16; float l1_agg1, inv_ws_h, inv_wa; } kh = {};      // agg[1 .. 4]; HeadArgs, HybArgs, LinArgs
     int forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev) override;
     int desc_at(const float* pts_dev, int pts_cols, int max_n, const int32_t* n_dev, float* out_dev) override;
 };
@@ -2006,121 +2003,116 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
     const int H = H_, W = W_;
     const size_t P = (size_t)H * W, B = batch;
     const bool h16 = conv_mfma_use_h16();       // the split-f16 matrix form (default) or the strict fp32 kernels (KPB_FP32_MATRIX=1)
-    const size_t n_x1 = B * P * 8, n_2 = B * (P / 4) * 16, n_3 = B * (P / 64) * 32, n_a3 = B * (P / 64) * 16,
-                 n_4 = B * (P / 1024) * 64, n_a4 = B * (P / 1024) * 16;
-    const size_t n_s = B * (P / 4 + P / 64 + P / 1024) + 64;
-    const size_t n_e = desc_out_dev ? B * (P / 64 + P / 1024) * ESTRIDE : 0;
-    const size_t n_p1 = B * (P / 4) * 8;
+    const bool dense = desc_out_dev != nullptr;
     const int nw1 = cdiv(W, B1_TW) * cdiv(H, B1H_TH) * 4, nw2 = cdiv(W / 2, 32) * cdiv(H / 2, 8) * 4;      // per-wave maxima of blocks 1 / 2
-    const size_t n_rng = (2 * B + B * (nw1 + nw2) + 63) / 64 * 64;
-    const size_t total = n_x1 + n_p1 + 3 * n_2 + 6 * n_3 + n_a3 + 5 * n_4 + n_4 / 2 + n_a4 + n_s + n_e + n_rng;
-    if (int rc = kpb_reserve(ctx, act, total * sizeof(float))) return rc;
-    float* p = static_cast<float*>(act.p);
-    x1 = p; p += n_x1;
-    p1 = p; p += n_p1;
-    t2 = p; p += n_2; x2 = p; p += n_2; a2 = p; p += n_2;
-    t3 = p; p += n_3; x3 = p; p += n_3; a3 = p; p += n_a3;
-    t4 = p; p += n_4; x4 = p; p += n_4; a4 = p; p += n_a4;
-    float* r3 = p; p += n_3;
-    float* r4 = p; p += n_4;
-    float* t3r3 = p; p += 2 * n_3;      // conv_mfma_h form of blocks 3 / 4: conv1's output and the identity branch side by side per pixel
-    float* t4r4 = p; p += 2 * n_4;
-    float* p2 = p; p += n_3 / 2;        // max_pool2d(x2, 4): [B][H/8][W/8][16]
-    float* p3 = p; p += n_4 / 2;        // max_pool2d(x3, 4): [B][H/32][W/32][32] (batches: maxpool4_nhwc)
-    S2 = p; p += B * (P / 4); S3 = p; p += B * (P / 64); S4 = p; p += B * (P / 1024) + 64;
-    E3 = E4 = nullptr;
-    if (desc_out_dev) { E3 = p; p += B * (P / 64) * ESTRIDE; E4 = p; p += B * (P / 1024) * ESTRIDE; }
-    unsigned* amax_x1 = reinterpret_cast<unsigned*>(p);      // [B], [B]: per-image largest x1 / a2 value (float bits)
-    unsigned* amax_a2 = amax_x1 + B;
-    float* wmax_x1 = p + 2 * B;                                // [B][nw1], [B][nw2]: the per-wave maxima they are folded from
-    float* wmax_a2 = wmax_x1 + B * nw1;
-    p += n_rng;
+    const size_t n_2 = B * (P / 4) * 16, n_3 = B * (P / 64) * 32, n_4 = B * (P / 1024) * 64;
+    float *p1, *t2, *x2, *t3, *x3, *t4, *x4, *r3, *r4, *t3r3, *t4r4, *p2, *p3, *S2, *S3, *S4, *E3, *E4, *wmax_x1, *wmax_a2;
+    unsigned *amax_x1, *amax_a2;
+    if (int rc = kpb_carve(ctx, act, [&](Arena& a) {
+            auto f32 = [&](size_t n) { return h16 ? nullptr : a.take(n); };      // what only the strict fp32 kernels touch,
+            auto f16 = [&](size_t n) { return h16 ? a.take(n) : nullptr; };      // and what only the split-f16 form does
+            x1 = a.take(B * P * 8);
+            p1 = a.take(B * (P / 4) * 8);
+            t2 = f32(n_2); x2 = f32(n_2); a2 = a.take(n_2);     // (alike_block2 hands block 3 p2 and leaves x2 unwritten)
+            t3 = f32(n_3); x3 = a.take(n_3); a3 = a.take(B * (P / 64) * 16);
+            t4 = f32(n_4); x4 = a.take(n_4); a4 = a.take(B * (P / 1024) * 16);
+            r3 = f32(n_3); r4 = f32(n_4);
+            t3r3 = f16(2 * n_3);        // conv_mfma_h form of blocks 3 / 4: conv1's output and the identity branch side by side per pixel
+            t4r4 = f16(2 * n_4);
+            p2 = f16(n_3 / 2);          // max_pool2d(x2, 4): [B][H/8][W/8][16]
+            p3 = h16 && batch >= 16 ? a.take(n_4 / 2) : nullptr;        // max_pool2d(x3, 4): [B][H/32][W/32][32] (batches: maxpool4_nhwc)
+            // every group's share of the score logit.  (S4 carried 64 floats of slack: no kernel reads past a map's end -- alike_score_lin, their only
+            // reader, clamps its taps to the map.)
+            S2 = a.take(B * (P / 4)); S3 = a.take(B * (P / 64)); S4 = a.take(B * (P / 1024));
+            E3 = dense ? a.take(B * (P / 64) * ESTRIDE) : nullptr;
+            E4 = dense ? a.take(B * (P / 1024) * ESTRIDE) : nullptr;
+            amax_x1 = h16 ? a.take<unsigned>(B) : nullptr;      // [B], [B]: per-image largest x1 / a2 value (float bits),
+            amax_a2 = h16 ? a.take<unsigned>(B) : nullptr;
+            wmax_x1 = f16(B * nw1);                             // [B][nw1], [B][nw2]: the per-wave maxima they are folded from
+            wmax_a2 = f16(B * nw2);
+        }))
+        return rc;
     this->B = batch; this->H = H; this->W = W;
     hipStream_t st = ctx->stream;
 
-    Block1Args b1{img_dev, x1, p1, wp("b1c1.w"), wp("b1c1.b"), wp("b1c2.w"), wp("b1c2.b"), H, W};
+    Block1Args b1{img_dev, x1, p1, k1.w1, k1.b1, k1.w2, k1.b2, H, W};
     ConvArgs c;
     if (h16) {
-        Block1HArgs hb{b1, reinterpret_cast<const uint4*>(wp("b1c1.pairs")), reinterpret_cast<const uint4*>(wp("b1c2.pairs")),
-                       k.at("b1c1.inv_ws"), k.at("b1c2.inv_ws"), k.at("b1c1.l1"), k.at("b1c1.bmax"), wmax_x1, 0};       // XCD-aware map: +4 % on block 1 (not bound by its halo re-reads), off
+        Block1HArgs hb{b1, k1.w1pk, k1.w2pk, k1.inv_ws1, k1.inv_ws2, k1.l1_c1, k1.bmax_c1, wmax_x1, 0};       // XCD-aware map: +4 % on block 1 (not bound by its halo re-reads), off
         KPB_LAUNCH(ctx, "alike_block1", alike_block1_h, dim3(cdiv(W, B1_TW), cdiv(H, B1H_TH), batch), dim3(256), 0, st, hb);
         KPB_LAUNCH(ctx, "amax_reduce", amax_reduce, dim3(batch), dim3(256), 0, st, wmax_x1, nw1, amax_x1);
         // block2 @ H/2 (ALike.py:139-140) + agg2, fused; it hands block 3 the 4 x 4 max-pool of its output (141)
-        Block2Args b2{p1, x2, a2, S2, p2, reinterpret_cast<const uint4*>(wp("b2c1.h16")), reinterpret_cast<const uint4*>(wp("b2c2.h16")),
-                      reinterpret_cast<const uint4*>(wp("agg2.h16")), wp("b2c1.b"), wp("b2c2.bsum"), wp("head.ws") + 16, H / 2, W / 2,
-                      k.at("b2c1.inv_ws"), k.at("b2c2.inv_ws"), k.at("agg2.inv_ws"), k.at("b2c1.l1"), k.at("b2c1.bmax"), k.at("b2c2.l1"), k.at("b2ds.l1"),
-                      k.at("b2c2.bsummax"), amax_x1, wmax_a2, 1};     // XCD-aware map: -5 % (profiles/r04_ab_knobs.txt)
+        Block2Args b2{p1, x2, a2, S2, p2, k2.w1pk, k2.w2pk, k2.wapk, k2.b1, k2.bsum, kh.wsc + 16, H / 2, W / 2,
+                      k2.inv_ws1, k2.inv_ws2, k2.inv_wsa, k2.l1_c1, k2.bmax_c1, k2.l1_c2, k2.l1_ds, k2.bmax_sum, amax_x1, wmax_a2, 1};     // XCD-aware map: -5 % (profiles/r04_ab_knobs.txt)
         KPB_LAUNCH(ctx, "alike_block2", alike_block2, dim3(cdiv(W / 2, 32), cdiv(H / 2, 8), batch), dim3(256), 0, st, b2);
         KPB_LAUNCH(ctx, "amax_reduce", amax_reduce, dim3(batch), dim3(256), 0, st, wmax_a2, nw2, amax_a2);
         // blocks 3 and 4 @ H/8, H/32 (141-144) on conv_mfma_h: conv1 carries the identity branch ds(pooled input) as 32 / 64 more
         // output channels whose weights sit on the centre tap only (no ReLU on those tiles); conv2 then reads conv1's half of that
         // buffer and adds the other half.  Block 4's conv1 max-pools x3 4 x 4 while it stages it.
-        auto block_h = [&](const char* n1, const char* n2, const float* in, float* tr, float* xo, int cin, int cout, int Hi, int Wi, bool prepooled) {
-            const std::string k1 = std::string(n1) + ".h", k2 = std::string(n2) + ".wp";
-            ConvM m{.in = in, .out = tr, .wp = wp(k1.c_str()), .bias = wp((std::string(n1) + ".hb").c_str()), .Hi = prepooled ? Hi / 4 : Hi, .Wi = prepooled ? Wi / 4 : Wi,
+        auto block_h = [&](const Res& r, const float* in, float* tr, float* xo, int cin, int cout, int Hi, int Wi, bool prepooled) {
+            ConvM m{.in = in, .out = tr, .wp = r.w1h, .bias = r.b1h, .Hi = prepooled ? Hi / 4 : Hi, .Wi = prepooled ? Wi / 4 : Wi,
                     .H = Hi / 4, .W = Wi / 4, .CIN = cin, .COUT = 2 * cout, .NCH = 1, .relu = 2, .nblk = cout / 32, .istride = cin, .ostride = 2 * cout,
-                    .unscale = 1.0f / wscale.at(k1), .relu_nt = cout / 32};
-            auto launch = [&](const char* n, const CmForm& f, const ConvM& cm) {     // profiled as conv3x3_<n>
-                return launch_conv_mfma_h<CM_C16, CM_C32, CM_C32_1T, CM_C16_LAT, CM_C32_LAT, CM_P4_LAT>(ctx, ("conv3x3_" + std::string(n)).c_str(), f, cm, batch); };
+                    .unscale = r.un1, .relu_nt = cout / 32};
+            auto launch = [&](const char* prof, const CmForm& f, const ConvM& cm) {
+                return launch_conv_mfma_h<CM_C16, CM_C32, CM_C32_1T, CM_C16_LAT, CM_C32_LAT, CM_P4_LAT>(ctx, prof, f, cm, batch); };
             // small layers are bound by per-workgroup latency: 8-row tiles (r02: b3c1 0.36 -> 0.32 ms, b3c2 0.58 -> 0.49 ms).  A handful of images (the drop-in
             // path runs ONE): a 15 x 20 map in 16 x 16 tiles with two n-tiles each is 4 workgroups of pure latency (41 us); 8-row tiles with one n-tile each are 16
             // (same weights, same arithmetic per output)
             if (batch < 16 && !prepooled) m.nblk = 2 * cout / 32;
             const CmForm f1 = !prepooled ? CM_P4_LAT : batch < 16 ? CM_C16_LAT : cin == 32 ? CM_C32 : CM_C16;     // (only a handful of images leave x3 unpooled)
-            if (int rc = launch(n1, f1, m)) return rc;
-            const ConvM c2{.in = tr, .out = xo, .wp = wp(k2.c_str()), .bias = wp((std::string(n2) + ".bp").c_str()), .res = tr + cout, .Hi = Hi / 4, .Wi = Wi / 4,
+            if (int rc = launch(r.prof1.c_str(), f1, m)) return rc;
+            const ConvM c2{.in = tr, .out = xo, .wp = r.w2p, .bias = r.b2p, .res = tr + cout, .Hi = Hi / 4, .Wi = Wi / 4,
                            .H = Hi / 4, .W = Wi / 4, .CIN = cout, .COUT = cout, .NCH = cout / 32, .nblk = batch < 16 ? cout / 32 : 1, .istride = 2 * cout,
-                           .ostride = cout, .unscale = 1.0f / wscale.at(k2), .rstride = 2 * cout};
-            return launch(n2, batch < 16 ? CM_C32_LAT : cout == 32 ? CM_C32_1T : CM_C32, c2);
+                           .ostride = cout, .unscale = r.un2, .rstride = 2 * cout};
+            return launch(r.prof2.c_str(), batch < 16 ? CM_C32_LAT : cout == 32 ? CM_C32_1T : CM_C32, c2);
         };
-        if (int rc = block_h("b3c1", "b3c2", p2, t3r3, x3, 16, 32, H / 2, W / 2, true)) return rc;
+        if (int rc = block_h(blk[3], p2, t3r3, x3, 16, 32, H / 2, W / 2, true)) return rc;
         if (batch >= 16) {      // block 4's input pooled once, by a kernel of its own (see maxpool4_nhwc); a handful of images keep the fused form (one launch fewer)
             KPB_LAUNCH(ctx, "maxpool4_x3", maxpool4_nhwc, dim3((unsigned)(((size_t)(H / 32) * (W / 32) * 8 + 255) / 256), batch), dim3(256), 0, st, x3, p3, H / 32, W / 32, 32);
-            if (int rc = block_h("b4c1", "b4c2", p3, t4r4, x4, 32, 64, H / 8, W / 8, true)) return rc;
-        } else if (int rc = block_h("b4c1", "b4c2", x3, t4r4, x4, 32, 64, H / 8, W / 8, false))
+            if (int rc = block_h(blk[4], p3, t4r4, x4, 32, 64, H / 8, W / 8, true)) return rc;
+        } else if (int rc = block_h(blk[4], x3, t4r4, x4, 32, 64, H / 8, W / 8, false))
             return rc;
     } else {
         // strict fp32: block 1 and the 3x3 convolutions on the fp32 vector ALUs, conv2 of blocks 3 / 4 on the fp32 MFMA
-        auto conv2 = [&](const char* n, const float* in, float* out, const float* res, int h, int w, int c) {    // identity branch precomputed (ALike.py:72-80)
-            const std::string k = n;
-            const ConvM m{.in = in, .out = out, .wp = wp((k + ".wp").c_str()), .bias = wp((k + ".bp").c_str()), .res = res, .Hi = h, .Wi = w, .H = h, .W = w,
+        auto conv2 = [&](const Res& r, const float* in, float* out, const float* res, int h, int w, int c) {    // identity branch precomputed (ALike.py:72-80)
+            const ConvM m{.in = in, .out = out, .wp = r.w2p, .bias = r.b2p, .res = res, .Hi = h, .Wi = w, .H = h, .W = w,
                           .CIN = c, .COUT = c, .NCH = c / 32, .nblk = 1, .istride = c, .ostride = c};
             return launch_conv_mfma<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32}>(
-                ctx, ("conv3x3_" + k).c_str(), CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = c / 32}, m, batch);
+                ctx, r.prof2.c_str(), CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = c / 32}, m, batch);
         };
         KPB_LAUNCH(ctx, "alike_block1", alike_block1, dim3(cdiv(W, B1_TW), cdiv(H, B1_TH), batch), dim3(256), 0, st, b1);
-        c = ConvArgs{p1, t2, wp("b2c1.w"), wp("b2c1.b"), nullptr, nullptr, nullptr, nullptr, H / 2, W / 2};      // pooled by block1
+        c = ConvArgs{p1, t2, blk[2].w1, blk[2].b1, nullptr, nullptr, nullptr, nullptr, H / 2, W / 2};      // pooled by block1
         launch_conv<8, 16, 1, false, 4, 1>(ctx, "conv3x3_b2c1", st, c, batch);
-        c = ConvArgs{t2, x2, wp("b2c2.w"), wp("b2c2.b"), p1, wp("b2ds.w"), wp("b2ds.b"), nullptr, H / 2, W / 2};
+        c = ConvArgs{t2, x2, blk[2].w2, blk[2].b2, p1, blk[2].dsw, blk[2].dsb, nullptr, H / 2, W / 2};
         launch_conv<16, 16, 1, true, 8, 1>(ctx, "conv3x3_b2c2", st, c, batch);
         // block3 @ H/8 (141-142): pool4
-        c = ConvArgs{x2, t3, wp("b3c1.w"), wp("b3c1.b"), nullptr, wp("b3ds.w"), wp("b3ds.b"), r3, H / 8, W / 8};
+        c = ConvArgs{x2, t3, blk[3].w1, blk[3].b1, nullptr, blk[3].dsw, blk[3].dsb, r3, H / 8, W / 8};
         launch_conv<16, 32, 4, false, 4, 1, true, 16>(ctx, "conv3x3_b3c1", st, c, batch);        // 80 columns at 480x640: 16-wide tiles divide them
-        if (int rc = conv2("b3c2", t3, x3, r3, H / 8, W / 8, 32)) return rc;
+        if (int rc = conv2(blk[3], t3, x3, r3, H / 8, W / 8, 32)) return rc;
         // block4 @ H/32 (143-144): pool4
-        c = ConvArgs{x3, t4, wp("b4c1.w"), wp("b4c1.b"), nullptr, wp("b4ds.w"), wp("b4ds.b"), r4, H / 32, W / 32};
+        c = ConvArgs{x3, t4, blk[4].w1, blk[4].b1, nullptr, blk[4].dsw, blk[4].dsb, r4, H / 32, W / 32};
         launch_conv<32, 64, 4, false, 4, 1, true, 16>(ctx, "conv3x3_b4c1", st, c, batch);
-        if (int rc = conv2("b4c2", t4, x4, r4, H / 32, W / 32, 64)) return rc;
+        if (int rc = conv2(blk[4], t4, x4, r4, H / 32, W / 32, 64)) return rc;
         // aggregation 1x1 + ReLU of block 2 (147-148); agg1 is fused into the head
-        KPB_LAUNCH(ctx, "conv1x1_agg2", conv1x1_relu<16>, dim3((unsigned)((B * P / 4 + 255) / 256)), dim3(256), 0, st, x2, a2, wp("agg2.w"), wp("head.ws") + 16, S2, B * P / 4, nullptr, nullptr);
+        KPB_LAUNCH(ctx, "conv1x1_agg2", conv1x1_relu<16>, dim3((unsigned)((B * P / 4 + 255) / 256)), dim3(256), 0, st, x2, a2, kh.agg[2], kh.wsc + 16, S2, B * P / 4, nullptr, nullptr);
     }
     // aggregation 1x1 + ReLU (149-150), each with its share of the score logit and -- dense mode -- of every head row
     if (batch < 16) {
-        const AggArgs g3{x3, a3, wp("agg3.w"), wp("head.ws") + 32, S3, B * P / 64, wp("head.wT") + 32 * 64, E3};
-        const AggArgs g4{x4, a4, wp("agg4.w"), wp("head.ws") + 48, S4, B * P / 1024, wp("head.wT") + 48 * 64, E4};
+        const AggArgs g3{x3, a3, kh.agg[3], kh.wsc + 32, S3, B * P / 64, kh.whT + 32 * 64, E3};
+        const AggArgs g4{x4, a4, kh.agg[4], kh.wsc + 48, S4, B * P / 1024, kh.whT + 48 * 64, E4};
         const unsigned nb3 = (unsigned)((B * P / 64 + 255) / 256), nb4 = (unsigned)((B * P / 1024 + 255) / 256);
         KPB_LAUNCH(ctx, "conv1x1_agg34", conv1x1_relu_34, dim3(nb3 + nb4), dim3(256), 0, st, g3, g4, nb3);
     } else {
-        KPB_LAUNCH(ctx, "conv1x1_agg3", conv1x1_relu<32>, dim3((unsigned)((B * P / 64 + 255) / 256)), dim3(256), 0, st, x3, a3, wp("agg3.w"), wp("head.ws") + 32, S3, B * P / 64, wp("head.wT") + 32 * 64, E3);
-        KPB_LAUNCH(ctx, "conv1x1_agg4", conv1x1_relu<64>, dim3((unsigned)((B * P / 1024 + 255) / 256)), dim3(256), 0, st, x4, a4, wp("agg4.w"), wp("head.ws") + 48, S4, B * P / 1024, wp("head.wT") + 48 * 64, E4);
+        KPB_LAUNCH(ctx, "conv1x1_agg3", conv1x1_relu<32>, dim3((unsigned)((B * P / 64 + 255) / 256)), dim3(256), 0, st, x3, a3, kh.agg[3], kh.wsc + 32, S3, B * P / 64, kh.whT + 32 * 64, E3);
+        KPB_LAUNCH(ctx, "conv1x1_agg4", conv1x1_relu<64>, dim3((unsigned)((B * P / 1024 + 255) / 256)), dim3(256), 0, st, x4, a4, kh.agg[4], kh.wsc + 48, S4, B * P / 1024, kh.whT + 48 * 64, E4);
     }
     // upsample + concat + head (151-162)
-    if (desc_out_dev) {
-        HybArgs hy{x1, a2, E3, E4, wp("agg1.w"), wp("head.wT"), wp("head.ws"), score_out_dev, desc_out_dev, H, W, amax_x1, amax_a2, 0.f, 1.f, 1.f, nullptr, 1.f};
+    if (dense) {
+        HybArgs hy{x1, a2, E3, E4, kh.agg[1], kh.whT, kh.wsc, score_out_dev, desc_out_dev, H, W, amax_x1, amax_a2, 0.f, 1.f, 1.f, nullptr, 1.f};
         const int work4 = cdiv(H, 4) * cdiv(W / 32, SEG_TILES);     // four consecutive rows of one 128-pixel column band per workgroup
         if (h16) {
-            hy.l1_agg1 = k.at("agg1.l1"); hy.inv_ws_h = k.at("head.inv_ws"); hy.ws_h = 1.0f / hy.inv_ws_h;
-            hy.a1h16 = reinterpret_cast<const uint4*>(wp("agg1.h16")); hy.inv_wa = k.at("agg1.inv_wa");
+            hy.l1_agg1 = kh.l1_agg1; hy.inv_ws_h = kh.inv_ws_h; hy.ws_h = 1.0f / hy.inv_ws_h;
+            hy.a1h16 = kh.a1h16; hy.inv_wa = kh.inv_wa;
             // row groups per persistent workgroup: 30 (15: +1-2 %, 40 / 60: the same, 120: +1 %; profiles/r04_ab_knobs.txt); H is a
             // multiple of 32 (kpb_net_forward checks), so every group has its four rows
             // -- as long as that leaves about two rounds of workgroups for the chip's 768 slots: a single image walks 2 groups per workgroup
@@ -2129,11 +2121,11 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
             const int bands_ = cdiv(W / 32, HP_TILES), groups_ = H / 4;
             const int hp = std::max(2, std::min(30, (int)(((long long)bands_ * groups_ * batch) / 1536)));
             KPB_LAUNCH(ctx, "alike_head_dense", alike_head_f16p, dim3(cdiv(W / 32, HP_TILES) * cdiv(H / 4, hp), batch), dim3(256), 0, st, hy,
-                       reinterpret_cast<const uint4*>(wp("head.wh16")), hp);
+                       kh.wh16, hp);
         } else
             KPB_LAUNCH(ctx, "alike_head_dense", alike_head_hyb, dim3(work4, batch), dim3(256), 0, st, hy);
     } else {
-        LinArgs la{x1, S2, S3, S4, wp("agg1.w"), wp("head.ws"), score_out_dev, H, W,
+        LinArgs la{x1, S2, S3, S4, kh.agg[1], kh.wsc, score_out_dev, H, W,
                    (float)(H / 2 - 1) / (float)(H - 1), (float)(W / 2 - 1) / (float)(W - 1), (float)(H / 8 - 1) / (float)(H - 1), (float)(W / 8 - 1) / (float)(W - 1),
                    (float)(H / 32 - 1) / (float)(H - 1), (float)(W / 32 - 1) / (float)(W - 1)};
         KPB_LAUNCH(ctx, "alike_head_score", alike_score_lin, dim3(cdiv(H * W, 256), batch), dim3(256), 0, st, la);
@@ -2146,7 +2138,7 @@ int AlikeNet::desc_at(const float* pts_dev, int pts_cols, int max_n, const int32
 {
     if (B == 0) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_desc_at: no forward has run");
     const int kpw = (long long)B * max_n >= 32768 ? 8 : 1;
-    DescAtArgs a{head_args(nullptr, nullptr), pts_dev, n_dev, out_dev, pts_cols, max_n, kpw};
+    DescAtArgs a{HeadArgs{x1, a2, a3, a4, kh.agg[1], kh.whT, kh.wsc, nullptr, nullptr, H, W}, pts_dev, n_dev, out_dev, pts_cols, max_n, kpw};
     KPB_LAUNCH(ctx, "alike_desc_at", alike_desc_at, dim3(cdiv(max_n, 4 * kpw), B), dim3(256), 0, ctx->stream, a);
     KPB_HIP(ctx, hipGetLastError());
     return KPB_OK;
@@ -2169,7 +2161,7 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         if (!bl.get(nd.n, nd.d))
             return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not ALIKE-t shaped "
                             "(this build supports c1..c4 = 8,16,32,64, dim = 64)", nd.n);
-    AlikeNet* net = new AlikeNet();
+    auto net = std::make_unique<AlikeNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_ALIKE; net->dim = dim; net->desc_div = 1;
     WeightStage ws;
     std::vector<float> tmp;
@@ -2186,8 +2178,8 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             const float s1 = weight_scale_h(w1, 8 * 27), s2 = weight_scale_h(w2, 8 * 72);
             ws.put("b1c1.pairs", pack_b1c1_pairs(w1, s1));
             ws.put("b1c2.pairs", pack_b1c2_pairs(w2, s2));
-            net->k["b1c1.inv_ws"] = 1.0f / s1; net->k["b1c2.inv_ws"] = 1.0f / s2;
-            net->k["b1c1.l1"] = l1_rows(w1, 8, 27); net->k["b1c1.bmax"] = max_abs(bl.get("b1c1.b", {c1}), 8);
+            net->k1.inv_ws1 = 1.0f / s1; net->k1.inv_ws2 = 1.0f / s2;
+            net->k1.l1_c1 = l1_rows(w1, 8, 27); net->k1.bmax_c1 = max_abs(bl.get("b1c1.b", {c1}), 8);
         }
         ws.put_raw("b1c2.b", bl.get("b1c2.b", {c1}), 8);
     }
@@ -2218,19 +2210,20 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         for (int i = 0; i < 16; ++i) tmp[i] = b2[i] + bd[i];
         ws.put("b2c2.bsum", tmp);
         ws.put("agg2.h16", pack_1x1_h16(wa, sa));
-        net->k["b2c1.inv_ws"] = 1.0f / s1; net->k["b2c2.inv_ws"] = 1.0f / s2; net->k["agg2.inv_ws"] = 1.0f / sa;
-        net->k["b2c1.l1"] = l1_rows(w1, 16, 72); net->k["b2c1.bmax"] = max_abs(bl.get("b2c1.b", {c2}), 16);
-        net->k["b2c2.l1"] = l1_rows(w2, 16, 144); net->k["b2ds.l1"] = l1_rows(wd, 16, 8); net->k["b2c2.bsummax"] = max_abs(tmp.data(), 16);
-        net->k["agg1.l1"] = l1_rows(bl.get("agg1.w", {dim / 4, c1}), 16, 8);
+        net->k2.inv_ws1 = 1.0f / s1; net->k2.inv_ws2 = 1.0f / s2; net->k2.inv_wsa = 1.0f / sa;
+        net->k2.l1_c1 = l1_rows(w1, 16, 72); net->k2.bmax_c1 = max_abs(bl.get("b2c1.b", {c2}), 16);
+        net->k2.l1_c2 = l1_rows(w2, 16, 144); net->k2.l1_ds = l1_rows(wd, 16, 8); net->k2.bmax_sum = max_abs(tmp.data(), 16);
+        net->kh.l1_agg1 = l1_rows(bl.get("agg1.w", {dim / 4, c1}), 16, 8);
     }
+    // both return 1 / the power-of-two scale the split-f16 pack was made with (ConvM::unscale)
     auto put_mfma = [&](const char* name, const float* w, int cout, int cin, int ntb) {
         if (conv_mfma_use_h16()) {
             const float sc = weight_scale_h(w, (size_t)cout * cin * 9);
             ws.put(name, pack_mfma_h(w, cout, cin, 3, 32, ntb, sc));
-            ws.wscale[name] = sc;
-        } else {
-            ws.put(name, pack_mfma(w, cout, cin, 3, 32, ntb));
+            return 1.0f / sc;
         }
+        ws.put(name, pack_mfma(w, cout, cin, 3, 32, ntb));
+        return 1.0f;
     };
     auto put_c1ds = [&](const char* name, const float* w1, const float* b1, const float* wds, const float* bds, int cout, int cin) {
         // OIHW [2 cout][cin][3][3]: rows 0 .. cout-1 = conv1, rows cout .. = the 1x1 identity branch on the centre tap
@@ -2241,18 +2234,17 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             bb[o] = b1[o]; bb[cout + o] = bds[o];
         }
         const float sc = weight_scale_h(w.data(), w.size());
-        const std::string k = std::string(name) + ".h";
-        ws.put(k, pack_mfma_h(w.data(), 2 * cout, cin, 3, cin == 16 ? 16 : 32, 2, sc));
-        ws.wscale[k] = sc;
+        ws.put(std::string(name) + ".h", pack_mfma_h(w.data(), 2 * cout, cin, 3, cin == 16 ? 16 : 32, 2, sc));
         ws.put(std::string(name) + ".hb", bb);
+        return 1.0f / sc;
     };
     if (conv_mfma_use_h16()) {
-        put_c1ds("b3c1", bl.get("b3c1.w", {c3, c2, 3, 3}), bl.get("b3c1.b", {c3}), bl.get("b3ds.w", {c3, c2}), bl.get("b3ds.b", {c3}), 32, 16);
-        put_c1ds("b4c1", bl.get("b4c1.w", {c4, c3, 3, 3}), bl.get("b4c1.b", {c4}), bl.get("b4ds.w", {c4, c3}), bl.get("b4ds.b", {c4}), 64, 32);
+        net->blk[3].un1 = put_c1ds("b3c1", bl.get("b3c1.w", {c3, c2, 3, 3}), bl.get("b3c1.b", {c3}), bl.get("b3ds.w", {c3, c2}), bl.get("b3ds.b", {c3}), 32, 16);
+        net->blk[4].un1 = put_c1ds("b4c1", bl.get("b4c1.w", {c4, c3, 3, 3}), bl.get("b4c1.b", {c4}), bl.get("b4ds.w", {c4, c3}), bl.get("b4ds.b", {c4}), 64, 32);
     }
-    put_mfma("b3c2.wp", bl.get("b3c2.w", {c3, c3, 3, 3}), 32, 32, 1);
+    net->blk[3].un2 = put_mfma("b3c2.wp", bl.get("b3c2.w", {c3, c3, 3, 3}), 32, 32, 1);
     ws.put("b3c2.bp", pad_bias(bl.get("b3c2.b", {c3}), 32, 32));
-    put_mfma("b4c2.wp", bl.get("b4c2.w", {c4, c4, 3, 3}), 64, 64, 2);
+    net->blk[4].un2 = put_mfma("b4c2.wp", bl.get("b4c2.w", {c4, c4, 3, 3}), 64, 64, 2);
     ws.put("b4c2.bp", pad_bias(bl.get("b4c2.b", {c4}), 64, 64));
     for (int i = 1; i <= 4; ++i) {
         char nm[16];
@@ -2269,7 +2261,7 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         float hmax = 0.0f;
         for (int o = 0; o < 64; ++o) for (int cc = 0; cc < 32; ++cc) hmax = std::max(hmax, std::fabs(hw[o * 64 + cc]));
         const float sh = weight_scale_h(&hmax, 1);
-        net->k["head.inv_ws"] = 1.0f / sh;
+        net->kh.inv_ws_h = 1.0f / sh;
         std::vector<uint16_t> hl(2 * 2 * 2 * 2 * 32 * 8);
         for (int kb = 0; kb < 2; ++kb) for (int nh = 0; nh < 2; ++nh) for (int hh = 0; hh < 2; ++hh) for (int n = 0; n < 32; ++n) for (int j = 0; j < 8; ++j) {
             // k slot (hh, j) of block kb: group 1 (up2 a2) keeps channel 8 hh + j; group 0 (agg1) is produced by an MFMA whose accumulator
@@ -2290,7 +2282,7 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         {
             const float* a1w = bl.get("agg1.w", {dim / 4, c1});            // [16][8]
             const float sa1 = weight_scale_h(a1w, 16 * 8);
-            net->k["agg1.inv_wa"] = 1.0f / sa1;
+            net->kh.inv_wa = 1.0f / sa1;
             std::vector<uint16_t> fr(2 * 64 * 8, 0);
             for (int o = 0; o < 16; ++o) for (int c = 0; c < 8; ++c) {
                 const float w = a1w[o * 8 + c] * sa1;
@@ -2304,7 +2296,26 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             ws.put("agg1.h16", tmp);
         }
     }
-    if (int rc = ws.upload(net)) { delete net; return rc; }
-    *out = net;
+    if (int rc = ws.upload(net.get())) return rc;
+    const bool h16 = conv_mfma_use_h16();
+    net->k1.w1 = ws.dev("b1c1.w"); net->k1.b1 = ws.dev("b1c1.b"); net->k1.w2 = ws.dev("b1c2.w"); net->k1.b2 = ws.dev("b1c2.b");
+    net->k1.w1pk = ws.dev<uint4>("b1c1.pairs"); net->k1.w2pk = ws.dev<uint4>("b1c2.pairs");
+    net->k2.w1pk = ws.dev<uint4>("b2c1.h16"); net->k2.w2pk = ws.dev<uint4>("b2c2.h16"); net->k2.wapk = ws.dev<uint4>("agg2.h16");
+    net->k2.b1 = ws.dev("b2c1.b"); net->k2.bsum = ws.dev("b2c2.bsum");
+    for (int i = 2; i <= 4; ++i) {
+        AlikeNet::Res& r = net->blk[i];
+        const std::string c1n = "b" + std::to_string(i) + "c1", c2n = "b" + std::to_string(i) + "c2", dsn = "b" + std::to_string(i) + "ds";
+        r.w1 = ws.dev(c1n + ".w"); r.b1 = ws.dev(c1n + ".b"); r.w2 = ws.dev(c2n + ".w"); r.b2 = ws.dev(c2n + ".b");
+        r.dsw = ws.dev(dsn + ".w"); r.dsb = ws.dev(dsn + ".b");
+        r.prof1 = "conv3x3_" + c1n; r.prof2 = "conv3x3_" + c2n;
+        if (i == 2) continue;
+        r.w2p = ws.dev(c2n + ".wp"); r.b2p = ws.dev(c2n + ".bp");
+        if (h16) { r.w1h = ws.dev(c1n + ".h"); r.b1h = ws.dev(c1n + ".hb"); }
+    }
+    for (int i = 1; i <= 4; ++i) net->kh.agg[i] = ws.dev("agg" + std::to_string(i) + ".w");
+    net->kh.whT = ws.dev("head.wT"); net->kh.wsc = ws.dev("head.ws");
+    net->kh.wh16 = ws.dev<uint4>("head.wh16"); net->kh.a1h16 = ws.dev<uint4>("agg1.h16");
+    if (int rc = ws.bound(ctx)) return rc;
+    *out = net.release();
     return KPB_OK;
 }

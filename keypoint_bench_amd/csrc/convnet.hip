@@ -708,6 +708,12 @@ struct Layer {      // one convolution of a network plan
     bool pool_out = false;      // the output max-pooled 2 x 2 (SuperPoint's MaxPool2d after conv1b / 2b / 3b)
     int cc = 32;    // channels per LDS chunk of conv_mfma (32, or 16 for stride 2 / CIN not a multiple of 32)
     int ntb = 2;    // 32-wide output tiles per workgroup
+    // what a launch needs of the staged weights, bound once at create: stage_layer leaves the host scalars, bind_layer the device pointers and the profile name
+    float unscale = 1.0f;               // split-f16 form: 1 / the power-of-two scale the pack was made with (conv_mfma_h)
+    float xb = 0.0f, xun = 1.0f;        // ntb == 5 (DISK up_3): the score channel's bias and 1 / the scale of its pack
+    const float *w = nullptr, *b = nullptr, *xw = nullptr;
+    const float* slope = nullptr;       // DISK: the PReLU slopes of the layer's input
+    std::string prof;                   // profile name of its launch
 };
 
 struct UpSrc { const float* src; int c; };      // ConvM::up_src, up_c
@@ -723,10 +729,11 @@ struct MfmaOpt {
     float l2_eps = 0.0f;                // > 0: F.normalize(eps = l2_eps) of every output row in the epilogue (XFeat block_fusion.2, split-f16 form)
 };
 
-int launch_mfma(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const MfmaOpt& o = {})
+int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const MfmaOpt& o = {})
 {
     const int S = L.stride, CC = L.cc, PAD = L.ks / 2;
-    ConvM a{.in = in, .out = out, .wp = net->wp((L.name + ".w").c_str()), .bias = net->wp((L.name + ".b").c_str()), .xf = o.xf,
+    const char* name = L.prof.c_str();
+    ConvM a{.in = in, .out = out, .wp = L.w, .bias = L.b, .xf = o.xf,
             .Hi = Hi, .Wi = Wi, .H = (Hi + 2 * PAD - L.ks) / S + 1, .W = (Wi + 2 * PAD - L.ks) / S + 1, .CIN = L.cin, .COUT = L.cout, .NCH = L.cin / CC,
             .relu = L.relu, .nblk = (L.cout + 32 * L.ntb - 1) / (32 * L.ntb), .istride = L.cin, .ostride = L.cout,
             .aux0 = reinterpret_cast<const float*>(o.unfold_mr), .unfold_w = o.unfold_w};
@@ -735,7 +742,7 @@ int launch_mfma(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, co
     hipStream_t st = ctx->stream;
     const bool x = o.xf != nullptr;
     if (conv_mfma_use_h16()) {
-        a.unscale = 1.0f / (net->wscale.at(L.name + ".w"));
+        a.unscale = L.unscale;
         if (L.ks == 1 && S == 1 && CC == 32 && !L.pool_out && !x && !o.pre) {     // 1x1: gemm_h
             const dim3 grid(cdiv(a.H * a.W, 128), 1, B * a.nblk), block(256);
             if (o.l2_eps > 0.0f) {
@@ -767,7 +774,7 @@ int launch_mfma(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, co
         if (L.ntb == 5) {
             // 129 = 4 x 32 + 1 (DISK up_3): four MFMA tiles (two workgroups of two: 64 accumulator registers, three waves per SIMD)
             // and the score channel on the VALU of the first workgroup
-            a.nblk = 2; a.xw = net->wp((L.name + ".xw").c_str()); a.xb = net->wscale.at(L.name + ".xb"); a.xun = 1.0f / net->wscale.at(L.name + ".xs"); a.xco = L.cout - 1;
+            a.nblk = 2; a.xw = L.xw; a.xb = L.xb; a.xun = L.xun; a.xco = L.cout - 1;
             f.xc = true;
         }
         return launch_conv_mfma_h<
@@ -786,11 +793,12 @@ int launch_mfma(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, co
 
 struct ValuSkip { const float* gray = nullptr; const float* w = nullptr; const float* b = nullptr; int n = 0; };     // ConvV::gray, skw, skb, skn
 
-int launch_valu(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const ValuSkip& skip = {})
+int launch_valu(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const ValuSkip& skip = {})
 {
+    const char* name = L.prof.c_str();
     ConvV a;
     a.gray = skip.gray; a.skw = skip.w; a.skb = skip.b; a.skn = skip.n;
-    a.in = in; a.out = out; a.w = net->wp((L.name + ".w").c_str()); a.bias = net->wp((L.name + ".b").c_str()); a.xf = nullptr;
+    a.in = in; a.out = out; a.w = L.w; a.bias = L.b; a.xf = nullptr;
     a.Hi = Hi; a.Wi = Wi; a.KS = L.ks; a.S = L.stride; a.PAD = L.ks / 2;
     a.H = (Hi + 2 * a.PAD - L.ks) / L.stride + 1; a.W = (Wi + 2 * a.PAD - L.ks) / L.stride + 1;
     a.CIN = L.cin; a.COUT = L.cout; a.COUT8 = ((L.cout + 7) / 8) * 8; a.relu = L.relu;
@@ -815,22 +823,22 @@ int launch_valu(kpb_ctx* ctx, const char* name, kpb_net* net, const Layer& L, co
     return KPB_OK;
 }
 
-void stage_layer(WeightStage& ws, const Layer& L, const float* w, const float* b)
+void stage_layer(WeightStage& ws, Layer& L, const float* w, const float* b)
 {
     if (L.mfma) {
         if (conv_mfma_use_h16() && L.ntb == 5) {       // cout = 4 x 32 + 1: the last channel goes to the VALU side of conv_mfma_h<XC>
             const int T = L.ks * L.ks, co = L.cout - 1;
             const float sc = weight_scale_h(w, (size_t)co * L.cin * T);
             ws.put(L.name + ".w", pack_mfma_h(w, co, L.cin, L.ks, L.cc, 2, sc));
-            ws.wscale[L.name + ".w"] = sc;
+            L.unscale = 1.0f / sc;
             const float xs = weight_scale_h(w + (size_t)co * L.cin * T, (size_t)L.cin * T);
             ws.put(L.name + ".xw", pack_xc_pairs(w + (size_t)co * L.cin * T, L.cin, T, xs));
-            ws.wscale[L.name + ".xs"] = xs;
-            ws.wscale[L.name + ".xb"] = b ? b[co] : 0.0f;     // a host-side scalar, carried with the scales
+            L.xun = 1.0f / xs;
+            L.xb = b ? b[co] : 0.0f;
         } else if (conv_mfma_use_h16()) {
             const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * L.ks * L.ks);
             ws.put(L.name + ".w", pack_mfma_h(w, L.cout, L.cin, L.ks, L.cc, L.ntb, sc));
-            ws.wscale[L.name + ".w"] = sc;
+            L.unscale = 1.0f / sc;
         } else {
             ws.put(L.name + ".w", pack_mfma(w, L.cout, L.cin, L.ks, L.cc, L.ntb));
         }
@@ -841,63 +849,63 @@ void stage_layer(WeightStage& ws, const Layer& L, const float* w, const float* b
     }
 }
 
+// after WeightStage::upload: the layer's device pointers, and its profile name (prefix + layer name: "sp_conv1b", "xf_block2.0", "disk_up3")
+void bind_layer(WeightStage& ws, Layer& L, const char* prefix, bool slope = false)
+{
+    L.w = ws.dev(L.name + ".w");
+    L.b = ws.dev(L.name + ".b");
+    if (L.mfma && L.ntb == 5 && conv_mfma_use_h16()) L.xw = ws.dev(L.name + ".xw");
+    if (slope) L.slope = ws.dev(L.name + ".slope");
+    L.prof = prefix + L.name;
+}
+
 // ================================================================================================ SuperPoint
+enum { SP_1A, SP_1B, SP_2A, SP_2B, SP_3A, SP_3B, SP_4A, SP_4B, SP_PA, SP_PB, SP_DA, SP_DB, SP_LAYERS };    // superpoint_create's plan order
+
 struct SuperPointNet : kpb_net {
-    std::map<std::string, Layer> L;
-    kpb_buf aux;                    // per-image maxima of the grey image (the scale conv1b's generated input is split at)
-    ~SuperPointNet() override { if (aux.p) (void)hipFree(aux.p); }
+    Layer L[SP_LAYERS];
+    float l1_1a = 0.0f, bmax_1a = 0.0f;     // |conv1a output| <= amax(gray) l1_1a + bmax_1a: the scale conv1b's generated input is split at
     int forward(const float* img, int batch, int H_, int W_, float* score_out, float* desc_out) override
     {
         if ((H_ % 8) || (W_ % 8)) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: SuperPoint needs H and W multiples of 8 (got %dx%d)", H_, W_);
         if (!desc_out) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: SuperPoint writes its 256 x H/8 x W/8 descriptor map; desc_out_dev is required");
         const int H = H_, W = W_, Hc = H / 8, Wc = W / 8;
         const size_t P = (size_t)H * W, B = batch;
-        // activations (floats per image)
-        const size_t n_gray = P, n_1a = P * 64, n_1b = P / 4 * 64, n_2a = P / 4 * 64, n_2b = P / 16 * 64, n_3a = P / 16 * 128,
-                     n_3b = P / 64 * 128, n_4a = P / 64 * 128, n_4b = P / 64 * 128, n_pa = P / 64 * 256, n_semi = P / 64 * 65, n_da = P / 64 * 256;
-        const size_t total = B * (n_gray + n_1a + n_1b + n_2a + n_2b + n_3a + n_3b + n_4a + n_4b + n_pa + n_semi + n_da);
-        if (int rc = kpb_reserve(ctx, act, total * sizeof(float))) return rc;
-        float* p = static_cast<float*>(act.p);
-        float* gray = p; p += B * n_gray;
-        float* x1a = p; p += B * n_1a;
-        float* x1b = p; p += B * n_1b;
-        float* x2a = p; p += B * n_2a;
-        float* x2b = p; p += B * n_2b;
-        float* x3a = p; p += B * n_3a;
-        float* x3b = p; p += B * n_3b;
-        float* x4a = p; p += B * n_4a;
-        float* x4b = p; p += B * n_4b;
-        float* cpa = p; p += B * n_pa;
-        float* semi = p; p += B * n_semi;
-        float* cda = p; p += B * n_da;
-        this->B = batch; this->H = H; this->W = W;
-        hipStream_t st = ctx->stream;
-        KPB_LAUNCH(ctx, "sp_rgb_sum", rgb_sum, dim3((unsigned)((P + 255) / 256), batch), dim3(256), 0, st, img, gray, P);
-        int rc;
         // conv1a (:44) is not launched on the split-f16 path: conv1b computes its channels from the gray image while it stages its tile
         // (conv_mfma_h<GEN>, r05), split at the scale of the bound amax(gray) l1 + bmax of conv1a's output.  r05's two earlier forms -- conv1a as
         // its own kernel handing over fp32 or pre-split halves, KPB_PRESPLIT=0 / 1 -- were measured, superseded and removed (r06).
         const bool fused = conv_mfma_use_h16();
-        PreSplit ps;
-        if (fused) {
-            if ((rc = kpb_reserve(ctx, aux, (size_t)batch * sizeof(unsigned)))) return rc;
-            unsigned* amax_gray = static_cast<unsigned*>(aux.p);
+        float *gray, *x1a, *x1b, *x2a, *x2b, *x3a, *x3b, *x4a, *x4b, *cpa, *semi, *cda;
+        unsigned* amax_gray;        // per-image maxima of the grey image (float bits)
+        if (int rc = kpb_carve(ctx, act, [&](Arena& a) {
+                gray = a.take(B * P);
+                x1a = fused ? nullptr : a.take(B * P * 64);
+                x1b = a.take(B * (P / 4) * 64); x2a = a.take(B * (P / 4) * 64); x2b = a.take(B * (P / 16) * 64);
+                x3a = a.take(B * (P / 16) * 128); x3b = a.take(B * (P / 64) * 128); x4a = a.take(B * (P / 64) * 128); x4b = a.take(B * (P / 64) * 128);
+                cpa = a.take(B * (P / 64) * 256); semi = a.take(B * (P / 64) * 65); cda = a.take(B * (P / 64) * 256);
+                amax_gray = fused ? a.take<unsigned>(B) : nullptr;
+            }))
+            return rc;
+        this->B = batch; this->H = H; this->W = W;
+        hipStream_t st = ctx->stream;
+        KPB_LAUNCH(ctx, "sp_rgb_sum", rgb_sum, dim3((unsigned)((P + 255) / 256), batch), dim3(256), 0, st, img, gray, P);
+        int rc;
+        const PreSplit ps{amax_gray, l1_1a, bmax_1a, L[SP_1A].w, L[SP_1A].b};
+        if (fused)
             KPB_LAUNCH(ctx, "sp_gray_amax", plane_abs_max, dim3(batch), dim3(1024), 0, st, gray, P, amax_gray);
-            ps.amax = amax_gray; ps.l1 = wscale.at("conv1a.l1"); ps.bmax = wscale.at("conv1a.bmax");
-            ps.gen_w = wp("conv1a.w"); ps.gen_b = wp("conv1a.b");
-        } else
-            KPB_LAUNCH(ctx, "sp_conv1a", conv1a_c64, dim3(cdiv(W, 16), cdiv(H, 32), batch), dim3(256), 0, st, gray, x1a, wp("conv1a.w"), wp("conv1a.b"), H, W, 32);   // :44
-        if ((rc = launch_mfma(ctx, "sp_conv1b", this, L.at("conv1b"), fused ? gray : x1a, x1b, batch, H, W, {.pre = fused ? &ps : nullptr}))) return rc;      // :45-46 (+pool)
-        if ((rc = launch_mfma(ctx, "sp_conv2a", this, L.at("conv2a"), x1b, x2a, batch, H / 2, W / 2))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_conv2b", this, L.at("conv2b"), x2a, x2b, batch, H / 2, W / 2))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_conv3a", this, L.at("conv3a"), x2b, x3a, batch, H / 4, W / 4))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_conv3b", this, L.at("conv3b"), x3a, x3b, batch, H / 4, W / 4))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_conv4a", this, L.at("conv4a"), x3b, x4a, batch, Hc, Wc))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_conv4b", this, L.at("conv4b"), x4a, x4b, batch, Hc, Wc))) return rc;
-        if ((rc = launch_mfma(ctx, "sp_convPa", this, L.at("convPa"), x4b, cpa, batch, Hc, Wc))) return rc;    // :56
-        if ((rc = launch_mfma(ctx, "sp_convPb", this, L.at("convPb"), cpa, semi, batch, Hc, Wc))) return rc;  // :57
-        if ((rc = launch_mfma(ctx, "sp_convDa", this, L.at("convDa"), x4b, cda, batch, Hc, Wc))) return rc;    // :59
-        if ((rc = launch_mfma(ctx, "sp_convDb", this, L.at("convDb"), cda, desc_out, batch, Hc, Wc))) return rc; // :60
+        else
+            KPB_LAUNCH(ctx, "sp_conv1a", conv1a_c64, dim3(cdiv(W, 16), cdiv(H, 32), batch), dim3(256), 0, st, gray, x1a, L[SP_1A].w, L[SP_1A].b, H, W, 32);   // :44
+        if ((rc = launch_mfma(ctx, L[SP_1B], fused ? gray : x1a, x1b, batch, H, W, {.pre = fused ? &ps : nullptr}))) return rc;      // :45-46 (+pool)
+        if ((rc = launch_mfma(ctx, L[SP_2A], x1b, x2a, batch, H / 2, W / 2))) return rc;
+        if ((rc = launch_mfma(ctx, L[SP_2B], x2a, x2b, batch, H / 2, W / 2))) return rc;
+        if ((rc = launch_mfma(ctx, L[SP_3A], x2b, x3a, batch, H / 4, W / 4))) return rc;
+        if ((rc = launch_mfma(ctx, L[SP_3B], x3a, x3b, batch, H / 4, W / 4))) return rc;
+        if ((rc = launch_mfma(ctx, L[SP_4A], x3b, x4a, batch, Hc, Wc))) return rc;
+        if ((rc = launch_mfma(ctx, L[SP_4B], x4a, x4b, batch, Hc, Wc))) return rc;
+        if ((rc = launch_mfma(ctx, L[SP_PA], x4b, cpa, batch, Hc, Wc))) return rc;    // :56
+        if ((rc = launch_mfma(ctx, L[SP_PB], cpa, semi, batch, Hc, Wc))) return rc;  // :57
+        if ((rc = launch_mfma(ctx, L[SP_DA], x4b, cda, batch, Hc, Wc))) return rc;    // :59
+        if ((rc = launch_mfma(ctx, L[SP_DB], cda, desc_out, batch, Hc, Wc))) return rc; // :60
         KPB_LAUNCH(ctx, "sp_l2norm", l2norm_nhwc, dim3((unsigned)((B * Hc * Wc + 3) / 4)), dim3(256), 0, st, desc_out, 256, B * Hc * Wc, 0.0f);
         KPB_LAUNCH(ctx, "sp_softmax_d2s", softmax65_d2s, dim3(cdiv(Hc * Wc, 4 * PXW), batch), dim3(256), 0, st, semi, score_out, Hc, Wc, Hc * Wc);
         KPB_HIP(ctx, hipGetLastError());
@@ -914,19 +922,17 @@ int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         {"conv1a", 1, 64, 3, 1, false}, {"conv1b", 64, 64, 3, 1, true, true, true}, {"conv2a", 64, 64, 3, 1, true}, {"conv2b", 64, 64, 3, 1, true, true, true},
         {"conv3a", 64, 128, 3, 1, true}, {"conv3b", 128, 128, 3, 1, true, true, true}, {"conv4a", 128, 128, 3, 1, true}, {"conv4b", 128, 128, 3, 1, true},
         {"convPa", 128, 256, 3, 1, true}, {"convPb", 256, 65, 1, 1, true, false}, {"convDa", 128, 256, 3, 1, true}, {"convDb", 256, 256, 1, 1, true, false}};
-    SuperPointNet* net = new SuperPointNet();
+    static_assert(sizeof(plan) / sizeof(plan[0]) == SP_LAYERS, "one plan entry per SP_* index");
+    auto net = std::make_unique<SuperPointNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_SUPERPOINT; net->dim = 256; net->desc_div = 8;
     WeightStage ws;
-    for (const Layer& L : plan) {
+    for (int i = 0; i < SP_LAYERS; ++i) {
+        Layer& L = net->L[i] = plan[i];
         const float* w = bl.get((L.name + ".weight").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
         const float* b = bl.get((L.name + ".bias").c_str(), {(uint32_t)L.cout});
-        if (!w || !b) {
-            delete net;
-            return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SuperPoint tensor %s.weight/.bias missing or mis-shaped", L.name.c_str());
-        }
+        if (!w || !b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SuperPoint tensor %s.weight/.bias missing or mis-shaped", L.name.c_str());
         stage_layer(ws, L, w, b);
-        net->L.emplace(L.name, L);
-        if (L.name == "conv1a") {       // |conv1a output| <= amax(gray) l1 + bmax (its channels' largest L1 norm, its largest |bias|)
+        if (i == SP_1A) {       // |conv1a output| <= amax(gray) l1 + bmax (its channels' largest L1 norm, its largest |bias|)
             float l1 = 0.0f, bmax = 0.0f;
             for (int co = 0; co < L.cout; ++co) {
                 float r = 0.0f;
@@ -934,12 +940,14 @@ int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
                 l1 = std::max(l1, r);
                 bmax = std::max(bmax, std::fabs(b[co]));
             }
-            ws.wscale["conv1a.l1"] = l1 * 1.0001f;      // the bound is taken in fp32: a hair of slack for its own rounding
-            ws.wscale["conv1a.bmax"] = bmax;
+            net->l1_1a = l1 * 1.0001f;      // the bound is taken in fp32: a hair of slack for its own rounding
+            net->bmax_1a = bmax;
         }
     }
-    if (int rc = ws.upload(net)) { delete net; return rc; }
-    *out = net;
+    if (int rc = ws.upload(net.get())) return rc;
+    for (Layer& L : net->L) bind_layer(ws, L, "sp_");
+    if (int rc = ws.bound(ctx)) return rc;
+    *out = net.release();
     return KPB_OK;
 }
 
@@ -956,15 +964,19 @@ const XFeatPlan XF[] = {
     {"block_fusion.0", 64, 64, 3, 1, true}, {"block_fusion.1", 64, 64, 3, 1, true}, {"block_fusion.2", 64, 64, 1, 1, false},
     {"keypoint_head.0", 64, 64, 1, 1, true}, {"keypoint_head.1", 64, 64, 1, 1, true}, {"keypoint_head.2", 64, 64, 1, 1, true},
     {"keypoint_head.3", 64, 65, 1, 1, false}};
+enum { XF_B1_0, XF_B1_1, XF_B1_2, XF_B1_3, XF_B2_0, XF_B2_1, XF_B3_0, XF_B3_1, XF_B3_2, XF_B4_0, XF_B4_1, XF_B4_2, XF_B5_0, XF_B5_1, XF_B5_2, XF_B5_3,
+       XF_FUS_0, XF_FUS_1, XF_FUS_2, XF_KP_0, XF_KP_1, XF_KP_2, XF_KP_3, XF_LAYERS };     // XF's order
+static_assert(sizeof(XF) / sizeof(XF[0]) == XF_LAYERS, "one plan entry per XF_* index");
 
 struct XFeatNet : kpb_net {
-    std::map<std::string, Layer> L;
-    int conv(const char* n, const float* in, float* out, int batch, int Hi, int Wi)
+    Layer L[XF_LAYERS];
+    const float *skip_w = nullptr, *skip_b = nullptr;       // the skip connection's Conv2d(1, 24, 1)
+    // the fused matrix form of block1.2 + block1.3 (xfeat_block1_23): its fragments, biases and the constants of XfB1Args
+    struct { const uint4 *wA, *wB; const float *bA, *bB; float inv_wsA, inv_wsB, l1A, bmaxA; } b23 = {};
+    int conv(int i, const float* in, float* out, int batch, int Hi, int Wi)
     {
-        const Layer& l = L.at(n);
-        const std::string tag = std::string("xf_") + n;
-        if (l.mfma) return launch_mfma(ctx, tag.c_str(), this, l, in, out, batch, Hi, Wi);
-        return launch_valu(ctx, tag.c_str(), this, l, in, out, batch, Hi, Wi);
+        if (L[i].mfma) return launch_mfma(ctx, L[i], in, out, batch, Hi, Wi);
+        return launch_valu(ctx, L[i], in, out, batch, Hi, Wi);
     }
     int forward(const float* img, int batch, int H_, int W_, float* score_out, float* desc_out) override
     {
@@ -973,27 +985,28 @@ struct XFeatNet : kpb_net {
         const int H = H_, W = W_;
         const size_t P = (size_t)H * W, B = batch;
         const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16, H32 = H / 32, W32 = W / 32;
-        // floats per image of each activation
-        const size_t n_gray = P, n_a = P * 4, n_b = P / 4 * 8, n_c = P / 4 * 8, n_x1 = P / 16 * 32, n_t = P / 16 * 32, n_x2 = P / 16 * 32,
-                     n_8 = P / 64 * 64, n_16 = P / 256 * 64, n_32a = P / 1024 * 128, n_semi = P / 64 * 65;
-        const size_t total = B * (n_gray + n_a + n_b + n_c + n_x1 + n_t + n_x2 + 6 * n_8 + 3 * n_16 + 3 * n_32a + n_semi) + 64;
-        if (int rc = kpb_reserve(ctx, act, total * sizeof(float) + 16 * XF_STAT_BLOCKS * B + 8 * B)) return rc;
-        float* p = static_cast<float*>(act.p);
-        double* stats = reinterpret_cast<double*>(p); p += 4 * XF_STAT_BLOCKS * B;          // [B][XF_STAT_BLOCKS] pairs of doubles
-        float* mrbuf = p; p += 2 * B;                                                      // (mean, 1 / std) per image
-        float* gray = p; p += B * n_gray;
-        float* a1 = p; p += B * n_a; float* b1 = p; p += B * n_b; float* c1 = p; p += B * n_c;
-        float* x1 = p; p += B * n_x1; float* t2 = p; p += B * n_t; float* x2 = p; p += B * n_x2;
-        float* u8[6]; for (auto& q : u8) { q = p; p += B * n_8; }
-        float* u16[3]; for (auto& q : u16) { q = p; p += B * n_16; }
-        float* u32[3]; for (auto& q : u32) { q = p; p += B * n_32a; }
-        float* semi = p; p += B * n_semi;
+        const bool h16 = conv_mfma_use_h16();
+        double* stats;      // [B][XF_STAT_BLOCKS] (sum, sum of squares)
+        float2* mr;         // (mean, 1 / std) per image
+        float *gray, *b1, *c1, *x1, *t2, *x2, *u8[6], *u16[3], *u32[3], *semi;
+        if (int rc = kpb_carve(ctx, act, [&](Arena& a) {
+                stats = a.take<double>(B * XF_STAT_BLOCKS * 2);
+                mr = a.take<float2>(B);
+                gray = a.take(B * P);
+                b1 = a.take(B * (P / 4) * 8);
+                c1 = h16 ? nullptr : a.take(B * (P / 4) * 8);       // block1.2's output: in LDS in the split-f16 form (xfeat_block1_23)
+                x1 = a.take(B * (P / 16) * 32); t2 = a.take(B * (P / 16) * 32); x2 = a.take(B * (P / 16) * 32);
+                for (float*& q : u8) q = a.take(B * (P / 64) * 64);
+                for (float*& q : u16) q = a.take(B * (P / 256) * 64);
+                for (float*& q : u32) q = a.take(B * (P / 1024) * 128);
+                semi = a.take(B * (P / 64) * 65);
+            }))
+            return rc;
         this->B = batch; this->H = H; this->W = W;
         hipStream_t st = ctx->stream;
         KPB_LAUNCH(ctx, "xf_gray_stats", gray_mean_stats, dim3(XF_STAT_BLOCKS, batch), dim3(256), 0, st, img, gray, stats, P);
         // the split-f16 form normalises the grey image where it is read (three consumers) from per-image (mean, 1 / std)
-        const bool fold_norm = conv_mfma_use_h16() && L.at("keypoint_head.0").mfma && W % 8 == 0;
-        float2* mr = reinterpret_cast<float2*>(mrbuf);
+        const bool fold_norm = h16 && L[XF_KP_0].mfma && W % 8 == 0;
         KPB_LAUNCH(ctx, "xf_instnorm_params", instnorm_params, dim3(cdiv(batch, 256)), dim3(256), 0, st, stats, P, mr, batch);
         if (!fold_norm) {
             KPB_LAUNCH(ctx, "xf_instnorm", instnorm_apply, dim3((unsigned)((P / 4 + 255) / 256), batch), dim3(256), 0, st, gray, mr, P);
@@ -1002,66 +1015,62 @@ struct XFeatNet : kpb_net {
         int rc;
         // block1 (XFeat.py:30-35) and the skip connection (27-28, 127)
         {   // block1.0 + block1.1 fused: the 4-channel full-resolution map never reaches HBM (r04)
-            const Layer &l0 = L.at("block1.0"), &l1 = L.at("block1.1");
+            const Layer &l0 = L[XF_B1_0], &l1 = L[XF_B1_1];
             if (l0.mfma || l1.mfma || l0.cin != 1 || l0.cout != 4 || l0.ks != 3 || l0.stride != 1 || l1.cin != 4 || l1.cout != 8 || l1.ks != 3 || l1.stride != 2 ||
                 !l0.relu || !l1.relu)
                 return kpb_fail(ctx, KPB_E_INVALID, "XFeat block1.0 / block1.1: unexpected layer plan");
             KPB_LAUNCH(ctx, "xf_block1.01", xfeat_block1_01, dim3(cdiv(W2, XB_TW), cdiv(H2, XB_TH), batch), dim3(256), 0, st, gray, b1,
-                       wp("block1.0.w"), wp("block1.0.b"), wp("block1.1.w"), wp("block1.1.b"), H, W, mr);
-            (void)a1;
+                       l0.w, l0.b, l1.w, l1.b, H, W, mr);
         }
-        if (conv_mfma_use_h16()) {      // block1.2 + block1.3 + skip on the matrix cores, the map between them in LDS (xfeat_block1_23)
-            XfB1Args xa{b1, x1, reinterpret_cast<const uint4*>(wp("block1.23.wA")), reinterpret_cast<const uint4*>(wp("block1.23.wB")),
-                        wp("block1.23.bA"), wp("block1.23.bB"), gray, wp("skip1.w"), wp("skip1.b"), mr, H2, W2,
-                        wscale.at("block1.23.inv_wsA"), wscale.at("block1.23.inv_wsB"), wscale.at("block1.23.l1A"), wscale.at("block1.23.bmaxA")};
+        if (h16) {      // block1.2 + block1.3 + skip on the matrix cores, the map between them in LDS (xfeat_block1_23)
+            XfB1Args xa{b1, x1, b23.wA, b23.wB, b23.bA, b23.bB, gray, skip_w, skip_b, mr, H2, W2, b23.inv_wsA, b23.inv_wsB, b23.l1A, b23.bmaxA};
             KPB_LAUNCH(ctx, "xf_block1.23", xfeat_block1_23, dim3(cdiv(W4, XQ_TW), cdiv(H4, XQ_TH), batch), dim3(256), 0, st, xa);
-            (void)c1;
         } else {
-        if ((rc = conv("block1.2", b1, c1, batch, H2, W2))) return rc;
+        if ((rc = conv(XF_B1_2, b1, c1, batch, H2, W2))) return rc;
         // block1's last layer with the skip connection (AvgPool2d(4) -> Conv2d(1, 24, 1), XFeat.py:27-28, 127) added in its epilogue:
         // as a kernel of its own (r02: xf_skip_add, 1.12 ms per 512 images) it read x1 back and wrote it again
         {
-            const Layer& l = L.at("block1.3");
+            const Layer& l = L[XF_B1_3];
             if (l.mfma || l.ks != 3 || l.cin != 8 || l.stride != 2 || ((l.cout + 7) / 8) * 8 != 32)
                 return kpb_fail(ctx, KPB_E_INVALID, "XFeat block1.3: unexpected layer plan");
-            if ((rc = launch_valu(ctx, "xf_block1.3", this, l, c1, x1, batch, H2, W2, {.gray = gray, .w = wp("skip1.w"), .b = wp("skip1.b"), .n = 24}))) return rc;
+            if ((rc = launch_valu(ctx, l, c1, x1, batch, H2, W2, {.gray = gray, .w = skip_w, .b = skip_b, .n = 24}))) return rc;
         }
         }
-        if ((rc = conv("block2.0", x1, t2, batch, H4, W4))) return rc;
-        if ((rc = conv("block2.1", t2, x2, batch, H4, W4))) return rc;
-        if ((rc = conv("block3.0", x2, u8[0], batch, H4, W4))) return rc;
-        if ((rc = conv("block3.1", u8[0], u8[1], batch, H8, W8))) return rc;
-        if ((rc = conv("block3.2", u8[1], u8[2], batch, H8, W8))) return rc;          // x3
-        if ((rc = conv("block4.0", u8[2], u16[0], batch, H8, W8))) return rc;
-        if ((rc = conv("block4.1", u16[0], u16[1], batch, H16, W16))) return rc;
-        if ((rc = conv("block4.2", u16[1], u16[2], batch, H16, W16))) return rc;       // x4
-        if ((rc = conv("block5.0", u16[2], u32[0], batch, H16, W16))) return rc;
-        if ((rc = conv("block5.1", u32[0], u32[1], batch, H32, W32))) return rc;
-        if ((rc = conv("block5.2", u32[1], u32[2], batch, H32, W32))) return rc;
+        if ((rc = conv(XF_B2_0, x1, t2, batch, H4, W4))) return rc;
+        if ((rc = conv(XF_B2_1, t2, x2, batch, H4, W4))) return rc;
+        if ((rc = conv(XF_B3_0, x2, u8[0], batch, H4, W4))) return rc;
+        if ((rc = conv(XF_B3_1, u8[0], u8[1], batch, H8, W8))) return rc;
+        if ((rc = conv(XF_B3_2, u8[1], u8[2], batch, H8, W8))) return rc;          // x3
+        if ((rc = conv(XF_B4_0, u8[2], u16[0], batch, H8, W8))) return rc;
+        if ((rc = conv(XF_B4_1, u16[0], u16[1], batch, H16, W16))) return rc;
+        if ((rc = conv(XF_B4_2, u16[1], u16[2], batch, H16, W16))) return rc;       // x4
+        if ((rc = conv(XF_B5_0, u16[2], u32[0], batch, H16, W16))) return rc;
+        if ((rc = conv(XF_B5_1, u32[0], u32[1], batch, H32, W32))) return rc;
+        if ((rc = conv(XF_B5_2, u32[1], u32[2], batch, H32, W32))) return rc;
         float* x5 = u32[0];                                                             // 64 channels reuse the 128-channel slot
-        if ((rc = conv("block5.3", u32[2], x5, batch, H32, W32))) return rc;
+        if ((rc = conv(XF_B5_3, u32[2], x5, batch, H32, W32))) return rc;
         KPB_LAUNCH(ctx, "xf_pyramid_sum", pyramid_sum, dim3(cdiv(H8 * W8 * 16, 256), batch), dim3(256), 0, st, u8[2], u16[2], x5, u8[3],
                    H8, W8, H16, W16, H32, W32);
-        if ((rc = conv("block_fusion.0", u8[3], u8[4], batch, H8, W8))) return rc;
-        if ((rc = conv("block_fusion.1", u8[4], u8[5], batch, H8, W8))) return rc;
-        if (conv_mfma_use_h16() && L.at("block_fusion.2").mfma) {     // F.normalize in the product's epilogue (a wave holds whole 64-channel rows)
-            if ((rc = launch_mfma(ctx, "xf_block_fusion.2", this, L.at("block_fusion.2"), u8[5], desc_out, batch, H8, W8, {.l2_eps = 1e-12f}))) return rc;
+        if ((rc = conv(XF_FUS_0, u8[3], u8[4], batch, H8, W8))) return rc;
+        if ((rc = conv(XF_FUS_1, u8[4], u8[5], batch, H8, W8))) return rc;
+        if (h16 && L[XF_FUS_2].mfma) {     // F.normalize in the product's epilogue (a wave holds whole 64-channel rows)
+            if ((rc = launch_mfma(ctx, L[XF_FUS_2], u8[5], desc_out, batch, H8, W8, {.l2_eps = 1e-12f}))) return rc;
         } else {
-        if ((rc = conv("block_fusion.2", u8[5], desc_out, batch, H8, W8))) return rc;
+        if ((rc = conv(XF_FUS_2, u8[5], desc_out, batch, H8, W8))) return rc;
         KPB_LAUNCH(ctx, "xf_l2norm", l2norm_nhwc, dim3((unsigned)((B * H8 * W8 + 4 * PXW - 1) / (4 * PXW))), dim3(256), 0, st, desc_out, 64, B * H8 * W8, 1e-12f);   // F.normalize
         }
         // keypoint head on the 8x8-unfolded normalised image (XFeat.py:138-139)
-        if (conv_mfma_use_h16() && L.at("keypoint_head.0").mfma && W % 8 == 0) {
+        if (fold_norm) {
             // the first layer reads the 8 x 8 cells straight from the normalised image (ConvM::unfold_w): as a kernel of its own the
             // unfolding wrote and re-read 0.63 GB per 512 images (xf_unfold8, 0.24 ms)
-            if ((rc = launch_mfma(ctx, "xf_keypoint_head.0", this, L.at("keypoint_head.0"), gray, u8[1], batch, H8, W8, {.unfold_w = W, .unfold_mr = mr}))) return rc;
+            if ((rc = launch_mfma(ctx, L[XF_KP_0], gray, u8[1], batch, H8, W8, {.unfold_w = W, .unfold_mr = mr}))) return rc;
         } else {
             KPB_LAUNCH(ctx, "xf_unfold8", unfold8, dim3(cdiv(H8 * W8 * 16, 256), batch), dim3(256), 0, st, gray, u8[0], H, W);
-            if ((rc = conv("keypoint_head.0", u8[0], u8[1], batch, H8, W8))) return rc;
+            if ((rc = conv(XF_KP_0, u8[0], u8[1], batch, H8, W8))) return rc;
         }
-        if ((rc = conv("keypoint_head.1", u8[1], u8[0], batch, H8, W8))) return rc;
-        if ((rc = conv("keypoint_head.2", u8[0], u8[1], batch, H8, W8))) return rc;
-        if ((rc = conv("keypoint_head.3", u8[1], semi, batch, H8, W8))) return rc;
+        if ((rc = conv(XF_KP_1, u8[1], u8[0], batch, H8, W8))) return rc;
+        if ((rc = conv(XF_KP_2, u8[0], u8[1], batch, H8, W8))) return rc;
+        if ((rc = conv(XF_KP_3, u8[1], semi, batch, H8, W8))) return rc;
         KPB_LAUNCH(ctx, "xf_softmax_d2s", softmax65_d2s, dim3(cdiv(H8 * W8, 4 * PXW), batch), dim3(256), 0, st, semi, score_out, H8, W8, H8 * W8);
         KPB_HIP(ctx, hipGetLastError());
         return KPB_OK;
@@ -1072,16 +1081,14 @@ struct XFeatNet : kpb_net {
 
 int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
-    XFeatNet* net = new XFeatNet();
+    auto net = std::make_unique<XFeatNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_XFEAT; net->dim = 64; net->desc_div = 8;
     WeightStage ws;
-    for (const XFeatPlan& q : XF) {
+    for (int i = 0; i < XF_LAYERS; ++i) {
+        const XFeatPlan& q = XF[i];
         const float* w = bl.get((std::string(q.name) + ".w").c_str(), {(uint32_t)q.cout, (uint32_t)q.cin, (uint32_t)q.ks, (uint32_t)q.ks});
         const float* b = bl.get((std::string(q.name) + ".b").c_str(), {(uint32_t)q.cout});
-        if (!w || !b) {
-            delete net;
-            return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat tensor %s.w/.b missing or mis-shaped", q.name);
-        }
+        if (!w || !b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat tensor %s.w/.b missing or mis-shaped", q.name);
         // the 24-channel stage (block1.3 out, block2, block3.0 in) is stored with 32 channels, the extra 8 are
         // exact zeros (zero weights, zero bias, ReLU), which puts block2 and block3.0 on the MFMA kernel
         const int cin = q.cin == 24 ? 32 : q.cin, cout = q.cout == 24 ? 32 : q.cout, T = q.ks * q.ks;
@@ -1092,21 +1099,18 @@ int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
                 for (int t = 0; t < T; ++t) wpad[((size_t)o * cin + c) * T + t] = w[((size_t)o * q.cin + c) * T + t];
         }
         w = wpad.data(); b = bpad.data();
-        Layer L{q.name, cin, cout, q.ks, q.stride, (cin % 32 == 0), q.relu};
+        Layer& L = net->L[i] = Layer{q.name, cin, cout, q.ks, q.stride, (cin % 32 == 0), q.relu};
         L.cc = q.stride == 2 ? 16 : 32;
         if (cout <= 32 && q.ks == 3 && q.stride == 1) L.ntb = 1;      // block2: one 32-wide output tile, not a half-empty pair
         stage_layer(ws, L, w, b);
-        net->L.emplace(L.name, L);
     }
     if (conv_mfma_use_h16()) {      // the fused matrix form of block1.2 + block1.3 (xfeat_block1_23)
         const float* wA = bl.get("block1.2.w", {8, 8, 3, 3});
         const float* bA = bl.get("block1.2.b", {8});
         const float* wB = bl.get("block1.3.w", {24, 8, 3, 3});
         const float* bB = bl.get("block1.3.b", {24});
-        if (!wA || !bA || !wB || !bB || !net->L.at("block1.2").relu || !net->L.at("block1.3").relu) {
-            delete net;
+        if (!wA || !bA || !wB || !bB || !net->L[XF_B1_2].relu || !net->L[XF_B1_3].relu)
             return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat block1.2 / block1.3: unexpected layer plan");
-        }
         const float scA = weight_scale_h(wA, 8 * 8 * 9), scB = weight_scale_h(wB, 24 * 8 * 9);
         ws.put("block1.23.wA", pack_xf_pairs(wA, scA));
         ws.put("block1.23.wB", pack_xf_s2(wB, 24, scB));
@@ -1119,18 +1123,25 @@ int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             l1 = std::max(l1, s1);
             bmax = std::max(bmax, std::fabs(bA[o]));
         }
-        ws.wscale["block1.23.inv_wsA"] = 1.0f / scA;
-        ws.wscale["block1.23.inv_wsB"] = 1.0f / scB;
-        ws.wscale["block1.23.l1A"] = l1 * 1.0001f;       // the bound is taken in fp32: a hair of slack for its own rounding
-        ws.wscale["block1.23.bmaxA"] = bmax;
+        net->b23.inv_wsA = 1.0f / scA;
+        net->b23.inv_wsB = 1.0f / scB;
+        net->b23.l1A = l1 * 1.0001f;       // the bound is taken in fp32: a hair of slack for its own rounding
+        net->b23.bmaxA = bmax;
     }
     const float* sw = bl.get("skip1.w", {24});
     const float* sb = bl.get("skip1.b", {24});
-    if (!sw || !sb) { delete net; return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat skip1 tensors missing"); }
+    if (!sw || !sb) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat skip1 tensors missing");
     ws.put_raw("skip1.w", sw, 24);
     ws.put_raw("skip1.b", sb, 24);
-    if (int rc = ws.upload(net)) { delete net; return rc; }
-    *out = net;
+    if (int rc = ws.upload(net.get())) return rc;
+    for (Layer& L : net->L) bind_layer(ws, L, "xf_");
+    net->skip_w = ws.dev("skip1.w"); net->skip_b = ws.dev("skip1.b");
+    if (conv_mfma_use_h16()) {
+        net->b23.wA = ws.dev<uint4>("block1.23.wA"); net->b23.wB = ws.dev<uint4>("block1.23.wB");
+        net->b23.bA = ws.dev("block1.23.bA"); net->b23.bB = ws.dev("block1.23.bB");
+    }
+    if (int rc = ws.bound(ctx)) return rc;
+    *out = net.release();
     return KPB_OK;
 }
 
@@ -1351,27 +1362,30 @@ __global__ __launch_bounds__(256) void disk_head(const float* __restrict__ feat,
     }
 }
 
+enum { DK_DOWN1, DK_DOWN2, DK_DOWN3, DK_DOWN4, DK_UP0, DK_UP1, DK_UP2, DK_UP3, DK_LAYERS };       // disk_create's plan order; down_0 is a kernel of its own
+
 struct DiskNet : kpb_net {
-    std::map<std::string, Layer> L;
+    Layer L[DK_LAYERS];
+    const float *down0_w = nullptr, *down0_b = nullptr;
     static constexpr int SUM_BLOCKS = 128;
-    int stats_xf(const float* t, size_t P, int C, const char* slope_name, double* sums, float* xf, int batch)
+    int stats_xf(const float* t, size_t P, int C, const float* slope, double* sums, float* xf, int batch)
     {
         hipStream_t st = ctx->stream;
         const int R = 512 / C > 0 ? 512 / C : 1;
         KPB_LAUNCH(ctx, "disk_chan_sums", chan_sums, dim3(SUM_BLOCKS, batch), dim3(C, R), (size_t)R * C * 2 * sizeof(double), st, t, sums, P, C, C, 0, nullptr);
-        KPB_LAUNCH(ctx, "disk_make_xf", make_xf, dim3(cdiv(batch * C, 256)), dim3(256), 0, st, sums, SUM_BLOCKS, wp(slope_name), xf, P, C, batch * C, nullptr);
+        KPB_LAUNCH(ctx, "disk_make_xf", make_xf, dim3(cdiv(batch * C, 256)), dim3(256), 0, st, sums, SUM_BLOCKS, slope, xf, P, C, batch * C, nullptr);
         return KPB_OK;
     }
     // the statistics of [up2(bot) | hor] (Cb + Ch channels at 2 Hb x 2 Wb) without the map: the upsampled channels from the half-resolution source
     // (up_chan_sums), the horizontal ones from their own tensor, into one row of partial pairs per block (r06)
-    int stats_xf_up(const float* bot, const float* hor, int Hb, int Wb, int Cb, int Ch, const char* slope_name, double* sums, float* mm, float* xf, int batch)
+    int stats_xf_up(const float* bot, const float* hor, int Hb, int Wb, int Cb, int Ch, const float* slope, double* sums, float* mm, float* xf, int batch)
     {
         hipStream_t st = ctx->stream;
         const int C = Cb + Ch, CQ = Cb / 4, RU = 256 / CQ, R = 512 / Ch > 0 ? 512 / Ch : 1;
         const size_t P = (size_t)4 * Hb * Wb;
         KPB_LAUNCH(ctx, "disk_up_chan_sums", up_chan_sums, dim3(SUM_BLOCKS, batch), dim3(CQ, RU), (size_t)RU * CQ * 8 * sizeof(double), st, bot, sums, Hb, Wb, Cb, C, 0, mm);
         KPB_LAUNCH(ctx, "disk_chan_sums", chan_sums, dim3(SUM_BLOCKS, batch), dim3(Ch, R), (size_t)R * Ch * 2 * sizeof(double), st, hor, sums, P, Ch, C, Cb, mm);
-        KPB_LAUNCH(ctx, "disk_make_xf", make_xf, dim3(cdiv(batch * C, 256)), dim3(256), 0, st, sums, SUM_BLOCKS, wp(slope_name), xf, P, C, batch * C, mm);
+        KPB_LAUNCH(ctx, "disk_make_xf", make_xf, dim3(cdiv(batch * C, 256)), dim3(256), 0, st, sums, SUM_BLOCKS, slope, xf, P, C, batch * C, mm);
         return KPB_OK;
     }
     int forward(const float* img, int batch, int H_, int W_, float* score_out, float* desc_out) override
@@ -1383,22 +1397,23 @@ struct DiskNet : kpb_net {
         if (!desc_out) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: DISK writes its 128 x H x W descriptor map; desc_out_dev is required");
         const int H = H_, W = W_;
         const size_t P = (size_t)H * W, B = batch;
-        // floats per image
-        const size_t n_in = P * 4, n_f1 = P * 16, n_p1 = P / 4 * 16, n_f2 = P / 4 * 32, n_p2 = P / 16 * 32, n_f3 = P / 16 * 64, n_p3 = P / 64 * 64,
-                     n_f4 = P / 64 * 64, n_p4 = P / 256 * 64, n_f5 = P / 256 * 64, n_c0 = P / 64 * 128, n_u0 = P / 64 * 64, n_c1 = P / 16 * 128,
-                     n_u1 = P / 16 * 64, n_c2 = P / 4 * 96, n_u2 = P / 4 * 64, n_c3 = conv_mfma_use_h16() ? 0 : P * 80 /* only the strict-fp32 path materialises [up(u2) | f1] */, n_lg = P * 129;
-        const size_t total = B * (n_in + n_f1 + n_p1 + n_f2 + n_p2 + n_f3 + n_p3 + n_f4 + n_p4 + n_f5 + n_c0 + n_u0 + n_c1 + n_u1 + n_c2 + n_u2 + n_c3 + n_lg)
-                             + B * SUM_BLOCKS * 128 * 4 + B * SUM_BLOCKS * 128 * 2 + B * 128 * 4 + 64;
-        if (int rc = kpb_reserve(ctx, act, total * sizeof(float))) return rc;
-        float* p = static_cast<float*>(act.p);
-        double* sums = reinterpret_cast<double*>(p); p += B * SUM_BLOCKS * 128 * 4;     // [B][SUM_BLOCKS][<= 128 channels] pairs of doubles: per-block partial sums
-        float* mm = p; p += B * SUM_BLOCKS * 128 * 2;                                      // [B][SUM_BLOCKS][<= 128 channels] (min, max): per-block ranges (stats_xf_up)
-        float* xf = p; p += B * 128 * 4;
-        auto take = [&](size_t n) { float* q = p; p += B * n; return q; };
-        float *in4 = take(n_in), *f1 = take(n_f1), *p1 = take(n_p1), *f2 = take(n_f2), *p2 = take(n_p2), *f3 = take(n_f3), *p3 = take(n_p3),
-              *f4 = take(n_f4), *p4 = take(n_p4), *f5 = take(n_f5), *c0 = take(n_c0), *u0 = take(n_u0), *c1 = take(n_c1), *u1 = take(n_u1),
-              *c2 = take(n_c2), *u2 = take(n_u2), *c3 = take(n_c3), *lg = take(n_lg);
-        (void)in4;
+        const bool fuse_up = conv_mfma_use_h16();        // r06: the concatenated decoder inputs of up_2 and up_3 are not written (profiles/r06_disk_fused_upsample_ab.txt)
+        double* sums;       // [B][SUM_BLOCKS][<= 128 channels] (sum, sum of squares): per-block partial sums
+        float *mm, *xf, *f1, *p1, *f2, *p2, *f3, *p3, *f4, *p4, *f5, *c0, *u0, *c1, *u1, *c2, *u2, *c3, *lg;
+        if (int rc = kpb_carve(ctx, act, [&](Arena& a) {
+                sums = a.take<double>(B * SUM_BLOCKS * 128 * 2);
+                mm = fuse_up ? a.take(B * SUM_BLOCKS * 128 * 2) : nullptr;      // [B][SUM_BLOCKS][<= 128 channels] (min, max): per-block ranges (stats_xf_up)
+                xf = a.take(B * 128 * 4);
+                f1 = a.take(B * P * 16); p1 = a.take(B * (P / 4) * 16); f2 = a.take(B * (P / 4) * 32); p2 = a.take(B * (P / 16) * 32);
+                f3 = a.take(B * (P / 16) * 64); p3 = a.take(B * (P / 64) * 64); f4 = a.take(B * (P / 64) * 64); p4 = a.take(B * (P / 256) * 64);
+                f5 = a.take(B * (P / 256) * 64); c0 = a.take(B * (P / 64) * 128); u0 = a.take(B * (P / 64) * 64); c1 = a.take(B * (P / 16) * 128);
+                u1 = a.take(B * (P / 16) * 64);
+                c2 = fuse_up ? nullptr : a.take(B * (P / 4) * 96);      // [up(u1) | f2] and [up(u2) | f1]: only the strict-fp32 path materialises them
+                u2 = a.take(B * (P / 4) * 64);
+                c3 = fuse_up ? nullptr : a.take(B * P * 80);
+                lg = a.take(B * P * 129);
+            }))
+            return rc;
         this->B = batch; this->H = H; this->W = W;
         hipStream_t st = ctx->stream;
         int rc;
@@ -1409,49 +1424,44 @@ struct DiskNet : kpb_net {
             KPB_LAUNCH(ctx, "disk_upsample_concat", upsample2_concat, dim3((unsigned)(((size_t)4 * hb * wb * ((cb + chh) / 4) + 255) / 256), batch), dim3(256), 0, st,
                        bot, hor, o, hb, wb, cb, chh);
         };
-        // down path (disk.py:233-250, 274-282).  down_0 has no norm / gate and reads the planar RGB image through a
-        // 3-channel NHWC repack done by conv_valu's generic addressing: repack first.
-        {
-            // [B,3,H,W] -> [B,H,W,3] is avoided: conv_valu reads NHWC, so down_0 uses the planar-input variant below
-        }
+        // down path (disk.py:233-250, 274-282).  down_0 has no norm / gate and reads the planar RGB image itself (disk_down0)
         if ((rc = launch_valu_planar(img, f1, batch, H, W))) return rc;
         pool(f1, p1, H, W, 16);
-        if ((rc = stats_xf(p1, P / 4, 16, "down1.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_down1", this, L.at("down1"), p1, f2, batch, H / 2, W / 2, {.xf = xf}))) return rc;
+        if ((rc = stats_xf(p1, P / 4, 16, L[DK_DOWN1].slope, sums, xf, batch))) return rc;
+        if ((rc = launch_mfma(ctx, L[DK_DOWN1], p1, f2, batch, H / 2, W / 2, {.xf = xf}))) return rc;
         pool(f2, p2, H / 2, W / 2, 32);
-        if ((rc = stats_xf(p2, P / 16, 32, "down2.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_down2", this, L.at("down2"), p2, f3, batch, H / 4, W / 4, {.xf = xf}))) return rc;
+        if ((rc = stats_xf(p2, P / 16, 32, L[DK_DOWN2].slope, sums, xf, batch))) return rc;
+        if ((rc = launch_mfma(ctx, L[DK_DOWN2], p2, f3, batch, H / 4, W / 4, {.xf = xf}))) return rc;
         pool(f3, p3, H / 4, W / 4, 64);
-        if ((rc = stats_xf(p3, P / 64, 64, "down3.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_down3", this, L.at("down3"), p3, f4, batch, H / 8, W / 8, {.xf = xf}))) return rc;
+        if ((rc = stats_xf(p3, P / 64, 64, L[DK_DOWN3].slope, sums, xf, batch))) return rc;
+        if ((rc = launch_mfma(ctx, L[DK_DOWN3], p3, f4, batch, H / 8, W / 8, {.xf = xf}))) return rc;
         pool(f4, p4, H / 8, W / 8, 64);
-        if ((rc = stats_xf(p4, P / 256, 64, "down4.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_down4", this, L.at("down4"), p4, f5, batch, H / 16, W / 16, {.xf = xf}))) return rc;
+        if ((rc = stats_xf(p4, P / 256, 64, L[DK_DOWN4].slope, sums, xf, batch))) return rc;
+        if ((rc = launch_mfma(ctx, L[DK_DOWN4], p4, f5, batch, H / 16, W / 16, {.xf = xf}))) return rc;
         // up path (disk.py:114-141, 284-288)
         upcat(f5, f4, c0, H / 16, W / 16, 64, 64);
-        if ((rc = stats_xf(c0, P / 64, 128, "up0.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_up0", this, L.at("up0"), c0, u0, batch, H / 8, W / 8, {.xf = xf}))) return rc;
+        if ((rc = stats_xf(c0, P / 64, 128, L[DK_UP0].slope, sums, xf, batch))) return rc;
+        if ((rc = launch_mfma(ctx, L[DK_UP0], c0, u0, batch, H / 8, W / 8, {.xf = xf}))) return rc;
         upcat(u0, f3, c1, H / 8, W / 8, 64, 64);
-        if ((rc = stats_xf(c1, P / 16, 128, "up1.slope", sums, xf, batch))) return rc;
-        if ((rc = launch_mfma(ctx, "disk_up1", this, L.at("up1"), c1, u1, batch, H / 4, W / 4, {.xf = xf}))) return rc;
-        const bool fuse_up = conv_mfma_use_h16();        // r06: the concatenated decoder inputs of up_2 and up_3 are not written (profiles/r06_disk_fused_upsample_ab.txt)
+        if ((rc = stats_xf(c1, P / 16, 128, L[DK_UP1].slope, sums, xf, batch))) return rc;
+        if ((rc = launch_mfma(ctx, L[DK_UP1], c1, u1, batch, H / 4, W / 4, {.xf = xf}))) return rc;
         if (fuse_up) {
-            if ((rc = stats_xf_up(u1, f2, H / 4, W / 4, 64, 32, "up2.slope", sums, mm, xf, batch))) return rc;
+            if ((rc = stats_xf_up(u1, f2, H / 4, W / 4, 64, 32, L[DK_UP2].slope, sums, mm, xf, batch))) return rc;
             const UpSrc up{u1, 64};
-            if ((rc = launch_mfma(ctx, "disk_up2", this, L.at("up2"), f2, u2, batch, H / 2, W / 2, {.xf = xf, .up = &up}))) return rc;
+            if ((rc = launch_mfma(ctx, L[DK_UP2], f2, u2, batch, H / 2, W / 2, {.xf = xf, .up = &up}))) return rc;
         } else {
             upcat(u1, f2, c2, H / 4, W / 4, 64, 32);
-            if ((rc = stats_xf(c2, P / 4, 96, "up2.slope", sums, xf, batch))) return rc;
-            if ((rc = launch_mfma(ctx, "disk_up2", this, L.at("up2"), c2, u2, batch, H / 2, W / 2, {.xf = xf}))) return rc;
+            if ((rc = stats_xf(c2, P / 4, 96, L[DK_UP2].slope, sums, xf, batch))) return rc;
+            if ((rc = launch_mfma(ctx, L[DK_UP2], c2, u2, batch, H / 2, W / 2, {.xf = xf}))) return rc;
         }
         if (fuse_up) {      // r06: [up(u2) | f1] is not written -- up_3 evaluates the upsampling while it stages, the statistics come from u2 and f1
-            if ((rc = stats_xf_up(u2, f1, H / 2, W / 2, 64, 16, "up3.slope", sums, mm, xf, batch))) return rc;
+            if ((rc = stats_xf_up(u2, f1, H / 2, W / 2, 64, 16, L[DK_UP3].slope, sums, mm, xf, batch))) return rc;
             const UpSrc up{u2, 64};
-            if ((rc = launch_mfma(ctx, "disk_up3", this, L.at("up3"), f1, lg, batch, H, W, {.xf = xf, .up = &up}))) return rc;
+            if ((rc = launch_mfma(ctx, L[DK_UP3], f1, lg, batch, H, W, {.xf = xf, .up = &up}))) return rc;
         } else {
             upcat(u2, f1, c3, H / 2, W / 2, 64, 16);
-            if ((rc = stats_xf(c3, P, 80, "up3.slope", sums, xf, batch))) return rc;
-            if ((rc = launch_mfma(ctx, "disk_up3", this, L.at("up3"), c3, lg, batch, H, W, {.xf = xf}))) return rc;
+            if ((rc = stats_xf(c3, P, 80, L[DK_UP3].slope, sums, xf, batch))) return rc;
+            if ((rc = launch_mfma(ctx, L[DK_UP3], c3, lg, batch, H, W, {.xf = xf}))) return rc;
         }
         KPB_LAUNCH(ctx, "disk_head", disk_head, dim3((unsigned)((B * P + 15) / 16)), dim3(256), 0, st, lg, desc_out, score_out, B * P);
         KPB_HIP(ctx, hipGetLastError());
@@ -1490,7 +1500,7 @@ __global__ __launch_bounds__(256) void disk_down0(const float* img, float* out, 
 
 int DiskNet::launch_valu_planar(const float* img, float* f1, int batch, int H, int W)
 {
-    KPB_LAUNCH(ctx, "disk_down0", disk_down0, dim3(cdiv(H * W, 256), 1, batch), dim3(256), 0, ctx->stream, img, f1, wp("down0.w"), wp("down0.b"), H, W);
+    KPB_LAUNCH(ctx, "disk_down0", disk_down0, dim3(cdiv(H * W, 256), 1, batch), dim3(256), 0, ctx->stream, img, f1, down0_w, down0_b, H, W);
     return KPB_OK;
 }
 
@@ -1498,10 +1508,10 @@ int DiskNet::launch_valu_planar(const float* img, float* f1, int batch, int H, i
 
 int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
-    DiskNet* net = new DiskNet();
+    auto net = std::make_unique<DiskNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_DISK; net->dim = 128; net->desc_div = 1;
     WeightStage ws;
-    auto fail = [&](const char* n) { delete net; return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: DISK tensor %s missing or mis-shaped", n); };
+    auto fail = [&](const char* n) { return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: DISK tensor %s missing or mis-shaped", n); };
     {   // down_0
         const float* w = bl.get("down0.w", {16, 3, 5, 5});
         const float* b = bl.get("down0.b", {16});
@@ -1513,8 +1523,10 @@ int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     }
     struct { const char* n; int cin, cout; } plan[] = {{"down1", 16, 32}, {"down2", 32, 64}, {"down3", 64, 64}, {"down4", 64, 64},
                                                        {"up0", 128, 64}, {"up1", 128, 64}, {"up2", 96, 64}};
-    for (auto& q : plan) {
-        Layer L{q.n, q.cin, q.cout, 5, 1, true, false};
+    static_assert(sizeof(plan) / sizeof(plan[0]) == DK_UP3, "one plan entry per DK_* index in front of up_3");
+    for (int i = 0; i < DK_UP3; ++i) {
+        const auto& q = plan[i];
+        Layer& L = net->L[i] = Layer{q.n, q.cin, q.cout, 5, 1, true, false};
         L.cc = (q.cin % 32 == 0) ? 32 : 16;
         const float* w = bl.get((L.name + ".w").c_str(), {(uint32_t)q.cout, (uint32_t)q.cin, 5, 5});
         const float* b = bl.get((L.name + ".b").c_str(), {(uint32_t)q.cout});
@@ -1522,19 +1534,21 @@ int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         if (!w || !b || !sl) return fail(q.n);
         stage_layer(ws, L, w, b);
         ws.put_raw(L.name + ".slope", sl, q.cin);
-        net->L.emplace(L.name, L);
     }
     {   // up_3: 80 -> 129 = 128 descriptor channels + the score logit, five 32-wide tiles in one workgroup
         const float* w = bl.get("up3.w", {129, 80, 5, 5});
         const float* b = bl.get("up3.b", {129});
         const float* sl = bl.get("up3.slope", {80});
         if (!w || !b || !sl) return fail("up3");
-        Layer L3{"up3", 80, 129, 5, 1, true, false}; L3.cc = 16; L3.ntb = 5;
+        Layer& L3 = net->L[DK_UP3] = Layer{"up3", 80, 129, 5, 1, true, false};
+        L3.cc = 16; L3.ntb = 5;
         stage_layer(ws, L3, w, b);
         ws.put_raw("up3.slope", sl, 80);
-        net->L.emplace("up3", L3);
     }
-    if (int rc = ws.upload(net)) { delete net; return rc; }
-    *out = net;
+    if (int rc = ws.upload(net.get())) return rc;
+    for (Layer& L : net->L) bind_layer(ws, L, "disk_", true);
+    net->down0_w = ws.dev("down0.w"); net->down0_b = ws.dev("down0.b");
+    if (int rc = ws.bound(ctx)) return rc;
+    *out = net.release();
     return KPB_OK;
 }

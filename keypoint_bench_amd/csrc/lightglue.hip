@@ -865,7 +865,7 @@ struct kpb_lg {
 
 namespace {
 
-struct LgNetShim : kpb_net {     // WeightStage::upload wants a kpb_net; only ctx / wdev / off are used
+struct LgNetShim : kpb_net {     // WeightStage::upload wants a kpb_net; only ctx / wdev are used
     int forward(const float*, int, int, int, float*, float*) override { return KPB_E_INVALID; }
 };
 
@@ -928,7 +928,7 @@ KPB_API int kpb_lg_create(kpb_ctx* ctx, const void* blob, size_t len, float desc
         if (conv_mfma_use_h16()) {
             const float sc = weight_scale_h(w, (size_t)cout * cin);
             ws.put(name + ".w", pack_mfma_h(w, (int)cout, (int)cin, 1, 32, 2, sc));
-            ws.wscale[name + ".w"] = sc;
+            lg->wscale[name + ".w"] = sc;
         } else {
             ws.put(name + ".w", pack_mfma(w, (int)cout, (int)cin, 1, 32, 2));
         }
@@ -953,7 +953,7 @@ KPB_API int kpb_lg_create(kpb_ctx* ctx, const void* blob, size_t len, float desc
         }
         const float sc = weight_scale_h(wr.data(), wr.size());
         ws.put(name + ".w", pack_mfma_h(wr.data(), (int)cout, (int)cin, 1, 32, 2, sc));
-        ws.wscale[name + ".w"] = sc;
+        lg->wscale[name + ".w"] = sc;
         ws.put(name + ".b", pad_bias(br.data(), (int)cout, 64));
         return true;
     };
@@ -999,7 +999,7 @@ KPB_API int kpb_lg_create(kpb_ctx* ctx, const void* blob, size_t len, float desc
     LgNetShim shim;
     shim.ctx = ctx;
     if (int rc = ws.upload(&shim)) { delete lg; return rc; }
-    lg->wdev = shim.wdev; lg->off = shim.off; lg->wscale = shim.wscale;
+    lg->wdev = shim.wdev; lg->off = ws.off;
     shim.wdev = nullptr;
     *out = lg;
     return KPB_OK;

@@ -3,26 +3,50 @@
 #include "kpb_common.h"
 
 #include <map>
+#include <memory>
 
 struct kpb_net {
     kpb_ctx* ctx = nullptr;
     int arch = 0;
     int dim = 0;        // descriptor channels
     int desc_div = 1;   // descriptor map is (H/desc_div) x (W/desc_div)
-    float* wdev = nullptr;                 // all repacked weights
-    std::map<std::string, size_t> off;     // name -> float offset in wdev
-    std::map<std::string, float> wscale;   // name -> power-of-two scale a split-f16 pack was made with (conv_mfma_h)
-    kpb_buf act;                           // activations of the last forward
+    float* wdev = nullptr;                 // all repacked weights: every network keeps typed pointers into it, bound once at create (WeightStage::dev)
+    kpb_buf act;                           // activations of the last forward, carved by kpb_carve
     int B = 0, H = 0, W = 0;
-    virtual ~kpb_net() {}
+    virtual ~kpb_net() { (void)hipFree(wdev); (void)hipFree(act.p); }      // on the context's device: kpb_net_destroy, or a create that failed part way
     virtual int forward(const float* img, int batch, int H, int W, float* score_out, float* desc_out) = 0;
     virtual int desc_at(const float* pts, int pts_cols, int max_n, const int32_t* n_dev, float* out)
     {
         (void)pts; (void)pts_cols; (void)max_n; (void)n_dev; (void)out;
         return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_desc_at: this network materialises its descriptor map; use kpb_sample");
     }
-    float* wp(const char* n) { return wdev + off.at(n); }
 };
+
+// The activations of one forward, carved from kpb_net::act.  A forward lists its buffers ONCE, as take() calls in a callable; kpb_carve runs the list
+// twice -- without a base to add the sizes up, then, after the reserve, to hand out the pointers -- so the total and the pointers cannot disagree.
+// Every piece starts on a 256-byte boundary (hipMalloc's own alignment; the rule WeightStage::put follows) and comes out typed.
+struct Arena {
+    char* base = nullptr;       // null: measuring
+    size_t off = 0;
+    template <class T = float> T* take(size_t n)
+    {
+        T* q = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (n * sizeof(T) + 255) / 256 * 256;
+        return q;
+    }
+};
+
+template <class List> int kpb_carve(kpb_ctx* ctx, kpb_buf& act, List&& list)
+{
+    Arena measure;
+    list(measure);
+    if (int rc = kpb_reserve(ctx, act, measure.off)) return rc;
+    static const bool log_alloc = getenv("KPB_LOG_ALLOC") && *getenv("KPB_LOG_ALLOC") == '1';      // what the forward asked for, beside kpb_reserve's own line
+    if (log_alloc) fprintf(stderr, "kpb_arena %zu\n", measure.off);
+    Arena bind{static_cast<char*>(act.p)};
+    list(bind);
+    return KPB_OK;
+}
 
 struct KpbwRec { char name[40]; uint32_t ndim; uint32_t dims[4]; uint32_t off; };
 
@@ -61,11 +85,13 @@ struct KpbwBlob {
     }
 };
 
-// host-side staging of repacked tensors; upload() copies them into one device allocation
+// host-side staging of repacked tensors; upload() copies them into one device allocation, after which dev() resolves a staged name to its device
+// pointer.  The stage lives inside a create function only: a network keeps the pointers, not the names.
 struct WeightStage {
     std::vector<float> host;
     std::map<std::string, size_t> off;
-    std::map<std::string, float> wscale;
+    const float* wdev = nullptr;
+    std::string missing;        // the first name dev() did not find
     void put(const std::string& name, const std::vector<float>& v)
     {
         while (host.size() % 64) host.push_back(0.0f);   // 256-byte alignment for scalar/vector loads
@@ -80,9 +106,19 @@ struct WeightStage {
             return kpb_fail(ctx, KPB_E_NOMEM, "kpb_net_create: weight allocation failed");
         if (hipMemcpy(net->wdev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
             return kpb_fail(ctx, KPB_E_HIP, "kpb_net_create: weight upload failed");
-        net->off = off;
-        net->wscale = wscale;
+        wdev = net->wdev;
         return KPB_OK;
+    }
+    template <class T = float> const T* dev(const std::string& name)
+    {
+        auto it = off.find(name);
+        if (it != off.end()) return reinterpret_cast<const T*>(wdev + it->second);
+        if (missing.empty()) missing = name;
+        return nullptr;
+    }
+    int bound(kpb_ctx* ctx) const      // after the last dev(): a name that did not resolve is a refused create, not a null pointer in a kernel's arguments
+    {
+        return missing.empty() ? KPB_OK : kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: no staged tensor %s to bind", missing.c_str());
     }
 };
 

@@ -3,20 +3,30 @@
 
 #define KPB_API extern "C" __attribute__((visibility("default")))
 
+// runs network code behind the C API: no C++ exception may cross it
+template <class F> static int guarded(kpb_ctx* ctx, const char* what, F&& f)
+{
+    try { return f(); }
+    catch (const std::bad_alloc&) { return kpb_fail(ctx, KPB_E_NOMEM, "%s: out of host memory", what); }
+    catch (const std::exception& e) { return kpb_fail(ctx, KPB_E_INVALID, "%s: %s", what, e.what()); }
+}
+
 KPB_API int kpb_net_create(kpb_ctx* ctx, int arch, const void* blob, size_t len, kpb_net** out)
 {
     if (!ctx || !out || !blob) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_create: null argument");
     *out = nullptr;
-    KpbwBlob bl;
-    if (!bl.parse(blob, len) || (int)bl.arch != arch) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: malformed .kpbw blob");
-    switch (arch) {
-    case KPB_ARCH_ALIKE: return alike_create(ctx, bl, out);
-    case KPB_ARCH_SUPERPOINT: return superpoint_create(ctx, bl, out);
-    case KPB_ARCH_XFEAT: return xfeat_create(ctx, bl, out);
-    case KPB_ARCH_DISK: return disk_create(ctx, bl, out);
-    case KPB_ARCH_R2D2: return r2d2_create(ctx, bl, out);
-    default: return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_create: unknown arch %d", arch);
-    }
+    return guarded(ctx, "kpb_net_create", [&] {
+        KpbwBlob bl;
+        if (!bl.parse(blob, len) || (int)bl.arch != arch) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: malformed .kpbw blob");
+        switch (arch) {
+        case KPB_ARCH_ALIKE: return alike_create(ctx, bl, out);
+        case KPB_ARCH_SUPERPOINT: return superpoint_create(ctx, bl, out);
+        case KPB_ARCH_XFEAT: return xfeat_create(ctx, bl, out);
+        case KPB_ARCH_DISK: return disk_create(ctx, bl, out);
+        case KPB_ARCH_R2D2: return r2d2_create(ctx, bl, out);
+        default: return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_create: unknown arch %d", arch);
+        }
+    });
 }
 
 KPB_API void kpb_net_destroy(kpb_net* net)
@@ -24,8 +34,6 @@ KPB_API void kpb_net_destroy(kpb_net* net)
     if (!net) return;
     (void)hipSetDevice(net->ctx->device);
     (void)hipStreamSynchronize(net->ctx->stream);
-    if (net->wdev) (void)hipFree(net->wdev);
-    if (net->act.p) (void)hipFree(net->act.p);
     delete net;
 }
 
@@ -41,7 +49,7 @@ KPB_API int kpb_net_forward(kpb_net* net, const float* img_dev, int batch, int H
     if (!img_dev || !score_out_dev || batch <= 0 || H <= 0 || W <= 0)
         return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: bad argument");
     KPB_HIP(ctx, hipSetDevice(ctx->device));
-    return net->forward(img_dev, batch, H, W, score_out_dev, desc_out_dev);
+    return guarded(ctx, "kpb_net_forward", [&] { return net->forward(img_dev, batch, H, W, score_out_dev, desc_out_dev); });
 }
 
 KPB_API int kpb_net_desc_at(kpb_net* net, const float* pts_dev, int pts_cols, int max_n, const int32_t* n_dev,
@@ -52,5 +60,5 @@ KPB_API int kpb_net_desc_at(kpb_net* net, const float* pts_dev, int pts_cols, in
     if (max_n == 0) return KPB_OK;
     if (!pts_dev || !out_dev || pts_cols < 2 || max_n < 0) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_desc_at: bad argument");
     KPB_HIP(ctx, hipSetDevice(ctx->device));
-    return net->desc_at(pts_dev, pts_cols, max_n, n_dev, out_dev);
+    return guarded(ctx, "kpb_net_desc_at", [&] { return net->desc_at(pts_dev, pts_cols, max_n, n_dev, out_dev); });
 }

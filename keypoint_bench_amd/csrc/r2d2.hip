@@ -85,10 +85,13 @@ constexpr int r2_cc_fp32(const R2Layer& L) { return L.ks == 2 ? 16 : 32; }      
 constexpr int r2_ntb_fp32(const R2Layer& L) { return L.cout == 32 ? 1 : 2; }
 
 struct R2d2Net : kpb_net {
-    int conv(const R2Layer& L, const float* in, float* out, int batch, int H, int W)
+    struct Bound { const float* w; const float* b; float unscale = 1.0f; } lay[9];      // R2D2_PLAN's layers: packed weights, bias, 1 / the split-f16 pack's scale
+    const float* head_w = nullptr;
+    const float* head_b = nullptr;
+    int conv(int i, const float* in, float* out, int batch, int H, int W)
     {
-        const std::string n = L.name;
-        ConvM a{.in = in, .out = out, .wp = wp((n + ".w").c_str()), .bias = wp((n + ".b").c_str()), .Hi = H, .Wi = W, .H = H, .W = W, .CIN = L.cin, .COUT = L.cout,
+        const R2Layer& L = R2D2_PLAN[i];
+        ConvM a{.in = in, .out = out, .wp = lay[i].w, .bias = lay[i].b, .Hi = H, .Wi = W, .H = H, .W = W, .CIN = L.cin, .COUT = L.cout,
                 .NCH = L.cin / 32, .relu = L.relu, .nblk = cdiv(L.cout, 64), .istride = L.cin, .ostride = L.cout};
         if (!conv_mfma_use_h16()) {
             const int cc = r2_cc_fp32(L), ntb = r2_ntb_fp32(L);
@@ -97,7 +100,7 @@ struct R2d2Net : kpb_net {
                                     CmForm{.ks = 3, .s = 1, .cc = 32, .dil = 4}, CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 4}, CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 8},
                                     CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 16}>(ctx, L.name, CmForm{.ks = L.ks, .s = 1, .cc = cc, .ntb = ntb, .dil = L.dil}, a, batch);
         }
-        a.unscale = 1.0f / wscale.at(n + ".w");
+        a.unscale = lay[i].unscale;
         if (L.ks == 2) {        // tap-gathered product: K = 4 taps x cin, 128 pixels x 64 output channels per workgroup
             a.NCH = 4 * (L.cin / 32); a.tap_dil = L.dil;
             KPB_LAUNCH(ctx, L.name, (gemm_h<2, 1, GE_PLAIN, false, 2>), dim3(cdiv(H * W, 128), 1, batch * a.nblk), dim3(256), 0, ctx->stream, a);
@@ -118,14 +121,14 @@ struct R2d2Net : kpb_net {
         const size_t P = (size_t)H * W, B = batch;
         // every layer runs at full resolution: two ping-pong maps of the widest layer (128 channels: 157 MB per 480 x 640 image each) carry the narrower early
         // maps too; conv8 writes into the caller's descriptor map, which the head then normalises in place
-        if (int rc = kpb_reserve(ctx, act, 2 * B * P * 128 * sizeof(float))) return rc;
-        float* pp[2] = {static_cast<float*>(act.p), static_cast<float*>(act.p) + B * P * 128};
+        float* pp[2];
+        if (int rc = kpb_carve(ctx, act, [&](Arena& a) { for (float*& q : pp) q = a.take(B * P * 128); })) return rc;
         this->B = batch; this->H = H; this->W = W;
         hipStream_t st = ctx->stream;
-        KPB_LAUNCH(ctx, "r2d2_conv0", r2d2_conv0, dim3((unsigned)((P + 255) / 256), 4, batch), dim3(256), 0, st, img, pp[0], wp("conv0.w"), wp("conv0.b"), H, W);
+        KPB_LAUNCH(ctx, "r2d2_conv0", r2d2_conv0, dim3((unsigned)((P + 255) / 256), 4, batch), dim3(256), 0, st, img, pp[0], lay[0].w, lay[0].b, H, W);
         for (int i = 1; i < 9; ++i)
-            if (int rc = conv(R2D2_PLAN[i], pp[(i - 1) & 1], i == 8 ? desc_out : pp[i & 1], batch, H, W)) return rc;
-        KPB_LAUNCH(ctx, "r2d2_head", r2d2_head, dim3((unsigned)((B * P + 15) / 16)), dim3(256), 0, st, desc_out, score_out, wp("head.w"), wp("head.b"), B * P);
+            if (int rc = conv(i, pp[(i - 1) & 1], i == 8 ? desc_out : pp[i & 1], batch, H, W)) return rc;
+        KPB_LAUNCH(ctx, "r2d2_head", r2d2_head, dim3((unsigned)((B * P + 15) / 16)), dim3(256), 0, st, desc_out, score_out, head_w, head_b, B * P);
         KPB_HIP(ctx, hipGetLastError());
         return KPB_OK;
     }
@@ -135,14 +138,12 @@ struct R2d2Net : kpb_net {
 
 int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
-    R2d2Net* net = new R2d2Net();
+    auto net = std::make_unique<R2d2Net>();
     net->ctx = ctx; net->arch = KPB_ARCH_R2D2; net->dim = 128; net->desc_div = 1;
     WeightStage ws;
-    auto bad = [&](const char* what) {
-        delete net;
-        return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: R2D2 tensor %s missing or mis-shaped", what);
-    };
-    for (const R2Layer& L : R2D2_PLAN) {
+    auto bad = [&](const char* what) { return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: R2D2 tensor %s missing or mis-shaped", what); };
+    for (int i = 0; i < 9; ++i) {
+        const R2Layer& L = R2D2_PLAN[i];
         const std::string n = L.name;
         const float* w = bl.get((n + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
         const float* b = bl.get((n + ".b").c_str(), {(uint32_t)L.cout});
@@ -157,7 +158,7 @@ int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         } else if (conv_mfma_use_h16()) {      // tap-major fragments, two n-tiles per workgroup: the same pack serves the halo form and the tap-gathered one
             const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * L.ks * L.ks);
             ws.put(n + ".w", pack_mfma_h(w, L.cout, L.cin, L.ks, 32, 2, sc));
-            ws.wscale[n + ".w"] = sc;
+            net->lay[i].unscale = 1.0f / sc;
             ws.put(n + ".b", pad_bias(b, L.cout, 64));
         } else {
             ws.put(n + ".w", pack_mfma(w, L.cout, L.cin, L.ks, r2_cc_fp32(L), r2_ntb_fp32(L)));
@@ -173,7 +174,13 @@ int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     hw.insert(hw.end(), sw, sw + 128);
     ws.put("head.w", hw);
     ws.put("head.b", hb);
-    if (int rc = ws.upload(net)) { delete net; return rc; }
-    *out = net;
+    if (int rc = ws.upload(net.get())) return rc;
+    for (int i = 0; i < 9; ++i) {
+        const std::string n = R2D2_PLAN[i].name;
+        net->lay[i].w = ws.dev(n + ".w"); net->lay[i].b = ws.dev(n + ".b");
+    }
+    net->head_w = ws.dev("head.w"); net->head_b = ws.dev("head.b");
+    if (int rc = ws.bound(ctx)) return rc;
+    *out = net.release();
     return KPB_OK;
 }
