@@ -523,8 +523,9 @@ __global__ __launch_bounds__(256) void lg_decide(DecideArgs a)
     if (!a.active_pair[b]) return;
     const int s0 = 2 * b, s1 = 2 * b + 1;
     const bool last = a.layer == NL - 1;
-    bool finish = last;
-    if (!last && a.do_stop) {
+    // a side the previous layer pruned to nothing: the reference leaves its loop before this layer (lightglue.py:553-554) and reports it as the last one, no match
+    bool finish = last || a.cnt[s0] == 0 || a.cnt[s1] == 0;
+    if (!finish && a.do_stop) {
         int unconf = 0;
         for (int side = 0; side < 2; ++side) {
             const int s = s0 + side, n = a.cnt[s];

@@ -30,6 +30,8 @@ GOLDEN_TESTS = [
     "tests/test_gpu_xfeat.py",
     "tests/test_gpu_disk.py",
     "tests/test_gpu_lightglue.py::test_lightglue_against_reference_golden",
+    # lg_flash / lg_rotary / lg_residual (and conv_mfma as the Linear) at the keypoint counts where the 32-key blocks and 128-query workgroups end
+    "tests/test_gpu_lightglue_counts.py",
     "tests/test_gpu_pipeline.py",
     # bench.py's variant_fp32 figure: the ALIKE configuration at the benchmark's 256 pairs
     "tests/test_gpu_bench_scale.py::test_bench_configuration_against_the_oracle_at_the_benchmark_batch[alike]",
