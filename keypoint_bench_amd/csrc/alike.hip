@@ -2296,7 +2296,7 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             ws.put("agg1.h16", tmp);
         }
     }
-    if (int rc = ws.upload(net.get())) return rc;
+    if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     const bool h16 = conv_mfma_use_h16();
     net->k1.w1 = ws.dev("b1c1.w"); net->k1.b1 = ws.dev("b1c1.b"); net->k1.w2 = ws.dev("b1c2.w"); net->k1.b2 = ws.dev("b1c2.b");
     net->k1.w1pk = ws.dev<uint4>("b1c1.pairs"); net->k1.w2pk = ws.dev<uint4>("b1c2.pairs");

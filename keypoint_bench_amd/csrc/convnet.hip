@@ -944,7 +944,7 @@ int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             net->bmax_1a = bmax;
         }
     }
-    if (int rc = ws.upload(net.get())) return rc;
+    if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     for (Layer& L : net->L) bind_layer(ws, L, "sp_");
     if (int rc = ws.bound(ctx)) return rc;
     *out = net.release();
@@ -1133,7 +1133,7 @@ int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     if (!sw || !sb) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat skip1 tensors missing");
     ws.put_raw("skip1.w", sw, 24);
     ws.put_raw("skip1.b", sb, 24);
-    if (int rc = ws.upload(net.get())) return rc;
+    if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     for (Layer& L : net->L) bind_layer(ws, L, "xf_");
     net->skip_w = ws.dev("skip1.w"); net->skip_b = ws.dev("skip1.b");
     if (conv_mfma_use_h16()) {
@@ -1545,7 +1545,7 @@ int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         stage_layer(ws, L3, w, b);
         ws.put_raw("up3.slope", sl, 80);
     }
-    if (int rc = ws.upload(net.get())) return rc;
+    if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     for (Layer& L : net->L) bind_layer(ws, L, "disk_", true);
     net->down0_w = ws.dev("down0.w"); net->down0_b = ws.dev("down0.b");
     if (int rc = ws.bound(ctx)) return rc;

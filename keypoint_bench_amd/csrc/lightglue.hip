@@ -852,23 +852,31 @@ __global__ void lg_init_out(int* out_k, int* out_stop, const int* stop, int B, i
 }  // namespace
 
 // ================================================================================================ host side
+// One Linear as the launches see it: packed weights and padded bias in kpb_lg::wdev, bound once by kpb_lg_create; unscale = 1 / (the power-of-two
+// weight scale of a split-f16 pack)
+struct LgLinear { const float *w = nullptr, *b = nullptr; float unscale = 1.0f; };
+
+struct LgLayer {
+    // split-f16 form: wqkv (rows in the order of lg_qkv_row) and toqkv (to_qk over to_v); strict fp32: wqkv, toqk, tov
+    LgLinear wqkv, toqkv, toqk, tov, sout, sffn0, sffn3, toout, cffn0, cffn3, fproj;
+    const float *sln_g = nullptr, *sln_b = nullptr, *cln_g = nullptr, *cln_b = nullptr;
+    const float *mw = nullptr, *mb = nullptr, *cw = nullptr, *cb = nullptr;       // cw / cb: every layer but the last
+};
+
 struct kpb_lg {
     kpb_ctx* ctx = nullptr;
     int input_dim = 256;
     float desc_scale = 8.0f;
-    float* wdev = nullptr;
-    std::map<std::string, size_t> off;
-    std::map<std::string, float> wscale;   // split-f16 packs: the power-of-two weight scale of each Linear
+    float* wdev = nullptr;                 // all repacked weights; the members below point into it
+    LgLinear input_proj;                   // w null: the descriptors are 256 wide already
+    const float* posenc_wr = nullptr;
+    LgLayer layer[NL];
     kpb_buf ws;
     int attn_f16 = 0;                      // kpb_lg_set_attention: 1 = the reference's GPU arithmetic (lg_flash_h<true>)
-    float* wp(const std::string& n) { return wdev + off.at(n); }
+    ~kpb_lg() { (void)hipFree(wdev); (void)hipFree(ws.p); }        // on the context's device: kpb_lg_destroy, or a create that failed part way
 };
 
 namespace {
-
-struct LgNetShim : kpb_net {     // WeightStage::upload wants a kpb_net; only ctx / wdev are used
-    int forward(const float*, int, int, int, float*, float*) override { return KPB_E_INVALID; }
-};
 
 // One Linear over the tokens of every sequence.  Split-f16 form: gemm_h, rows past cnt[s] neither read nor written; `epi` selects
 // the fused epilogue (conv_mfma.h GE_*) and `x` carries its operands.  Strict fp32 form: conv_mfma<LG_LINEAR_F32>, plain epilogue only.
@@ -879,13 +887,13 @@ struct LgEpi {
     const float* cosb = nullptr; const float* sinb = nullptr; float* out1 = nullptr; float* out2 = nullptr;   // GE_ROTARY (out1 also GE_SPLIT2)
 };
 
-int lg_linear(kpb_ctx* ctx, kpb_lg* lg, const char* tag, const std::string& name, int cin, int cout, const float* in, int istride,
+int lg_linear(kpb_ctx* ctx, const char* tag, const LgLinear& l, int cin, int cout, const float* in, int istride,
               float* out, int ostride, int ooff, int S, int MP, const int* active, const int* cnt, const LgEpi& x = LgEpi())
 {
-    ConvM a{.in = in, .out = out, .wp = lg->wp(name + ".w"), .bias = lg->wp(name + ".b"), .active = active, .Hi = MP / 16, .Wi = 16, .H = MP / 16, .W = 16,
+    ConvM a{.in = in, .out = out, .wp = l.w, .bias = l.b, .active = active, .Hi = MP / 16, .Wi = 16, .H = MP / 16, .W = 16,
             .CIN = cin, .COUT = cout, .NCH = cin / 32, .nblk = (cout + 63) / 64, .istride = istride, .ostride = ostride, .ooff = ooff};
     if (conv_mfma_use_h16()) {
-        a.unscale = 1.0f / (lg->wscale.at(name + ".w"));
+        a.unscale = l.unscale;
         a.rowcnt = cnt; a.res = x.res; a.rstride = x.rstride; a.aux0 = x.cosb; a.aux1 = x.sinb; a.out1 = x.out1; a.out2 = x.out2;
         // 128-row tiles: four workgroups per CU (8-15 % faster than 256-row tiles, r02)
         const dim3 grid(cdiv(MP, 128), 1, S * a.nblk);
@@ -916,94 +924,87 @@ KPB_API int kpb_lg_create(kpb_ctx* ctx, const void* blob, size_t len, float desc
 {
     if (!ctx || !blob || !out) return kpb_fail(ctx, KPB_E_INVALID, "kpb_lg_create: null argument");
     *out = nullptr;
-    KpbwBlob bl;
-    if (!bl.parse(blob, len) || bl.arch != KPB_ARCH_LIGHTGLUE) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_lg_create: malformed .kpbw blob");
-    kpb_lg* lg = new kpb_lg();
-    lg->ctx = ctx; lg->desc_scale = desc_scale;
-    WeightStage ws;
-    auto fail = [&](const std::string& n) { delete lg; return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_lg_create: tensor %s missing or mis-shaped", n.c_str()); };
-    auto linear = [&](const std::string& key, const std::string& name, uint32_t cout, uint32_t cin) -> bool {
-        const float* w = bl.get((key + ".weight").c_str(), {cout, cin});
-        const float* b = bl.get((key + ".bias").c_str(), {cout});
-        if (!w || !b) return false;
-        if (conv_mfma_use_h16()) {
-            const float sc = weight_scale_h(w, (size_t)cout * cin);
-            ws.put(name + ".w", pack_mfma_h(w, (int)cout, (int)cin, 1, 32, 2, sc));
-            lg->wscale[name + ".w"] = sc;
-        } else {
-            ws.put(name + ".w", pack_mfma(w, (int)cout, (int)cin, 1, 32, 2));
-        }
-        ws.put(name + ".b", pad_bias(b, (int)cout, 64));
-        return true;
-    };
-    // split-f16 form only: the rows of `key` in the order `perm` (GE_ROTARY), or `key` and `key2` stacked (GE_SPLIT2)
-    auto linear_rows = [&](const std::string& key, const std::string& key2, const std::string& name, uint32_t cout, uint32_t cin, bool permute) -> bool {
-        const uint32_t c1 = key2.empty() ? cout : cout / 2;
-        const float* w = bl.get((key + ".weight").c_str(), {c1, cin});
-        const float* b = bl.get((key + ".bias").c_str(), {c1});
-        const float* w2 = key2.empty() ? nullptr : bl.get((key2 + ".weight").c_str(), {c1, cin});
-        const float* b2 = key2.empty() ? nullptr : bl.get((key2 + ".bias").c_str(), {c1});
-        if (!w || !b || (!key2.empty() && (!w2 || !b2))) return false;
-        std::vector<float> wr((size_t)cout * cin), br(cout);
-        for (uint32_t o = 0; o < cout; ++o) {
-            const float* srcw = o < c1 ? w : w2;
-            const float* srcb = o < c1 ? b : b2;
-            const uint32_t r = o < c1 ? (permute ? (uint32_t)lg_qkv_row((int)o) : o) : o - c1;
-            std::memcpy(&wr[(size_t)o * cin], srcw + (size_t)r * cin, cin * sizeof(float));
-            br[o] = srcb[r];
-        }
-        const float sc = weight_scale_h(wr.data(), wr.size());
-        ws.put(name + ".w", pack_mfma_h(wr.data(), (int)cout, (int)cin, 1, 32, 2, sc));
-        lg->wscale[name + ".w"] = sc;
-        ws.put(name + ".b", pad_bias(br.data(), (int)cout, 64));
-        return true;
-    };
-    auto vec = [&](const std::string& key, const std::string& name, std::vector<uint32_t> dims) -> bool {
-        const float* v = bl.get(key.c_str(), dims);
-        if (!v) return false;
-        size_t n = 1; for (uint32_t d : dims) n *= d;
-        ws.put_raw(name, v, n);
-        return true;
-    };
-    {
-        auto it = bl.t.find("input_proj.weight");
-        if (it != bl.t.end()) {
+    return guarded(ctx, "kpb_lg_create", [&] {
+        KpbwBlob bl;
+        if (!bl.parse(blob, len) || bl.arch != KPB_ARCH_LIGHTGLUE) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_lg_create: malformed .kpbw blob");
+        auto lg = std::make_unique<kpb_lg>();
+        lg->ctx = ctx; lg->desc_scale = desc_scale;
+        WeightStage ws;
+        std::vector<std::pair<const float**, std::string>> binds;       // every staged tensor with the member it is bound to once the stage is on the device
+        auto fail = [&](const std::string& n) { return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_lg_create: tensor %s missing or mis-shaped", n.c_str()); };
+        // one Linear; split-f16 form also: the rows of `key` in the order of lg_qkv_row (GE_ROTARY), or `key` and `key2` stacked (GE_SPLIT2)
+        auto linear_rows = [&](const std::string& key, const std::string& key2, const std::string& name, LgLinear& dst, uint32_t cout, uint32_t cin,
+                               bool permute) -> bool {
+            const uint32_t c1 = key2.empty() ? cout : cout / 2;
+            const float* w = bl.get((key + ".weight").c_str(), {c1, cin});
+            const float* b = bl.get((key + ".bias").c_str(), {c1});
+            const float* w2 = key2.empty() ? nullptr : bl.get((key2 + ".weight").c_str(), {c1, cin});
+            const float* b2 = key2.empty() ? nullptr : bl.get((key2 + ".bias").c_str(), {c1});
+            if (!w || !b || (!key2.empty() && (!w2 || !b2))) return false;
+            std::vector<float> wr((size_t)cout * cin), br(cout);
+            for (uint32_t o = 0; o < cout; ++o) {
+                const float* srcw = o < c1 ? w : w2;
+                const float* srcb = o < c1 ? b : b2;
+                const uint32_t r = o < c1 ? (permute ? (uint32_t)lg_qkv_row((int)o) : o) : o - c1;
+                std::memcpy(&wr[(size_t)o * cin], srcw + (size_t)r * cin, cin * sizeof(float));
+                br[o] = srcb[r];
+            }
+            const bool h16 = conv_mfma_use_h16();
+            const float sc = h16 ? weight_scale_h(wr.data(), wr.size()) : 1.0f;
+            ws.put(name + ".w", h16 ? pack_mfma_h(wr.data(), (int)cout, (int)cin, 1, 32, 2, sc) : pack_mfma(wr.data(), (int)cout, (int)cin, 1, 32, 2));
+            ws.put(name + ".b", pad_bias(br.data(), (int)cout, 64));
+            dst.unscale = 1.0f / sc;
+            binds.insert(binds.end(), {{&dst.w, name + ".w"}, {&dst.b, name + ".b"}});
+            return true;
+        };
+        auto linear = [&](const std::string& key, const std::string& name, LgLinear& dst, uint32_t cout, uint32_t cin) {
+            return linear_rows(key, "", name, dst, cout, cin, false);
+        };
+        auto vec = [&](const std::string& key, const std::string& name, const float*& dst, std::vector<uint32_t> dims) -> bool {
+            const float* v = bl.get(key.c_str(), dims);
+            if (!v) return false;
+            size_t n = 1; for (uint32_t d : dims) n *= d;
+            ws.put_raw(name, v, n);
+            binds.push_back({&dst, name});
+            return true;
+        };
+        if (auto it = bl.t.find("input_proj.weight"); it != bl.t.end()) {
             lg->input_dim = (int)it->second.second[1];
-            if (lg->input_dim % 32 || !linear("input_proj", "input_proj", 256, (uint32_t)lg->input_dim)) return fail("input_proj");
+            if (lg->input_dim % 32 || !linear("input_proj", "input_proj", lg->input_proj, 256, (uint32_t)lg->input_dim)) return fail("input_proj");
         }
-    }
-    if (!vec("posenc.Wr.weight", "posenc.Wr", {32, 2})) return fail("posenc.Wr.weight");
-    for (int i = 0; i < NL; ++i) {
-        const std::string sa = "transformers." + std::to_string(i) + ".self_attn", ca = "transformers." + std::to_string(i) + ".cross_attn";
-        const std::string L = "L" + std::to_string(i);
-        // the self-attention q/k/v product and the cross-attention qk / v products: fused forms for split-f16 (see lg_linear)
-        if (conv_mfma_use_h16() ? (!linear_rows(sa + ".Wqkv", "", L + ".Wqkv_r", 768, 256, true) ||
-                                   !linear_rows(ca + ".to_qk", ca + ".to_v", L + ".toqkv", 512, 256, false))
-                                : (!linear(sa + ".Wqkv", L + ".Wqkv", 768, 256) || !linear(ca + ".to_qk", L + ".toqk", 256, 256) ||
-                                   !linear(ca + ".to_v", L + ".tov", 256, 256)))
-            return fail(L);
-        if (!linear(sa + ".out_proj", L + ".sout", 256, 256) ||
-            !linear(sa + ".ffn.0", L + ".sffn0", 512, 512) || !linear(sa + ".ffn.3", L + ".sffn3", 256, 512) ||
-            !vec(sa + ".ffn.1.weight", L + ".sln.g", {512}) || !vec(sa + ".ffn.1.bias", L + ".sln.b", {512}) ||
-            !linear(ca + ".to_out", L + ".toout", 256, 256) ||
-            !linear(ca + ".ffn.0", L + ".cffn0", 512, 512) || !linear(ca + ".ffn.3", L + ".cffn3", 256, 512) ||
-            !vec(ca + ".ffn.1.weight", L + ".cln.g", {512}) || !vec(ca + ".ffn.1.bias", L + ".cln.b", {512}))
-            return fail(L);
-        const std::string la = "log_assignment." + std::to_string(i);
-        if (!linear(la + ".final_proj", L + ".fproj", 256, 256) || !vec(la + ".matchability.weight", L + ".mw", {1, 256}) || !vec(la + ".matchability.bias", L + ".mb", {1}))
-            return fail(la);
-        if (i < NL - 1) {
-            const std::string tc = "token_confidence." + std::to_string(i) + ".token.0";
-            if (!vec(tc + ".weight", L + ".cw", {1, 256}) || !vec(tc + ".bias", L + ".cb", {1})) return fail(tc);
+        if (!vec("posenc.Wr.weight", "posenc.Wr", lg->posenc_wr, {32, 2})) return fail("posenc.Wr.weight");
+        for (int i = 0; i < NL; ++i) {
+            const std::string sa = "transformers." + std::to_string(i) + ".self_attn", ca = "transformers." + std::to_string(i) + ".cross_attn";
+            const std::string L = "L" + std::to_string(i);
+            LgLayer& ly = lg->layer[i];
+            // the self-attention q/k/v product and the cross-attention qk / v products: fused forms for split-f16 (see lg_linear)
+            if (conv_mfma_use_h16() ? (!linear_rows(sa + ".Wqkv", "", L + ".Wqkv_r", ly.wqkv, 768, 256, true) ||
+                                       !linear_rows(ca + ".to_qk", ca + ".to_v", L + ".toqkv", ly.toqkv, 512, 256, false))
+                                    : (!linear(sa + ".Wqkv", L + ".Wqkv", ly.wqkv, 768, 256) || !linear(ca + ".to_qk", L + ".toqk", ly.toqk, 256, 256) ||
+                                       !linear(ca + ".to_v", L + ".tov", ly.tov, 256, 256)))
+                return fail(L);
+            if (!linear(sa + ".out_proj", L + ".sout", ly.sout, 256, 256) ||
+                !linear(sa + ".ffn.0", L + ".sffn0", ly.sffn0, 512, 512) || !linear(sa + ".ffn.3", L + ".sffn3", ly.sffn3, 256, 512) ||
+                !vec(sa + ".ffn.1.weight", L + ".sln.g", ly.sln_g, {512}) || !vec(sa + ".ffn.1.bias", L + ".sln.b", ly.sln_b, {512}) ||
+                !linear(ca + ".to_out", L + ".toout", ly.toout, 256, 256) ||
+                !linear(ca + ".ffn.0", L + ".cffn0", ly.cffn0, 512, 512) || !linear(ca + ".ffn.3", L + ".cffn3", ly.cffn3, 256, 512) ||
+                !vec(ca + ".ffn.1.weight", L + ".cln.g", ly.cln_g, {512}) || !vec(ca + ".ffn.1.bias", L + ".cln.b", ly.cln_b, {512}))
+                return fail(L);
+            const std::string la = "log_assignment." + std::to_string(i);
+            if (!linear(la + ".final_proj", L + ".fproj", ly.fproj, 256, 256) || !vec(la + ".matchability.weight", L + ".mw", ly.mw, {1, 256}) ||
+                !vec(la + ".matchability.bias", L + ".mb", ly.mb, {1}))
+                return fail(la);
+            if (i < NL - 1) {
+                const std::string tc = "token_confidence." + std::to_string(i) + ".token.0";
+                if (!vec(tc + ".weight", L + ".cw", ly.cw, {1, 256}) || !vec(tc + ".bias", L + ".cb", ly.cb, {1})) return fail(tc);
+            }
         }
-    }
-    LgNetShim shim;
-    shim.ctx = ctx;
-    if (int rc = ws.upload(&shim)) { delete lg; return rc; }
-    lg->wdev = shim.wdev; lg->off = ws.off;
-    shim.wdev = nullptr;
-    *out = lg;
-    return KPB_OK;
+        if (int rc = ws.upload(ctx, &lg->wdev)) return rc;
+        for (auto& [member, name] : binds) *member = ws.dev(name);
+        if (int rc = ws.bound(ctx)) return rc;
+        *out = lg.release();
+        return KPB_OK;
+    });
 }
 
 KPB_API void kpb_lg_destroy(kpb_lg* lg)
@@ -1011,8 +1012,6 @@ KPB_API void kpb_lg_destroy(kpb_lg* lg)
     if (!lg) return;
     (void)hipSetDevice(lg->ctx->device);
     (void)hipStreamSynchronize(lg->ctx->stream);
-    if (lg->wdev) (void)hipFree(lg->wdev);
-    if (lg->ws.p) (void)hipFree(lg->ws.p);
     delete lg;
 }
 
@@ -1040,138 +1039,133 @@ KPB_API int kpb_lg_match(kpb_lg* lg, const float* pts0_dev, const float* pts1_de
     if (C != lg->input_dim) return kpb_fail(ctx, KPB_E_INVALID, "kpb_lg_match: descriptor maps have %d channels, the weights expect %d", C, lg->input_dim);
     if (C > 256) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_lg_match: input_dim %d > 256", C);
     KPB_HIP(ctx, hipSetDevice(ctx->device));
-    const int B = batch, S = 2 * B, MP = ((max_k + 127) / 128) * 128;
-    const size_t T = (size_t)S * MP;
-    // workspace carve (floats unless noted)
-    size_t need = 0;
-    auto take = [&](size_t n) { const size_t o = need; need += (n + 63) / 64 * 64; return o; };
-    const size_t o_kpx = take(T * 2), o_cos0 = take(T * NF), o_sin0 = take(T * NF), o_cos1 = take(T * NF), o_sin1 = take(T * NF),
-                 o_din = take(T * C), o_cat0 = take(T * 512), o_cat1 = take(T * 512), o_qkv = take(T * 768), o_q = take(T * D), o_k = take(T * D),
-                 o_v = take(T * D), o_ctx = take(T * D), o_h1 = take(T * 512), o_y = take(T * D), o_conf = take(T), o_msc = take(T), o_z = take(T),
-                 o_md = take(T * D), o_sim = take((size_t)B * MP * MP), o_mx = take(T), o_lg = take(T), o_bv = take(T),
-                 o_ind0 = take(T), o_ind1 = take(T), o_dst = take(T), o_bi = take(T), o_ints = take((size_t)8 * S + 64), o_ls = take(T),
-                 o_pmx = take((size_t)B * (MP / 32) * MP), o_psum = take((size_t)B * (MP / 32) * MP),      // column partials per chunk of LG_CROWS rows
-                 o_pbv = take((size_t)B * (MP / 32) * MP), o_pbi = take((size_t)B * (MP / 32) * MP),
-                 o_kf = take(T * D), o_vf = take(T * D),      // K / V in MFMA operand order, (hi, lo) halves: 4 bytes per element
-                 o_kve = take((size_t)S * NH * (MP / 32) * 2);  // per 32-key block: exponents of the K and V scales
-    const bool fresh = need * sizeof(float) > lg->ws.cap;
-    if (int rc = kpb_reserve(ctx, lg->ws, need * sizeof(float))) return rc;
-    float* base = static_cast<float*>(lg->ws.p);
-    hipStream_t st = ctx->stream;
-    if (fresh) KPB_HIP(ctx, hipMemsetAsync(base, 0, need * sizeof(float), st));   // padded rows must stay finite
-    float *kpx = base + o_kpx, *cosb[2] = {base + o_cos0, base + o_cos1}, *sinb[2] = {base + o_sin0, base + o_sin1}, *din = base + o_din,
-          *cat[2] = {base + o_cat0, base + o_cat1}, *qkv = base + o_qkv, *q = base + o_q, *k = base + o_k, *v = base + o_v, *cx = base + o_ctx,
-          *h1 = base + o_h1, *y = base + o_y, *conf = base + o_conf, *msc = base + o_msc, *zlog = base + o_z, *md = base + o_md, *sim = base + o_sim,
-          *mxo = base + o_mx, *lgo = base + o_lg, *bestv = base + o_bv, *lso = base + o_ls, *pmx = base + o_pmx, *psum = base + o_psum, *pbv = base + o_pbv;
-    int* pbi = reinterpret_cast<int*>(base + o_pbi);
-    const int NCHK = MP / LG_CROWS;
-    static_assert(LG_CROWS == 32, "the partial arrays are carved for 32-row chunks");
-    int *ind[2] = {reinterpret_cast<int*>(base + o_ind0), reinterpret_cast<int*>(base + o_ind1)}, *dst = reinterpret_cast<int*>(base + o_dst),
-        *besti = reinterpret_cast<int*>(base + o_bi), *ints = reinterpret_cast<int*>(base + o_ints);
-    uint4 *kfrag = reinterpret_cast<uint4*>(base + o_kf), *vfrag = reinterpret_cast<uint4*>(base + o_vf);
-    int* kvexp = reinterpret_cast<int*>(base + o_kve);
-    int *cnt = ints, *cnt_orig = ints + S, *newcnt = ints + 2 * S, *active_seq = ints + 3 * S, *fin_seq = ints + 4 * S, *active_pair = ints + 5 * S,
-        *fin_pair = ints + 5 * S + B, *stop = ints + 6 * S, *done_pair = ints + 6 * S + B;
+    return guarded(ctx, "kpb_lg_match", [&] {
+        const int B = batch, S = 2 * B, MP = ((max_k + 127) / 128) * 128;
+        const size_t T = (size_t)S * MP;
+        const int NCHK = MP / LG_CROWS;
+        static_assert(LG_CROWS == 32, "the partial arrays are carved for 32-row chunks");
+        const size_t PN = (size_t)B * NCHK * MP;      // column partials per chunk of LG_CROWS rows
+        float *kpx, *cosb[2], *sinb[2], *din, *cat[2], *qkv, *q, *k, *v, *cx, *h1, *y, *conf, *msc, *zlog, *md, *sim, *mxo, *lgo, *bestv, *lso, *pmx, *psum, *pbv;
+        int *ind[2], *dst, *besti, *ints, *pbi, *kvexp;
+        uint4 *kfrag, *vfrag;
+        const size_t cap0 = lg->ws.cap;
+        if (int rc = kpb_carve(ctx, lg->ws, [&](Arena& a) {
+                kpx = a.take(T * 2); cosb[0] = a.take(T * NF); sinb[0] = a.take(T * NF); cosb[1] = a.take(T * NF); sinb[1] = a.take(T * NF);
+                din = a.take(T * C); cat[0] = a.take(T * 512); cat[1] = a.take(T * 512); qkv = a.take(T * 768); q = a.take(T * D); k = a.take(T * D);
+                v = a.take(T * D); cx = a.take(T * D); h1 = a.take(T * 512); y = a.take(T * D); conf = a.take(T); msc = a.take(T); zlog = a.take(T);
+                md = a.take(T * D); sim = a.take((size_t)B * MP * MP); mxo = a.take(T); lgo = a.take(T); bestv = a.take(T);
+                ind[0] = a.take<int>(T); ind[1] = a.take<int>(T); dst = a.take<int>(T); besti = a.take<int>(T); ints = a.take<int>((size_t)8 * S + 64);
+                lso = a.take(T); pmx = a.take(PN); psum = a.take(PN); pbv = a.take(PN); pbi = a.take<int>(PN);
+                kfrag = a.take<uint4>(T * D / 4); vfrag = a.take<uint4>(T * D / 4);      // K / V in MFMA operand order, (hi, lo) halves: 4 bytes per element
+                kvexp = a.take<int>((size_t)S * NH * (MP / 32) * 2);                     // per 32-key block: exponents of the K and V scales
+            }))
+            return rc;
+        hipStream_t st = ctx->stream;
+        // it grew: padded rows must stay finite.  All of cap is zeroed, kpb_reserve's 1/8 slack included: a later, slightly larger call that fits in
+        // the slack carves rows from it and, not having grown, gets no fill of its own
+        if (lg->ws.cap != cap0) KPB_HIP(ctx, hipMemsetAsync(lg->ws.p, 0, lg->ws.cap, st));
+        int *cnt = ints, *cnt_orig = ints + S, *newcnt = ints + 2 * S, *active_seq = ints + 3 * S, *fin_seq = ints + 4 * S, *active_pair = ints + 5 * S,
+            *fin_pair = ints + 5 * S + B, *stop = ints + 6 * S, *done_pair = ints + 6 * S + B;
 
-    KPB_LAUNCH(ctx, "lg_init_out", lg_init_out, dim3(cdiv(B, 256)), dim3(256), 0, st, out_k_dev, out_stop_dev, stop, B, 0);
-    PrepArgs pa{pts0_dev, pts1_dev, n0_dev, n1_dev, lg->wp("posenc.Wr"), kpx, cosb[0], sinb[0], ind[0], cnt, cnt_orig, active_seq, active_pair, stop, done_pair,
-                max_k, MP, (float)(img_w - 1), (float)(img_h - 1)};
-    KPB_LAUNCH(ctx, "lg_prepare", lg_prepare, dim3(S), dim3(256), 0, st, pa);
-    SampleArgs sa{desc0_dev, desc1_dev, sb, sc, sh, sw, kpx, cnt, din, C, Hd, Wd, MP, lg->desc_scale};
-    KPB_LAUNCH(ctx, "lg_sample", lg_sample, dim3(cdiv(max_k, 4), S), dim3(256), 0, st, sa);
-    int rc;
-    if (lg->off.count("input_proj.w")) {
-        if ((rc = lg_linear(ctx, lg, "lg_input_proj", "input_proj", C, 256, din, C, cat[0], 512, 0, S, MP, active_seq, cnt))) return rc;
-    } else {
-        KPB_HIP(ctx, hipMemcpy2DAsync(cat[0], 512 * sizeof(float), din, 256 * sizeof(float), 256 * sizeof(float), T, hipMemcpyDeviceToDevice, st));
-    }
-    const dim3 tokgrid4(cdiv(max_k, 4), S), tokgrid64(cdiv(max_k * 64, 256), S);
-    const bool h16 = conv_mfma_use_h16();
-    auto ffn = [&](const std::string& L, const char* pfx, float* c) -> int {     // x + ffn(cat([x, msg])), lightglue.py:185 / 241-242
-        int r;
-        if ((r = lg_linear(ctx, lg, "lg_ffn0", L + pfx + "ffn0", 512, 512, c, 512, h1, 512, 0, S, MP, active_seq, cnt))) return r;
-        KPB_LAUNCH(ctx, "lg_ln_gelu", lg_ln_gelu, tokgrid4, dim3(256), 0, st, h1, lg->wp(L + (pfx[1] == 's' ? ".sln.g" : ".cln.g")),
-                   lg->wp(L + (pfx[1] == 's' ? ".sln.b" : ".cln.b")), cnt, active_seq, MP);
-        if (h16) {          // the residual sum rides in the product's epilogue: c[:, :256] = c[:, :256] + ffn3(h1)
-            LgEpi x; x.epi = GE_RESIDUAL; x.res = c; x.rstride = 512;
-            return lg_linear(ctx, lg, "lg_ffn3", L + pfx + "ffn3", 512, 256, h1, 512, c, 512, 0, S, MP, active_seq, cnt, x);
+        KPB_LAUNCH(ctx, "lg_init_out", lg_init_out, dim3(cdiv(B, 256)), dim3(256), 0, st, out_k_dev, out_stop_dev, stop, B, 0);
+        PrepArgs pa{pts0_dev, pts1_dev, n0_dev, n1_dev, lg->posenc_wr, kpx, cosb[0], sinb[0], ind[0], cnt, cnt_orig, active_seq, active_pair, stop, done_pair,
+                    max_k, MP, (float)(img_w - 1), (float)(img_h - 1)};
+        KPB_LAUNCH(ctx, "lg_prepare", lg_prepare, dim3(S), dim3(256), 0, st, pa);
+        SampleArgs sa{desc0_dev, desc1_dev, sb, sc, sh, sw, kpx, cnt, din, C, Hd, Wd, MP, lg->desc_scale};
+        KPB_LAUNCH(ctx, "lg_sample", lg_sample, dim3(cdiv(max_k, 4), S), dim3(256), 0, st, sa);
+        int rc;
+        if (lg->input_proj.w) {
+            if ((rc = lg_linear(ctx, "lg_input_proj", lg->input_proj, C, 256, din, C, cat[0], 512, 0, S, MP, active_seq, cnt))) return rc;
+        } else {
+            KPB_HIP(ctx, hipMemcpy2DAsync(cat[0], 512 * sizeof(float), din, 256 * sizeof(float), 256 * sizeof(float), T, hipMemcpyDeviceToDevice, st));
         }
-        if ((r = lg_linear(ctx, lg, "lg_ffn3", L + pfx + "ffn3", 512, 256, h1, 512, y, 256, 0, S, MP, active_seq, cnt))) return r;
-        KPB_LAUNCH(ctx, "lg_residual", lg_residual, tokgrid64, dim3(256), 0, st, c, y, cnt, active_seq, MP);
+        const dim3 tokgrid4(cdiv(max_k, 4), S), tokgrid64(cdiv(max_k * 64, 256), S);
+        const bool h16 = conv_mfma_use_h16();
+        auto ffn = [&](const LgLinear& ffn0, const float* ln_g, const float* ln_b, const LgLinear& ffn3, float* c) -> int {     // x + ffn(cat([x, msg])), lightglue.py:185 / 241-242
+            int r;
+            if ((r = lg_linear(ctx, "lg_ffn0", ffn0, 512, 512, c, 512, h1, 512, 0, S, MP, active_seq, cnt))) return r;
+            KPB_LAUNCH(ctx, "lg_ln_gelu", lg_ln_gelu, tokgrid4, dim3(256), 0, st, h1, ln_g, ln_b, cnt, active_seq, MP);
+            if (h16) {          // the residual sum rides in the product's epilogue: c[:, :256] = c[:, :256] + ffn3(h1)
+                LgEpi x; x.epi = GE_RESIDUAL; x.res = c; x.rstride = 512;
+                return lg_linear(ctx, "lg_ffn3", ffn3, 512, 256, h1, 512, c, 512, 0, S, MP, active_seq, cnt, x);
+            }
+            if ((r = lg_linear(ctx, "lg_ffn3", ffn3, 512, 256, h1, 512, y, 256, 0, S, MP, active_seq, cnt))) return r;
+            KPB_LAUNCH(ctx, "lg_residual", lg_residual, tokgrid64, dim3(256), 0, st, c, y, cnt, active_seq, MP);
+            return KPB_OK;
+        };
+        for (int i = 0; i < NL; ++i) {
+            const LgLayer& L = lg->layer[i];
+            float* c = cat[i & 1];
+            float *cs = cosb[i & 1], *sn = sinb[i & 1];
+            // self attention (lightglue.py:173-185)
+            if (h16) {          // q, k rotated and all three laid out head-major by the product's own epilogue
+                LgEpi x; x.epi = GE_ROTARY; x.cosb = cs; x.sinb = sn; x.out1 = k; x.out2 = v;
+                if ((rc = lg_linear(ctx, "lg_Wqkv", L.wqkv, 256, 768, c, 512, q, 256, 0, S, MP, active_seq, cnt, x))) return rc;
+            } else {
+                if ((rc = lg_linear(ctx, "lg_Wqkv", L.wqkv, 256, 768, c, 512, qkv, 768, 0, S, MP, active_seq, cnt))) return rc;
+                KPB_LAUNCH(ctx, "lg_rotary", lg_rotary, dim3(cdiv(max_k * 128, 256), S), dim3(256), 0, st, qkv, cs, sn, q, k, v, cnt, active_seq, MP);
+            }
+            if (h16) {
+                FragArgs fr{k, v, kfrag, vfrag, kvexp, cnt, active_seq, MP, 0, lg->attn_f16};
+                KPB_LAUNCH(ctx, "lg_kv_frags", lg_kv_frags, dim3(cdiv(max_k, 32), NH, S), dim3(256), 0, st, fr);
+                FlashHArgs fa{q, kfrag, vfrag, kvexp, cx, cnt, active_seq, MP, 0, 0.125f};
+                if (lg->attn_f16) KPB_LAUNCH(ctx, "lg_flash_self", lg_flash_h<true>, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fa);
+                else KPB_LAUNCH(ctx, "lg_flash_self", lg_flash_h<false>, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fa);
+            } else {
+                FlashArgs fa{q, k, v, cx, cnt, active_seq, MP, 0, 0.125f};
+                KPB_LAUNCH(ctx, "lg_flash_self", lg_flash, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fa);
+            }
+            if ((rc = lg_linear(ctx, "lg_out_proj", L.sout, 256, 256, cx, 256, c, 512, 256, S, MP, active_seq, cnt))) return rc;
+            if ((rc = ffn(L.sffn0, L.sln_g, L.sln_b, L.sffn3, c))) return rc;
+            // cross attention (lightglue.py:216-243)
+            if (h16) {
+                LgEpi x; x.epi = GE_SPLIT2; x.out1 = v;
+                if ((rc = lg_linear(ctx, "lg_to_qkv", L.toqkv, 256, 512, c, 512, q, 256, 0, S, MP, active_seq, cnt, x))) return rc;
+            } else {
+                if ((rc = lg_linear(ctx, "lg_to_qk", L.toqk, 256, 256, c, 512, q, 256, 0, S, MP, active_seq, cnt))) return rc;
+                if ((rc = lg_linear(ctx, "lg_to_v", L.tov, 256, 256, c, 512, v, 256, 0, S, MP, active_seq, cnt))) return rc;
+            }
+            if (h16) {
+                FragArgs fr{q, v, kfrag, vfrag, kvexp, cnt, active_seq, MP, 1, lg->attn_f16};
+                KPB_LAUNCH(ctx, "lg_kv_frags", lg_kv_frags, dim3(cdiv(max_k, 32), NH, S), dim3(256), 0, st, fr);
+                FlashHArgs fc{q, kfrag, vfrag, kvexp, cx, cnt, active_seq, MP, 1, 0.125f};
+                if (lg->attn_f16) KPB_LAUNCH(ctx, "lg_flash_cross", lg_flash_h<true>, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fc);
+                else KPB_LAUNCH(ctx, "lg_flash_cross", lg_flash_h<false>, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fc);
+            } else {
+                FlashArgs fc{q, q, v, cx, cnt, active_seq, MP, 1, 0.125f};
+                KPB_LAUNCH(ctx, "lg_flash_cross", lg_flash, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fc);
+            }
+            if ((rc = lg_linear(ctx, "lg_to_out", L.toout, 256, 256, cx, 256, c, 512, 256, S, MP, active_seq, cnt))) return rc;
+            if ((rc = ffn(L.cffn0, L.cln_g, L.cln_b, L.cffn3, c))) return rc;
+            // confidences, stop / prune decision (lightglue.py:557-579)
+            const bool last = i == NL - 1;
+            KPB_LAUNCH(ctx, "lg_conf", lg_conf, tokgrid4, dim3(256), 0, st, c, last ? L.mw : L.cw, last ? L.mb : L.cb, L.mw, L.mb, conf, msc, zlog, cnt, active_seq, MP,
+                       last ? 0 : 1);
+            const double thr = std::min(std::max(0.8 + 0.1 * std::exp(-4.0 * i / NL), 0.0), 1.0);
+            DecideArgs da{conf, msc, cnt, cnt_orig, newcnt, dst, active_pair, active_seq, fin_pair, fin_seq, stop, done_pair, MP, i, prm->prune_min_kpts,
+                          (float)thr, prm->depth_confidence, (float)(1.0 - (double)prm->width_confidence), prm->depth_confidence > 0 ? 1 : 0,
+                          prm->width_confidence > 0 ? 1 : 0};
+            KPB_LAUNCH(ctx, "lg_decide", lg_decide, dim3(B), dim3(256), 0, st, da);
+            // the projected descriptors of the pairs that finish at this layer (lightglue.py:606-614); their assignment runs after the loop
+            if ((rc = lg_linear(ctx, "lg_final_proj", L.fproj, 256, 256, c, 512, md, 256, 0, S, MP, fin_seq, cnt))) return rc;
+            if (!last) {
+                KPB_LAUNCH(ctx, "lg_gather", lg_gather, tokgrid64, dim3(256), 0, st, c, cat[(i + 1) & 1], cs, sn, cosb[(i + 1) & 1], sinb[(i + 1) & 1],
+                           ind[i & 1], ind[(i + 1) & 1], dst, cnt, active_seq, MP);
+                KPB_LAUNCH(ctx, "lg_commit_counts", lg_commit_counts, dim3(cdiv(S, 256)), dim3(256), 0, st, cnt, newcnt, active_seq, S);
+            }
+        }
+        // the assignment of every finished pair (lightglue.py:606-614), ONCE: a pair's projected descriptors, matchability logits, counts and index map stay as its last
+        // layer left them (every later kernel skips inactive sequences).  (r03 .. r05 launched the stage after every layer for the pairs finishing there: 40 empty
+        // launches per call when all pairs run to the last layer.)
+        KPB_LAUNCH(ctx, "lg_sim", lg_sim, dim3(cdiv(max_k, 128), cdiv(max_k, 32), B), dim3(256), 0, st, md, sim, cnt, done_pair, MP);
+        const int nrow = cdiv(max_k, 4), ntile = cdiv(max_k, 256) * NCHK;
+        KPB_LAUNCH(ctx, "lg_lse", lg_lse, dim3(nrow + ntile, B), dim3(256), 0, st, sim, mxo, lgo, zlog, lso, pmx, psum, cnt, done_pair, MP, NCHK, nrow);
+        KPB_LAUNCH(ctx, "lg_lse", lg_lse_colfin, dim3(cdiv(max_k, 256), B), dim3(256), 0, st, pmx, psum, mxo, lgo, cnt, done_pair, MP, NCHK);
+        KPB_LAUNCH(ctx, "lg_best", lg_best, dim3(nrow + ntile, B), dim3(256), 0, st, sim, mxo, lgo, lso, bestv, besti, pbv, pbi, cnt, done_pair, MP, NCHK, nrow);
+        KPB_LAUNCH(ctx, "lg_emit", lg_emit, dim3(B), dim3(256), 0, st, bestv, besti, pbv, pbi, NCHK, ind[0], ind[1], stop, cnt, done_pair, out_pairs_dev, out_scores_dev,
+                   out_k_dev, MP, max_k, prm->filter_threshold);
+        if (out_stop_dev) KPB_LAUNCH(ctx, "lg_init_out", lg_init_out, dim3(cdiv(B, 256)), dim3(256), 0, st, out_k_dev, out_stop_dev, stop, B, 1);
+        KPB_HIP(ctx, hipGetLastError());
         return KPB_OK;
-    };
-    for (int i = 0; i < NL; ++i) {
-        const std::string L = "L" + std::to_string(i);
-        float* c = cat[i & 1];
-        float *cs = cosb[i & 1], *sn = sinb[i & 1];
-        // self attention (lightglue.py:173-185)
-        if (h16) {          // q, k rotated and all three laid out head-major by the product's own epilogue
-            LgEpi x; x.epi = GE_ROTARY; x.cosb = cs; x.sinb = sn; x.out1 = k; x.out2 = v;
-            if ((rc = lg_linear(ctx, lg, "lg_Wqkv", L + ".Wqkv_r", 256, 768, c, 512, q, 256, 0, S, MP, active_seq, cnt, x))) return rc;
-        } else {
-            if ((rc = lg_linear(ctx, lg, "lg_Wqkv", L + ".Wqkv", 256, 768, c, 512, qkv, 768, 0, S, MP, active_seq, cnt))) return rc;
-            KPB_LAUNCH(ctx, "lg_rotary", lg_rotary, dim3(cdiv(max_k * 128, 256), S), dim3(256), 0, st, qkv, cs, sn, q, k, v, cnt, active_seq, MP);
-        }
-        if (h16) {
-            FragArgs fr{k, v, kfrag, vfrag, kvexp, cnt, active_seq, MP, 0, lg->attn_f16};
-            KPB_LAUNCH(ctx, "lg_kv_frags", lg_kv_frags, dim3(cdiv(max_k, 32), NH, S), dim3(256), 0, st, fr);
-            FlashHArgs fa{q, kfrag, vfrag, kvexp, cx, cnt, active_seq, MP, 0, 0.125f};
-            if (lg->attn_f16) KPB_LAUNCH(ctx, "lg_flash_self", lg_flash_h<true>, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fa);
-            else KPB_LAUNCH(ctx, "lg_flash_self", lg_flash_h<false>, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fa);
-        } else {
-            FlashArgs fa{q, k, v, cx, cnt, active_seq, MP, 0, 0.125f};
-            KPB_LAUNCH(ctx, "lg_flash_self", lg_flash, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fa);
-        }
-        if ((rc = lg_linear(ctx, lg, "lg_out_proj", L + ".sout", 256, 256, cx, 256, c, 512, 256, S, MP, active_seq, cnt))) return rc;
-        if ((rc = ffn(L, ".s", c))) return rc;
-        // cross attention (lightglue.py:216-243)
-        if (h16) {
-            LgEpi x; x.epi = GE_SPLIT2; x.out1 = v;
-            if ((rc = lg_linear(ctx, lg, "lg_to_qkv", L + ".toqkv", 256, 512, c, 512, q, 256, 0, S, MP, active_seq, cnt, x))) return rc;
-        } else {
-            if ((rc = lg_linear(ctx, lg, "lg_to_qk", L + ".toqk", 256, 256, c, 512, q, 256, 0, S, MP, active_seq, cnt))) return rc;
-            if ((rc = lg_linear(ctx, lg, "lg_to_v", L + ".tov", 256, 256, c, 512, v, 256, 0, S, MP, active_seq, cnt))) return rc;
-        }
-        if (h16) {
-            FragArgs fr{q, v, kfrag, vfrag, kvexp, cnt, active_seq, MP, 1, lg->attn_f16};
-            KPB_LAUNCH(ctx, "lg_kv_frags", lg_kv_frags, dim3(cdiv(max_k, 32), NH, S), dim3(256), 0, st, fr);
-            FlashHArgs fc{q, kfrag, vfrag, kvexp, cx, cnt, active_seq, MP, 1, 0.125f};
-            if (lg->attn_f16) KPB_LAUNCH(ctx, "lg_flash_cross", lg_flash_h<true>, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fc);
-            else KPB_LAUNCH(ctx, "lg_flash_cross", lg_flash_h<false>, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fc);
-        } else {
-            FlashArgs fc{q, q, v, cx, cnt, active_seq, MP, 1, 0.125f};
-            KPB_LAUNCH(ctx, "lg_flash_cross", lg_flash, dim3(cdiv(max_k, 128), NH, S), dim3(256), 0, st, fc);
-        }
-        if ((rc = lg_linear(ctx, lg, "lg_to_out", L + ".toout", 256, 256, cx, 256, c, 512, 256, S, MP, active_seq, cnt))) return rc;
-        if ((rc = ffn(L, ".c", c))) return rc;
-        // confidences, stop / prune decision (lightglue.py:557-579)
-        const bool last = i == NL - 1;
-        KPB_LAUNCH(ctx, "lg_conf", lg_conf, tokgrid4, dim3(256), 0, st, c, last ? lg->wp(L + ".mw") : lg->wp(L + ".cw"), last ? lg->wp(L + ".mb") : lg->wp(L + ".cb"),
-                   lg->wp(L + ".mw"), lg->wp(L + ".mb"), conf, msc, zlog, cnt, active_seq, MP, last ? 0 : 1);
-        const double thr = std::min(std::max(0.8 + 0.1 * std::exp(-4.0 * i / NL), 0.0), 1.0);
-        DecideArgs da{conf, msc, cnt, cnt_orig, newcnt, dst, active_pair, active_seq, fin_pair, fin_seq, stop, done_pair, MP, i, prm->prune_min_kpts,
-                      (float)thr, prm->depth_confidence, (float)(1.0 - (double)prm->width_confidence), prm->depth_confidence > 0 ? 1 : 0,
-                      prm->width_confidence > 0 ? 1 : 0};
-        KPB_LAUNCH(ctx, "lg_decide", lg_decide, dim3(B), dim3(256), 0, st, da);
-        // the projected descriptors of the pairs that finish at this layer (lightglue.py:606-614); their assignment runs after the loop
-        if ((rc = lg_linear(ctx, lg, "lg_final_proj", L + ".fproj", 256, 256, c, 512, md, 256, 0, S, MP, fin_seq, cnt))) return rc;
-        if (!last) {
-            KPB_LAUNCH(ctx, "lg_gather", lg_gather, tokgrid64, dim3(256), 0, st, c, cat[(i + 1) & 1], cs, sn, cosb[(i + 1) & 1], sinb[(i + 1) & 1],
-                       ind[i & 1], ind[(i + 1) & 1], dst, cnt, active_seq, MP);
-            KPB_LAUNCH(ctx, "lg_commit_counts", lg_commit_counts, dim3(cdiv(S, 256)), dim3(256), 0, st, cnt, newcnt, active_seq, S);
-        }
-    }
-    // the assignment of every finished pair (lightglue.py:606-614), ONCE: a pair's projected descriptors, matchability logits, counts and index map stay as its last
-    // layer left them (every later kernel skips inactive sequences).  (r03 .. r05 launched the stage after every layer for the pairs finishing there: 40 empty
-    // launches per call when all pairs run to the last layer.)
-    KPB_LAUNCH(ctx, "lg_sim", lg_sim, dim3(cdiv(max_k, 128), cdiv(max_k, 32), B), dim3(256), 0, st, md, sim, cnt, done_pair, MP);
-    const int nrow = cdiv(max_k, 4), ntile = cdiv(max_k, 256) * NCHK;
-    KPB_LAUNCH(ctx, "lg_lse", lg_lse, dim3(nrow + ntile, B), dim3(256), 0, st, sim, mxo, lgo, zlog, lso, pmx, psum, cnt, done_pair, MP, NCHK, nrow);
-    KPB_LAUNCH(ctx, "lg_lse", lg_lse_colfin, dim3(cdiv(max_k, 256), B), dim3(256), 0, st, pmx, psum, mxo, lgo, cnt, done_pair, MP, NCHK);
-    KPB_LAUNCH(ctx, "lg_best", lg_best, dim3(nrow + ntile, B), dim3(256), 0, st, sim, mxo, lgo, lso, bestv, besti, pbv, pbi, cnt, done_pair, MP, NCHK, nrow);
-    KPB_LAUNCH(ctx, "lg_emit", lg_emit, dim3(B), dim3(256), 0, st, bestv, besti, pbv, pbi, NCHK, ind[0], ind[1], stop, cnt, done_pair, out_pairs_dev, out_scores_dev,
-               out_k_dev, MP, max_k, prm->filter_threshold);
-    if (out_stop_dev) KPB_LAUNCH(ctx, "lg_init_out", lg_init_out, dim3(cdiv(B, 256)), dim3(256), 0, st, out_k_dev, out_stop_dev, stop, B, 1);
-    KPB_HIP(ctx, hipGetLastError());
-    return KPB_OK;
+    });
 }

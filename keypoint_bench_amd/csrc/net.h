@@ -1,4 +1,4 @@
-// net.h -- extractor-network interface behind kpb_net_* and the .kpbw weight container parser.
+// net.h -- extractor-network interface behind kpb_net_*, the .kpbw weight container parser, and what the nets share with the LightGlue matcher.
 #pragma once
 #include "kpb_common.h"
 
@@ -21,6 +21,14 @@ struct kpb_net {
         return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_desc_at: this network materialises its descriptor map; use kpb_sample");
     }
 };
+
+// runs network and matcher code behind the C API: no C++ exception may cross it
+template <class F> int guarded(kpb_ctx* ctx, const char* what, F&& f)
+{
+    try { return f(); }
+    catch (const std::bad_alloc&) { return kpb_fail(ctx, KPB_E_NOMEM, "%s: out of host memory", what); }
+    catch (const std::exception& e) { return kpb_fail(ctx, KPB_E_INVALID, "%s: %s", what, e.what()); }
+}
 
 // The activations of one forward, carved from kpb_net::act.  A forward lists its buffers ONCE, as take() calls in a callable; kpb_carve runs the list
 // twice -- without a base to add the sizes up, then, after the reserve, to hand out the pointers -- so the total and the pointers cannot disagree.
@@ -85,8 +93,8 @@ struct KpbwBlob {
     }
 };
 
-// host-side staging of repacked tensors; upload() copies them into one device allocation, after which dev() resolves a staged name to its device
-// pointer.  The stage lives inside a create function only: a network keeps the pointers, not the names.
+// host-side staging of repacked tensors, for the nets' creates and kpb_lg_create alike (so its messages name the stage, not a caller); upload()
+// copies them into one device allocation, after which dev() resolves a staged name to its device pointer.  The stage lives inside a create function only: a network keeps the pointers, not the names.
 struct WeightStage {
     std::vector<float> host;
     std::map<std::string, size_t> off;
@@ -99,14 +107,13 @@ struct WeightStage {
         host.insert(host.end(), v.begin(), v.end());
     }
     void put_raw(const std::string& name, const float* p, size_t n) { put(name, std::vector<float>(p, p + n)); }
-    int upload(kpb_net* net)
+    int upload(kpb_ctx* ctx, float** owner)       // *owner (kpb_net::wdev, kpb_lg::wdev) frees the allocation, also when the upload or the binding fails
     {
-        kpb_ctx* ctx = net->ctx;
-        if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&net->wdev, host.size() * sizeof(float)) != hipSuccess)
-            return kpb_fail(ctx, KPB_E_NOMEM, "kpb_net_create: weight allocation failed");
-        if (hipMemcpy(net->wdev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-            return kpb_fail(ctx, KPB_E_HIP, "kpb_net_create: weight upload failed");
-        wdev = net->wdev;
+        if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(owner, host.size() * sizeof(float)) != hipSuccess)
+            return kpb_fail(ctx, KPB_E_NOMEM, "WeightStage::upload: weight allocation failed");
+        if (hipMemcpy(*owner, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            return kpb_fail(ctx, KPB_E_HIP, "WeightStage::upload: weight copy to the device failed");
+        wdev = *owner;
         return KPB_OK;
     }
     template <class T = float> const T* dev(const std::string& name)
@@ -118,7 +125,7 @@ struct WeightStage {
     }
     int bound(kpb_ctx* ctx) const      // after the last dev(): a name that did not resolve is a refused create, not a null pointer in a kernel's arguments
     {
-        return missing.empty() ? KPB_OK : kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: no staged tensor %s to bind", missing.c_str());
+        return missing.empty() ? KPB_OK : kpb_fail(ctx, KPB_E_WEIGHTS, "WeightStage::bound: no staged tensor %s to bind", missing.c_str());
     }
 };
 

@@ -3,14 +3,6 @@
 
 #define KPB_API extern "C" __attribute__((visibility("default")))
 
-// runs network code behind the C API: no C++ exception may cross it
-template <class F> static int guarded(kpb_ctx* ctx, const char* what, F&& f)
-{
-    try { return f(); }
-    catch (const std::bad_alloc&) { return kpb_fail(ctx, KPB_E_NOMEM, "%s: out of host memory", what); }
-    catch (const std::exception& e) { return kpb_fail(ctx, KPB_E_INVALID, "%s: %s", what, e.what()); }
-}
-
 KPB_API int kpb_net_create(kpb_ctx* ctx, int arch, const void* blob, size_t len, kpb_net** out)
 {
     if (!ctx || !out || !blob) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_create: null argument");

@@ -174,7 +174,7 @@ int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     hw.insert(hw.end(), sw, sw + 128);
     ws.put("head.w", hw);
     ws.put("head.b", hb);
-    if (int rc = ws.upload(net.get())) return rc;
+    if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     for (int i = 0; i < 9; ++i) {
         const std::string n = R2D2_PLAN[i].name;
         net->lay[i].w = ws.dev(n + ".w"); net->lay[i].b = ws.dev(n + ".b");

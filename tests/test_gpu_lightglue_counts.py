@@ -14,7 +14,8 @@ workspace is padded to MP = ceil(max_k / 128) * 128 and zeroed only when it grow
                 trace).  The (40,36) cases put points on the corners and edges of the image: the border taps of lg_sample.
   batch         ONE kpb_lg_match call of seven pairs (1,40) (33,31) (129,127) (5,200) (0,7) (7,0) (200,200), max_k = 200, the padding rows of the point buffers
                 NaN: every pair bit for bit what the single-pair call gives; an empty side stops at 1, as the reference's loop does (it breaks before layer 0).
-  dirty arena   (33,31) and (1,40) after (300,280) on one matcher (the workspace re-carved at MP = 128 over what MP = 384 left, no memset) against a fresh matcher.
+  dirty arena   (33,31) and (1,40) after (300,280) on one matcher (the workspace re-carved at MP = 128 over what MP = 384 left, no memset) against a fresh matcher,
+                which then grows to (300,280) itself.
   strides       channels_last descriptor maps through lg_sample against the NCHW run.
   f16           attention="f16" at (1,40) (31,33) (33,31) (129,127) against the oracle fed half operands (refused with KPB_E_UNSUPPORTED under KPB_FP32_MATRIX=1).
 
@@ -280,7 +281,8 @@ def test_a_small_call_on_the_workspace_a_large_call_left_dirty():
     """The workspace is zeroed only when it grows.  After (300,280) it is carved for MP = 384 and full of that call's values -- integers (index maps, 0x7FFFFFFF
     "no winner" marks, -1 "pruned" marks: NaN bit patterns) as much as floats; (33,31) and (1,40) re-carve it at MP = 128 without a memset, so their padded rows and
     their partial arrays hold whatever lies there.  A fresh matcher's workspace is all zeros.  The two must agree bit for bit, and the large call must still
-    reproduce itself afterwards."""
+    reproduce itself afterwards.  The other direction: the fresh matcher, carved at MP = 128 by its two small calls, then runs (300,280), which reserves the
+    workspace again at MP = 384 and zero-fills it; it must give the first matcher's bits."""
     w = W256
     a = _matcher(w, FULL)
     first = _bits(_run(a, w, 300, 280))
@@ -290,6 +292,7 @@ def test_a_small_call_on_the_workspace_a_large_call_left_dirty():
     assert len(small_fresh[0][0]) >= 20 and len(small_fresh[1][0]) == 1
     assert small_dirty == small_fresh
     assert _bits(_run(a, w, 300, 280)) == first
+    assert _bits(_run(b, w, 300, 280)) == first
 
 
 def test_channels_last_descriptor_maps_through_lg_sample():

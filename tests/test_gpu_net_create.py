@@ -3,6 +3,8 @@
 1. A weight blob that lacks a tensor, or carries it with one dimension changed, is refused by kpb_net_create itself with KPB_E_WEIGHTS and a message
    that names the tensor or its layer -- not by a later forward -- and leaves the context able to create and run the intact net.  A first-layer and a
    last-layer tensor of each of the five architectures.
+   kpb_lg_create likewise: the LightGlue blob without a tensor of its first layer, of its last assignment head or of a token-confidence head, or with one
+   weight a column short, is refused with the layer's name before any kernel runs; the context then creates the intact matcher and matches a pair.
 2. A net carves its activations again when the image grows and when it shrinks: shape A, a larger shape B that changes the size of every level, then A
    again on the same image, give the same BITS at A, score and descriptors.  Every kernel is a fixed sequence of operations (test_gpu_determinism.py),
    so bitwise equality is the yardstick for all five nets; nothing here is compared at a tolerance.
@@ -120,6 +122,43 @@ def test_create_refuses_a_missing_or_misshaped_tensor(arch, tensor, message, sha
         assert float(score.abs().max()) > 0.0 and float(desc.abs().max()) > 0.0
     finally:
         net.close()
+
+
+# (tensor, the shape it is carried with or None = left out, the name kpb_lg_create reports)
+LG_REFUSED = [
+    ("transformers.0.self_attn.Wqkv.weight", None, "L0"),
+    ("log_assignment.8.matchability.bias", None, "log_assignment.8"),
+    ("token_confidence.3.token.0.weight", None, "token_confidence.3.token.0"),
+    ("transformers.4.cross_attn.to_out.weight", (256, 255), "L4"),
+]
+
+
+def test_lightglue_create_refuses_a_missing_or_misshaped_tensor():
+    from test_gpu_lightglue_counts import FULL, W256, _matcher, _run
+    m = _matcher(W256, FULL)            # the seeded SuperPoint-width matcher of the counts file; nothing created yet
+    arch_id, t = weights.unpack(m._blob)
+    ctx = Context.get(DEV)
+    ctx.prof_enable(True)               # every kernel launch of this context is recorded from here on
+    try:
+        ctx.prof_report()
+        for tensor, shape, layer in LG_REFUSED:
+            assert tensor in t
+            bad = {k: v for k, v in t.items() if k != tensor}
+            if shape is not None:
+                bad[tensor] = t[tensor][:shape[0], :shape[1]]
+                assert bad[tensor].shape == shape != t[tensor].shape
+            blob = weights.pack(bad, arch_id)
+            h = c_void_p()
+            rc = ctx.lib.kpb_lg_create(ctx.handle, blob, len(blob), 8.0, ctypes.byref(h))
+            assert rc == KPB_E_WEIGHTS, (tensor, rc)
+            assert ctx.lib.kpb_last_error(ctx.handle).decode() == "kpb_lg_create: tensor %s missing or mis-shaped" % layer
+            assert not h.value, tensor            # *out stays null
+        assert ctx.prof_report() == {}, "a refused kpb_lg_create launched a kernel"
+    finally:
+        ctx.prof_enable(False)
+    pairs, scores, stop = _run(m, W256, 33, 31)         # the same context, after four refused creates
+    assert m._ctx is ctx and stop == 9
+    assert len(pairs) >= 20 and np.all(np.isfinite(scores)) and np.all(scores > 0)
 
 
 # (architecture, smallest shape A, shape B that changes every level's size, batch, dense)
