@@ -405,16 +405,19 @@ extern "C" __attribute__((visibility("default"))) int kpb_val_keypoints(
     // workspace can hold them: a device too full for the cells gets the evaluate-in-place form (every pass computes its cells: the
     // same bits, 2.8 instead of 2.4 ms per 256 pairs), not KPB_E_NOMEM
     bool store = cells * 4 <= ctx->covis_store_bytes;
-    const size_t small = (size_t)batch * (2 * (size_t)max_m + max_n + 1);
-    if (store && kpb_reserve(ctx, ctx->ws_misc, (small + cells + 64) * 4) != KPB_OK) store = false;
-    if (!store)
-        if (int rc = kpb_reserve(ctx, ctx->ws_misc, small * 4)) return rc;
-    float* rmin = (float*)ctx->ws_misc.p;
-    float* cmin = rmin + (size_t)batch * max_m;
-    int32_t* cnt = (int32_t*)(cmin + (size_t)batch * max_n);
-    unsigned* dmax = (unsigned*)(cnt + (size_t)batch * max_m);
+    float *rmin = nullptr, *cmin = nullptr, *dm = nullptr; int32_t* cnt = nullptr; unsigned* dmax = nullptr;
+    const auto list = [&](Arena& a) {      // (ws_misc: nothing of an earlier call is expected in it)
+        rmin = a.take((size_t)batch * max_m); cmin = a.take((size_t)batch * max_n);
+        cnt = a.take<int32_t>((size_t)batch * max_m); dmax = a.take<unsigned>(batch);
+        dm = store ? a.take(cells) : nullptr;
+    };
+    int rc = kpb_carve(ctx, ctx->ws_misc, list);
+    if (rc && store) {      // no room for the cells: the evaluate-in-place form, and no trace of the attempt in kpb_last_error
+        store = false;
+        if ((rc = kpb_carve(ctx, ctx->ws_misc, list)) == KPB_OK) ctx->err[0] = 0;
+    }
+    if (rc) return rc;
     KPB_HIP(ctx, hipMemsetAsync(dmax, 0, (size_t)batch * 4, ctx->stream));
-    float* dm = store ? reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(dmax + batch) + 255) & ~(uintptr_t)255) : nullptr;
     ValArgs a{k0_dev, k01_dev, k1_dev, k10_dev, max_m, max_n, m_dev, n_dev, scale_dev, th, rmin, cmin, dmax, cnt,
               out_pairs_dev, out_dist_dev, cap, out_errors_dev, out_counts_dev, dm};
     KPB_LAUNCH(ctx, "covis_stats", covis_stats, dim3(cdiv(max_m + (store ? 0 : max_n), 4), batch), dim3(256), 0, ctx->stream, a);

@@ -1139,10 +1139,19 @@ int next_pow2(int v)
     return p;
 }
 
-int env_int(const char* name, int dflt)
+// f(integral_constant<int, r>) for a run-time radius 1 .. 8 (anything else: 8): the specialised NMS kernels take their radius as a template argument
+template <class F> void nms_radius(int r, F&& f)
 {
-    const char* s = getenv(name);
-    return s ? atoi(s) : dflt;
+    switch (r) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+    }
 }
 
 struct NmsPlan {
@@ -1159,7 +1168,7 @@ struct NmsPlan {
     float cmin;
     unsigned char* ubits; int wb;       // [B][H][wb] sweep 0's bitmap of undecided pixels (NmsArgs)
     unsigned char* cbits;               // [B][H][wb] confirmed maxima (NmsArgs)
-    size_t nclear;      // ints at lastchg that nms_open clears: lastchg, negflag and the histograms
+    size_t nclear;      // ints of the piece at lastchg that nms_open clears with one memset: lastchg, negflag and the histograms
 };
 
 int nms_plan(kpb_ctx* ctx, int batch, int H, int W, int r, NmsPlan& p, int prune_k = 0, int border = 0, float cmin = 0.0f)
@@ -1172,19 +1181,21 @@ int nms_plan(kpb_ctx* ctx, int batch, int H, int W, int r, NmsPlan& p, int prune
     const size_t nflag = (size_t)batch * p.ntiles;
     // The tail is one workgroup per image and latency-bound (about 1.4 ms whatever the batch); four more tiled sweeps
     // cost about 8 us per 480x640 image.  It pays once the batch fills the chip.  KPB_NMS_TILED=1 / =0 force a choice.
-    const int tiled = env_int("KPB_NMS_TILED", -1);
+    const int tiled = kpb_env_int("KPB_NMS_TILED", -1);
     const bool big = (size_t)batch * H * W >= (size_t)192 * 480 * 640;
     const bool tail = r >= 1 && r <= 8 && (tiled == 0 || (tiled < 0 && big));
-    const bool prune = tail && prune_k > 0 && prune_k < H * W && env_int("KPB_NMS_PRUNE", 1);
-    const size_t head = (2 * (size_t)batch + 3) & ~(size_t)3;        // lastchg[B], negflag[B]; the histograms start on 16 bytes (nms_tail reads uint4s)
+    const bool prune = tail && prune_k > 0 && prune_k < H * W && kpb_env_int("KPB_NMS_PRUNE", 1);
+    // ONE piece for what nms_open clears with one memset: lastchg[B] and negflag[B] -- adjacent, nms_status copies both back as 2 * batch ints -- then,
+    // from the next multiple of 16 bytes on (nms_tail reads them as uint4s; 2 * batch ints end on one for even batches only), the histograms
+    const size_t head = (2 * (size_t)batch + 3) & ~(size_t)3;
     p.nclear = head + (prune ? (size_t)batch * NMS_HBINS : 0);
-    if (int rc = kpb_reserve(ctx, ctx->ws_nms_state, (p.nclear + 2 * nflag) * sizeof(int))) return rc;
-    int* base = static_cast<int*>(ctx->ws_nms_state.p);
-    p.lastchg = base;
-    p.negflag = base + batch;
-    p.chist = prune ? reinterpret_cast<unsigned*>(base + head) : nullptr;
-    p.tchg[0] = base + p.nclear;
-    p.tchg[1] = p.tchg[0] + nflag;
+    if (int rc = kpb_carve(ctx, ctx->ws_nms_state, [&](Arena& a) {
+            p.lastchg = a.take<int>(p.nclear);
+            p.tchg[0] = a.take<int>(nflag);
+            p.tchg[1] = a.take<int>(nflag);
+        })) return rc;
+    p.negflag = p.lastchg + batch;
+    p.chist = prune ? reinterpret_cast<unsigned*>(p.lastchg + head) : nullptr;
     p.ulist = nullptr;
     p.ucap = 0;
     p.prune_k = prune ? prune_k : 0; p.border = border; p.cmin = cmin;
@@ -1192,12 +1203,13 @@ int nms_plan(kpb_ctx* ctx, int batch, int H, int W, int r, NmsPlan& p, int prune
     if (tail) {
         p.ucap = std::max(4096, H * W / 8);
         p.wb = (cdiv(W, 8) + 3) & ~3;
-        const size_t nbits = (size_t)batch * H * p.wb;       // (a multiple of 4: wb is)
-        if (int rc = kpb_reserve(ctx, ctx->ws_nms_list, (size_t)batch * 5 * (size_t)p.ucap * sizeof(int) + 2 * nbits)) return rc;
-        p.ulist = static_cast<int2*>(ctx->ws_nms_list.p);
-        p.slist = reinterpret_cast<int*>(p.ulist + (size_t)batch * 2 * p.ucap);
-        p.ubits = reinterpret_cast<unsigned char*>(p.slist + (size_t)batch * p.ucap);
-        p.cbits = p.ubits + nbits;
+        const size_t nbits = (size_t)batch * H * p.wb;
+        if (int rc = kpb_carve(ctx, ctx->ws_nms_list, [&](Arena& a) {
+                p.ulist = a.take<int2>((size_t)batch * 2 * p.ucap);
+                p.slist = a.take<int>((size_t)batch * p.ucap);
+                p.ubits = a.take<unsigned char>(nbits);
+                p.cbits = a.take<unsigned char>(nbits);
+            })) return rc;
     }
     if (!(ctx->lds_attr_done & KPB_ATTR_NMS)) {
         KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(nms_sweep),
@@ -1230,17 +1242,8 @@ int nms_launch(kpb_ctx* ctx, const NmsPlan& p, const float* src, float* cur, int
         // one round confirms too few maxima for the bound and the tail overflows)
         a.max_local = (p.ulist && s == 0) ? (p.chist ? 2 : 3) : 64;
         const dim3 grid(p.ntiles, batch), block(NMS_THREADS);
-        switch (r) {
-        case 1: KPB_LAUNCH(ctx, "nms_sweep", nms_sweep_r<1>, grid, block, 0, ctx->stream, a); break;
-        case 2: KPB_LAUNCH(ctx, "nms_sweep", nms_sweep_r<2>, grid, block, 0, ctx->stream, a); break;
-        case 3: KPB_LAUNCH(ctx, "nms_sweep", nms_sweep_r<3>, grid, block, 0, ctx->stream, a); break;
-        case 4: KPB_LAUNCH(ctx, "nms_sweep", nms_sweep_r<4>, grid, block, 0, ctx->stream, a); break;
-        case 5: KPB_LAUNCH(ctx, "nms_sweep", nms_sweep_r<5>, grid, block, 0, ctx->stream, a); break;
-        case 6: KPB_LAUNCH(ctx, "nms_sweep", nms_sweep_r<6>, grid, block, 0, ctx->stream, a); break;
-        case 7: KPB_LAUNCH(ctx, "nms_sweep", nms_sweep_r<7>, grid, block, 0, ctx->stream, a); break;
-        case 8: KPB_LAUNCH(ctx, "nms_sweep", nms_sweep_r<8>, grid, block, 0, ctx->stream, a); break;
-        default: KPB_LAUNCH(ctx, "nms_sweep", nms_sweep, grid, block, p.lds, ctx->stream, a); break;
-        }
+        if (r >= 1 && r <= 8) nms_radius(r, [&](auto R) { KPB_LAUNCH(ctx, "nms_sweep", nms_sweep_r<decltype(R)::value>, grid, block, 0, ctx->stream, a); });
+        else KPB_LAUNCH(ctx, "nms_sweep", nms_sweep, grid, block, p.lds, ctx->stream, a);
     }
     KPB_HIP(ctx, hipGetLastError());
     return KPB_OK;
@@ -1259,18 +1262,9 @@ int nms_open(kpb_ctx* ctx, const NmsPlan& p, const float* src, float* cur, int b
         return nms_launch(ctx, p, src, cur, batch, H, W, r, 0, chunk);
     }
     if (int rc = nms_launch(ctx, p, src, cur, batch, H, W, r, 0, 1)) return rc;
-    TailArgs t{cur, p.ulist, p.slist, p.lastchg, p.ucap, H, W, r, env_int("KPB_NMS_TAIL_ROUNDS", 256), p.ubits, p.wb, p.chist, p.prune_k,
+    TailArgs t{cur, p.ulist, p.slist, p.lastchg, p.ucap, H, W, r, kpb_env_int("KPB_NMS_TAIL_ROUNDS", 256), p.ubits, p.wb, p.chist, p.prune_k,
                reinterpret_cast<unsigned*>(p.cbits)};
-    switch (r) {
-    case 1: KPB_LAUNCH(ctx, "nms_tail", nms_tail<1>, dim3(batch), dim3(TAIL_THREADS), 0, ctx->stream, t); break;
-    case 2: KPB_LAUNCH(ctx, "nms_tail", nms_tail<2>, dim3(batch), dim3(TAIL_THREADS), 0, ctx->stream, t); break;
-    case 3: KPB_LAUNCH(ctx, "nms_tail", nms_tail<3>, dim3(batch), dim3(TAIL_THREADS), 0, ctx->stream, t); break;
-    case 4: KPB_LAUNCH(ctx, "nms_tail", nms_tail<4>, dim3(batch), dim3(TAIL_THREADS), 0, ctx->stream, t); break;
-    case 5: KPB_LAUNCH(ctx, "nms_tail", nms_tail<5>, dim3(batch), dim3(TAIL_THREADS), 0, ctx->stream, t); break;
-    case 6: KPB_LAUNCH(ctx, "nms_tail", nms_tail<6>, dim3(batch), dim3(TAIL_THREADS), 0, ctx->stream, t); break;
-    case 7: KPB_LAUNCH(ctx, "nms_tail", nms_tail<7>, dim3(batch), dim3(TAIL_THREADS), 0, ctx->stream, t); break;
-    default: KPB_LAUNCH(ctx, "nms_tail", nms_tail<8>, dim3(batch), dim3(TAIL_THREADS), 0, ctx->stream, t); break;
-    }
+    nms_radius(r, [&](auto R) { KPB_LAUNCH(ctx, "nms_tail", nms_tail<decltype(R)::value>, dim3(batch), dim3(TAIL_THREADS), 0, ctx->stream, t); });
     KPB_HIP(ctx, hipMemsetAsync(p.tchg[0], 1, (size_t)batch * p.ntiles * sizeof(int), ctx->stream));   // "previous" flags of sweep 1
     KPB_HIP(ctx, hipGetLastError());
     sweeps_run = 1;
@@ -1280,7 +1274,7 @@ int nms_open(kpb_ctx* ctx, const NmsPlan& p, const float* src, float* cur, int b
 // reads lastchg/negflag back; returns number of images that changed in sweep (sweeps_run - 1), sets neg
 int nms_status(kpb_ctx* ctx, const NmsPlan& p, int batch, int sweeps_run, int& pending, int& neg)
 {
-    std::vector<int> h(2 * (size_t)batch);
+    std::vector<int> h(2 * (size_t)batch);      // lastchg[B] and negflag[B]: adjacent in nms_plan's cleared piece
     KPB_HIP(ctx, hipMemcpyAsync(h.data(), p.lastchg, h.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pending = 0; neg = 0;
@@ -1384,8 +1378,7 @@ int det_select(kpb_ctx* ctx, const DetState& d)
     s.cbits = bits ? reinterpret_cast<const unsigned*>(d.plan.cbits) : nullptr; s.wb = d.plan.wb;
     size_t lds = (size_t)s.kpad * sizeof(unsigned long long);
     if (d.batch < 64 && s.nchunks > 1) {       // too few images to fill the chip with one workgroup each: scan in (chunks x batch) workgroups first
-        if (int rc = kpb_reserve(ctx, ctx->ws_sel, (size_t)d.batch * s.nchunks * sizeof(int))) return rc;
-        s.chunk_cnt = static_cast<int*>(ctx->ws_sel.p);
+        if (int rc = kpb_carve(ctx, ctx->ws_sel, [&](Arena& a) { s.chunk_cnt = a.take<int>((size_t)d.batch * s.nchunks); })) return rc;
         s.lcap = (int)((64 * 1024 - lds) / sizeof(unsigned long long));        // (the attribute set in nms_plan allows 64 KB)
         lds = 64 * 1024;
         KPB_LAUNCH(ctx, "select_scan", select_scan, dim3(s.nchunks, d.batch), dim3(SEL_THREADS), 0, ctx->stream, s);
@@ -1419,8 +1412,7 @@ extern "C" __attribute__((visibility("default"))) int kpb_detect(kpb_ctx* ctx, c
     d.score = score_dev; d.batch = batch; d.H = H; d.W = W; d.prm = *prm;
     if (d.prm.top_k > H * W) d.prm.top_k = H * W;   // N can never exceed H*W: same rows, smaller buffers
     d.out_kps = out_kps_dev; d.out_idx = out_idx_dev; d.out_n = out_n_dev;
-    if (int rc = kpb_reserve(ctx, ctx->ws_cand, (size_t)batch * P * sizeof(unsigned long long))) return rc;
-    d.cand = static_cast<unsigned long long*>(ctx->ws_cand.p);
+    if (int rc = kpb_carve(ctx, ctx->ws_cand, [&](Arena& a) { d.cand = a.take<unsigned long long>((size_t)batch * P); })) return rc;
     {   // a confirmed maximum counts toward the pruning bound only if the detection could output it
         const float cmin = std::max(prm->threshold, prm->min_score > 0.0f ? prm->min_score : prm->threshold);
         const int border = std::max(prm->border_dist, 0);
@@ -1429,8 +1421,7 @@ extern "C" __attribute__((visibility("default"))) int kpb_detect(kpb_ctx* ctx, c
     d.sweeps_run = 0;
     d.cur = nullptr;
     if (prm->nms_dist > 0) {
-        if (int rc = kpb_reserve(ctx, ctx->ws_nms_map, (size_t)batch * P * sizeof(float))) return rc;
-        d.cur = static_cast<float*>(ctx->ws_nms_map.p);
+        if (int rc = kpb_carve(ctx, ctx->ws_nms_map, [&](Arena& a) { d.cur = a.take((size_t)batch * P); })) return rc;
         // tiled sweeps enqueued before the first look at the status: an ALIKE map is at its fixed point after 3-4 of them; a sweep
         // with nothing to do still costs its launch (5 us each on the single map of the drop-in path), an early look costs a
         // synchronisation -- 6 for batches (amortised), 4 when a few images are all there is

@@ -146,15 +146,15 @@ struct kpb_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     char err[512] = {0};
-    // named workspaces, grown on demand (first call of a shape = warm-up), never freed before destroy
+    // named workspaces, grown on demand (first call of a shape = warm-up), never freed before destroy (kpb_ctx_destroy lists them: add a new one there)
     kpb_buf ws_nms_state;   // per-image / per-tile sweep flags
     kpb_buf ws_nms_map;     // [batch][H*W] working map
     kpb_buf ws_nms_list;    // [batch][2][cap] undecided pixels handed from sweep 0 to the sparse tail
     kpb_buf ws_cand;        // [batch][H*W] uint64 candidate list (key<<32 | ~idx)
     kpb_buf ws_match;       // per-tile row/column minima
-    kpb_buf ws_misc;
+    kpb_buf ws_misc;        // shared by the match prefilter, covisibility and LK: each carves it anew from offset 0 at every call, so nothing may be
+                            // kept in it across calls (one allocation for the three keeps the footprint down)
     kpb_buf ws_sel;         // [batch][chunks] candidate counts of the two-phase selection (small batches)
-    int* host_flags = nullptr;  // pinned, for status read-back
     // kpb_detect: select_topk leaves (last sweep that changed, negative flag, keypoint count) of every image HERE -- pinned host
     // memory the kernel writes directly -- so that completing a detection is one stream synchronisation, not two copies back
     int* host_det = nullptr;
@@ -236,6 +236,33 @@ inline int kpb_reserve(kpb_ctx* ctx, kpb_buf& b, size_t bytes)
     // KPB_LOG_ALLOC=1: where each workspace landed (scripts/head_modes.py reads these lines: placement against the caller's buffers)
     static const bool log_alloc = getenv("KPB_LOG_ALLOC") && *getenv("KPB_LOG_ALLOC") == '1';
     if (log_alloc) fprintf(stderr, "kpb_alloc %p %zu\n", b.p, want);
+    return KPB_OK;
+}
+
+// A workspace carved into typed pieces: a network's activations (kpb_net::act), LightGlue's workspace, an operator's kpb_ctx::ws_*.  The caller lists its
+// buffers ONCE, as take() calls in a callable; kpb_carve runs the list twice -- without a base to add the sizes up, then, after the reserve, to hand out the
+// pointers -- so the total and the pointers cannot disagree.  Every piece starts on a 256-byte boundary (hipMalloc's own alignment; the rule
+// WeightStage::put follows) and comes out typed.  What one memset clears or one copy reads back is taken as ONE piece and split by the caller.
+struct Arena {
+    char* base = nullptr;       // null: measuring
+    size_t off = 0;
+    template <class T = float> T* take(size_t n)
+    {
+        T* q = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (n * sizeof(T) + 255) / 256 * 256;
+        return q;
+    }
+};
+
+template <class List> int kpb_carve(kpb_ctx* ctx, kpb_buf& buf, List&& list)
+{
+    Arena measure;
+    list(measure);
+    if (int rc = kpb_reserve(ctx, buf, measure.off)) return rc;
+    static const bool log_alloc = getenv("KPB_LOG_ALLOC") && *getenv("KPB_LOG_ALLOC") == '1';      // what the call asked for, beside kpb_reserve's own line
+    if (log_alloc) fprintf(stderr, "kpb_arena %zu\n", measure.off);
+    Arena bind{static_cast<char*>(buf.p)};
+    list(bind);
     return KPB_OK;
 }
 

@@ -175,14 +175,11 @@ extern "C" __attribute__((visibility("default"))) int kpb_lk_track(
     KPB_HIP(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)H * W, plane = (size_t)C * P;
     // workspace: p1, p2, cur [n][2]; pooled image 1 / image 2, dx, dy of image 2 (each at most one full-size plane set)
-    if (int rc = kpb_reserve(ctx, ctx->ws_misc, ((size_t)6 * n + 4 * plane) * sizeof(float))) return rc;
-    float* p1 = static_cast<float*>(ctx->ws_misc.p);
-    float* p2 = p1 + 2 * (size_t)n;
-    float* cur = p2 + 2 * (size_t)n;
-    float* l1 = cur + 2 * (size_t)n;
-    float* l2 = l1 + plane;
-    float* dx = l2 + plane;
-    float* dy = dx + plane;
+    float *p1 = nullptr, *p2 = nullptr, *cur = nullptr, *l1 = nullptr, *l2 = nullptr, *dx = nullptr, *dy = nullptr;
+    if (int rc = kpb_carve(ctx, ctx->ws_misc, [&](Arena& a) {      // (ws_misc: nothing of an earlier call is expected in it)
+            p1 = a.take(2 * (size_t)n); p2 = a.take(2 * (size_t)n); cur = a.take(2 * (size_t)n);
+            l1 = a.take(plane); l2 = a.take(plane); dx = a.take(plane); dy = a.take(plane);
+        })) return rc;
     hipStream_t st = ctx->stream;
     KPB_LAUNCH(ctx, "lk_init", lk_init, dim3(cdiv(n, 256)), dim3(256), 0, st, pts1_dev, pts2_dev, pts_stride, unit_dev, n, H, W, prm->distance, p1, p2, cur);
     const size_t lds = (size_t)4 * C * prm->win_size * prm->win_size * sizeof(float);

@@ -602,11 +602,9 @@ extern "C" __attribute__((visibility("default"))) int kpb_match(kpb_ctx* ctx, co
     if (max_m > 16384) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_match: max_m %d > 16384", max_m);
     const int tiles_i = cdiv(max_n, MTI), tiles_j = cdiv(max_m, MTJ);
     const size_t nr = (size_t)batch * tiles_j * max_n, nc = (size_t)batch * tiles_i * max_m;
-    const size_t bytes = (nr + nc) * (sizeof(double) + sizeof(int)) + 64;
-    if (int rc = kpb_reserve(ctx, ctx->ws_match, bytes)) return rc;
-    double* rs = static_cast<double*>(ctx->ws_match.p);
-    double* cs = rs + nr;
-    int* rj = reinterpret_cast<int*>(cs + nc);
+    double *rs = nullptr, *cs = nullptr;
+    int* rj = nullptr;          // rj[nr] and ci[nc] in ONE piece: the prefilter marks both empty with one 32-bit fill
+    if (int rc = kpb_carve(ctx, ctx->ws_match, [&](Arena& a) { rs = a.take<double>(nr); cs = a.take<double>(nc); rj = a.take<int>(nr + nc); })) return rc;
     int* ci = rj + nr;
     // prefilter on the matrix cores + exact refinement (see match_prep): C a multiple of 32 up to 256, at least two slots per row and column
     static const int prefilter = kpb_env_int("KPB_MATCH_PREFILTER", 1);
@@ -618,20 +616,19 @@ extern "C" __attribute__((visibility("default"))) int kpb_match(kpb_ctx* ctx, co
     if (pre) {
         const int P8 = C / 8, cap = 8 * (max_n + max_m);
         const size_t nh0 = (size_t)batch * max_n * P8, nh1 = (size_t)batch * max_m * P8;
-        const size_t words = 4 * 2 * (nh0 + nh1) + 3 * ((size_t)batch * (max_n + max_m)) + 4 * (size_t)batch + 2 * (size_t)batch * cap + 64;
-        if (int rc = kpb_reserve(ctx, ctx->ws_misc, words * 4)) return rc;
-        uint4* h0 = static_cast<uint4*>(ctx->ws_misc.p);
-        uint4* h1 = h0 + 2 * nh0;
-        float* nrm0 = reinterpret_cast<float*>(h1 + 2 * nh1);
-        float* nrm1 = nrm0 + (size_t)batch * max_n;
-        unsigned* rowmin = reinterpret_cast<unsigned*>(nrm1 + (size_t)batch * max_m);
-        unsigned* colmin = rowmin + (size_t)batch * max_n;
-        int* rcnt = reinterpret_cast<int*>(colmin + (size_t)batch * max_m);
-        int* ccnt = rcnt + (size_t)batch * max_n;
-        int* flag = ccnt + (size_t)batch * max_m;
+        const size_t n0 = (size_t)batch * max_n, n1 = (size_t)batch * max_m;
+        uint4 *h0 = nullptr, *h1 = nullptr; float *nrm0 = nullptr, *nrm1 = nullptr; unsigned *rowmin = nullptr, *colmin = nullptr;
+        int *rcnt = nullptr, *ccnt = nullptr, *flag = nullptr; int2* cand = nullptr;
+        if (int rc = kpb_carve(ctx, ctx->ws_misc, [&](Arena& a) {      // (ws_misc: nothing of an earlier call is expected in it)
+                h0 = a.take<uint4>(2 * nh0); h1 = a.take<uint4>(2 * nh1);
+                nrm0 = a.take<float>(n0); nrm1 = a.take<float>(n1);
+                rowmin = a.take<unsigned>(n0); colmin = a.take<unsigned>(n1);
+                rcnt = a.take<int>(n0); ccnt = a.take<int>(n1);
+                flag = a.take<int>(4 * (size_t)batch);      // flag[B], ncand[B], nmax[B][2] in ONE piece: cleared by the one memset below
+                cand = a.take<int2>((size_t)batch * cap);
+            })) return rc;
         int* ncand = flag + batch;
         unsigned* nmax = reinterpret_cast<unsigned*>(ncand + batch);
-        int2* cand = reinterpret_cast<int2*>(nmax + 2 * batch + ((reinterpret_cast<uintptr_t>(nmax + 2 * batch) & 4) ? 1 : 0));
         KPB_HIP(ctx, hipMemsetAsync(flag, 0, (size_t)batch * 4 * sizeof(int), ctx->stream));      // flag, ncand, nmax
         PreArgs pa{d0_dev, d1_dev, n_dev, m_dev, C, max_n, max_m, h0, h1, nrm0, nrm1, rowmin, colmin, rcnt, ccnt, flag, ncand, nmax};
         // empty slots are marked by the index INT_MAX (match_finalize skips them): one coalesced 32-bit fill of both index arrays

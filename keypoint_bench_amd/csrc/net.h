@@ -30,32 +30,6 @@ template <class F> int guarded(kpb_ctx* ctx, const char* what, F&& f)
     catch (const std::exception& e) { return kpb_fail(ctx, KPB_E_INVALID, "%s: %s", what, e.what()); }
 }
 
-// The activations of one forward, carved from kpb_net::act.  A forward lists its buffers ONCE, as take() calls in a callable; kpb_carve runs the list
-// twice -- without a base to add the sizes up, then, after the reserve, to hand out the pointers -- so the total and the pointers cannot disagree.
-// Every piece starts on a 256-byte boundary (hipMalloc's own alignment; the rule WeightStage::put follows) and comes out typed.
-struct Arena {
-    char* base = nullptr;       // null: measuring
-    size_t off = 0;
-    template <class T = float> T* take(size_t n)
-    {
-        T* q = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += (n * sizeof(T) + 255) / 256 * 256;
-        return q;
-    }
-};
-
-template <class List> int kpb_carve(kpb_ctx* ctx, kpb_buf& act, List&& list)
-{
-    Arena measure;
-    list(measure);
-    if (int rc = kpb_reserve(ctx, act, measure.off)) return rc;
-    static const bool log_alloc = getenv("KPB_LOG_ALLOC") && *getenv("KPB_LOG_ALLOC") == '1';      // what the forward asked for, beside kpb_reserve's own line
-    if (log_alloc) fprintf(stderr, "kpb_arena %zu\n", measure.off);
-    Arena bind{static_cast<char*>(act.p)};
-    list(bind);
-    return KPB_OK;
-}
-
 struct KpbwRec { char name[40]; uint32_t ndim; uint32_t dims[4]; uint32_t off; };
 
 struct KpbwBlob {
