@@ -76,8 +76,12 @@ int kpb_sync(kpb_ctx* ctx);
  *   KPB_OPT_COVIS_STORE_BYTES  kpb_val_keypoints keeps its M x N distance cells (4 bytes each) in the context's workspace when they fit
  *                              this many bytes (default 4 GiB) and re-evaluates them in every pass when they do not -- or when the
  *                              workspace cannot grow; both forms give the same bits (tests/test_gpu_covis.py runs both).  0 = never keep.
+ *   KPB_OPT_ALIKE_COARSE_FUSED 1 (default): at 16 images or more the split-f16 ALIKE forward finishes blocks 3 and 4 inside their second convolution (aggregation,
+ *                              score and head shares, and block 3's max-pool from on-chip memory: four launches, the blocks' outputs never written); 0: the seven
+ *                              separate launches at any batch.  Both give the same bits (tests/test_gpu_alike_coarse_tail.py).  Any other value is invalid.
  * Returns KPB_E_INVALID for an unknown option or a negative value. */
 #define KPB_OPT_COVIS_STORE_BYTES 1
+#define KPB_OPT_ALIKE_COARSE_FUSED 2
 int kpb_ctx_set_option(kpb_ctx* ctx, int option, int64_t value);
 
 /* Per-kernel timing for bench.py's roofline leg: when enabled every kernel launch is bracketed by two

@@ -161,6 +161,7 @@ class Context:
         self.check(self.lib.kpb_sync(self.handle))
 
     OPT_COVIS_STORE_BYTES = 1       # KPB_OPT_COVIS_STORE_BYTES
+    OPT_ALIKE_COARSE_FUSED = 2      # KPB_OPT_ALIKE_COARSE_FUSED
 
     def set_option(self, option: int, value: int):
         """kpb_ctx_set_option (include/kpb.h): a limit of this context, e.g. OPT_COVIS_STORE_BYTES."""

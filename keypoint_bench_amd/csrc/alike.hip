@@ -932,7 +932,7 @@ std::vector<float> pack_h16(const float* w, int CIN, const float* ds_w, float sc
 }
 
 // ------------------------------------------------------------------------------------------------ 1x1 + ReLU
-constexpr int ESTRIDE = 68;             // channels of a projected map: 64 descriptor rows + score row + pad (float4 aligned)
+constexpr int ESTRIDE = CM_ESTRIDE;      // channels of a projected map: 64 descriptor rows + score row + pad (float4 aligned)
 
 // out = relu(w . in) (ALike.py:147-150); smap = this group's share of the score logit; with E != null also the group's
 // share of every head row, E[p][o] = sum_c wproj[c][o] out[p][c] (see alike_head: the head commutes with upsampling)
@@ -1965,6 +1965,8 @@ float max_abs(const float* b, int n)
 constexpr CmForm CM_C16{.ks = 3, .s = 1, .cc = 16, .ntb = 1, .mt = 2, .wn = 2}, CM_C32{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
                  CM_C32_1T{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CM_C16_LAT{.ks = 3, .s = 1, .cc = 16, .wpre = true},
                  CM_C32_LAT{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .wpre = true}, CM_P4_LAT{.ks = 3, .s = 1, .cc = 32, .pool_in = true, .ntb = 1, .pf = 4, .wpre = true};
+// conv2 of blocks 3 / 4 finishing the block in its epilogue (CmForm::tail; KPB_OPT_ALIKE_COARSE_FUSED): block 3's also pools its output for block 4
+constexpr CmForm CM_B3C2_TAIL{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .tail = 2}, CM_B4C2_TAIL{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .tail = 1};
 
 template <int CIN, int COUT, int POOL, bool RES, int CDS, int RPOOL, bool DSOUT = false, int TW = 32>
 void launch_conv(kpb_ctx* ctx, const char* name, hipStream_t st, const ConvArgs& a, int B)
@@ -2004,6 +2006,8 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
     const size_t P = (size_t)H * W, B = batch;
     const bool h16 = conv_mfma_use_h16();       // the split-f16 matrix form (default) or the strict fp32 kernels (KPB_FP32_MATRIX=1)
     const bool dense = desc_out_dev != nullptr;
+    // blocks 3 / 4 finished inside their conv2 (CmForm::tail): x3 / x4 are not written, maxpool4_x3 and the two aggregations are not launched
+    const bool fused = h16 && batch >= 16 && ctx->alike_coarse_fused;
     const int nw1 = cdiv(W, B1_TW) * cdiv(H, B1H_TH) * 4, nw2 = cdiv(W / 2, 32) * cdiv(H / 2, 8) * 4;      // per-wave maxima of blocks 1 / 2
     const size_t n_2 = B * (P / 4) * 16, n_3 = B * (P / 64) * 32, n_4 = B * (P / 1024) * 64;
     float *p1, *t2, *x2, *t3, *x3, *t4, *x4, *r3, *r4, *t3r3, *t4r4, *p2, *p3, *S2, *S3, *S4, *E3, *E4, *wmax_x1, *wmax_a2;
@@ -2014,8 +2018,8 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
             x1 = a.take(B * P * 8);
             p1 = a.take(B * (P / 4) * 8);
             t2 = f32(n_2); x2 = f32(n_2); a2 = a.take(n_2);     // (alike_block2 hands block 3 p2 and leaves x2 unwritten)
-            t3 = f32(n_3); x3 = a.take(n_3); a3 = a.take(B * (P / 64) * 16);
-            t4 = f32(n_4); x4 = a.take(n_4); a4 = a.take(B * (P / 1024) * 16);
+            t3 = f32(n_3); x3 = fused ? nullptr : a.take(n_3); a3 = a.take(B * (P / 64) * 16);
+            t4 = f32(n_4); x4 = fused ? nullptr : a.take(n_4); a4 = a.take(B * (P / 1024) * 16);
             r3 = f32(n_3); r4 = f32(n_4);
             t3r3 = f16(2 * n_3);        // conv_mfma_h form of blocks 3 / 4: conv1's output and the identity branch side by side per pixel
             t4r4 = f16(2 * n_4);
@@ -2049,25 +2053,36 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
         // blocks 3 and 4 @ H/8, H/32 (141-144) on conv_mfma_h: conv1 carries the identity branch ds(pooled input) as 32 / 64 more
         // output channels whose weights sit on the centre tap only (no ReLU on those tiles); conv2 then reads conv1's half of that
         // buffer and adds the other half.  Block 4's conv1 max-pools x3 4 x 4 while it stages it.
-        auto block_h = [&](const Res& r, const float* in, float* tr, float* xo, int cin, int cout, int Hi, int Wi, bool prepooled) {
+        // tail (fused): conv2 writes (a3, S3, E3, p3) / (a4, S4, E4) instead of xo -- group gi of the aggregation and head weights, pool: block 3's pooled output
+        auto block_h = [&](const Res& r, const float* in, float* tr, float* xo, int cin, int cout, int Hi, int Wi, bool prepooled, int gi = 0, float* ao = nullptr,
+                           float* So = nullptr, float* Eo = nullptr, float* pool = nullptr) {
             ConvM m{.in = in, .out = tr, .wp = r.w1h, .bias = r.b1h, .Hi = prepooled ? Hi / 4 : Hi, .Wi = prepooled ? Wi / 4 : Wi,
                     .H = Hi / 4, .W = Wi / 4, .CIN = cin, .COUT = 2 * cout, .NCH = 1, .relu = 2, .nblk = cout / 32, .istride = cin, .ostride = 2 * cout,
                     .unscale = r.un1, .relu_nt = cout / 32};
             auto launch = [&](const char* prof, const CmForm& f, const ConvM& cm) {
-                return launch_conv_mfma_h<CM_C16, CM_C32, CM_C32_1T, CM_C16_LAT, CM_C32_LAT, CM_P4_LAT>(ctx, prof, f, cm, batch); };
+                return launch_conv_mfma_h<CM_C16, CM_C32, CM_C32_1T, CM_C16_LAT, CM_C32_LAT, CM_P4_LAT, CM_B3C2_TAIL, CM_B4C2_TAIL>(ctx, prof, f, cm, batch); };
             // small layers are bound by per-workgroup latency: 8-row tiles (r02: b3c1 0.36 -> 0.32 ms, b3c2 0.58 -> 0.49 ms).  A handful of images (the drop-in
             // path runs ONE): a 15 x 20 map in 16 x 16 tiles with two n-tiles each is 4 workgroups of pure latency (41 us); 8-row tiles with one n-tile each are 16
             // (same weights, same arithmetic per output)
             if (batch < 16 && !prepooled) m.nblk = 2 * cout / 32;
             const CmForm f1 = !prepooled ? CM_P4_LAT : batch < 16 ? CM_C16_LAT : cin == 32 ? CM_C32 : CM_C16;     // (only a handful of images leave x3 unpooled)
             if (int rc = launch(r.prof1.c_str(), f1, m)) return rc;
-            const ConvM c2{.in = tr, .out = xo, .wp = r.w2p, .bias = r.b2p, .res = tr + cout, .Hi = Hi / 4, .Wi = Wi / 4,
-                           .H = Hi / 4, .W = Wi / 4, .CIN = cout, .COUT = cout, .NCH = cout / 32, .nblk = batch < 16 ? cout / 32 : 1, .istride = 2 * cout,
-                           .ostride = cout, .unscale = r.un2, .rstride = 2 * cout};
+            ConvM c2{.in = tr, .out = xo, .wp = r.w2p, .bias = r.b2p, .res = tr + cout, .Hi = Hi / 4, .Wi = Wi / 4,
+                     .H = Hi / 4, .W = Wi / 4, .CIN = cout, .COUT = cout, .NCH = cout / 32, .nblk = batch < 16 ? cout / 32 : 1, .istride = 2 * cout,
+                     .ostride = cout, .unscale = r.un2, .rstride = 2 * cout};
+            if (ao) {
+                c2.tl_w = kh.agg[gi]; c2.tl_wsg = kh.wsc + 16 * (gi - 1); c2.tl_wproj = kh.whT + 16 * (gi - 1) * 64;
+                c2.tl_agg = ao; c2.tl_smap = So; c2.tl_E = Eo; c2.tl_pool = pool;
+                return launch(r.prof2.c_str(), pool ? CM_B3C2_TAIL : CM_B4C2_TAIL, c2);
+            }
             return launch(r.prof2.c_str(), batch < 16 ? CM_C32_LAT : cout == 32 ? CM_C32_1T : CM_C32, c2);
         };
-        if (int rc = block_h(blk[3], p2, t3r3, x3, 16, 32, H / 2, W / 2, true)) return rc;
-        if (batch >= 16) {      // block 4's input pooled once, by a kernel of its own (see maxpool4_nhwc); a handful of images keep the fused form (one launch fewer)
+        if (fused) {
+            if (int rc = block_h(blk[3], p2, t3r3, nullptr, 16, 32, H / 2, W / 2, true, 3, a3, S3, E3, p3)) return rc;
+            if (int rc = block_h(blk[4], p3, t4r4, nullptr, 32, 64, H / 8, W / 8, true, 4, a4, S4, E4)) return rc;
+        } else if (int rc = block_h(blk[3], p2, t3r3, x3, 16, 32, H / 2, W / 2, true))
+            return rc;
+        else if (batch >= 16) {      // block 4's input pooled once, by a kernel of its own (see maxpool4_nhwc); a handful of images keep the fused form (one launch fewer)
             KPB_LAUNCH(ctx, "maxpool4_x3", maxpool4_nhwc, dim3((unsigned)(((size_t)(H / 32) * (W / 32) * 8 + 255) / 256), batch), dim3(256), 0, st, x3, p3, H / 32, W / 32, 32);
             if (int rc = block_h(blk[4], p3, t4r4, x4, 32, 64, H / 8, W / 8, true)) return rc;
         } else if (int rc = block_h(blk[4], x3, t4r4, x4, 32, 64, H / 8, W / 8, false))
@@ -2096,8 +2111,10 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
         // aggregation 1x1 + ReLU of block 2 (147-148); agg1 is fused into the head
         KPB_LAUNCH(ctx, "conv1x1_agg2", conv1x1_relu<16>, dim3((unsigned)((B * P / 4 + 255) / 256)), dim3(256), 0, st, x2, a2, kh.agg[2], kh.wsc + 16, S2, B * P / 4, nullptr, nullptr);
     }
-    // aggregation 1x1 + ReLU (149-150), each with its share of the score logit and -- dense mode -- of every head row
-    if (batch < 16) {
+    // aggregation 1x1 + ReLU (149-150), each with its share of the score logit and -- dense mode -- of every head row (fused: conv2 of blocks 3 / 4 has done it)
+    if (fused)
+        ;
+    else if (batch < 16) {
         const AggArgs g3{x3, a3, kh.agg[3], kh.wsc + 32, S3, B * P / 64, kh.whT + 32 * 64, E3};
         const AggArgs g4{x4, a4, kh.agg[4], kh.wsc + 48, S4, B * P / 1024, kh.whT + 48 * 64, E4};
         const unsigned nb3 = (unsigned)((B * P / 64 + 255) / 256), nb4 = (unsigned)((B * P / 1024 + 255) / 256);

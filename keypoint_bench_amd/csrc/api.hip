@@ -59,6 +59,10 @@ extern "C" __attribute__((visibility("default"))) int kpb_ctx_set_option(kpb_ctx
     if (value < 0) return kpb_fail(ctx, KPB_E_INVALID, "kpb_ctx_set_option: negative value");
     switch (option) {
     case KPB_OPT_COVIS_STORE_BYTES: ctx->covis_store_bytes = (size_t)value; return KPB_OK;
+    case KPB_OPT_ALIKE_COARSE_FUSED:
+        if (value > 1) return kpb_fail(ctx, KPB_E_INVALID, "kpb_ctx_set_option: KPB_OPT_ALIKE_COARSE_FUSED takes 0 or 1 (got %lld)", (long long)value);
+        ctx->alike_coarse_fused = (int)value;
+        return KPB_OK;
     default: return kpb_fail(ctx, KPB_E_INVALID, "kpb_ctx_set_option: unknown option %d", option);
     }
 }

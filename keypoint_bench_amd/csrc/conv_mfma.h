@@ -55,7 +55,13 @@ struct ConvM {
     int unfold_w = 0;             // gemm_h<.., UNFOLD>: `in` is a single-channel [B][8 H][unfold_w] image and row r, channel c stand for pixel
                                   // (8 (r / W) + c / 8, 8 (r % W) + c % 8): XFeat's _unfold2d(x, 8) read in place (XFeat.py:96-103, 138)
     int tap_dil = 0;              // gemm_h<.., TAPK>: the dilation of the gathered taps (see there)
+    // conv_mfma_h<tail> (ALIKE's conv2 of blocks 3 / 4, CmForm::tail): what the epilogue writes INSTEAD of `out` -- the 1 x 1 aggregation of the block's output
+    // (tl_w [COUT][16]) + ReLU into tl_agg [B][H][W][16], its share of the score logit (tl_wsg [16]) into tl_smap [B][H][W], with tl_E also its share of every head row
+    // (tl_wproj [16][64]) into tl_E [B][H][W][CM_ESTRIDE], and with tail == 2 the 4 x 4 max-pool of the output into tl_pool [B][H / 4][W / 4][COUT]
+    const float* tl_w = nullptr; const float* tl_wsg = nullptr; const float* tl_wproj = nullptr;
+    float* tl_agg = nullptr; float* tl_smap = nullptr; float* tl_E = nullptr; float* tl_pool = nullptr;
 };
+constexpr int CM_ESTRIDE = 68;          // floats of a projected pixel: 64 descriptor rows + score row + pad (float4 aligned); alike.hip's ESTRIDE
 
 // gemm_h epilogues.  GE_RESIDUAL: out = res + (W x + b), rows of `res` rstride floats apart (lightglue.py:185 / 242, x + ffn(...)).
 // GE_ROTARY: the 768 columns of Wqkv arrive permuted (lg_pack_qkv_rows): workgroup nb = 3 head + which (q, k, v) owns the 32 even
@@ -98,11 +104,19 @@ struct CmForm {
     // = input extent at stride 1 for odd AND even ks (an even kernel's two taps sit at -dil / 2 and +dil / 2: R2D2's 2 x 2 layers).  The halo of the input tile grows
     // to (ks - 1) dil pixels: a 16 x 16 output tile of a 3 x 3 layer stages 20 x 20 pixels at dil = 2 (61 KB with the row padding) -- two workgroups per CU, see waves().
     int dil = 1;
+    // (r07) ALIKE's conv2 of blocks 3 / 4 at batch size: the epilogue FINISHES the ResBlock on chip.  The block's output x3 / x4 has three readers and all of them read it
+    // whole -- the 1 x 1 aggregation (with its score and head shares), and for x3 the 4 x 4 max-pool that feeds block 4 -- so the tile goes to LDS as fp32 (128 pixels
+    // per pass, over the input tile, which is dead after the last tap) instead of HBM, two waves run the aggregation one pixel per lane from there (cm_tail_agg: the
+    // fmaf chains of conv1x1_relu_body) and, with tail == 2, a third wave pools it.  x3 / x4 are never written: 0.61 MB written and twice read per 480 x 640 image, and
+    // three launches.  1: aggregation; 2: aggregation + pool.  One workgroup must own every channel of its pixels (nblk = 1).
+    int tail = 0;
     constexpr bool operator==(const CmForm&) const = default;
     constexpr int tile_h() const { return 8 * mt / wn; }       // output rows of a workgroup tile
     // conv_mfma_h: waves per SIMD the register allocation is held to: what r02's code reached without being told (accumulators 16 mt ntb) -- left alone, the
     // allocator keeps a second copy of the accumulators in VGPRs for the rare rescale (+64 registers, a wave per SIMD lost on every two-tile layer)
-    constexpr int waves() const { return wpre ? 1 : dil > 1 ? 2 /* the dilated tiles are 56-61 KB of LDS: two workgroups per CU is all that fits */ : mt * ntb >= 4 ? ((ks == 5 && cc == 32) || pool_in ? 2 : 3) : (mt * ntb == 2 ? (ks == 3 && cc == 16 ? 3 : 4) : 5); }
+    // (tail, 16 x 16 tiles: the accumulators of the pass that waits stay live under the first pass's aggregation -- at three waves per SIMD, 168 registers, the form spilled
+    //  2-60 registers however few columns of E a round took; block 4's conv2 is 1 024 workgroups of 50 KB per 512 images, two rounds of the chip at two OR three per CU)
+    constexpr int waves() const { return wpre ? 1 : tail && mt == 4 ? 2 : dil > 1 ? 2 /* the dilated tiles are 56-61 KB of LDS: two workgroups per CU is all that fits */ : mt * ntb >= 4 ? ((ks == 5 && cc == 32) || pool_in ? 2 : 3) : (mt * ntb == 2 ? (ks == 3 && cc == 16 ? 3 : 4) : 5); }
 };
 
 template <CmForm F>
@@ -111,7 +125,7 @@ __global__ __launch_bounds__(256) void conv_mfma(ConvM a)
     constexpr int KS = F.ks, S = F.s, CC = F.cc, NTB = F.ntb; constexpr bool POOL_IN = F.pool_in, POOL_OUT = F.pool_out, XF = F.xf;
     constexpr int DIL = F.dil;
     static_assert(F == CmForm{.ks = KS, .s = S, .cc = CC, .pool_in = POOL_IN, .pool_out = POOL_OUT, .xf = XF, .ntb = NTB, .dil = DIL},
-                  "conv_mfma: the strict-fp32 kernel has no mt, xc, pf, wpre, pre, wn, gen or up");
+                  "conv_mfma: the strict-fp32 kernel has no mt, xc, pf, wpre, pre, wn, gen, up or tail");
     constexpr int KC = CC / 2, PITCH = CC + 4, T = KS * KS, PAD = (KS - 1) * DIL / 2;
     constexpr int IH = 7 * S + (KS - 1) * DIL + 1, IW = 15 * S + (KS - 1) * DIL + 1, Q = CC / 4;
     static_assert(IH * IW * PITCH * 4 <= 65536, "conv_mfma: input tile exceeds the static LDS window");
@@ -342,6 +356,80 @@ __device__ __forceinline__ float4 cm_up2_mix(const float4 p00, const float4 p01,
     const float hy = 1.0f - ly, hx = 1.0f - lx;
     return make_float4(hy * (hx * p00.x + lx * p01.x) + ly * (hx * p10.x + lx * p11.x), hy * (hx * p00.y + lx * p01.y) + ly * (hx * p10.y + lx * p11.y),
                        hy * (hx * p00.z + lx * p01.z) + ly * (hx * p10.z + lx * p11.z), hy * (hx * p00.w + lx * p01.w) + ly * (hx * p10.w + lx * p11.w));
+}
+
+// CmForm::tail, the part of one wave: conv1x1_relu_body (alike.hip) on 64 pixels of the block's output that sit in LDS (`x`: this lane's pixel, CT floats) instead of
+// HBM -- the same fmaf chains in the same order, so the same bits.  The wave's pixels are four rows of a 16-wide tile: row g (lanes 16 g ..) starts at pixel
+// row_pix[g] of the map and has ncol[g] columns inside it (0: the row is below the map).  TWO waves take the same 64 pixels: both run the aggregation (512 fmas a
+// pixel), half 0 stores it with its score share and projects head rows 0 .. 31, half 1 projects rows 32 .. 63 and appends the score share (1 024 fmas a pixel between
+// them: with one wave per pixel set half the workgroup idled through them).  strip: 16 x 16 floats of LDS of the wave's own.
+template <int CT>
+__device__ __forceinline__ void cm_tail_agg(const float* x, float* strip, const float* w_ /*[CT][16]*/, const float* wsg_ /*[16]*/,
+                                            const float* wproj_ /*[16][64]*/, float* __restrict__ out, float* __restrict__ smap, float* __restrict__ E,
+                                            const size_t (&row_pix)[4], const int (&ncol)[4], int lane, int half)
+{
+    // The three weight arrays are wave-uniform and must arrive by scalar loads.  In conv1x1_relu_body __restrict__ on the kernel's own parameters proves them
+    // unclobbered; behind the hundreds of LDS stores of a convolution the compiler's walk up the memory dependences gives up before it gets there and fetched all 1 536
+    // floats with vector loads into 64 registers at a time (42 / 60 registers spilled).  Read through the constant address space they are scalar loads by definition;
+    // no kernel writes weights (they are bound at net create).
+    typedef const __attribute__((address_space(4))) float* cfp;
+    const cfp w = (cfp)w_, wsg = (cfp)wsg_, wproj = (cfp)wproj_;
+    float acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
+#pragma unroll 2
+    for (int c4 = 0; c4 < CT / 4; ++c4) {
+        const float4 v4 = *reinterpret_cast<const float4*>(x + c4 * 4);
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[j] = fmaf(v[c], w[(c4 * 4 + c) * 16 + j], acc[j]);
+    }
+    float sg = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) { acc[j] = relu(acc[j]); sg = fmaf(acc[j], wsg[j], sg); }
+    const int g_own = lane >> 4, col = lane & 15;
+    size_t pix = 0; bool live = false;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+        if (g == g_own) { pix = row_pix[g] + col; live = col < ncol[g]; }
+    if (live && half == 0) {
+        float* o = out + pix * 16;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            *reinterpret_cast<float4*>(o + 4 * q) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+        smap[pix] = sg;
+    }
+    if (!E) return;
+    // the wave's eight float4s of a projected pixel, four a round (16 registers beside the 16 of acc: all 17 at once, conv1x1_relu_body's form, spilled 42 / 60 registers
+    // at the 96 / 168 the two forms have).  A round's 16 pixels x 64 bytes of one tile row pass through the strip and leave one float4 per lane, the four lanes of a pixel
+    // on consecutive ones (a wave's LDS operations execute in order: no barrier).
+#pragma unroll
+    for (int rnd = 0; rnd < 2; ++rnd) {
+        const int q0 = 8 * half + 4 * rnd;          // wave-uniform
+        float4 r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            r[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int c = 0; c < 16; ++c) {
+                const cfp wr = wproj + c * 64 + 4 * (q0 + k);
+                r[k].x = fmaf(acc[c], wr[0], r[k].x); r[k].y = fmaf(acc[c], wr[1], r[k].y);
+                r[k].z = fmaf(acc[c], wr[2], r[k].z); r[k].w = fmaf(acc[c], wr[3], r[k].w);
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            if (g_own == g) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(strip + col * 16 + 4 * k) = r[k];
+            }
+            if ((lane >> 2) < ncol[g])
+                *reinterpret_cast<float4*>(E + (row_pix[g] + (lane >> 2)) * CM_ESTRIDE + 4 * (q0 + (lane & 3))) = *reinterpret_cast<const float4*>(strip + 4 * lane);
+        }
+    }
+    if (live && half == 1) *reinterpret_cast<float4*>(E + pix * CM_ESTRIDE + 64) = make_float4(sg, 0.f, 0.f, 0.f);
 }
 
 // (Tried, r02: requesting the weight fragments of tap t + 1 before the MFMAs of tap t in a second register set -- 12-15 % slower on every layer; the extra 32-64 VGPRs
@@ -799,6 +887,74 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
     }
     const float unscale = a.unscale * cm_unscale_of(e_cur);      // weight scale and activation scale, both powers of two
 
+    if constexpr (F.tail != 0) {
+        // CmForm::tail: the output tile goes to LDS, 128 pixels (eight tile rows) a pass, and is finished from there
+        static_assert(S == 1 && NTB == 1 && DIL == 1 && !POOL_OUT && !XC && !WPRE && !PRE && !UP && TH % 8 == 0, "conv_mfma_h<tail>: ALIKE's conv2 forms");
+        constexpr int CT = 32 * WN, XP = CT + 4;        // channels of the tile; floats per pixel in LDS: lanes XP floats apart read 16 bytes without bank conflicts
+        constexpr int NPASS = TH / 8;
+        static_assert((128 * XP + 4 * 256) * 4 <= IH * ROWP, "conv_mfma_h<tail>: a pass and the four waves' staging strips live in the input tile's LDS");
+        static_assert(F.tail == 1 || (NPASS == 1 && CT == 32), "conv_mfma_h<tail>: the pooling wave takes a 16 x 8 tile of 32 channels");
+        float* xt = reinterpret_cast<float*>(tile);
+        static_assert(MT == 1 || MT == 4, "conv_mfma_h<tail>: a wave's M tiles lie in ONE pass (rows 2 wv .. or 8 wm ..)");
+        const int rs = a.rstride ? a.rstride : a.COUT, co = nt0 * 32 + p;
+        const float* res = a.res + (size_t)b * a.H * a.W * rs + co;         // (a map of one image is far below 2^31 floats: 32-bit offsets from here)
+#pragma unroll
+        for (int pass = 0; pass < NPASS; ++pass) {
+            __syncthreads();        // the last tap's (the previous pass's) readers are done with the tile
+            if (2 * wm * MT / 8 == pass) {          // wave-uniform
+#pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                    const int lrow = 2 * (wm * MT + m) - 8 * pass;
+                    float rv[16];
+                    // the residual of a pixel outside the map is read at the map's edge instead: such a pixel is staged, but never stored, and no pool window holds one
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int gy = min(ty0 + 8 * pass + lrow + (i >> 4), a.H - 1), gx = min(tx0 + (i & 15), a.W - 1);
+                        rv[r] = res[(gy * a.W + gx) * rs];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+                        float o = fmaf(acc[m][0][r], unscale, biasv[0]);
+                        if (a.relu == 1 || (a.relu == 2 && nt0 < a.relu_nt)) o = relu(o);
+                        xt[((lrow + (i >> 4)) * 16 + (i & 15)) * XP + co] = relu(o + rv[r]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);      // one M tile's sixteen residual loads in flight at a time
+                }
+            }
+            __syncthreads();
+            if (F.tail == 2 && wv == 2) {
+                // max_pool2d(x, 4, 4) of the tile: 2 x 4 pooled pixels x 8 channel quads, one per lane, in maxpool4_nhwc's order
+                const int pp = lane >> 3, q = lane & 7, py = pp >> 2, px = pp & 3;
+                const int Ho = a.H / 4, Wo = a.W / 4, oy = ty0 / 4 + py, ox = tx0 / 4 + px;
+                const float* s = xt + ((4 * py) * 16 + 4 * px) * XP + 4 * q;
+                float4 mx = *reinterpret_cast<const float4*>(s);
+#pragma unroll
+                for (int dy = 0; dy < 4; ++dy)
+#pragma unroll
+                    for (int dx = 0; dx < 4; ++dx) {
+                        if (dy == 0 && dx == 0) continue;
+                        const float4 v = *reinterpret_cast<const float4*>(s + (dy * 16 + dx) * XP);
+                        mx.x = fmaxf(mx.x, v.x); mx.y = fmaxf(mx.y, v.y); mx.z = fmaxf(mx.z, v.z); mx.w = fmaxf(mx.w, v.w);
+                    }
+                if (oy < Ho && ox < Wo) *reinterpret_cast<float4*>(a.tl_pool + (((size_t)b * Ho + oy) * Wo + ox) * CT + 4 * q) = mx;
+            }
+            if (wv < 2 || a.tl_E) {         // waves 2 and 3 share the head projection of waves 0 and 1 (cm_tail_agg); the keypoint-only mode has none
+                const int wvs = __builtin_amdgcn_readfirstlane(wv), ps = wvs & 1;        // in a scalar register: the projection weights of a wave's half stay scalar loads
+                size_t row_pix[4]; int ncol[4];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int gy = ty0 + 8 * pass + 4 * ps + g;
+                    row_pix[g] = ((size_t)b * a.H + gy) * a.W + tx0;
+                    ncol[g] = gy < a.H ? min(16, a.W - tx0) : 0;
+                }
+                cm_tail_agg<CT>(xt + (ps * 64 + lane) * XP, xt + 128 * XP + wvs * 256, a.tl_w, a.tl_wsg, a.tl_wproj, a.tl_agg, a.tl_smap, a.tl_E, row_pix, ncol, lane, wvs >> 1);
+            }
+        }
+        return;
+    }
+
     // epilogue: as conv_mfma, per M tile; the accumulator carries the layer's weight scale x the activation scale of e_cur
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
@@ -859,8 +1015,8 @@ int cm_launch(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, in
         else KPB_LAUNCH(ctx, tag, conv_mfma<FS>, grid, dim3(256), 0, ctx->stream, a);
         return true;
     }()) || ...);
-    return found ? KPB_OK : kpb_fail(ctx, KPB_E_INVALID, "%s: no instance for %s: ks=%d s=%d cc=%d pool_in=%d pool_out=%d xf=%d ntb=%d mt=%d xc=%d pf=%d wpre=%d pre=%d wn=%d gen=%d up=%d dil=%d",
-        H ? "conv_mfma_h" : "conv_mfma", tag, f.ks, f.s, f.cc, f.pool_in, f.pool_out, f.xf, f.ntb, f.mt, f.xc, f.pf, f.wpre, f.pre, f.wn, f.gen, f.up, f.dil);
+    return found ? KPB_OK : kpb_fail(ctx, KPB_E_INVALID, "%s: no instance for %s: ks=%d s=%d cc=%d pool_in=%d pool_out=%d xf=%d ntb=%d mt=%d xc=%d pf=%d wpre=%d pre=%d wn=%d gen=%d up=%d dil=%d tail=%d",
+        H ? "conv_mfma_h" : "conv_mfma", tag, f.ks, f.s, f.cc, f.pool_in, f.pool_out, f.xf, f.ntb, f.mt, f.xc, f.pf, f.wpre, f.pre, f.wn, f.gen, f.up, f.dil, f.tail);
 }
 template <CmForm... FS> int launch_conv_mfma_h(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B) { return cm_launch<true, FS...>(ctx, tag, f, a, B); }
 template <CmForm... FS> int launch_conv_mfma(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B) { return cm_launch<false, FS...>(ctx, tag, f, a, B); }

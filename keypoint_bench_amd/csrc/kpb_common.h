@@ -173,6 +173,7 @@ struct kpb_ctx {
     // not in a process-wide static that a second device would find already set
     unsigned lds_attr_done = 0;
     size_t covis_store_bytes = (size_t)4 << 30;     // KPB_OPT_COVIS_STORE_BYTES (kpb_ctx_set_option)
+    int alike_coarse_fused = 1;                     // KPB_OPT_ALIKE_COARSE_FUSED
 };
 enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u };
 
