@@ -79,9 +79,16 @@ int kpb_sync(kpb_ctx* ctx);
  *   KPB_OPT_ALIKE_COARSE_FUSED 1 (default): at 16 images or more the split-f16 ALIKE forward finishes blocks 3 and 4 inside their second convolution (aggregation,
  *                              score and head shares, and block 3's max-pool from on-chip memory: four launches, the blocks' outputs never written); 0: the seven
  *                              separate launches at any batch.  Both give the same bits (tests/test_gpu_alike_coarse_tail.py).  Any other value is invalid.
+ *   KPB_OPT_DETECT_SIGNED      0 (default): kpb_detect and kpb_fast_nms compute the NMS fixed point, which is the reference's answer for NON-NEGATIVE maps, and refuse
+ *                              a map with a negative score (KPB_E_NEGATIVE).  1: they run the reference's loop itself on every image of the call -- synchronous rounds
+ *                              that stop as soon as the number of window maxima repeats (utils/extracter.py:49-98), negative and zero maxima counted as the reference
+ *                              counts them -- and never return KPB_E_NEGATIVE: exact detection on raw logits and other signed responses.  On a non-negative map both
+ *                              give the same rows; the rounds are slower.  With the option on, nms_dist > 0 and threshold < 0 are KPB_E_UNSUPPORTED (-0.0 is zero);
+ *                              nms_dist == 0 is unchanged.  A kpb_detect(sync = 0) keeps the setting it was enqueued under.  Any other value is invalid.
  * Returns KPB_E_INVALID for an unknown option or a negative value. */
 #define KPB_OPT_COVIS_STORE_BYTES 1
 #define KPB_OPT_ALIKE_COARSE_FUSED 2
+#define KPB_OPT_DETECT_SIGNED 3
 int kpb_ctx_set_option(kpb_ctx* ctx, int option, int64_t value);
 
 /* Per-kernel timing for bench.py's roofline leg: when enabled every kernel launch is bracketed by two
@@ -92,7 +99,8 @@ int kpb_prof_report(kpb_ctx* ctx, char* buf, size_t cap);
 
 /* ---- A1: utils/extracter.py:6-100 fast_nms --------------------------------------------------
  * score_dev [batch][H][W] fp32, non-negative; out_map_dev same shape (may not alias score_dev).
- * Synchronous: iterates sweeps until every image reached the fixed point. */
+ * Synchronous: iterates sweeps until every image reached the fixed point.
+ * Under KPB_OPT_DETECT_SIGNED the map may hold any sign: image b's result is the map of the round at which the reference's loop stops. */
 int kpb_fast_nms(kpb_ctx* ctx, const float* score_dev, int batch, int H, int W, int nms_dist,
                  float* out_map_dev);
 
@@ -104,7 +112,7 @@ int kpb_fast_nms(kpb_ctx* ctx, const float* score_dev, int batch, int H, int W, 
  * out_n_dev   [batch] number of valid rows (<= cap).
  * Row order: raster when N <= top_k, descending score (ties: ascending raster index) otherwise.
  * sync != 0: blocks until done, re-running sweeps for images that had not converged, and
- * returns KPB_E_NEGATIVE if any map held a negative score.  sync == 0: enqueue only; call
+ * returns KPB_E_NEGATIVE if any map held a negative score (never under KPB_OPT_DETECT_SIGNED).  sync == 0: enqueue only; call
  * kpb_detect_check() later -- score_dev and the outputs must stay alive until then, and a second kpb_detect before
  * that check is refused (KPB_E_INVALID): the context holds ONE pending detection. */
 int kpb_detect(kpb_ctx* ctx, const float* score_dev, int batch, int H, int W,

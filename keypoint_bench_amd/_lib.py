@@ -1,5 +1,6 @@
 """ctypes binding of libkpb.so (include/kpb.h).  There is no CPU fallback: if the HIP library is
 missing or no gfx950 device is visible, every entry point raises."""
+import contextlib
 import ctypes
 import os
 
@@ -162,10 +163,28 @@ class Context:
 
     OPT_COVIS_STORE_BYTES = 1       # KPB_OPT_COVIS_STORE_BYTES
     OPT_ALIKE_COARSE_FUSED = 2      # KPB_OPT_ALIKE_COARSE_FUSED
+    OPT_DETECT_SIGNED = 3           # KPB_OPT_DETECT_SIGNED
 
     def set_option(self, option: int, value: int):
         """kpb_ctx_set_option (include/kpb.h): a limit of this context, e.g. OPT_COVIS_STORE_BYTES."""
         self.check(self.lib.kpb_ctx_set_option(self.handle, int(option), int(value)))
+        if int(option) == self.OPT_DETECT_SIGNED:
+            self._detect_signed = int(value)
+
+    _detect_signed = 0      # what OPT_DETECT_SIGNED was last set to (the library has no getter)
+
+    @contextlib.contextmanager
+    def detect_signed(self, on: bool):
+        """on: OPT_DETECT_SIGNED = 1 for the calls inside the block, and what was set before comes back afterwards, also on an exception.
+        Not on: the context's own setting stands."""
+        before = self._detect_signed
+        if on and not before:
+            self.set_option(self.OPT_DETECT_SIGNED, 1)
+        try:
+            yield self
+        finally:
+            if self._detect_signed != before:
+                self.set_option(self.OPT_DETECT_SIGNED, before)
 
     def prof_enable(self, on: bool):
         self.check(self.lib.kpb_prof_enable(self.handle, 1 if on else 0))

@@ -806,7 +806,16 @@ struct SelArgs {
     int nchunks;                 //   cand[c * SEL_CHUNK ...] and their number here; null: select_topk scans the map itself
     int lcap;                    // two-phase form: candidates that fit in LDS behind the kpad selection slots
     const unsigned* cbits; int wb;      // r06: the NMS's bitmap of confirmed maxima ([B][H][wb bytes], NmsArgs): read instead of the map for an image the tail has settled
+    const int* rfin; const float* map1; // signed rounds (nms_round): 1 + the round image b stopped at (0: undecided) names its map -- `map` for an even round, map1 for an odd one; null: `map`
 };
+
+// the map of image img: the one plane there is, or the buffer nms_round's stop rule left the result in
+__device__ __forceinline__ const float* sel_map(const SelArgs& a, int img)
+{
+    const size_t P = (size_t)a.H * a.W;
+    if (a.rfin && ((a.rfin[img] - 1) & 1)) return a.map1 + (size_t)img * P;        // undecided (0): either plane, the rows are rewritten after more rounds
+    return a.map + (size_t)img * P;
+}
 
 __device__ __forceinline__ void emit(const SelArgs& a, int img, const unsigned long long* src, int n,
                                      unsigned long long* wsum)
@@ -840,8 +849,9 @@ __device__ __forceinline__ void emit(const SelArgs& a, int img, const unsigned l
     if (threadIdx.x == 0) {
         a.out_n[img] = base;
         if (a.host_status) {
-            a.host_status[3 * img + 0] = a.lastchg ? a.lastchg[img] : 0;
-            a.host_status[3 * img + 1] = a.negflag ? a.negflag[img] : 0;
+            // signed rounds: word 0 = the image is still undecided, and a negative score is no error
+            a.host_status[3 * img + 0] = a.rfin ? (a.rfin[img] == 0) : (a.lastchg ? a.lastchg[img] : 0);
+            a.host_status[3 * img + 1] = (a.negflag && !a.rfin) ? a.negflag[img] : 0;
             a.host_status[3 * img + 2] = base;
         }
     }
@@ -968,7 +978,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_scan(SelArgs a)
 {
     __shared__ unsigned long long wsum[SEL_WAVES];
     const int img = blockIdx.y, c = blockIdx.x, P = a.H * a.W;
-    const int n = scan_chunks(a, a.map + (size_t)img * P, a.cand + (size_t)img * P, c * SEL_CHUNK, min((c + 1) * SEL_CHUNK, P), c * SEL_CHUNK, wsum);
+    const int n = scan_chunks(a, sel_map(a, img), a.cand + (size_t)img * P, c * SEL_CHUNK, min((c + 1) * SEL_CHUNK, P), c * SEL_CHUNK, wsum);
     if (threadIdx.x == 0) a.chunk_cnt[(size_t)img * a.nchunks + c] = n;
 }
 
@@ -985,7 +995,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_topk(SelArgs a)
 
     const int img = blockIdx.x, tid = threadIdx.x;
     const int P = a.H * a.W;
-    const float* map = a.map + (size_t)img * P;
+    const float* map = sel_map(a, img);
     unsigned long long* cand = a.cand + (size_t)img * P;
 
     // A2 + A3: border mask and raster-order compaction of map > threshold
@@ -1285,6 +1295,158 @@ int nms_status(kpb_ctx* ctx, const NmsPlan& p, int batch, int sweeps_run, int& p
     return KPB_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ signed maps: the reference's rounds
+// KPB_OPT_DETECT_SIGNED (DESIGN.md "signed maps: the rounds, not the fixed point").  On a map with negative scores the reference's loop is no fixed-point
+// iteration: it stops as soon as the NUMBER of maxima repeats, and negative and zero maxima feed that number, so the stopping round -- and with it the
+// result -- belongs to the synchronous schedule.  nms_round is that schedule, one launch per round k on double-buffered maps:
+//   mask_k   first-index argmax of the zero-padded window at the centre, on the tile and an r halo (tile + 2r staged in LDS; the separable row-maximum /
+//            column test of nms_sweep, without its "alive" condition: zero and negative pixels are maxima too);
+//   count_k  the tile's own maxima, one atomic per workgroup;
+//   map_k+1  the tile with every pixel zeroed that lies within r of a maximum other than itself, written to the OTHER buffer.
+// The stop decision needs all of count_k, so launch k+1 takes it: if count_k == count_k-1 every workgroup leaves without writing (map_k is intact in its
+// buffer) and fin[img] = k + 1 is recorded; later launches see fin and leave at once.  map_0 is the caller's map, map_k (k >= 1) lives in buf[k & 1].
+constexpr int RTH = 32, RTW = 64, ROUND_THREADS = 256;
+
+struct RoundArgs {
+    const float* src;       // [B][P] map_0
+    float* buf[2];          // [B][P] each
+    int* fin;               // [B] 0 = undecided, else 1 + the round the loop stopped at
+    int* count;             // [B][4] count_k at [k & 3]; launch k clears the slot of k + 1
+    int H, W, r, tiles_x, round, cap;
+};
+
+__global__ __launch_bounds__(ROUND_THREADS) void nms_round(RoundArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int r = a.r, LH = RTH + 4 * r, LW = RTW + 4 * r;
+    float* t = reinterpret_cast<float*>(smem);      // map_k on the tile + 2r
+    float* e = t + LH * LW;                         // row maxima over [x-r, x+r]
+    int* maxlist = reinterpret_cast<int*>(e + LH * LW);     // [cap] maxima of tile + r
+    __shared__ int s_n, s_own, s_stop;
+
+    const int img = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x, k = a.round;
+    int* cnt = a.count + 4 * (size_t)img;
+    if (tid == 0) {
+        s_n = 0; s_own = 0;
+        s_stop = a.fin[img] != 0 || (k >= 2 && cnt[(k - 1) & 3] == cnt[(k - 2) & 3]);
+    }
+    __syncthreads();
+    if (s_stop) {       // every workgroup of the launch decides alike: the counts are complete, and fin is only ever set on this very condition
+        if (tile == 0 && tid == 0 && a.fin[img] == 0) a.fin[img] = k;        // stopped at round k - 1
+        return;
+    }
+    if (tile == 0 && tid == 0) cnt[(k + 1) & 3] = 0;        // last read by launch k - 1, next added to by launch k + 1
+
+    const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    const size_t P = (size_t)a.H * a.W;
+    const float* in = (k == 0 ? a.src : a.buf[k & 1]) + (size_t)img * P;
+    float* out = a.buf[(k + 1) & 1] + (size_t)img * P;
+    const int gy0 = ty * RTH - 2 * r, gx0 = tx * RTW - 2 * r;
+
+    for (int i = tid; i < LH * LW; i += ROUND_THREADS) {
+        const int ly = i / LW, lx = i - ly * LW;
+        const int gy = gy0 + ly, gx = gx0 + lx;
+        float v = 0.0f;  // F.unfold's zero padding (extracter.py:54-60)
+        if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) v = in[(size_t)gy * a.W + gx];
+        t[i] = v;
+    }
+    __syncthreads();
+    const int IW = LW - 2 * r, IH = LH - 2 * r;
+    // e[y][x] = max t[y][x-r .. x+r], all rows, columns [r, LW-r)
+    for (int i = tid; i < LH * IW; i += ROUND_THREADS) {
+        const int y = i / IW, x = i - y * IW + r;
+        const float* row = t + y * LW + x;
+        float m = row[-r];
+        for (int d = -r + 1; d <= r; ++d) m = fmaxf(m, row[d]);
+        e[y * LW + x] = m;
+    }
+    __syncthreads();
+    // mask_k on tile + r: argmax returns the FIRST index of the maximum (extracter.py:69-70), so the centre is strictly greater than the rows above and
+    // the cells to its left, >= the rest.  Only pixels of the image are tested; what lies outside is padding.  (-0.0 == 0.0: a zero is a zero.)
+    for (int i = tid; i < IH * IW; i += ROUND_THREADS) {
+        const int y = i / IW + r, x = i - (y - r) * IW + r;
+        const int gy = gy0 + y, gx = gx0 + x;
+        if (gy < 0 || gy >= a.H || gx < 0 || gx >= a.W) continue;
+        const float v = t[y * LW + x];
+        if (v == e[y * LW + x]) {
+            bool ok = true;
+            for (int d = 1; d <= r && ok; ++d) ok = v > t[y * LW + x - d];
+            for (int d = 1; d <= r && ok; ++d) ok = (v > e[(y - d) * LW + x]) && (v >= e[(y + d) * LW + x]);
+            if (ok) {
+                // two maxima never lie within r of each other (each would have to outrank the other), so at most one falls into any (r+1)^2 block: cap
+                const int slot = atomicAdd(&s_n, 1);
+                if (slot < a.cap) maxlist[slot] = y * LW + x;
+                if (y >= 2 * r && y < 2 * r + RTH && x >= 2 * r && x < 2 * r + RTW) atomicAdd(&s_own, 1);
+            }
+        }
+    }
+    __syncthreads();
+    const int nmax = min(s_n, a.cap), ks = 2 * r + 1;
+    if (tid == 0 && s_own) atomicAdd(&cnt[k & 3], s_own);
+    // suppression: the window of every maximum, the maximum itself excepted (extracter.py:81-96).  One thread per window column; a maximum's own
+    // cell is in no other maximum's window, so the stores race on nothing but zeros.
+    for (int i = tid; i < nmax * ks; i += ROUND_THREADS) {
+        const int m = i / ks, dx = i - m * ks - r;
+        float* col = t + maxlist[m] + dx - r * LW;
+        for (int dy = 0; dy < ks; ++dy)
+            if (dx != 0 || dy != r) col[dy * LW] = 0.0f;
+    }
+    __syncthreads();
+    // map_k+1: the whole tile (the other buffer holds map_k-1)
+    for (int i = tid; i < RTH * RTW; i += ROUND_THREADS) {
+        const int oy = i / RTW, ox = i - oy * RTW;
+        const int gy = ty * RTH + oy, gx = tx * RTW + ox;
+        if (gy < a.H && gx < a.W) out[(size_t)gy * a.W + gx] = t[(oy + 2 * r) * LW + ox + 2 * r];
+    }
+}
+
+struct RoundPlan {
+    float* buf[2];
+    int* fin;       // fin[B] and count[B][4]: one piece, one memset
+    int* count;
+    int tiles_x, ntiles, cap;
+    size_t lds;
+};
+
+int round_plan(kpb_ctx* ctx, int batch, int H, int W, int r, RoundPlan& p)
+{
+    if ((size_t)H * W >= ((size_t)1 << 30)) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "NMS: a %d x %d map is too large (2^30 pixels per image at most)", H, W);
+    const int LH = RTH + 4 * r, LW = RTW + 4 * r;
+    p.tiles_x = cdiv(W, RTW);
+    p.ntiles = p.tiles_x * cdiv(H, RTH);
+    p.cap = cdiv(LH - 2 * r, r + 1) * cdiv(LW - 2 * r, r + 1);
+    p.lds = (size_t)2 * LH * LW * sizeof(float) + (size_t)p.cap * sizeof(int);
+    const size_t P = (size_t)H * W;
+    if (int rc = kpb_carve(ctx, ctx->ws_nms_map, [&](Arena& a) {
+            p.buf[0] = a.take((size_t)batch * P);
+            p.buf[1] = a.take((size_t)batch * P);
+        })) return rc;
+    if (int rc = kpb_carve(ctx, ctx->ws_nms_rounds, [&](Arena& a) { p.fin = a.take<int>((size_t)5 * batch); })) return rc;
+    p.count = p.fin + batch;
+    if (!(ctx->lds_attr_done & KPB_ATTR_NMS_ROUND)) {
+        KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(nms_round), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
+        ctx->lds_attr_done |= KPB_ATTR_NMS_ROUND;
+    }
+    return KPB_OK;
+}
+
+// launches rounds first .. first + n - 1 (round 0 also clears the state)
+int round_launch(kpb_ctx* ctx, const RoundPlan& p, const float* src, int batch, int H, int W, int r, int first, int n)
+{
+    if (first == 0) KPB_HIP(ctx, hipMemsetAsync(p.fin, 0, (size_t)5 * batch * sizeof(int), ctx->stream));
+    for (int k = first; k < first + n; ++k) {
+        RoundArgs a;
+        a.src = src; a.buf[0] = p.buf[0]; a.buf[1] = p.buf[1]; a.fin = p.fin; a.count = p.count;
+        a.H = H; a.W = W; a.r = r; a.tiles_x = p.tiles_x; a.round = k; a.cap = p.cap;
+        KPB_LAUNCH(ctx, "nms_round", nms_round, dim3(p.ntiles, batch), dim3(ROUND_THREADS), p.lds, ctx->stream, a);
+    }
+    KPB_HIP(ctx, hipGetLastError());
+    return KPB_OK;
+}
+
+// rounds enqueued before the first look at the state / after each further look: an EdgePoint map stops at round 5 or 6, which launch 6 or 7 finds
+constexpr int ROUND_FIRST = 8, ROUND_MORE = 6;
+
 }  // namespace
 
 namespace {
@@ -1307,6 +1469,26 @@ extern "C" __attribute__((visibility("default"))) int kpb_fast_nms(kpb_ctx* ctx,
     const size_t bytes = (size_t)batch * H * W * sizeof(float);
     if (nms_dist == 0) {  // extracter.py:40-41
         KPB_HIP(ctx, hipMemcpyAsync(out_map_dev, score_dev, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return KPB_OK;
+    }
+    if (ctx->detect_signed) {      // the reference's rounds: image b's result is the map of the round it stopped at
+        RoundPlan rp;
+        if (int rc = round_plan(ctx, batch, H, W, nms_dist, rp)) return rc;
+        std::vector<int> fin((size_t)batch);
+        const size_t P = (size_t)H * W;
+        for (int run = 0, pending = 1; pending;) {
+            const int n = run == 0 ? ROUND_FIRST : ROUND_MORE;
+            if (int rc = round_launch(ctx, rp, score_dev, batch, H, W, nms_dist, run, n)) return rc;
+            run += n;
+            KPB_HIP(ctx, hipMemcpyAsync(fin.data(), rp.fin, fin.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            pending = 0;
+            for (int b = 0; b < batch; ++b) pending += fin[b] == 0;
+            if (pending && (size_t)run > P + 2) return kpb_fail(ctx, KPB_E_NOT_CONVERGED, "kpb_fast_nms: the count of maxima has not repeated after %d rounds", run);
+        }
+        for (int b = 0; b < batch; ++b)
+            KPB_HIP(ctx, hipMemcpyAsync(out_map_dev + b * P, rp.buf[(fin[b] - 1) & 1] + b * P, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return KPB_OK;
     }
@@ -1340,6 +1522,8 @@ struct DetState {
     int batch, H, W; kpb_detect_params prm;
     float* out_kps; int* out_idx; int* out_n;
     int sweeps_run;
+    int rounds;         // KPB_OPT_DETECT_SIGNED at the time of the call: the NMS is rplan's rounds, sweeps_run counts them
+    RoundPlan rplan;
 };
 
 DetState& det_state(kpb_ctx* ctx)
@@ -1355,12 +1539,15 @@ int det_select(kpb_ctx* ctx, const DetState& d)
 {
     SelArgs s;
     s.map = d.prm.nms_dist == 0 ? d.score : d.cur;
+    const bool rounds = d.rounds && d.prm.nms_dist > 0;
+    s.rfin = rounds ? d.rplan.fin : nullptr; s.map1 = rounds ? d.rplan.buf[1] : nullptr;
+    if (rounds) s.map = d.rplan.buf[0];
     s.cand = d.cand;
     s.out_kps = d.out_kps; s.out_idx = d.out_idx; s.out_n = d.out_n;
     s.H = d.H; s.W = d.W; s.border = d.prm.border_dist; s.top_k = d.prm.top_k;
     s.kpad = d.prm.top_k >= d.H * d.W ? 0 : next_pow2(d.prm.top_k);
     s.threshold = d.prm.threshold; s.min_score = d.prm.min_score;
-    s.signed_map = (d.prm.nms_dist >= 1 && d.prm.nms_dist <= 8) ? 1 : 0;
+    s.signed_map = (!rounds && d.prm.nms_dist >= 1 && d.prm.nms_dist <= 8) ? 1 : 0;       // the rounds keep the scores as they are
     s.lastchg = d.prm.nms_dist > 0 ? d.plan.lastchg : nullptr; s.negflag = d.prm.nms_dist > 0 ? d.plan.negflag : nullptr;
     if (ctx->host_det_cap < 3 * d.batch) {
         KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));        // an earlier call's select_topk may still be writing the old mirror
@@ -1374,7 +1561,7 @@ int det_select(kpb_ctx* ctx, const DetState& d)
     // the bitmap of confirmed maxima stands for the map right after sweep 0 + tail only (later sweeps do not keep it), and only at threshold 0 (or -0):
     // every maximum passes it and no suppressed pixel does.  A negative threshold keeps the zeroed non-maxima as well (map > threshold after NMS), a
     // NaN one keeps nothing: both read the map.
-    const bool bits = d.plan.cbits && d.sweeps_run == 1 && d.prm.threshold == 0.0f && s.signed_map;
+    const bool bits = !rounds && d.plan.cbits && d.sweeps_run == 1 && d.prm.threshold == 0.0f && s.signed_map;
     s.cbits = bits ? reinterpret_cast<const unsigned*>(d.plan.cbits) : nullptr; s.wb = d.plan.wb;
     size_t lds = (size_t)s.kpad * sizeof(unsigned long long);
     if (d.batch < 64 && s.nchunks > 1) {       // too few images to fill the chip with one workgroup each: scan in (chunks x batch) workgroups first
@@ -1406,9 +1593,13 @@ extern "C" __attribute__((visibility("default"))) int kpb_detect(kpb_ctx* ctx, c
     if (ctx->det_pending)   // one DetState per context: a second enqueue would drop the first call's convergence / sign check
         return kpb_fail(ctx, KPB_E_INVALID, "kpb_detect: the previous kpb_detect(sync=0) has not been completed by kpb_detect_check "
                                             "(its score map and outputs must stay alive until then)");
+    const bool rounds = ctx->detect_signed && prm->nms_dist > 0;
+    if (rounds && prm->threshold < 0.0f)        // map > threshold would keep suppressed pixels, and the negative ones the rounds never touched
+        return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_detect: KPB_OPT_DETECT_SIGNED takes a threshold >= 0 (got %g)", (double)prm->threshold);
     KPB_HIP(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)H * W;
     DetState& d = det_state(ctx);
+    d.rounds = rounds;
     d.score = score_dev; d.batch = batch; d.H = H; d.W = W; d.prm = *prm;
     if (d.prm.top_k > H * W) d.prm.top_k = H * W;   // N can never exceed H*W: same rows, smaller buffers
     d.out_kps = out_kps_dev; d.out_idx = out_idx_dev; d.out_n = out_n_dev;
@@ -1420,7 +1611,11 @@ extern "C" __attribute__((visibility("default"))) int kpb_detect(kpb_ctx* ctx, c
     }
     d.sweeps_run = 0;
     d.cur = nullptr;
-    if (prm->nms_dist > 0) {
+    if (rounds) {
+        if (int rc = round_plan(ctx, batch, H, W, prm->nms_dist, d.rplan)) return rc;
+        if (int rc = round_launch(ctx, d.rplan, score_dev, batch, H, W, prm->nms_dist, 0, ROUND_FIRST)) return rc;
+        d.sweeps_run = ROUND_FIRST;
+    } else if (prm->nms_dist > 0) {
         if (int rc = kpb_carve(ctx, ctx->ws_nms_map, [&](Arena& a) { d.cur = a.take((size_t)batch * P); })) return rc;
         // tiled sweeps enqueued before the first look at the status: an ALIKE map is at its fixed point after 3-4 of them; a sweep
         // with nothing to do still costs its launch (5 us each on the single map of the drop-in path), an early look costs a
@@ -1455,7 +1650,7 @@ extern "C" __attribute__((visibility("default"))) int kpb_detect_check(kpb_ctx* 
         int pending = 0, neg = 0;
         KPB_HIP(ctx, kpb_wait_stream(ctx, d.batch < 16));        // select_topk has written every image's status to pinned host memory
         for (int b = 0; b < d.batch; ++b) {
-            pending += (ctx->host_det[3 * b] >= d.sweeps_run);
+            pending += d.rounds ? (ctx->host_det[3 * b] != 0) : (ctx->host_det[3 * b] >= d.sweeps_run);
             neg |= ctx->host_det[3 * b + 1];
         }
         if (neg) {
@@ -1465,6 +1660,16 @@ extern "C" __attribute__((visibility("default"))) int kpb_detect_check(kpb_ctx* 
         }
         if (!pending) break;
         rerun = 1;
+        if (d.rounds) {     // word 0 of the mirror = undecided: more rounds, then the selection again
+            if ((size_t)d.sweeps_run > (size_t)d.H * d.W + 2) {
+                ctx->det_pending = 0;
+                return kpb_fail(ctx, KPB_E_NOT_CONVERGED, "kpb_detect: the count of maxima has not repeated after %d rounds", d.sweeps_run);
+            }
+            if (int rc = round_launch(ctx, d.rplan, d.score, d.batch, d.H, d.W, d.prm.nms_dist, d.sweeps_run, ROUND_MORE)) return rc;
+            d.sweeps_run += ROUND_MORE;
+            if (int rc = det_select(ctx, d)) return rc;
+            continue;
+        }
         if (d.sweeps_run > 100000) {
             ctx->det_pending = 0;
             return kpb_fail(ctx, KPB_E_NOT_CONVERGED, "kpb_detect: NMS did not converge");

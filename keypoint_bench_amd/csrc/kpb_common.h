@@ -149,6 +149,7 @@ struct kpb_ctx {
     // named workspaces, grown on demand (first call of a shape = warm-up), never freed before destroy (kpb_ctx_destroy lists them: add a new one there)
     kpb_buf ws_nms_state;   // per-image / per-tile sweep flags
     kpb_buf ws_nms_map;     // [batch][H*W] working map
+    kpb_buf ws_nms_rounds;  // signed rounds (KPB_OPT_DETECT_SIGNED): per-image stop round and the ring of maxima counts
     kpb_buf ws_nms_list;    // [batch][2][cap] undecided pixels handed from sweep 0 to the sparse tail
     kpb_buf ws_cand;        // [batch][H*W] uint64 candidate list (key<<32 | ~idx)
     kpb_buf ws_match;       // per-tile row/column minima
@@ -174,8 +175,9 @@ struct kpb_ctx {
     unsigned lds_attr_done = 0;
     size_t covis_store_bytes = (size_t)4 << 30;     // KPB_OPT_COVIS_STORE_BYTES (kpb_ctx_set_option)
     int alike_coarse_fused = 1;                     // KPB_OPT_ALIKE_COARSE_FUSED
+    int detect_signed = 0;                          // KPB_OPT_DETECT_SIGNED
 };
-enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u };
+enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u, KPB_ATTR_NMS_ROUND = 16u };
 
 extern char g_kpb_err[512];
 

@@ -9,6 +9,7 @@ from .._lib import Context, c_void_p, ptr
 
 class HipNet:
     ARCH = 0
+    signed_scores = False       # the score map is a raw logit (any sign): detect on it with signed=True (utils/extracter.py), as the pipelines do
 
     def __init__(self):
         self._handle = None

@@ -130,8 +130,9 @@ class PairPipeline:
             self._place_map(images)
         ctx.check(L.kpb_net_forward(net._handle, ptr(images), B2, H, W, ptr(self.score), ptr(self.desc)))
         net._forward_count += 1
-        ctx.check(L.kpb_detect(ctx.handle, ptr(self.score), B2, H, W, ctypes.byref(self.dprm), ptr(self.kps),
-                               ptr(self.idx), ptr(self.n), 0))
+        with ctx.detect_signed(getattr(net, "signed_scores", False)):      # the pending detection keeps the setting until kpb_detect_check
+            ctx.check(L.kpb_detect(ctx.handle, ptr(self.score), B2, H, W, ctypes.byref(self.dprm), ptr(self.kps),
+                                   ptr(self.idx), ptr(self.n), 0))
         self._enqueue_match()
 
     def _enqueue_covis(self):
@@ -261,8 +262,9 @@ class SequencePipeline:
                     t[0].copy_(t[self._last])
         ctx.check(L.kpb_net_forward(net._handle, ptr(images), f, H, W, ptr(self.score), ptr(self.desc)))
         net._forward_count += 1
-        ctx.check(L.kpb_detect(ctx.handle, ptr(self.score), f, H, W, ctypes.byref(self.dprm), ptr(self.kps[1:]), ptr(self.idx[1:]),
-                               ptr(self.n[1:]), 1))
+        with ctx.detect_signed(getattr(net, "signed_scores", False)):
+            ctx.check(L.kpb_detect(ctx.handle, ptr(self.score), f, H, W, ctypes.byref(self.dprm), ptr(self.kps[1:]), ptr(self.idx[1:]),
+                                   ptr(self.n[1:]), 1))
         if self.desc is not None:
             Hd, Wd = self.Hd, self.Wd
             ctx.check(L.kpb_sample(ctx.handle, ptr(self.desc), f, C, Hd, Wd, Hd * Wd * C, 1, Wd * C, C, ptr(self.kps[1:]), 3, K,

@@ -16,6 +16,7 @@ checkout so that main.py runs unchanged.  Without a ``task_fn`` pairs are batche
 and the task is evaluated for a whole batch on the device; host-resident dataset items travel through a pinned staging
 ring (HostStager) so that their PCIe copy runs under the previous batch's kernels.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -424,14 +425,22 @@ class PairRunner:
         kw = {"matcher": self.matcher} if self.task_fn is fund_ransac_row else {}
         # the tasks get the UNCROPPED images, as model_interface.py:242-259 hands batch['image0'] / batch['image1'] over
         # (MHA.py:59-60 takes its resize factors from their shape)
-        r = self.task_fn(idx, raw0, s0, d0, raw1, s1, d1, batch.get("warp01_params", {}), batch.get("warp10_params", {}),
-                         self.params, **kw)
+        with self._signed_scope():
+            r = self.task_fn(idx, raw0, s0, d0, raw1, s1, d1, batch.get("warp01_params", {}), batch.get("warp10_params", {}),
+                             self.params, **kw)
         self.results.append(r)
         return r
 
+    def _signed_scope(self):
+        """The task code's `detection(score, ...)` calls keep the reference's signatures, so a net whose score is a raw logit (HipNet.signed_scores) opts
+        them in through the context for the duration of the task: signed=net.signed_scores for every detection on the net's output."""
+        if not getattr(self.model, "signed_scores", False):
+            return contextlib.nullcontext()
+        from ._lib import Context
+        return Context.get(self.device).detect_signed(True)
+
     # ---- one frame of a sequence (model_interface.py:217-228, 261-276)
     def sequence_step(self, batch, idx, task_type="FundamentalMatrix"):
-        from .tasks.FundamentalMatrix import fundamental_matrix
         cur = dict(batch)
         img = as_image(batch["image0"], self.device)
         cur["image0"] = img[None] if img.dim() == 3 else img
@@ -445,6 +454,11 @@ class PairRunner:
             s1, d1 = self.model(cur["image0"])
         last_img = self.last_batch["image0"]
         self.last_batch = cur
+        with self._signed_scope():
+            return self._sequence_task(idx, task_type, last_img, cur, s0, s1, d0, d1)
+
+    def _sequence_task(self, idx, task_type, last_img, cur, s0, s1, d0, d1):
+        from .tasks.FundamentalMatrix import fundamental_matrix
         mp = self.params["matcher_params"]
         if task_type == "visual_odometer":    # 283-298: the per-frame motion; the chain is composed from the gathered rows
             from .tasks.visual_odometer import relative_motion, step_length

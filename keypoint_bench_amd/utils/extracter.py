@@ -18,9 +18,10 @@ def _as_maps(t: torch.Tensor):
     return t.detach().to(torch.float32).contiguous()
 
 
-def fast_nms(image_probs: torch.Tensor, nms_dist: int = 4, max_iter: int = -1, min_value: float = 0.0) -> torch.Tensor:
+def fast_nms(image_probs: torch.Tensor, nms_dist: int = 4, max_iter: int = -1, min_value: float = 0.0, signed: bool = False) -> torch.Tensor:
     """utils/extracter.py:6-100.  BxCxHxW non-negative map -> same shape, suppressed pixels = 0.
-    max_iter / min_value other than the defaults are not supported (the reference never passes them)."""
+    max_iter / min_value other than the defaults are not supported (the reference never passes them).
+    signed=True: the map may hold negative scores (raw logits); the reference's rounds are run as they are (KPB_OPT_DETECT_SIGNED, include/kpb.h)."""
     if max_iter != -1 or min_value != 0.0:
         raise NotImplementedError("fast_nms: only max_iter=-1, min_value=0.0 (the values detection() uses)")
     if nms_dist == 0:
@@ -31,12 +32,15 @@ def fast_nms(image_probs: torch.Tensor, nms_dist: int = 4, max_iter: int = -1, m
     B, C, H, W = x.shape
     ctx = Context.get(x.device)
     out = torch.empty_like(x)
-    ctx.check(ctx.lib.kpb_fast_nms(ctx.handle, ptr(x), B * C, H, W, int(nms_dist), ptr(out)))
+    with ctx.detect_signed(signed):
+        ctx.check(ctx.lib.kpb_fast_nms(ctx.handle, ptr(x), B * C, H, W, int(nms_dist), ptr(out)))
     return out
 
 
-def detection_batch(score_map: torch.Tensor, params: dict = None, sync: bool = True):
-    """All batch elements at once: returns (kps [B, top_k, 3], flat_idx [B, top_k], n [B]) device tensors."""
+def detection_batch(score_map: torch.Tensor, params: dict = None, sync: bool = True, signed: bool = False):
+    """All batch elements at once: returns (kps [B, top_k, 3], flat_idx [B, top_k], n [B]) device tensors.
+    signed=True: signed score maps, every image by the reference's rounds (KPB_OPT_DETECT_SIGNED); a sync=False call keeps that choice until
+    kpb_detect_check completes it."""
     if params is None:  # utils/extracter.py:200-205
         params = dict(nms_dist=4, threshold=0.0, border_dist=8, top_k=300, min_score=0.0)
     x = _as_maps(score_map)
@@ -48,14 +52,15 @@ def detection_batch(score_map: torch.Tensor, params: dict = None, sync: bool = T
     kps = torch.empty((B, top_k, 3), dtype=torch.float32, device=x.device)
     idx = torch.empty((B, top_k), dtype=torch.int32, device=x.device)
     n = torch.empty((B,), dtype=torch.int32, device=x.device)
-    ctx.check(ctx.lib.kpb_detect(ctx.handle, ptr(x), B, H, W, ctypes.byref(prm), ptr(kps), ptr(idx), ptr(n),
-                                 1 if sync else 0))
+    with ctx.detect_signed(signed):
+        ctx.check(ctx.lib.kpb_detect(ctx.handle, ptr(x), B, H, W, ctypes.byref(prm), ptr(kps), ptr(idx), ptr(n),
+                                     1 if sync else 0))
     return kps, idx, n
 
 
-def detection(score_map: torch.Tensor, params: dict = None):
-    """utils/extracter.py:193-221.  score_map Bx1xHxW -> Nx3 (x, y, prob) of batch element 0."""
-    kps, _, _ = detection_batch(score_map[:1], params, sync=True)
+def detection(score_map: torch.Tensor, params: dict = None, signed: bool = False):
+    """utils/extracter.py:193-221.  score_map Bx1xHxW -> Nx3 (x, y, prob) of batch element 0.  signed: see detection_batch."""
+    kps, _, _ = detection_batch(score_map[:1], params, sync=True, signed=signed)
     ctx = Context.get(kps.device)
     n = (ctypes.c_int32 * 1)()
     ctx.check(ctx.lib.kpb_detect_counts(ctx.handle, n, 1))      # host integer left by the kernels: no second read-back (n[0].item())
