@@ -1907,13 +1907,142 @@ __global__ __launch_bounds__(256) void alike_desc_at(DescAtArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ EdgePoint head
+// EdgePoint (models/EdgePoint.py:155-173) puts two small heads on ALIKE-t's trunk.  Both are fp32 fmaf chains in one fixed order, so a pixel's bits depend on neither
+// the batch nor the launch shape, and both are the same code in the split-f16 and the strict-fp32 build.
+// wsc, the score weights: sixteen rows {conv1.weight[c][0 .. 7], conv_score.weight[c]}, then conv_score.bias -- 145 floats.
+constexpr int EP_WROW = 9, EP_WBIAS = 16 * EP_WROW;
+
+// a1[c] = relu(conv1(x1)[c]) of one pixel (EdgePoint.py:155): k ascending.  w: the channel's row of wsc.
+template <class WP> __device__ __forceinline__ float ep_a1(const float (&x)[8], WP w)
+{
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc = fmaf(w[k], x[k], acc);
+    return relu(acc);
+}
+
+// score = conv_score(a1) (EdgePoint.py:173): a raw logit at full resolution, no sigmoid; bias first, then c ascending.  An HBM stream: 32 bytes read (a pixel's 8
+// channels of x1, two 16-byte loads per lane, 2 KB contiguous per wave) and 4 written per pixel for about 290 flops; two pixels per lane keep four loads in flight.
+// The weights are wave-uniform and never written by a kernel (bound at net create): read through the constant address space they are scalar loads (see cm_tail_agg),
+// four channels' rows a round -- all 145 at once are more than the scalar registers hold, and the compiler parked them in vector-register lanes (v_readlane per use).
+constexpr int EPS_PPL = 2;
+__global__ __launch_bounds__(256) void edgepoint_score(const float* __restrict__ x1, float* __restrict__ score, const float* __restrict__ wsc_, size_t npix)
+{
+    typedef const __attribute__((address_space(4))) float* cfp;
+    const cfp wsc = (cfp)wsc_;
+    const size_t p0 = (size_t)blockIdx.x * (256 * EPS_PPL) + threadIdx.x;
+    float x[EPS_PPL][8], sc[EPS_PPL];
+#pragma unroll
+    for (int i = 0; i < EPS_PPL; ++i) {
+        const size_t p = p0 + 256 * i;
+        float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+        if (p < npix) {
+            lo = *reinterpret_cast<const float4*>(x1 + p * 8);
+            hi = *reinterpret_cast<const float4*>(x1 + p * 8 + 4);
+        }
+        x[i][0] = lo.x; x[i][1] = lo.y; x[i][2] = lo.z; x[i][3] = lo.w; x[i][4] = hi.x; x[i][5] = hi.y; x[i][6] = hi.z; x[i][7] = hi.w;
+        sc[i] = wsc[EP_WBIAS];
+    }
+#pragma unroll 4
+    for (int c = 0; c < 16; ++c) {
+        const cfp w = wsc + c * EP_WROW;
+#pragma unroll
+        for (int i = 0; i < EPS_PPL; ++i) sc[i] = fmaf(w[8], ep_a1(x[i], w), sc[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < EPS_PPL; ++i)
+        if (p0 + 256 * i < npix) score[p0 + 256 * i] = sc[i];
+}
+
+// desc = convhead2(cat[conv_8(a1), conv_4(a2), a3, conv_transpose_4(a4)]) at H/8 x W/8 (EdgePoint.py:160-163, 172), not normalised.  One coarse pixel per wave step,
+// lane = output channel (256-byte rows, as alike_desc_at).  The strided 1 x 1 convolutions read one source pixel each -- a1 at (8y, 8x), a2 at (4y, 4x) -- and the 4 x 4
+// stride-4 transposed convolution reads a4[y >> 2][x >> 2] through the one weight slice [:, :, y & 3, x & 3].
+// Stage 1: lanes 0 .. 15 recompute a1 at (8y, 8x), a channel each with edgepoint_score's chain, and pass it round through LDS; then the four 16-lane groups each make
+// their quarter of the concatenated vector as bias + 16-term chain over their source vector through a table T[m][c][j] -- m = 0: conv_8, 1: conv_4, 2: the identity
+// (a3 is copied: a chain of exact zeros around 1 . a3[j]), 3 + 4 (y & 3) + (x & 3): the transposed convolution's slice.
+// Stage 2: each lane holds its row of convhead2 in 64 registers and takes the 64-term product, c ascending, over the vector read back from LDS (broadcast reads).
+// Each wave owns its LDS region and a wave's LDS operations execute in order: no barrier in the loop (as conv1x1_relu_body).  The table sits in LDS (19.8 KB).
+struct EpDescArgs {
+    const float *x1, *a2, *a3, *a4;     // [B][H][W][8], [B][H/2][W/2][16], [B][H/8][W/8][16], [B][H/32][W/32][16]
+    const float *wsc, *tab, *tabb, *whT;// the score weights (conv1's rows); T [19][16][16] and its biases [19][16]; convhead2 transposed [c][o]
+    float* desc;                        // [B][H/8][W/8][64]
+    int H, W;
+    unsigned npix;                      // B (H/8) (W/8)
+};
+__global__ __launch_bounds__(256) void edgepoint_desc(EpDescArgs a)           // (132 registers: held to 128 for a fourth wave per SIMD it spilled five)
+{
+    constexpr int NT = 19 * 256, NTB = 19 * 16;
+    __shared__ __attribute__((aligned(16))) float tabs[NT + NTB];       // the stage-1 table and its biases
+    __shared__ __attribute__((aligned(16))) float bc[4][64 + 16];       // per wave: the concatenated vector, then a1
+    for (int i = threadIdx.x; i < NT + NTB; i += 256) tabs[i] = i < NT ? a.tab[i] : a.tabb[i - NT];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
+    float* fb = bc[threadIdx.x >> 6];
+    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), nwaves = gridDim.x * 4;
+    const int Hc = a.H / 8, Wc = a.W / 8;
+    float wr[64], w1r[8];
+#pragma unroll
+    for (int c = 0; c < 64; ++c) wr[c] = a.whT[c * 64 + lane];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w1r[k] = a.wsc[j * EP_WROW + k];
+    // a step's loads -- x1 at (8y, 8x) and the group's source vector (group 0 reads a3 and replaces it with a1) -- are issued a step ahead: a step is a few hundred
+    // cycles of arithmetic behind a global round trip, and a wave walks some hundreds of coarse pixels
+    float4 nx[2], ns[4];
+    int nm = 0;
+    auto fetch = [&](unsigned p) {          // p is wave-uniform
+        const unsigned b = p / (unsigned)(Hc * Wc), r = p - b * (unsigned)(Hc * Wc);
+        const int y = (int)(r / (unsigned)Wc), x = (int)(r - (unsigned)y * Wc);
+        const float* xp = a.x1 + (((size_t)b * a.H + 8 * y) * a.W + 8 * x) * 8;
+        nx[0] = *reinterpret_cast<const float4*>(xp); nx[1] = *reinterpret_cast<const float4*>(xp + 4);
+        const float* src = g == 1 ? a.a2 + (((size_t)b * (a.H / 2) + 4 * y) * (a.W / 2) + 4 * x) * 16
+                         : g == 3 ? a.a4 + (((size_t)b * (a.H / 32) + (y >> 2)) * (a.W / 32) + (x >> 2)) * 16
+                                  : a.a3 + (size_t)p * 16;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ns[q] = *reinterpret_cast<const float4*>(src + 4 * q);
+        nm = g < 3 ? g : 3 + 4 * (y & 3) + (x & 3);
+    };
+    if (wave < a.npix) fetch(wave);
+    for (unsigned p = wave; p < a.npix; p += nwaves) {          // wave-uniform
+        const float xv[8] = {nx[0].x, nx[0].y, nx[0].z, nx[0].w, nx[1].x, nx[1].y, nx[1].z, nx[1].w};
+        float v[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { v[4 * q] = ns[q].x; v[4 * q + 1] = ns[q].y; v[4 * q + 2] = ns[q].z; v[4 * q + 3] = ns[q].w; }
+        const int m = nm;
+        if (p + nwaves < a.npix) fetch(p + nwaves);
+        const float a1 = ep_a1(xv, w1r);
+        if (g == 0) {
+            fb[64 + j] = a1;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 t = *reinterpret_cast<const float4*>(fb + 64 + 4 * q);
+                v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+            }
+        }
+        const float* T = tabs + m * 256 + j;
+        float f = tabs[NT + m * 16 + j];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) f = fmaf(v[c], T[c * 16], f);
+        fb[lane] = f;
+        float o = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const float4 t = *reinterpret_cast<const float4*>(fb + 4 * q);
+            o = fmaf(t.x, wr[4 * q], o); o = fmaf(t.y, wr[4 * q + 1], o); o = fmaf(t.z, wr[4 * q + 2], o); o = fmaf(t.w, wr[4 * q + 3], o);
+        }
+        a.desc[(size_t)p * 64 + lane] = o;
+    }
+}
+
 }  // namespace
 
 // ================================================================================================ host side
 namespace {
 
-struct AlikeNet : kpb_net {
-    float *x1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr;      // the maps of the last forward that desc_at reads
+// The encoder ALIKE-t and EdgePoint share (ALike.py:137-150, EdgePoint.py:146-158): block 1 .. block 4 and the aggregations 2 .. 4, in all three regimes (split-f16 batch
+// path with the fused tails from 16 images on, latency path below, strict fp32).  A net derives from it and adds its head.
+struct AlikeTrunk : kpb_net {
+    float *x1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr;      // the maps of the last forward that the heads and desc_at read
     // What forward needs of the staged weights, bound once at create: device pointers, and the host scalars of the split-f16 form -- reciprocal power-of-two
     // weight scales of the custom packs, and the L1 norms / bias maxima behind the bounds the fused kernels scale their intermediate maps by (conv_mfma.h,
     // cm_scale_of).  One struct per fused kernel; the members carry the names of the kernel arguments they fill.
@@ -1922,7 +2051,15 @@ struct AlikeNet : kpb_net {
     // blocks 2 .. 4 as strict fp32 sees them (ConvArgs: w1 .. dsb).  Blocks 3 / 4 keep conv2 as an MFMA pack in both forms (w2p, b2p, un2) and, in the
     // split-f16 form, conv1 + the identity branch as one pack (w1h, b1h, un1); prof1 / prof2 are the profile names of their conv1 / conv2
     struct Res { const float *w1, *b1, *w2, *b2, *dsw, *dsb, *w1h, *b1h, *w2p, *b2p; float un1, un2; std::string prof1, prof2; } blk[5] = {};      // [2 .. 4]
+    // (the trunk kernels write every group's share of ALIKE's score logit through wsc, and with E3 / E4 of its head rows through whT: a net without that head binds
+    //  64 zeros as wsc and runs the trunk with dense = false)
     struct { const float *agg[5], *whT, *wsc; const uint4 *wh16, *a1h16; float l1_agg1, inv_ws_h, inv_wa; } kh = {};      // agg[1 .. 4]; HeadArgs, HybArgs, LinArgs
+    // what a trunk run leaves in the arena beside x1, a2, a3, a4: the score shares, the projected maps (dense) and the per-image maxima (split-f16 form)
+    struct Maps { float *S2, *S3, *S4, *E3, *E4; unsigned *amax_x1, *amax_a2; };
+    int trunk(const float* img_dev, int batch, int H, int W, bool dense, Maps& m);
+};
+
+struct AlikeNet : AlikeTrunk {
     int forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev) override;
     int desc_at(const float* pts_dev, int pts_cols, int max_n, const int32_t* n_dev, float* out_dev) override;
 };
@@ -1998,14 +2135,11 @@ __global__ __launch_bounds__(256) void maxpool4_nhwc(const float* __restrict__ i
     *reinterpret_cast<float4*>(out + ((b * Ho + y) * (size_t)Wo + x) * C + c) = m;
 }
 
-int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev)
+// H and W are multiples of 32 (the nets' forwards check, each under its own name)
+int AlikeTrunk::trunk(const float* img_dev, int batch, int H, int W, bool dense, Maps& mo)
 {
-    if ((H_ % 32) || (W_ % 32))
-        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: ALIKE needs H and W multiples of 32 (got %dx%d)", H_, W_);
-    const int H = H_, W = W_;
     const size_t P = (size_t)H * W, B = batch;
     const bool h16 = conv_mfma_use_h16();       // the split-f16 matrix form (default) or the strict fp32 kernels (KPB_FP32_MATRIX=1)
-    const bool dense = desc_out_dev != nullptr;
     // blocks 3 / 4 finished inside their conv2 (CmForm::tail): x3 / x4 are not written, maxpool4_x3 and the two aggregations are not launched
     const bool fused = h16 && batch >= 16 && ctx->alike_coarse_fused;
     const int nw1 = cdiv(W, B1_TW) * cdiv(H, B1H_TH) * 4, nw2 = cdiv(W / 2, 32) * cdiv(H / 2, 8) * 4;      // per-wave maxima of blocks 1 / 2
@@ -2123,6 +2257,22 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
         KPB_LAUNCH(ctx, "conv1x1_agg3", conv1x1_relu<32>, dim3((unsigned)((B * P / 64 + 255) / 256)), dim3(256), 0, st, x3, a3, kh.agg[3], kh.wsc + 32, S3, B * P / 64, kh.whT + 32 * 64, E3);
         KPB_LAUNCH(ctx, "conv1x1_agg4", conv1x1_relu<64>, dim3((unsigned)((B * P / 1024 + 255) / 256)), dim3(256), 0, st, x4, a4, kh.agg[4], kh.wsc + 48, S4, B * P / 1024, kh.whT + 48 * 64, E4);
     }
+    mo = Maps{S2, S3, S4, E3, E4, amax_x1, amax_a2};
+    return KPB_OK;
+}
+
+int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev)
+{
+    if ((H_ % 32) || (W_ % 32))
+        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: ALIKE needs H and W multiples of 32 (got %dx%d)", H_, W_);
+    const int H = H_, W = W_;
+    const bool h16 = conv_mfma_use_h16();
+    const bool dense = desc_out_dev != nullptr;
+    Maps m;
+    if (int rc = trunk(img_dev, batch, H, W, dense, m)) return rc;
+    float *S2 = m.S2, *S3 = m.S3, *S4 = m.S4, *E3 = m.E3, *E4 = m.E4;
+    unsigned *amax_x1 = m.amax_x1, *amax_a2 = m.amax_a2;
+    hipStream_t st = ctx->stream;
     // upsample + concat + head (151-162)
     if (dense) {
         HybArgs hy{x1, a2, E3, E4, kh.agg[1], kh.whT, kh.wsc, score_out_dev, desc_out_dev, H, W, amax_x1, amax_a2, 0.f, 1.f, 1.f, nullptr, 1.f};
@@ -2161,26 +2311,28 @@ int AlikeNet::desc_at(const float* pts_dev, int pts_cols, int max_n, const int32
     return KPB_OK;
 }
 
-}  // namespace
+// this build carries the ALIKE-t channel plan (c1..c4 = 8,16,32,64, dim 64: config/config_MHA.yaml Alike_params, EdgePoint_params)
+constexpr uint32_t c1 = 8, c2 = 16, c3 = 32, c4 = 64, dim = 64;
+struct Need { const char* n; std::vector<uint32_t> d; };
 
-int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
+// the first tensor the blob lacks or holds in another shape: the trunk's, then the head's `more`; null when all are there
+const char* first_missing(const KpbwBlob& bl, const std::vector<Need>& more)
 {
-    // this build carries the ALIKE-t channel plan (c1..c4 = 8,16,32,64, dim 64: config/config_MHA.yaml Alike_params)
-    const uint32_t c1 = 8, c2 = 16, c3 = 32, c4 = 64, dim = 64;
-    struct { const char* n; std::vector<uint32_t> d; } need[] = {
+    std::vector<Need> need = {
         {"b1c1.w", {c1, 3, 3, 3}}, {"b1c1.b", {c1}}, {"b1c2.w", {c1, c1, 3, 3}}, {"b1c2.b", {c1}},
         {"b2c1.w", {c2, c1, 3, 3}}, {"b2c1.b", {c2}}, {"b2c2.w", {c2, c2, 3, 3}}, {"b2c2.b", {c2}}, {"b2ds.w", {c2, c1}}, {"b2ds.b", {c2}},
         {"b3c1.w", {c3, c2, 3, 3}}, {"b3c1.b", {c3}}, {"b3c2.w", {c3, c3, 3, 3}}, {"b3c2.b", {c3}}, {"b3ds.w", {c3, c2}}, {"b3ds.b", {c3}},
         {"b4c1.w", {c4, c3, 3, 3}}, {"b4c1.b", {c4}}, {"b4c2.w", {c4, c4, 3, 3}}, {"b4c2.b", {c4}}, {"b4ds.w", {c4, c3}}, {"b4ds.b", {c4}},
-        {"agg1.w", {dim / 4, c1}}, {"agg2.w", {dim / 4, c2}}, {"agg3.w", {dim / 4, c3}}, {"agg4.w", {dim / 4, c4}},
-        {"head.w", {dim + 1, dim}}};
+        {"agg1.w", {dim / 4, c1}}, {"agg2.w", {dim / 4, c2}}, {"agg3.w", {dim / 4, c3}}, {"agg4.w", {dim / 4, c4}}};
+    need.insert(need.end(), more.begin(), more.end());
     for (auto& nd : need)
-        if (!bl.get(nd.n, nd.d))
-            return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not ALIKE-t shaped "
-                            "(this build supports c1..c4 = 8,16,32,64, dim = 64)", nd.n);
-    auto net = std::make_unique<AlikeNet>();
-    net->ctx = ctx; net->arch = KPB_ARCH_ALIKE; net->dim = dim; net->desc_div = 1;
-    WeightStage ws;
+        if (!bl.get(nd.n, nd.d)) return nd.n;
+    return nullptr;
+}
+
+// the trunk half of a create: repacks, h16 packs, L1 norms and bias maxima of blocks 1 .. 4 and the four aggregations, staged ...
+void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
+{
     std::vector<float> tmp;
     {   // block1 conv1: [co][ci][ky][kx] -> [(ci,ky,kx)][co]
         const float* w = bl.get("b1c1.w", {c1, 3, 3, 3});
@@ -2230,7 +2382,6 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         net->k2.inv_ws1 = 1.0f / s1; net->k2.inv_ws2 = 1.0f / s2; net->k2.inv_wsa = 1.0f / sa;
         net->k2.l1_c1 = l1_rows(w1, 16, 72); net->k2.bmax_c1 = max_abs(bl.get("b2c1.b", {c2}), 16);
         net->k2.l1_c2 = l1_rows(w2, 16, 144); net->k2.l1_ds = l1_rows(wd, 16, 8); net->k2.bmax_sum = max_abs(tmp.data(), 16);
-        net->kh.l1_agg1 = l1_rows(bl.get("agg1.w", {dim / 4, c1}), 16, 8);
     }
     // both return 1 / the power-of-two scale the split-f16 pack was made with (ConvM::unscale)
     auto put_mfma = [&](const char* name, const float* w, int cout, int cin, int ntb) {
@@ -2268,6 +2419,42 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         snprintf(nm, 16, "agg%d.w", i);
         transpose(bl.get(nm, {dim / 4, ch[i]}), dim / 4, ch[i], tmp); ws.put(nm, tmp);
     }
+}
+
+// ... and bound once they are uploaded
+void trunk_bind(WeightStage& ws, AlikeTrunk* net)
+{
+    const bool h16 = conv_mfma_use_h16();
+    net->k1.w1 = ws.dev("b1c1.w"); net->k1.b1 = ws.dev("b1c1.b"); net->k1.w2 = ws.dev("b1c2.w"); net->k1.b2 = ws.dev("b1c2.b");
+    net->k1.w1pk = ws.dev<uint4>("b1c1.pairs"); net->k1.w2pk = ws.dev<uint4>("b1c2.pairs");
+    net->k2.w1pk = ws.dev<uint4>("b2c1.h16"); net->k2.w2pk = ws.dev<uint4>("b2c2.h16"); net->k2.wapk = ws.dev<uint4>("agg2.h16");
+    net->k2.b1 = ws.dev("b2c1.b"); net->k2.bsum = ws.dev("b2c2.bsum");
+    for (int i = 2; i <= 4; ++i) {
+        AlikeTrunk::Res& r = net->blk[i];
+        const std::string c1n = "b" + std::to_string(i) + "c1", c2n = "b" + std::to_string(i) + "c2", dsn = "b" + std::to_string(i) + "ds";
+        r.w1 = ws.dev(c1n + ".w"); r.b1 = ws.dev(c1n + ".b"); r.w2 = ws.dev(c2n + ".w"); r.b2 = ws.dev(c2n + ".b");
+        r.dsw = ws.dev(dsn + ".w"); r.dsb = ws.dev(dsn + ".b");
+        r.prof1 = "conv3x3_" + c1n; r.prof2 = "conv3x3_" + c2n;
+        if (i == 2) continue;
+        r.w2p = ws.dev(c2n + ".wp"); r.b2p = ws.dev(c2n + ".bp");
+        if (h16) { r.w1h = ws.dev(c1n + ".h"); r.b1h = ws.dev(c1n + ".hb"); }
+    }
+    for (int i = 1; i <= 4; ++i) net->kh.agg[i] = ws.dev("agg" + std::to_string(i) + ".w");
+}
+
+}  // namespace
+
+int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
+{
+    if (const char* n = first_missing(bl, {{"head.w", {dim + 1, dim}}}))
+        return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not ALIKE-t shaped "
+                        "(this build supports c1..c4 = 8,16,32,64, dim = 64)", n);
+    auto net = std::make_unique<AlikeNet>();
+    net->ctx = ctx; net->arch = KPB_ARCH_ALIKE; net->dim = dim; net->desc_div = 1;
+    WeightStage ws;
+    std::vector<float> tmp;
+    trunk_stage(bl, ws, net.get());
+    net->kh.l1_agg1 = l1_rows(bl.get("agg1.w", {dim / 4, c1}), 16, 8);
     {
         const float* hw = bl.get("head.w", {dim + 1, dim});
         transpose(hw, 64, 64, tmp); ws.put("head.wT", tmp);
@@ -2314,24 +2501,91 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         }
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
-    const bool h16 = conv_mfma_use_h16();
-    net->k1.w1 = ws.dev("b1c1.w"); net->k1.b1 = ws.dev("b1c1.b"); net->k1.w2 = ws.dev("b1c2.w"); net->k1.b2 = ws.dev("b1c2.b");
-    net->k1.w1pk = ws.dev<uint4>("b1c1.pairs"); net->k1.w2pk = ws.dev<uint4>("b1c2.pairs");
-    net->k2.w1pk = ws.dev<uint4>("b2c1.h16"); net->k2.w2pk = ws.dev<uint4>("b2c2.h16"); net->k2.wapk = ws.dev<uint4>("agg2.h16");
-    net->k2.b1 = ws.dev("b2c1.b"); net->k2.bsum = ws.dev("b2c2.bsum");
-    for (int i = 2; i <= 4; ++i) {
-        AlikeNet::Res& r = net->blk[i];
-        const std::string c1n = "b" + std::to_string(i) + "c1", c2n = "b" + std::to_string(i) + "c2", dsn = "b" + std::to_string(i) + "ds";
-        r.w1 = ws.dev(c1n + ".w"); r.b1 = ws.dev(c1n + ".b"); r.w2 = ws.dev(c2n + ".w"); r.b2 = ws.dev(c2n + ".b");
-        r.dsw = ws.dev(dsn + ".w"); r.dsb = ws.dev(dsn + ".b");
-        r.prof1 = "conv3x3_" + c1n; r.prof2 = "conv3x3_" + c2n;
-        if (i == 2) continue;
-        r.w2p = ws.dev(c2n + ".wp"); r.b2p = ws.dev(c2n + ".bp");
-        if (h16) { r.w1h = ws.dev(c1n + ".h"); r.b1h = ws.dev(c1n + ".hb"); }
-    }
-    for (int i = 1; i <= 4; ++i) net->kh.agg[i] = ws.dev("agg" + std::to_string(i) + ".w");
+    trunk_bind(ws, net.get());
     net->kh.whT = ws.dev("head.wT"); net->kh.wsc = ws.dev("head.ws");
     net->kh.wh16 = ws.dev<uint4>("head.wh16"); net->kh.a1h16 = ws.dev<uint4>("agg1.h16");
+    if (int rc = ws.bound(ctx)) return rc;
+    *out = net.release();
+    return KPB_OK;
+}
+
+// ================================================================================================ EdgePoint: the same trunk, its own head
+namespace {
+
+struct EdgePointNet : AlikeTrunk {
+    struct { const float *wsc, *tab, *tabb; } ke = {};        // the score weights; edgepoint_desc's stage-1 table and biases (kh.whT: convhead2 transposed)
+    int forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev) override;
+};
+
+int EdgePointNet::forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev)
+{
+    if ((H_ % 32) || (W_ % 32))     // the reference's torch.cat fails otherwise (EdgePoint.py:163); model_interface.py:192-204 crops to such sizes
+        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: EdgePoint needs H and W multiples of 32 (got %dx%d)", H_, W_);
+    const size_t npix = (size_t)batch * H_ * W_;
+    const size_t nb_score = (npix + 256 * EPS_PPL - 1) / (256 * EPS_PPL);
+    if (npix / 64 > 0xffffffffu || nb_score > 0x7fffffffu)
+        return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_net_forward: EdgePoint: %d images of %dx%d exceed the head kernels' index range", batch, H_, W_);
+    Maps m;
+    // the trunk in its non-dense form: no E3 / E4, and its score shares S2 .. S4 (through the zeros bound as kh.wsc) are ignored
+    if (int rc = trunk(img_dev, batch, H_, W_, false, m)) return rc;
+    hipStream_t st = ctx->stream;
+    KPB_LAUNCH(ctx, "edgepoint_score", edgepoint_score, dim3((unsigned)nb_score), dim3(256), 0, st, x1, score_out_dev, ke.wsc, npix);
+    if (desc_out_dev) {     // (the repeatability task needs the score only)
+        const unsigned nc = (unsigned)(npix / 64);
+        EpDescArgs d{x1, a2, a3, a4, ke.wsc, ke.tab, ke.tabb, kh.whT, desc_out_dev, H_, W_, nc};
+        // four waves a workgroup, at least four coarse pixels per wave (each loads its 64 weights once), at most eight workgroups per CU
+        KPB_LAUNCH(ctx, "edgepoint_desc", edgepoint_desc, dim3(std::min((nc + 15u) / 16u, 2048u)), dim3(256), 0, st, d);
+    }
+    KPB_HIP(ctx, hipGetLastError());
+    return KPB_OK;
+}
+
+}  // namespace
+
+int edgepoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
+{
+    const uint32_t q = dim / 4;
+    if (const char* n = first_missing(bl, {{"head.w", {dim, dim}}, {"score.w", {q}}, {"score.b", {1}}, {"d8.w", {q, q}}, {"d8.b", {q}}, {"d4.w", {q, q}}, {"d4.b", {q}},
+                                           {"ct4.w", {q, q, 4, 4}}, {"ct4.b", {q}}}))
+        return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not EdgePoint shaped "
+                        "(this build supports c1..c4 = 8,16,32,64, dim = 64, single head)", n);
+    auto net = std::make_unique<EdgePointNet>();
+    net->ctx = ctx; net->arch = KPB_ARCH_EDGEPOINT; net->dim = dim; net->desc_div = 8;
+    WeightStage ws;
+    std::vector<float> tmp;
+    trunk_stage(bl, ws, net.get());
+    ws.put("ep.zero", std::vector<float>(64, 0.0f));        // where ALIKE binds its score row: the trunk kernels' score shares come out zero and are not read
+    transpose(bl.get("head.w", {dim, dim}), 64, 64, tmp); ws.put("head.wT", tmp);
+    {   // edgepoint_score's weights: rows {conv1.weight[c][0 .. 7], conv_score.weight[c]}, then conv_score.bias
+        const float *w1 = bl.get("agg1.w", {q, c1}), *wsr = bl.get("score.w", {q});
+        tmp.assign(EP_WBIAS + 1, 0.0f);
+        for (int c = 0; c < 16; ++c) {
+            for (int k = 0; k < 8; ++k) tmp[c * EP_WROW + k] = w1[c * 8 + k];
+            tmp[c * EP_WROW + 8] = wsr[c];
+        }
+        tmp[EP_WBIAS] = bl.get("score.b", {1})[0];
+        ws.put("ep.score", tmp);
+    }
+    {   // stage-1 table of edgepoint_desc: T[m][c][j] and bias[m][j]
+        std::vector<float> tab(19 * 256, 0.0f), tb(19 * 16, 0.0f);
+        const float *w8 = bl.get("d8.w", {q, q}), *w4 = bl.get("d4.w", {q, q}), *wt = bl.get("ct4.w", {q, q, 4, 4});        // [j][c], [j][c], [c][j][ky][kx]
+        for (int c = 0; c < 16; ++c)
+            for (int j = 0; j < 16; ++j) {
+                tab[0 * 256 + c * 16 + j] = w8[j * 16 + c];
+                tab[1 * 256 + c * 16 + j] = w4[j * 16 + c];
+                tab[2 * 256 + c * 16 + j] = c == j ? 1.0f : 0.0f;
+                for (int k = 0; k < 16; ++k) tab[(3 + k) * 256 + c * 16 + j] = wt[(c * 16 + j) * 16 + k];
+            }
+        for (int j = 0; j < 16; ++j) {
+            tb[j] = bl.get("d8.b", {q})[j]; tb[16 + j] = bl.get("d4.b", {q})[j];
+            for (int k = 0; k < 16; ++k) tb[(3 + k) * 16 + j] = bl.get("ct4.b", {q})[j];
+        }
+        ws.put("ep.tab", tab); ws.put("ep.tabb", tb);
+    }
+    if (int rc = ws.upload(ctx, &net->wdev)) return rc;
+    trunk_bind(ws, net.get());
+    net->kh.whT = ws.dev("head.wT"); net->kh.wsc = ws.dev("ep.zero");
+    net->ke.wsc = ws.dev("ep.score"); net->ke.tab = ws.dev("ep.tab"); net->ke.tabb = ws.dev("ep.tabb");
     if (int rc = ws.bound(ctx)) return rc;
     *out = net.release();
     return KPB_OK;

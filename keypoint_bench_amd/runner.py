@@ -72,7 +72,15 @@ def build_model(params, dense_descriptors=True):
         if not (w and os.path.exists(w)):
             raise FileNotFoundError("r2d2 checkpoint %r not found" % (w,))
         return from_checkpoint(torch.load(w, map_location="cpu"))
-    raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2)" % (mt,))
+    if mt == "EdgePoint":    # model_interface.py:46-48
+        from .models.EdgePoint import EdgePoint
+        net = EdgePoint(params["EdgePoint_params"])
+        w = params["EdgePoint_params"].get("weight")
+        if not (w and os.path.exists(w)):
+            raise FileNotFoundError("EdgePoint checkpoint %r not found" % (w,))
+        net.load_state_dict(torch.load(w, map_location="cpu"))
+        return net.eval()
+    raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint)" % (mt,))
 
 
 # ------------------------------------------------------------------------------------------ sharding

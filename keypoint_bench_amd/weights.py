@@ -18,6 +18,7 @@ ARCH_XFEAT = 3
 ARCH_DISK = 4
 ARCH_LIGHTGLUE = 5
 ARCH_R2D2 = 6
+ARCH_EDGEPOINT = 7
 _REC = struct.Struct("<40sI4II")
 
 
@@ -76,6 +77,44 @@ def fold_alike(sd) -> dict:
         t["agg%d.w" % i] = w.reshape(w.shape[0], w.shape[1])
     w = _np(sd["convhead2.weight"]).astype(np.float32)
     t["head.w"] = w.reshape(w.shape[0], w.shape[1])
+    return t
+
+
+EDGEPOINT_PLAN = dict(c1=8, c2=16, c3=32, c4=64, dim=64)
+
+
+def fold_edgepoint(sd) -> dict:
+    """state_dict of EdgePoint (models/EdgePoint.py:84-141) -> the folded ALIKE-t trunk of fold_alike (head.w is convhead2, 64 x 64) plus the head's
+    own layers as csrc/alike.hip expects them: score (conv_score, 16 -> 1), d8 / d4 (conv_8 / conv_4, 1 x 1 with stride 8 / 4) and ct4
+    (conv_transpose_4, kept [in][out][ky][kx] as the state_dict has it).  Refused: a missing or mis-shaped tensor, any plan but 8,16,32,64 / 64."""
+    c1, c2, c3, c4, dim = (EDGEPOINT_PLAN[k] for k in ("c1", "c2", "c3", "c4", "dim"))
+    q = dim // 4
+    need = {"block1.conv1.weight": (c1, 3, 3, 3), "block1.conv2.weight": (c1, c1, 3, 3)}
+    for i, (ci, co) in ((2, (c1, c2)), (3, (c2, c3)), (4, (c3, c4))):
+        p = "block%d" % i
+        need.update({p + ".conv1.weight": (co, ci, 3, 3), p + ".conv2.weight": (co, co, 3, 3),
+                     p + ".downsample.weight": (co, ci, 1, 1), p + ".downsample.bias": (co,)})
+    for i, c in ((1, c1), (2, c2), (3, c3), (4, c4)):
+        need["conv%d.weight" % i] = (q, c, 1, 1)
+    for blk, co in (("block1", c1), ("block2", c2), ("block3", c3), ("block4", c4)):
+        for bn in ("bn1", "bn2"):
+            for leaf in ("weight", "bias", "running_mean", "running_var"):
+                need["%s.%s.%s" % (blk, bn, leaf)] = (co,)
+    need.update({"convhead2.weight": (dim, dim, 1, 1), "conv_score.weight": (1, q, 1, 1), "conv_score.bias": (1,),
+                 "conv_8.weight": (q, q, 1, 1), "conv_8.bias": (q,), "conv_4.weight": (q, q, 1, 1), "conv_4.bias": (q,),
+                 "conv_transpose_4.weight": (q, q, 4, 4), "conv_transpose_4.bias": (q,)})
+    for key, shape in need.items():
+        if key not in sd:
+            raise ValueError("EdgePoint state_dict: %s is missing" % key)
+        if tuple(sd[key].shape) != shape:
+            raise ValueError("EdgePoint state_dict: %s has shape %s, the supported plan (c1..c4 = 8,16,32,64, dim = 64) needs %s"
+                             % (key, tuple(sd[key].shape), shape))
+    t = fold_alike(sd)
+    f32 = lambda k: _np(sd[k]).astype(np.float32)
+    t["score.w"], t["score.b"] = f32("conv_score.weight").reshape(q), f32("conv_score.bias")
+    t["d8.w"], t["d8.b"] = f32("conv_8.weight").reshape(q, q), f32("conv_8.bias")
+    t["d4.w"], t["d4.b"] = f32("conv_4.weight").reshape(q, q), f32("conv_4.bias")
+    t["ct4.w"], t["ct4.b"] = f32("conv_transpose_4.weight"), f32("conv_transpose_4.bias")
     return t
 
 
