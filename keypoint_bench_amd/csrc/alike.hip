@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void alike_block1(Block1Args a)
 struct Block1HArgs {
     Block1Args b;
     const uint4* w1pk;   // [2 kb][hi / lo][64 lanes] fragments of conv1 (pack_b1c1_pairs), scaled by 1 / inv_ws1
-    const uint4* w2pk;   // [3 kb][hi / lo][64 lanes] fragments of conv2 (pack_b1c2_pairs), scaled by 1 / inv_ws2
+    const uint4* w2pk;   // [3 kb][hi / lo][64 lanes] fragments of conv2 (pack_win3x4_h16), scaled by 1 / inv_ws2
     float inv_ws1, inv_ws2;     // reciprocals of the two power-of-two weight scales
     float l1_c1, bmax_c1;       // max over output channels of sum |w| of conv1, max |bias|: |conv1 output| <= amax(input) l1 + bmax
     float* wmax_x1;             // [B][workgroups][4 waves]: every wave's largest x1 value (x1 >= 0); amax_reduce folds them per image
@@ -437,42 +437,13 @@ __global__ __launch_bounds__(256) void alike_block1_h(Block1HArgs ha)
 // piece 4 kb + g = (ky, half) for pieces 0..5; element j = (kx = 2 half + (j >> 2), cin = j & 3): w[cout][cin][ky][kx - s]
 std::vector<float> pack_b1c1_pairs(const float* w, float scale)
 {
-    std::vector<uint16_t> hl((size_t)2 * 2 * 64 * 8, 0);
-    for (int kb = 0; kb < 2; ++kb)
-        for (int l = 0; l < 64; ++l)
-            for (int j = 0; j < 8; ++j) {
-                const int n = l & 15, g = l >> 4, s2 = n >> 3, co = n & 7, piece = 4 * kb + g;
-                const int ky = piece >> 1, kx = 2 * (piece & 1) + (j >> 2) - s2, c = j & 3;
-                const float v = (piece < 6 && c < 3 && kx >= 0 && kx <= 2) ? w[((size_t)co * 3 + c) * 9 + ky * 3 + kx] * scale : 0.0f;
-                _Float16 hi = (_Float16)v;
-                const _Float16 lo = (_Float16)(v - (float)hi);
-                memcpy(&hl[(((size_t)kb * 2 + 0) * 64 + l) * 8 + j], &hi, 2);
-                memcpy(&hl[(((size_t)kb * 2 + 1) * 64 + l) * 8 + j], &lo, 2);
-            }
-    std::vector<float> out(hl.size() / 2);
-    memcpy(out.data(), hl.data(), hl.size() * 2);
-    return out;
+    return pack_lanes_h16(2, [&](int kb, int l, int j) {
+        const int n = l & 15, g = l >> 4, s2 = n >> 3, co = n & 7, piece = 4 * kb + g;
+        const int ky = piece >> 1, kx = 2 * (piece & 1) + (j >> 2) - s2, c = j & 3;
+        return (piece < 6 && c < 3 && kx >= 0 && kx <= 2) ? w[((size_t)co * 3 + c) * 9 + ky * 3 + kx] * scale : 0.0f;
+    });
 }
-
-// conv2 of block 1, OIHW [8][8][3][3] -> alike_block1_h fragments [3 kb = ky][hi / lo][64 lanes][8 halves = cin]:
-// lane (n = (s, cout), g = kx of the 3 x 4 window) holds w[cout][cin][ky][kx - s] (zero outside the kernel)
-std::vector<float> pack_b1c2_pairs(const float* w, float scale)
-{
-    std::vector<uint16_t> hl((size_t)3 * 2 * 64 * 8, 0);
-    for (int kb = 0; kb < 3; ++kb)
-        for (int l = 0; l < 64; ++l)
-            for (int j = 0; j < 8; ++j) {
-                const int n = l & 15, g = l >> 4, s2 = n >> 3, co = n & 7, kx = g - s2;
-                const float v = (kx >= 0 && kx <= 2) ? w[((size_t)co * 8 + j) * 9 + kb * 3 + kx] * scale : 0.0f;
-                _Float16 hi = (_Float16)v;
-                const _Float16 lo = (_Float16)(v - (float)hi);
-                memcpy(&hl[(((size_t)kb * 2 + 0) * 64 + l) * 8 + j], &hi, 2);
-                memcpy(&hl[(((size_t)kb * 2 + 1) * 64 + l) * 8 + j], &lo, 2);
-            }
-    std::vector<float> out(hl.size() / 2);
-    memcpy(out.data(), hl.data(), hl.size() * 2);
-    return out;
-}
+// (conv2 of block 1 is pack_win3x4_h16, conv_mfma.h)
 
 // ------------------------------------------------------------------------------------------------ conv3x3
 struct ConvArgs {
@@ -893,42 +864,45 @@ __global__ __launch_bounds__(256, 4) void alike_block2(Block2Args a)      // 39.
 // agg [16][16] (cout, cin) -> one k-block of fragments: piece g < 2 = channel octet g
 std::vector<float> pack_1x1_h16(const float* w, float scale)
 {
-    std::vector<uint16_t> hl((size_t)2 * 64 * 8, 0);
-    for (int l = 0; l < 64; ++l)
-        for (int j = 0; j < 8; ++j) {
-            const int n = l & 15, g = l >> 4;
-            const float v = g < 2 ? w[n * 16 + 8 * g + j] * scale : 0.0f;
-            _Float16 hi = (_Float16)v;
-            const _Float16 lo = (_Float16)(v - (float)hi);
-            memcpy(&hl[((size_t)0 * 64 + l) * 8 + j], &hi, 2);
-            memcpy(&hl[((size_t)1 * 64 + l) * 8 + j], &lo, 2);
-        }
-    std::vector<float> out(hl.size() / 2);
-    memcpy(out.data(), hl.data(), hl.size() * 2);
-    return out;
+    return pack_lanes_h16(1, [&](int, int l, int j) {
+        const int n = l & 15, g = l >> 4;
+        return g < 2 ? w[n * 16 + 8 * g + j] * scale : 0.0f;
+    });
 }
 
 // OIHW [16][CIN][3][3] (+ identity-branch [16][8]) -> alike_block2 fragments [KB][hi / lo][64 lanes][8 halves], as floats (bit patterns)
 std::vector<float> pack_h16(const float* w, int CIN, const float* ds_w, float scale)
 {
     const int OCT = CIN / 8, NK = 9 * OCT + (ds_w ? 1 : 0), KB = (NK + 3) / 4;
-    std::vector<uint16_t> hl((size_t)KB * 2 * 64 * 8, 0);
-    for (int kb = 0; kb < KB; ++kb)
-        for (int l = 0; l < 64; ++l)
-            for (int j = 0; j < 8; ++j) {
-                const int n = l & 15, g = l >> 4, kidx = 4 * kb + g;
-                float v = 0.0f;
-                if (kidx < 9 * OCT) { const int tap = kidx / OCT, o = kidx - tap * OCT; v = w[((size_t)n * CIN + 8 * o + j) * 9 + tap]; }
-                else if (ds_w && kidx == 9 * OCT) v = ds_w[n * 8 + j];
-                v *= scale;
-                _Float16 hi = (_Float16)v;
-                const _Float16 lo = (_Float16)(v - (float)hi);
-                memcpy(&hl[(((size_t)kb * 2 + 0) * 64 + l) * 8 + j], &hi, 2);
-                memcpy(&hl[(((size_t)kb * 2 + 1) * 64 + l) * 8 + j], &lo, 2);
-            }
-    std::vector<float> out(hl.size() / 2);
-    memcpy(out.data(), hl.data(), hl.size() * 2);
-    return out;
+    return pack_lanes_h16(KB, [&](int kb, int l, int j) {
+        const int n = l & 15, g = l >> 4, kidx = 4 * kb + g;
+        float v = 0.0f;
+        if (kidx < 9 * OCT) { const int tap = kidx / OCT, o = kidx - tap * OCT; v = w[((size_t)n * CIN + 8 * o + j) * 9 + tap]; }
+        else if (ds_w && kidx == 9 * OCT) v = ds_w[n * 8 + j];
+        return v * scale;
+    });
+}
+
+// head.w [65][64] -> the split-f16 fragments of the fine-group rows (alike_head_f16p): [hi/lo][kb][nh][h][n][j] halves, the hi plane then the lo plane,
+// value = head.w[o = 32 nh + n][c = 16 kb + 8 h + j] (rows 0..63 x channels 0..31)
+std::vector<float> pack_head_h16(const float* hw, float scale)
+{
+    H16Frags fr(2 * 2048);
+    for (int kb = 0; kb < 2; ++kb) for (int nh = 0; nh < 2; ++nh) for (int hh = 0; hh < 2; ++hh) for (int n = 0; n < 32; ++n) for (int j = 0; j < 8; ++j) {
+        // k slot (hh, j) of block kb: group 1 (up2 a2) keeps channel 8 hh + j; group 0 (agg1) is produced by an MFMA whose accumulator
+        // leaves lane half hh with channels {0..3, 8..11} + 4 hh (rows (r & 3) + 8 (r >> 2) + 4 hh of a 32 x 32 tile), so its k order is that
+        const int cch = kb == 0 ? (j < 4 ? j : j + 4) + 4 * hh : 16 + 8 * hh + j;
+        const size_t at = ((((size_t)kb * 2 + nh) * 2 + hh) * 32 + n) * 8 + j;
+        fr.set(at, 2048 + at, hw[(32 * nh + n) * 64 + cch] * scale);
+    }
+    return fr.floats();
+}
+
+// agg1 [16][8] (8 -> 16, 1x1) as the A operand of v_mfma_f32_32x32x16_f16 (r04): rows = output channels (16 of 32 used), k = input channel (8 of 16
+// used): lane (row o, k half) holds agg1[o][c = 0..7] in its eight halves for o < 16 and k half 0, zeros elsewhere
+std::vector<float> pack_agg1_h16(const float* a1w, float scale)
+{
+    return pack_lanes_h16(1, [&](int, int l, int c) { return l < 16 ? a1w[l * 8 + c] * scale : 0.0f; });
 }
 
 // ------------------------------------------------------------------------------------------------ 1x1 + ReLU
@@ -2050,7 +2024,7 @@ struct AlikeTrunk : kpb_net {
     struct { const uint4 *w1pk, *w2pk, *wapk; const float *b1, *bsum; float inv_ws1, inv_ws2, inv_wsa, l1_c1, bmax_c1, l1_c2, l1_ds, bmax_sum; } k2 = {};   // Block2Args
     // blocks 2 .. 4 as strict fp32 sees them (ConvArgs: w1 .. dsb).  Blocks 3 / 4 keep conv2 as an MFMA pack in both forms (w2p, b2p, un2) and, in the
     // split-f16 form, conv1 + the identity branch as one pack (w1h, b1h, un1); prof1 / prof2 are the profile names of their conv1 / conv2
-    struct Res { const float *w1, *b1, *w2, *b2, *dsw, *dsb, *w1h, *b1h, *w2p, *b2p; float un1, un2; std::string prof1, prof2; } blk[5] = {};      // [2 .. 4]
+    struct Res { const float *w1, *b1, *w2, *b2, *dsw, *dsb, *w1h, *b1h, *w2p, *b2p; float un1, un2; const char *prof1, *prof2; } blk[5] = {};      // [2 .. 4]
     // (the trunk kernels write every group's share of ALIKE's score logit through wsc, and with E3 / E4 of its head rows through whT: a net without that head binds
     //  64 zeros as wsc and runs the trunk with dense = false)
     struct { const float *agg[5], *whT, *wsc; const uint4 *wh16, *a1h16; float l1_agg1, inv_ws_h, inv_wa; } kh = {};      // agg[1 .. 4]; HeadArgs, HybArgs, LinArgs
@@ -2200,16 +2174,16 @@ int AlikeTrunk::trunk(const float* img_dev, int batch, int H, int W, bool dense,
             // (same weights, same arithmetic per output)
             if (batch < 16 && !prepooled) m.nblk = 2 * cout / 32;
             const CmForm f1 = !prepooled ? CM_P4_LAT : batch < 16 ? CM_C16_LAT : cin == 32 ? CM_C32 : CM_C16;     // (only a handful of images leave x3 unpooled)
-            if (int rc = launch(r.prof1.c_str(), f1, m)) return rc;
+            if (int rc = launch(r.prof1, f1, m)) return rc;
             ConvM c2{.in = tr, .out = xo, .wp = r.w2p, .bias = r.b2p, .res = tr + cout, .Hi = Hi / 4, .Wi = Wi / 4,
                      .H = Hi / 4, .W = Wi / 4, .CIN = cout, .COUT = cout, .NCH = cout / 32, .nblk = batch < 16 ? cout / 32 : 1, .istride = 2 * cout,
                      .ostride = cout, .unscale = r.un2, .rstride = 2 * cout};
             if (ao) {
                 c2.tl_w = kh.agg[gi]; c2.tl_wsg = kh.wsc + 16 * (gi - 1); c2.tl_wproj = kh.whT + 16 * (gi - 1) * 64;
                 c2.tl_agg = ao; c2.tl_smap = So; c2.tl_E = Eo; c2.tl_pool = pool;
-                return launch(r.prof2.c_str(), pool ? CM_B3C2_TAIL : CM_B4C2_TAIL, c2);
+                return launch(r.prof2, pool ? CM_B3C2_TAIL : CM_B4C2_TAIL, c2);
             }
-            return launch(r.prof2.c_str(), batch < 16 ? CM_C32_LAT : cout == 32 ? CM_C32_1T : CM_C32, c2);
+            return launch(r.prof2, batch < 16 ? CM_C32_LAT : cout == 32 ? CM_C32_1T : CM_C32, c2);
         };
         if (fused) {
             if (int rc = block_h(blk[3], p2, t3r3, nullptr, 16, 32, H / 2, W / 2, true, 3, a3, S3, E3, p3)) return rc;
@@ -2227,7 +2201,7 @@ int AlikeTrunk::trunk(const float* img_dev, int batch, int H, int W, bool dense,
             const ConvM m{.in = in, .out = out, .wp = r.w2p, .bias = r.b2p, .res = res, .Hi = h, .Wi = w, .H = h, .W = w,
                           .CIN = c, .COUT = c, .NCH = c / 32, .nblk = 1, .istride = c, .ostride = c};
             return launch_conv_mfma<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32}>(
-                ctx, r.prof2.c_str(), CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = c / 32}, m, batch);
+                ctx, r.prof2, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = c / 32}, m, batch);
         };
         KPB_LAUNCH(ctx, "alike_block1", alike_block1, dim3(cdiv(W, B1_TW), cdiv(H, B1_TH), batch), dim3(256), 0, st, b1);
         c = ConvArgs{p1, t2, blk[2].w1, blk[2].b1, nullptr, nullptr, nullptr, nullptr, H / 2, W / 2};      // pooled by block1
@@ -2330,7 +2304,10 @@ const char* first_missing(const KpbwBlob& bl, const std::vector<Need>& more)
     return nullptr;
 }
 
-// the trunk half of a create: repacks, h16 packs, L1 norms and bias maxima of blocks 1 .. 4 and the four aggregations, staged ...
+// the profile names of conv1 / conv2 of blocks 2 .. 4 (AlikeTrunk::Res::prof1, prof2)
+constexpr const char* RES_PROF[5][2] = {{}, {}, {"conv3x3_b2c1", "conv3x3_b2c2"}, {"conv3x3_b3c1", "conv3x3_b3c2"}, {"conv3x3_b4c1", "conv3x3_b4c2"}};
+
+// the trunk half of a create: repacks, h16 packs, L1 norms and bias maxima of blocks 1 .. 4 and the four aggregations, each staged with the members of *net it binds
 void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
 {
     std::vector<float> tmp;
@@ -2338,30 +2315,34 @@ void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
         const float* w = bl.get("b1c1.w", {c1, 3, 3, 3});
         tmp.assign(27 * 8, 0.f);
         for (int o = 0; o < 8; ++o) for (int k = 0; k < 27; ++k) tmp[k * 8 + o] = w[o * 27 + k];
-        ws.put("b1c1.w", tmp);
-        ws.put_raw("b1c1.b", bl.get("b1c1.b", {c1}), 8);
-        repack3x3(bl.get("b1c2.w", {c1, c1, 3, 3}), 8, 8, tmp); ws.put("b1c2.w", tmp);
+        ws.put(tmp, &net->k1.w1);
+        ws.put_raw(bl.get("b1c1.b", {c1}), 8, &net->k1.b1);
+        repack3x3(bl.get("b1c2.w", {c1, c1, 3, 3}), 8, 8, tmp); ws.put(tmp, &net->k1.w2);
         {   // split-f16 fragments, each pack scaled to max |w| in [2^12, 2^13), and the constants of conv1's output bound
             const float* w1 = bl.get("b1c1.w", {c1, 3, 3, 3});
             const float* w2 = bl.get("b1c2.w", {c1, c1, 3, 3});
             const float s1 = weight_scale_h(w1, 8 * 27), s2 = weight_scale_h(w2, 8 * 72);
-            ws.put("b1c1.pairs", pack_b1c1_pairs(w1, s1));
-            ws.put("b1c2.pairs", pack_b1c2_pairs(w2, s2));
+            ws.put(pack_b1c1_pairs(w1, s1), &net->k1.w1pk);
+            ws.put(pack_win3x4_h16(w2, s2), &net->k1.w2pk);
             net->k1.inv_ws1 = 1.0f / s1; net->k1.inv_ws2 = 1.0f / s2;
             net->k1.l1_c1 = l1_rows(w1, 8, 27); net->k1.bmax_c1 = max_abs(bl.get("b1c1.b", {c1}), 8);
         }
-        ws.put_raw("b1c2.b", bl.get("b1c2.b", {c1}), 8);
+        ws.put_raw(bl.get("b1c2.b", {c1}), 8, &net->k1.b2);
     }
     const uint32_t ch[5] = {0, c1, c2, c3, c4};
     for (int i = 2; i <= 4; ++i) {
         char nm[16];
         const uint32_t ci = ch[i - 1], co = ch[i];
-        snprintf(nm, 16, "b%dc1.w", i); repack3x3(bl.get(nm, {co, ci, 3, 3}), co, ci, tmp); ws.put(nm, tmp);
-        snprintf(nm, 16, "b%dc1.b", i); ws.put_raw(nm, bl.get(nm, {co}), co);
-        snprintf(nm, 16, "b%dc2.w", i); repack3x3(bl.get(nm, {co, co, 3, 3}), co, co, tmp); ws.put(nm, tmp);
-        snprintf(nm, 16, "b%dc2.b", i); ws.put_raw(nm, bl.get(nm, {co}), co);
-        snprintf(nm, 16, "b%dds.w", i); transpose(bl.get(nm, {co, ci}), co, ci, tmp); ws.put(nm, tmp);
-        snprintf(nm, 16, "b%dds.b", i); ws.put_raw(nm, bl.get(nm, {co}), co);
+        AlikeTrunk::Res& r = net->blk[i];
+        r.prof1 = RES_PROF[i][0]; r.prof2 = RES_PROF[i][1];
+        snprintf(nm, 16, "b%dc1.w", i); repack3x3(bl.get(nm, {co, ci, 3, 3}), co, ci, tmp); ws.put(tmp, &r.w1);
+        snprintf(nm, 16, "b%dc1.b", i);
+        if (i == 2) ws.put_raw(bl.get(nm, {co}), co, &r.b1, &net->k2.b1);       // alike_block2 reads conv1's bias as it is
+        else ws.put_raw(bl.get(nm, {co}), co, &r.b1);
+        snprintf(nm, 16, "b%dc2.w", i); repack3x3(bl.get(nm, {co, co, 3, 3}), co, co, tmp); ws.put(tmp, &r.w2);
+        snprintf(nm, 16, "b%dc2.b", i); ws.put_raw(bl.get(nm, {co}), co, &r.b2);
+        snprintf(nm, 16, "b%dds.w", i); transpose(bl.get(nm, {co, ci}), co, ci, tmp); ws.put(tmp, &r.dsw);
+        snprintf(nm, 16, "b%dds.b", i); ws.put_raw(bl.get(nm, {co}), co, &r.dsb);
     }
     {   // block 2 on the split-f16 MFMA kernel: fragments + combined biases
         const float* w1 = bl.get("b2c1.w", {c2, c1, 3, 3});
@@ -2371,29 +2352,29 @@ void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
         const float s1 = weight_scale_h(w1, 16 * 72);
         const float s2 = std::min(weight_scale_h(w2, 16 * 144), weight_scale_h(wd, 16 * 8));     // conv2 and the identity branch share one accumulation
         const float sa = weight_scale_h(wa, 16 * 16);
-        ws.put("b2c1.h16", pack_h16(w1, 8, nullptr, s1));
-        ws.put("b2c2.h16", pack_h16(w2, 16, wd, s2));
+        ws.put(pack_h16(w1, 8, nullptr, s1), &net->k2.w1pk);
+        ws.put(pack_h16(w2, 16, wd, s2), &net->k2.w2pk);
         const float* b2 = bl.get("b2c2.b", {c2});
         const float* bd = bl.get("b2ds.b", {c2});
         tmp.assign(16, 0.f);
         for (int i = 0; i < 16; ++i) tmp[i] = b2[i] + bd[i];
-        ws.put("b2c2.bsum", tmp);
-        ws.put("agg2.h16", pack_1x1_h16(wa, sa));
+        ws.put(tmp, &net->k2.bsum);
+        ws.put(pack_1x1_h16(wa, sa), &net->k2.wapk);
         net->k2.inv_ws1 = 1.0f / s1; net->k2.inv_ws2 = 1.0f / s2; net->k2.inv_wsa = 1.0f / sa;
         net->k2.l1_c1 = l1_rows(w1, 16, 72); net->k2.bmax_c1 = max_abs(bl.get("b2c1.b", {c2}), 16);
         net->k2.l1_c2 = l1_rows(w2, 16, 144); net->k2.l1_ds = l1_rows(wd, 16, 8); net->k2.bmax_sum = max_abs(tmp.data(), 16);
     }
     // both return 1 / the power-of-two scale the split-f16 pack was made with (ConvM::unscale)
-    auto put_mfma = [&](const char* name, const float* w, int cout, int cin, int ntb) {
+    auto put_mfma = [&](const float** dst, const float* w, int cout, int cin, int ntb) {
         if (conv_mfma_use_h16()) {
             const float sc = weight_scale_h(w, (size_t)cout * cin * 9);
-            ws.put(name, pack_mfma_h(w, cout, cin, 3, 32, ntb, sc));
+            ws.put(pack_mfma_h(w, cout, cin, 3, 32, ntb, sc), dst);
             return 1.0f / sc;
         }
-        ws.put(name, pack_mfma(w, cout, cin, 3, 32, ntb));
+        ws.put(pack_mfma(w, cout, cin, 3, 32, ntb), dst);
         return 1.0f;
     };
-    auto put_c1ds = [&](const char* name, const float* w1, const float* b1, const float* wds, const float* bds, int cout, int cin) {
+    auto put_c1ds = [&](AlikeTrunk::Res& r, const float* w1, const float* b1, const float* wds, const float* bds, int cout, int cin) {
         // OIHW [2 cout][cin][3][3]: rows 0 .. cout-1 = conv1, rows cout .. = the 1x1 identity branch on the centre tap
         std::vector<float> w((size_t)2 * cout * cin * 9, 0.0f), bb(2 * cout);
         memcpy(w.data(), w1, (size_t)cout * cin * 9 * sizeof(float));
@@ -2402,44 +2383,23 @@ void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
             bb[o] = b1[o]; bb[cout + o] = bds[o];
         }
         const float sc = weight_scale_h(w.data(), w.size());
-        ws.put(std::string(name) + ".h", pack_mfma_h(w.data(), 2 * cout, cin, 3, cin == 16 ? 16 : 32, 2, sc));
-        ws.put(std::string(name) + ".hb", bb);
-        return 1.0f / sc;
+        ws.put(pack_mfma_h(w.data(), 2 * cout, cin, 3, cin == 16 ? 16 : 32, 2, sc), &r.w1h);
+        ws.put(bb, &r.b1h);
+        r.un1 = 1.0f / sc;
     };
     if (conv_mfma_use_h16()) {
-        net->blk[3].un1 = put_c1ds("b3c1", bl.get("b3c1.w", {c3, c2, 3, 3}), bl.get("b3c1.b", {c3}), bl.get("b3ds.w", {c3, c2}), bl.get("b3ds.b", {c3}), 32, 16);
-        net->blk[4].un1 = put_c1ds("b4c1", bl.get("b4c1.w", {c4, c3, 3, 3}), bl.get("b4c1.b", {c4}), bl.get("b4ds.w", {c4, c3}), bl.get("b4ds.b", {c4}), 64, 32);
+        put_c1ds(net->blk[3], bl.get("b3c1.w", {c3, c2, 3, 3}), bl.get("b3c1.b", {c3}), bl.get("b3ds.w", {c3, c2}), bl.get("b3ds.b", {c3}), 32, 16);
+        put_c1ds(net->blk[4], bl.get("b4c1.w", {c4, c3, 3, 3}), bl.get("b4c1.b", {c4}), bl.get("b4ds.w", {c4, c3}), bl.get("b4ds.b", {c4}), 64, 32);
     }
-    net->blk[3].un2 = put_mfma("b3c2.wp", bl.get("b3c2.w", {c3, c3, 3, 3}), 32, 32, 1);
-    ws.put("b3c2.bp", pad_bias(bl.get("b3c2.b", {c3}), 32, 32));
-    net->blk[4].un2 = put_mfma("b4c2.wp", bl.get("b4c2.w", {c4, c4, 3, 3}), 64, 64, 2);
-    ws.put("b4c2.bp", pad_bias(bl.get("b4c2.b", {c4}), 64, 64));
+    net->blk[3].un2 = put_mfma(&net->blk[3].w2p, bl.get("b3c2.w", {c3, c3, 3, 3}), 32, 32, 1);
+    ws.put(pad_bias(bl.get("b3c2.b", {c3}), 32, 32), &net->blk[3].b2p);
+    net->blk[4].un2 = put_mfma(&net->blk[4].w2p, bl.get("b4c2.w", {c4, c4, 3, 3}), 64, 64, 2);
+    ws.put(pad_bias(bl.get("b4c2.b", {c4}), 64, 64), &net->blk[4].b2p);
     for (int i = 1; i <= 4; ++i) {
         char nm[16];
         snprintf(nm, 16, "agg%d.w", i);
-        transpose(bl.get(nm, {dim / 4, ch[i]}), dim / 4, ch[i], tmp); ws.put(nm, tmp);
+        transpose(bl.get(nm, {dim / 4, ch[i]}), dim / 4, ch[i], tmp); ws.put(tmp, &net->kh.agg[i]);
     }
-}
-
-// ... and bound once they are uploaded
-void trunk_bind(WeightStage& ws, AlikeTrunk* net)
-{
-    const bool h16 = conv_mfma_use_h16();
-    net->k1.w1 = ws.dev("b1c1.w"); net->k1.b1 = ws.dev("b1c1.b"); net->k1.w2 = ws.dev("b1c2.w"); net->k1.b2 = ws.dev("b1c2.b");
-    net->k1.w1pk = ws.dev<uint4>("b1c1.pairs"); net->k1.w2pk = ws.dev<uint4>("b1c2.pairs");
-    net->k2.w1pk = ws.dev<uint4>("b2c1.h16"); net->k2.w2pk = ws.dev<uint4>("b2c2.h16"); net->k2.wapk = ws.dev<uint4>("agg2.h16");
-    net->k2.b1 = ws.dev("b2c1.b"); net->k2.bsum = ws.dev("b2c2.bsum");
-    for (int i = 2; i <= 4; ++i) {
-        AlikeTrunk::Res& r = net->blk[i];
-        const std::string c1n = "b" + std::to_string(i) + "c1", c2n = "b" + std::to_string(i) + "c2", dsn = "b" + std::to_string(i) + "ds";
-        r.w1 = ws.dev(c1n + ".w"); r.b1 = ws.dev(c1n + ".b"); r.w2 = ws.dev(c2n + ".w"); r.b2 = ws.dev(c2n + ".b");
-        r.dsw = ws.dev(dsn + ".w"); r.dsb = ws.dev(dsn + ".b");
-        r.prof1 = "conv3x3_" + c1n; r.prof2 = "conv3x3_" + c2n;
-        if (i == 2) continue;
-        r.w2p = ws.dev(c2n + ".wp"); r.b2p = ws.dev(c2n + ".bp");
-        if (h16) { r.w1h = ws.dev(c1n + ".h"); r.b1h = ws.dev(c1n + ".hb"); }
-    }
-    for (int i = 1; i <= 4; ++i) net->kh.agg[i] = ws.dev("agg" + std::to_string(i) + ".w");
 }
 
 }  // namespace
@@ -2455,56 +2415,17 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     std::vector<float> tmp;
     trunk_stage(bl, ws, net.get());
     net->kh.l1_agg1 = l1_rows(bl.get("agg1.w", {dim / 4, c1}), 16, 8);
-    {
-        const float* hw = bl.get("head.w", {dim + 1, dim});
-        transpose(hw, 64, 64, tmp); ws.put("head.wT", tmp);
-        ws.put_raw("head.ws", hw + 64 * 64, 64);
-        // split-f16 fragments of the fine-group rows (alike_head_f16p): [hi/lo][kb][nh][h][n][j] halves,
-        // value = head.w[o = 32 nh + n][c = 16 kb + 8 h + j]; hi = f16(w), lo = f16(w - hi), to nearest
-        // (rows 0..63 x channels 0..31: the part this pack carries sets its power-of-two scale)
-        float hmax = 0.0f;
-        for (int o = 0; o < 64; ++o) for (int cc = 0; cc < 32; ++cc) hmax = std::max(hmax, std::fabs(hw[o * 64 + cc]));
-        const float sh = weight_scale_h(&hmax, 1);
-        net->kh.inv_ws_h = 1.0f / sh;
-        std::vector<uint16_t> hl(2 * 2 * 2 * 2 * 32 * 8);
-        for (int kb = 0; kb < 2; ++kb) for (int nh = 0; nh < 2; ++nh) for (int hh = 0; hh < 2; ++hh) for (int n = 0; n < 32; ++n) for (int j = 0; j < 8; ++j) {
-            // k slot (hh, j) of block kb: group 1 (up2 a2) keeps channel 8 hh + j; group 0 (agg1) is produced by an MFMA whose accumulator
-            // leaves lane half hh with channels {0..3, 8..11} + 4 hh (rows (r & 3) + 8 (r >> 2) + 4 hh of a 32 x 32 tile), so its k order is that
-            const int cch = kb == 0 ? (j < 4 ? j : j + 4) + 4 * hh : 16 + 8 * hh + j;
-            const float w = hw[(32 * nh + n) * 64 + cch] * sh;
-            const _Float16 hi = (_Float16)w;
-            const _Float16 lo = (_Float16)(w - (float)hi);
-            const size_t at = ((((size_t)kb * 2 + nh) * 2 + hh) * 32 + n) * 8 + j;
-            memcpy(&hl[at], &hi, 2);
-            memcpy(&hl[2048 + at], &lo, 2);
-        }
-        tmp.assign(2048, 0.f);
-        memcpy(tmp.data(), hl.data(), 8192);
-        ws.put("head.wh16", tmp);
-        // agg1 (8 -> 16, 1x1) as the A operand of v_mfma_f32_32x32x16_f16 (r04): rows = output channels (16 of 32 used), k = input
-        // channel (8 of 16 used): lane (row o, k half) holds agg1[o][c = 0..7] in its eight halves for o < 16 and k half 0, zeros elsewhere
-        {
-            const float* a1w = bl.get("agg1.w", {dim / 4, c1});            // [16][8]
-            const float sa1 = weight_scale_h(a1w, 16 * 8);
-            net->kh.inv_wa = 1.0f / sa1;
-            std::vector<uint16_t> fr(2 * 64 * 8, 0);
-            for (int o = 0; o < 16; ++o) for (int c = 0; c < 8; ++c) {
-                const float w = a1w[o * 8 + c] * sa1;
-                const _Float16 hi = (_Float16)w;
-                const _Float16 lo = (_Float16)(w - (float)hi);
-                memcpy(&fr[(size_t)o * 8 + c], &hi, 2);
-                memcpy(&fr[(size_t)(64 + o) * 8 + c], &lo, 2);
-            }
-            tmp.assign(512, 0.f);
-            memcpy(tmp.data(), fr.data(), 2048);
-            ws.put("agg1.h16", tmp);
-        }
-    }
+    const float* hw = bl.get("head.w", {dim + 1, dim});
+    transpose(hw, 64, 64, tmp); ws.put(tmp, &net->kh.whT);
+    ws.put_raw(hw + 64 * 64, 64, &net->kh.wsc);
+    float hmax = 0.0f;      // rows 0..63 x channels 0..31: the part the split-f16 pack carries sets its power-of-two scale
+    for (int o = 0; o < 64; ++o) for (int cc = 0; cc < 32; ++cc) hmax = std::max(hmax, std::fabs(hw[o * 64 + cc]));
+    const float* a1w = bl.get("agg1.w", {dim / 4, c1});
+    const float sh = weight_scale_h(&hmax, 1), sa1 = weight_scale_h(a1w, 16 * 8);
+    net->kh.inv_ws_h = 1.0f / sh; net->kh.inv_wa = 1.0f / sa1;
+    ws.put(pack_head_h16(hw, sh), &net->kh.wh16);
+    ws.put(pack_agg1_h16(a1w, sa1), &net->kh.a1h16);
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
-    trunk_bind(ws, net.get());
-    net->kh.whT = ws.dev("head.wT"); net->kh.wsc = ws.dev("head.ws");
-    net->kh.wh16 = ws.dev<uint4>("head.wh16"); net->kh.a1h16 = ws.dev<uint4>("agg1.h16");
-    if (int rc = ws.bound(ctx)) return rc;
     *out = net.release();
     return KPB_OK;
 }
@@ -2554,8 +2475,8 @@ int edgepoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     WeightStage ws;
     std::vector<float> tmp;
     trunk_stage(bl, ws, net.get());
-    ws.put("ep.zero", std::vector<float>(64, 0.0f));        // where ALIKE binds its score row: the trunk kernels' score shares come out zero and are not read
-    transpose(bl.get("head.w", {dim, dim}), 64, 64, tmp); ws.put("head.wT", tmp);
+    ws.put(std::vector<float>(64, 0.0f), &net->kh.wsc);        // where ALIKE binds its score row: the trunk kernels' score shares come out zero and are not read
+    transpose(bl.get("head.w", {dim, dim}), 64, 64, tmp); ws.put(tmp, &net->kh.whT);
     {   // edgepoint_score's weights: rows {conv1.weight[c][0 .. 7], conv_score.weight[c]}, then conv_score.bias
         const float *w1 = bl.get("agg1.w", {q, c1}), *wsr = bl.get("score.w", {q});
         tmp.assign(EP_WBIAS + 1, 0.0f);
@@ -2564,7 +2485,7 @@ int edgepoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             tmp[c * EP_WROW + 8] = wsr[c];
         }
         tmp[EP_WBIAS] = bl.get("score.b", {1})[0];
-        ws.put("ep.score", tmp);
+        ws.put(tmp, &net->ke.wsc);
     }
     {   // stage-1 table of edgepoint_desc: T[m][c][j] and bias[m][j]
         std::vector<float> tab(19 * 256, 0.0f), tb(19 * 16, 0.0f);
@@ -2580,13 +2501,9 @@ int edgepoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             tb[j] = bl.get("d8.b", {q})[j]; tb[16 + j] = bl.get("d4.b", {q})[j];
             for (int k = 0; k < 16; ++k) tb[(3 + k) * 16 + j] = bl.get("ct4.b", {q})[j];
         }
-        ws.put("ep.tab", tab); ws.put("ep.tabb", tb);
+        ws.put(tab, &net->ke.tab); ws.put(tb, &net->ke.tabb);
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
-    trunk_bind(ws, net.get());
-    net->kh.whT = ws.dev("head.wT"); net->kh.wsc = ws.dev("ep.zero");
-    net->ke.wsc = ws.dev("ep.score"); net->ke.tab = ws.dev("ep.tab"); net->ke.tabb = ws.dev("ep.tabb");
-    if (int rc = ws.bound(ctx)) return rc;
     *out = net.release();
     return KPB_OK;
 }

@@ -1287,20 +1287,48 @@ inline float weight_scale_h(const float* w, size_t n)
     return std::ldexp(1.0f, 13 - e);
 }
 
-inline uint16_t f16_bits_rtn(float x)   // fp32 -> f16 to nearest even, as the device's v_cvt_pk_f16_f32 (cm_split2)
+// The halves of one split-f16 pack, and the ONE place where the host splits a value for them: hi = f16(v) to nearest even, as the device's
+// v_cvt_pk_f16_f32, and lo = f16(v - hi) (cm_split2 is the device counterpart).  (float)hi is exact, so for every finite v the residual, and with it
+// lo, has the same bits however hi is widened.  floats() hands the halves on as bit patterns in the float vector that WeightStage carries.
+struct H16Frags {
+    std::vector<uint16_t> h;
+    explicit H16Frags(size_t halves) : h(halves, 0) {}
+    void set(size_t hi_at, size_t lo_at, float v)
+    {
+        const _Float16 hi = (_Float16)v, lo = (_Float16)(v - (float)hi);
+        std::memcpy(&h[hi_at], &hi, 2);
+        std::memcpy(&h[lo_at], &lo, 2);
+    }
+    std::vector<float> floats() const
+    {
+        std::vector<float> f(h.size() / 2);
+        std::memcpy(f.data(), h.data(), h.size() * 2);
+        return f;
+    }
+};
+
+// The fragment layout of the hand-scheduled split-f16 kernels, [KB][hi / lo][64 lanes][8 halves]: half ((kb 2 + h) 64 + lane) 8 + j of the pack
+// is the hi (h = 0) or lo (h = 1) part of value(kb, lane, j)
+template <class F> std::vector<float> pack_lanes_h16(int KB, F&& value)
 {
-    const _Float16 h = (_Float16)x;
-    uint16_t b;
-    std::memcpy(&b, &h, 2);
-    return b;
+    H16Frags fr((size_t)KB * 2 * 64 * 8);
+    for (int kb = 0; kb < KB; ++kb)
+        for (int l = 0; l < 64; ++l)
+            for (int j = 0; j < 8; ++j) {
+                const size_t at = ((size_t)kb * 2 * 64 + l) * 8 + j;
+                fr.set(at, at + 64 * 8, value(kb, l, j));
+            }
+    return fr.floats();
 }
 
-inline float f16_bits_to_float(uint16_t hb)
+// A 3 x 3 convolution of 8 -> 8 channels over a 3 x 4 window (conv2 of alike_block1_h, conv A of xfeat_block1_23), OIHW [8][8][3][3] ->
+// [3 kb = ky][hi / lo][64 lanes][8 halves = cin]: lane (n = (s, cout), g = column of the window) holds w[cout][cin][ky][g - s], zero outside the kernel
+inline std::vector<float> pack_win3x4_h16(const float* w, float scale)
 {
-    const int e = (hb >> 10) & 0x1F;
-    const int man = hb & 0x3FF;
-    float v = e == 0 ? std::ldexp((float)man, -24) : std::ldexp((float)(man | 0x400), e - 25);
-    return (hb & 0x8000) ? -v : v;
+    return pack_lanes_h16(3, [&](int ky, int l, int cin) {
+        const int n = l & 15, g = l >> 4, s2 = n >> 3, co = n & 7, kx = g - s2;
+        return (kx >= 0 && kx <= 2) ? w[((size_t)co * 8 + cin) * 9 + ky * 3 + kx] * scale : 0.0f;
+    });
 }
 
 // OIHW -> conv_mfma_h fragment order [ntile][tap][chunk][kb][hi/lo][h][32] x 8 halves, scaled by `scale`; the result
@@ -1308,7 +1336,7 @@ inline float f16_bits_to_float(uint16_t hb)
 std::vector<float> pack_mfma_h(const float* w, int COUT, int CIN, int KS, int CC, int NTB, float scale)
 {
     const int KC = CC / 2, NKB = CC / 16, T = KS * KS, NCH = CIN / CC, NT = ((COUT + 32 * NTB - 1) / (32 * NTB)) * NTB;
-    std::vector<uint16_t> out((size_t)NT * T * NCH * NKB * 4 * 32 * 8, 0);
+    H16Frags fr((size_t)NT * T * NCH * NKB * 4 * 32 * 8);
     for (int nt = 0; nt < NT; ++nt)
         for (int tap = 0; tap < T; ++tap)
             for (int ch = 0; ch < NCH; ++ch)
@@ -1318,34 +1346,23 @@ std::vector<float> pack_mfma_h(const float* w, int COUT, int CIN, int KS, int CC
                             for (int e = 0; e < 8; ++e) {
                                 const int o = nt * 32 + j, c = ch * CC + h * KC + 8 * kb + e;
                                 if (o >= COUT) continue;
-                                const float x = w[((size_t)o * CIN + c) * T + tap] * scale;
-                                const uint16_t hi = f16_bits_rtn(x);
-                                const uint16_t lo = f16_bits_rtn(x - f16_bits_to_float(hi));
                                 const size_t base = (((((size_t)nt * T + tap) * NCH + ch) * NKB + kb) * 4) * 32;
-                                out[((base + (0 + h) * 32 + j) * 8) + e] = hi;
-                                out[((base + (2 + h) * 32 + j) * 8) + e] = lo;
+                                fr.set(((base + (0 + h) * 32 + j) * 8) + e, ((base + (2 + h) * 32 + j) * 8) + e, w[((size_t)o * CIN + c) * T + tap] * scale);
                             }
-    std::vector<float> f(out.size() / 2);
-    std::memcpy(f.data(), out.data(), out.size() * 2);
-    return f;
+    return fr.floats();
 }
 
 // One output channel's weights OIHW-row [CIN][KS][KS] -> [tap][CIN / 2] x (hi pair, lo pair) of halves, scaled: what conv_mfma_h<XC> multiplies
 // two channels at a time (v_dot2c_f32_f16)
 inline std::vector<float> pack_xc_pairs(const float* w1, int CIN, int T, float scale)
 {
-    std::vector<uint16_t> out((size_t)T * CIN * 2, 0);
+    H16Frags fr((size_t)T * CIN * 2);
     for (int t = 0; t < T; ++t)
         for (int c = 0; c < CIN; ++c) {
-            const float x = w1[(size_t)c * T + t] * scale;
-            const uint16_t hi = f16_bits_rtn(x), lo = f16_bits_rtn(x - f16_bits_to_float(hi));
             const size_t pair = ((size_t)t * CIN + c) >> 1;
-            out[pair * 4 + (c & 1)] = hi;
-            out[pair * 4 + 2 + (c & 1)] = lo;
+            fr.set(pair * 4 + (c & 1), pair * 4 + 2 + (c & 1), w1[(size_t)c * T + t] * scale);
         }
-    std::vector<float> f(out.size() / 2);
-    std::memcpy(f.data(), out.data(), out.size() * 2);
-    return f;
+    return fr.floats();
 }
 
 // The split-f16 matrix form is the product; KPB_FP32_MATRIX=1 selects the strict-fp32 kernels everywhere (fp32 MFMA / fp32 vector

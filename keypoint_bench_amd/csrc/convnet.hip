@@ -399,43 +399,14 @@ __global__ __launch_bounds__(256, 4) void xfeat_block1_23(XfB1Args a)
     }
 }
 
-// conv A of xfeat_block1_23, OIHW [8][8][3][3] -> [3 kb = ky][hi / lo][64 lanes][8 halves = cin]: lane (n = (s, cout), g = column of the
-// 3 x 4 window) holds w[cout][cin][ky][g - s], zero outside the kernel (alike.hip's pack_b1c2_pairs: the same product)
-std::vector<float> pack_xf_pairs(const float* w, float scale)
-{
-    std::vector<uint16_t> hl((size_t)3 * 2 * 64 * 8, 0);
-    for (int kb = 0; kb < 3; ++kb)
-        for (int l = 0; l < 64; ++l)
-            for (int j = 0; j < 8; ++j) {
-                const int n = l & 15, g = l >> 4, s2 = n >> 3, co = n & 7, kx = g - s2;
-                const float v = (kx >= 0 && kx <= 2) ? w[((size_t)co * 8 + j) * 9 + kb * 3 + kx] * scale : 0.0f;
-                const uint16_t hi = f16_bits_rtn(v), lo = f16_bits_rtn(v - f16_bits_to_float(hi));
-                hl[(((size_t)kb * 2 + 0) * 64 + l) * 8 + j] = hi;
-                hl[(((size_t)kb * 2 + 1) * 64 + l) * 8 + j] = lo;
-            }
-    std::vector<float> out(hl.size() / 2);
-    std::memcpy(out.data(), hl.data(), hl.size() * 2);
-    return out;
-}
-
-// conv B, OIHW [COUT <= 32][8][3][3] -> [2 m-tiles][3 kb = ky][hi / lo][64 lanes][8 halves = cin]: lane (m = output channel of the tile,
-// kq = kx; kq = 3 and channels >= COUT are zero)
+// conv B of xfeat_block1_23 (conv A is pack_win3x4_h16, conv_mfma.h), OIHW [COUT <= 32][8][3][3] -> [2 m-tiles][3 kb = ky][hi / lo][64 lanes][8 halves = cin]:
+// lane (m = output channel of the tile, kq = kx; kq = 3 and channels >= COUT are zero)
 std::vector<float> pack_xf_s2(const float* w, int cout, float scale)
 {
-    std::vector<uint16_t> hl((size_t)2 * 3 * 2 * 64 * 8, 0);
-    for (int mt = 0; mt < 2; ++mt)
-        for (int kb = 0; kb < 3; ++kb)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int m = l & 15, kq = l >> 4, co = 16 * mt + m;
-                    const float v = (kq <= 2 && co < cout) ? w[((size_t)co * 8 + j) * 9 + kb * 3 + kq] * scale : 0.0f;
-                    const uint16_t hi = f16_bits_rtn(v), lo = f16_bits_rtn(v - f16_bits_to_float(hi));
-                    hl[((((size_t)mt * 3 + kb) * 2 + 0) * 64 + l) * 8 + j] = hi;
-                    hl[((((size_t)mt * 3 + kb) * 2 + 1) * 64 + l) * 8 + j] = lo;
-                }
-    std::vector<float> out(hl.size() / 2);
-    std::memcpy(out.data(), hl.data(), hl.size() * 2);
-    return out;
+    return pack_lanes_h16(6, [&](int kb, int l, int cin) {
+        const int mt = kb / 3, ky = kb % 3, m = l & 15, kq = l >> 4, co = 16 * mt + m;
+        return (kq <= 2 && co < cout) ? w[((size_t)co * 8 + cin) * 9 + ky * 3 + kq] * scale : 0.0f;
+    });
 }
 
 // SuperPoint conv1a (1 -> 64, 3x3, ReLU; SuperPoint.py:44): 16 lanes share a pixel, each lane keeps the 9 taps of its
@@ -708,7 +679,7 @@ struct Layer {      // one convolution of a network plan
     bool pool_out = false;      // the output max-pooled 2 x 2 (SuperPoint's MaxPool2d after conv1b / 2b / 3b)
     int cc = 32;    // channels per LDS chunk of conv_mfma (32, or 16 for stride 2 / CIN not a multiple of 32)
     int ntb = 2;    // 32-wide output tiles per workgroup
-    // what a launch needs of the staged weights, bound once at create: stage_layer leaves the host scalars, bind_layer the device pointers and the profile name
+    // what a launch needs of the staged weights, bound once at create by stage_layer: host scalars, device pointers and the profile name
     float unscale = 1.0f;               // split-f16 form: 1 / the power-of-two scale the pack was made with (conv_mfma_h)
     float xb = 0.0f, xun = 1.0f;        // ntb == 5 (DISK up_3): the score channel's bias and 1 / the scale of its pack
     const float *w = nullptr, *b = nullptr, *xw = nullptr;
@@ -823,40 +794,32 @@ int launch_valu(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B
     return KPB_OK;
 }
 
-void stage_layer(WeightStage& ws, Layer& L, const float* w, const float* b)
+// L is the net's own Layer (net->L[i]): the stage binds its pointers at the upload.  Profile name = prefix + layer name: "sp_conv1b", "xf_block2.0", "disk_up3"
+void stage_layer(WeightStage& ws, Layer& L, const char* prefix, const float* w, const float* b)
 {
+    L.prof = prefix + L.name;
     if (L.mfma) {
         if (conv_mfma_use_h16() && L.ntb == 5) {       // cout = 4 x 32 + 1: the last channel goes to the VALU side of conv_mfma_h<XC>
             const int T = L.ks * L.ks, co = L.cout - 1;
             const float sc = weight_scale_h(w, (size_t)co * L.cin * T);
-            ws.put(L.name + ".w", pack_mfma_h(w, co, L.cin, L.ks, L.cc, 2, sc));
+            ws.put(pack_mfma_h(w, co, L.cin, L.ks, L.cc, 2, sc), &L.w);
             L.unscale = 1.0f / sc;
             const float xs = weight_scale_h(w + (size_t)co * L.cin * T, (size_t)L.cin * T);
-            ws.put(L.name + ".xw", pack_xc_pairs(w + (size_t)co * L.cin * T, L.cin, T, xs));
+            ws.put(pack_xc_pairs(w + (size_t)co * L.cin * T, L.cin, T, xs), &L.xw);
             L.xun = 1.0f / xs;
             L.xb = b ? b[co] : 0.0f;
         } else if (conv_mfma_use_h16()) {
             const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * L.ks * L.ks);
-            ws.put(L.name + ".w", pack_mfma_h(w, L.cout, L.cin, L.ks, L.cc, L.ntb, sc));
+            ws.put(pack_mfma_h(w, L.cout, L.cin, L.ks, L.cc, L.ntb, sc), &L.w);
             L.unscale = 1.0f / sc;
         } else {
-            ws.put(L.name + ".w", pack_mfma(w, L.cout, L.cin, L.ks, L.cc, L.ntb));
+            ws.put(pack_mfma(w, L.cout, L.cin, L.ks, L.cc, L.ntb), &L.w);
         }
-        ws.put(L.name + ".b", pad_bias(b, L.cout, 32 * L.ntb));
+        ws.put(pad_bias(b, L.cout, 32 * L.ntb), &L.b);
     } else {
-        ws.put(L.name + ".w", pack_valu(w, L.cout, L.cin, L.ks));
-        ws.put(L.name + ".b", pad_bias(b, L.cout, 8));
+        ws.put(pack_valu(w, L.cout, L.cin, L.ks), &L.w);
+        ws.put(pad_bias(b, L.cout, 8), &L.b);
     }
-}
-
-// after WeightStage::upload: the layer's device pointers, and its profile name (prefix + layer name: "sp_conv1b", "xf_block2.0", "disk_up3")
-void bind_layer(WeightStage& ws, Layer& L, const char* prefix, bool slope = false)
-{
-    L.w = ws.dev(L.name + ".w");
-    L.b = ws.dev(L.name + ".b");
-    if (L.mfma && L.ntb == 5 && conv_mfma_use_h16()) L.xw = ws.dev(L.name + ".xw");
-    if (slope) L.slope = ws.dev(L.name + ".slope");
-    L.prof = prefix + L.name;
 }
 
 // ================================================================================================ SuperPoint
@@ -931,7 +894,7 @@ int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         const float* w = bl.get((L.name + ".weight").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
         const float* b = bl.get((L.name + ".bias").c_str(), {(uint32_t)L.cout});
         if (!w || !b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SuperPoint tensor %s.weight/.bias missing or mis-shaped", L.name.c_str());
-        stage_layer(ws, L, w, b);
+        stage_layer(ws, L, "sp_", w, b);
         if (i == SP_1A) {       // |conv1a output| <= amax(gray) l1 + bmax (its channels' largest L1 norm, its largest |bias|)
             float l1 = 0.0f, bmax = 0.0f;
             for (int co = 0; co < L.cout; ++co) {
@@ -945,8 +908,6 @@ int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         }
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
-    for (Layer& L : net->L) bind_layer(ws, L, "sp_");
-    if (int rc = ws.bound(ctx)) return rc;
     *out = net.release();
     return KPB_OK;
 }
@@ -1102,7 +1063,7 @@ int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         Layer& L = net->L[i] = Layer{q.name, cin, cout, q.ks, q.stride, (cin % 32 == 0), q.relu};
         L.cc = q.stride == 2 ? 16 : 32;
         if (cout <= 32 && q.ks == 3 && q.stride == 1) L.ntb = 1;      // block2: one 32-wide output tile, not a half-empty pair
-        stage_layer(ws, L, w, b);
+        stage_layer(ws, L, "xf_", w, b);
     }
     if (conv_mfma_use_h16()) {      // the fused matrix form of block1.2 + block1.3 (xfeat_block1_23)
         const float* wA = bl.get("block1.2.w", {8, 8, 3, 3});
@@ -1112,10 +1073,10 @@ int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         if (!wA || !bA || !wB || !bB || !net->L[XF_B1_2].relu || !net->L[XF_B1_3].relu)
             return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat block1.2 / block1.3: unexpected layer plan");
         const float scA = weight_scale_h(wA, 8 * 8 * 9), scB = weight_scale_h(wB, 24 * 8 * 9);
-        ws.put("block1.23.wA", pack_xf_pairs(wA, scA));
-        ws.put("block1.23.wB", pack_xf_s2(wB, 24, scB));
-        ws.put("block1.23.bA", pad_bias(bA, 8, 8));
-        ws.put("block1.23.bB", pad_bias(bB, 24, 32));
+        ws.put(pack_win3x4_h16(wA, scA), &net->b23.wA);
+        ws.put(pack_xf_s2(wB, 24, scB), &net->b23.wB);
+        ws.put(pad_bias(bA, 8, 8), &net->b23.bA);
+        ws.put(pad_bias(bB, 24, 32), &net->b23.bB);
         float l1 = 0.0f, bmax = 0.0f;
         for (int o = 0; o < 8; ++o) {
             float s1 = 0.0f;
@@ -1131,16 +1092,9 @@ int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     const float* sw = bl.get("skip1.w", {24});
     const float* sb = bl.get("skip1.b", {24});
     if (!sw || !sb) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat skip1 tensors missing");
-    ws.put_raw("skip1.w", sw, 24);
-    ws.put_raw("skip1.b", sb, 24);
+    ws.put_raw(sw, 24, &net->skip_w);
+    ws.put_raw(sb, 24, &net->skip_b);
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
-    for (Layer& L : net->L) bind_layer(ws, L, "xf_");
-    net->skip_w = ws.dev("skip1.w"); net->skip_b = ws.dev("skip1.b");
-    if (conv_mfma_use_h16()) {
-        net->b23.wA = ws.dev<uint4>("block1.23.wA"); net->b23.wB = ws.dev<uint4>("block1.23.wB");
-        net->b23.bA = ws.dev("block1.23.bA"); net->b23.bB = ws.dev("block1.23.bB");
-    }
-    if (int rc = ws.bound(ctx)) return rc;
     *out = net.release();
     return KPB_OK;
 }
@@ -1518,8 +1472,8 @@ int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         if (!w || !b) return fail("down0");
         std::vector<float> t(75 * 16);
         for (int o = 0; o < 16; ++o) for (int k = 0; k < 75; ++k) t[k * 16 + o] = w[o * 75 + k];
-        ws.put("down0.w", t);
-        ws.put_raw("down0.b", b, 16);
+        ws.put(t, &net->down0_w);
+        ws.put_raw(b, 16, &net->down0_b);
     }
     struct { const char* n; int cin, cout; } plan[] = {{"down1", 16, 32}, {"down2", 32, 64}, {"down3", 64, 64}, {"down4", 64, 64},
                                                        {"up0", 128, 64}, {"up1", 128, 64}, {"up2", 96, 64}};
@@ -1532,8 +1486,8 @@ int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         const float* b = bl.get((L.name + ".b").c_str(), {(uint32_t)q.cout});
         const float* sl = bl.get((L.name + ".slope").c_str(), {(uint32_t)q.cin});
         if (!w || !b || !sl) return fail(q.n);
-        stage_layer(ws, L, w, b);
-        ws.put_raw(L.name + ".slope", sl, q.cin);
+        stage_layer(ws, L, "disk_", w, b);
+        ws.put_raw(sl, q.cin, &L.slope);
     }
     {   // up_3: 80 -> 129 = 128 descriptor channels + the score logit, five 32-wide tiles in one workgroup
         const float* w = bl.get("up3.w", {129, 80, 5, 5});
@@ -1542,13 +1496,10 @@ int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         if (!w || !b || !sl) return fail("up3");
         Layer& L3 = net->L[DK_UP3] = Layer{"up3", 80, 129, 5, 1, true, false};
         L3.cc = 16; L3.ntb = 5;
-        stage_layer(ws, L3, w, b);
-        ws.put_raw("up3.slope", sl, 80);
+        stage_layer(ws, L3, "disk_", w, b);
+        ws.put_raw(sl, 80, &L3.slope);
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
-    for (Layer& L : net->L) bind_layer(ws, L, "disk_", true);
-    net->down0_w = ws.dev("down0.w"); net->down0_b = ws.dev("down0.b");
-    if (int rc = ws.bound(ctx)) return rc;
     *out = net.release();
     return KPB_OK;
 }

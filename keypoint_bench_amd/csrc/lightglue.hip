@@ -930,11 +930,10 @@ KPB_API int kpb_lg_create(kpb_ctx* ctx, const void* blob, size_t len, float desc
         auto lg = std::make_unique<kpb_lg>();
         lg->ctx = ctx; lg->desc_scale = desc_scale;
         WeightStage ws;
-        std::vector<std::pair<const float**, std::string>> binds;       // every staged tensor with the member it is bound to once the stage is on the device
         auto fail = [&](const std::string& n) { return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_lg_create: tensor %s missing or mis-shaped", n.c_str()); };
         // one Linear; split-f16 form also: the rows of `key` in the order of lg_qkv_row (GE_ROTARY), or `key` and `key2` stacked (GE_SPLIT2)
-        auto linear_rows = [&](const std::string& key, const std::string& key2, const std::string& name, LgLinear& dst, uint32_t cout, uint32_t cin,
-                               bool permute) -> bool {
+        // (dst, like vec's, is a member of *lg: the stage binds it at the upload)
+        auto linear_rows = [&](const std::string& key, const std::string& key2, LgLinear& dst, uint32_t cout, uint32_t cin, bool permute) -> bool {
             const uint32_t c1 = key2.empty() ? cout : cout / 2;
             const float* w = bl.get((key + ".weight").c_str(), {c1, cin});
             const float* b = bl.get((key + ".bias").c_str(), {c1});
@@ -951,57 +950,51 @@ KPB_API int kpb_lg_create(kpb_ctx* ctx, const void* blob, size_t len, float desc
             }
             const bool h16 = conv_mfma_use_h16();
             const float sc = h16 ? weight_scale_h(wr.data(), wr.size()) : 1.0f;
-            ws.put(name + ".w", h16 ? pack_mfma_h(wr.data(), (int)cout, (int)cin, 1, 32, 2, sc) : pack_mfma(wr.data(), (int)cout, (int)cin, 1, 32, 2));
-            ws.put(name + ".b", pad_bias(br.data(), (int)cout, 64));
+            ws.put(h16 ? pack_mfma_h(wr.data(), (int)cout, (int)cin, 1, 32, 2, sc) : pack_mfma(wr.data(), (int)cout, (int)cin, 1, 32, 2), &dst.w);
+            ws.put(pad_bias(br.data(), (int)cout, 64), &dst.b);
             dst.unscale = 1.0f / sc;
-            binds.insert(binds.end(), {{&dst.w, name + ".w"}, {&dst.b, name + ".b"}});
             return true;
         };
-        auto linear = [&](const std::string& key, const std::string& name, LgLinear& dst, uint32_t cout, uint32_t cin) {
-            return linear_rows(key, "", name, dst, cout, cin, false);
-        };
-        auto vec = [&](const std::string& key, const std::string& name, const float*& dst, std::vector<uint32_t> dims) -> bool {
+        auto linear = [&](const std::string& key, LgLinear& dst, uint32_t cout, uint32_t cin) { return linear_rows(key, "", dst, cout, cin, false); };
+        auto vec = [&](const std::string& key, const float*& dst, std::vector<uint32_t> dims) -> bool {
             const float* v = bl.get(key.c_str(), dims);
             if (!v) return false;
             size_t n = 1; for (uint32_t d : dims) n *= d;
-            ws.put_raw(name, v, n);
-            binds.push_back({&dst, name});
+            ws.put_raw(v, n, &dst);
             return true;
         };
         if (auto it = bl.t.find("input_proj.weight"); it != bl.t.end()) {
             lg->input_dim = (int)it->second.second[1];
-            if (lg->input_dim % 32 || !linear("input_proj", "input_proj", lg->input_proj, 256, (uint32_t)lg->input_dim)) return fail("input_proj");
+            if (lg->input_dim % 32 || !linear("input_proj", lg->input_proj, 256, (uint32_t)lg->input_dim)) return fail("input_proj");
         }
-        if (!vec("posenc.Wr.weight", "posenc.Wr", lg->posenc_wr, {32, 2})) return fail("posenc.Wr.weight");
+        if (!vec("posenc.Wr.weight", lg->posenc_wr, {32, 2})) return fail("posenc.Wr.weight");
         for (int i = 0; i < NL; ++i) {
             const std::string sa = "transformers." + std::to_string(i) + ".self_attn", ca = "transformers." + std::to_string(i) + ".cross_attn";
             const std::string L = "L" + std::to_string(i);
             LgLayer& ly = lg->layer[i];
             // the self-attention q/k/v product and the cross-attention qk / v products: fused forms for split-f16 (see lg_linear)
-            if (conv_mfma_use_h16() ? (!linear_rows(sa + ".Wqkv", "", L + ".Wqkv_r", ly.wqkv, 768, 256, true) ||
-                                       !linear_rows(ca + ".to_qk", ca + ".to_v", L + ".toqkv", ly.toqkv, 512, 256, false))
-                                    : (!linear(sa + ".Wqkv", L + ".Wqkv", ly.wqkv, 768, 256) || !linear(ca + ".to_qk", L + ".toqk", ly.toqk, 256, 256) ||
-                                       !linear(ca + ".to_v", L + ".tov", ly.tov, 256, 256)))
+            if (conv_mfma_use_h16() ? (!linear_rows(sa + ".Wqkv", "", ly.wqkv, 768, 256, true) ||
+                                       !linear_rows(ca + ".to_qk", ca + ".to_v", ly.toqkv, 512, 256, false))
+                                    : (!linear(sa + ".Wqkv", ly.wqkv, 768, 256) || !linear(ca + ".to_qk", ly.toqk, 256, 256) ||
+                                       !linear(ca + ".to_v", ly.tov, 256, 256)))
                 return fail(L);
-            if (!linear(sa + ".out_proj", L + ".sout", ly.sout, 256, 256) ||
-                !linear(sa + ".ffn.0", L + ".sffn0", ly.sffn0, 512, 512) || !linear(sa + ".ffn.3", L + ".sffn3", ly.sffn3, 256, 512) ||
-                !vec(sa + ".ffn.1.weight", L + ".sln.g", ly.sln_g, {512}) || !vec(sa + ".ffn.1.bias", L + ".sln.b", ly.sln_b, {512}) ||
-                !linear(ca + ".to_out", L + ".toout", ly.toout, 256, 256) ||
-                !linear(ca + ".ffn.0", L + ".cffn0", ly.cffn0, 512, 512) || !linear(ca + ".ffn.3", L + ".cffn3", ly.cffn3, 256, 512) ||
-                !vec(ca + ".ffn.1.weight", L + ".cln.g", ly.cln_g, {512}) || !vec(ca + ".ffn.1.bias", L + ".cln.b", ly.cln_b, {512}))
+            if (!linear(sa + ".out_proj", ly.sout, 256, 256) ||
+                !linear(sa + ".ffn.0", ly.sffn0, 512, 512) || !linear(sa + ".ffn.3", ly.sffn3, 256, 512) ||
+                !vec(sa + ".ffn.1.weight", ly.sln_g, {512}) || !vec(sa + ".ffn.1.bias", ly.sln_b, {512}) ||
+                !linear(ca + ".to_out", ly.toout, 256, 256) ||
+                !linear(ca + ".ffn.0", ly.cffn0, 512, 512) || !linear(ca + ".ffn.3", ly.cffn3, 256, 512) ||
+                !vec(ca + ".ffn.1.weight", ly.cln_g, {512}) || !vec(ca + ".ffn.1.bias", ly.cln_b, {512}))
                 return fail(L);
             const std::string la = "log_assignment." + std::to_string(i);
-            if (!linear(la + ".final_proj", L + ".fproj", ly.fproj, 256, 256) || !vec(la + ".matchability.weight", L + ".mw", ly.mw, {1, 256}) ||
-                !vec(la + ".matchability.bias", L + ".mb", ly.mb, {1}))
+            if (!linear(la + ".final_proj", ly.fproj, 256, 256) || !vec(la + ".matchability.weight", ly.mw, {1, 256}) ||
+                !vec(la + ".matchability.bias", ly.mb, {1}))
                 return fail(la);
             if (i < NL - 1) {
                 const std::string tc = "token_confidence." + std::to_string(i) + ".token.0";
-                if (!vec(tc + ".weight", L + ".cw", ly.cw, {1, 256}) || !vec(tc + ".bias", L + ".cb", ly.cb, {1})) return fail(tc);
+                if (!vec(tc + ".weight", ly.cw, {1, 256}) || !vec(tc + ".bias", ly.cb, {1})) return fail(tc);
             }
         }
         if (int rc = ws.upload(ctx, &lg->wdev)) return rc;
-        for (auto& [member, name] : binds) *member = ws.dev(name);
-        if (int rc = ws.bound(ctx)) return rc;
         *out = lg.release();
         return KPB_OK;
     });

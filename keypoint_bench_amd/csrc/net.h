@@ -10,7 +10,7 @@ struct kpb_net {
     int arch = 0;
     int dim = 0;        // descriptor channels
     int desc_div = 1;   // descriptor map is (H/desc_div) x (W/desc_div)
-    float* wdev = nullptr;                 // all repacked weights: every network keeps typed pointers into it, bound once at create (WeightStage::dev)
+    float* wdev = nullptr;                 // all repacked weights: every network keeps typed pointers into it, bound once at create (WeightStage::put)
     kpb_buf act;                           // activations of the last forward, carved by kpb_carve
     int B = 0, H = 0, W = 0;
     virtual ~kpb_net() { (void)hipFree(wdev); (void)hipFree(act.p); }      // on the context's device: kpb_net_destroy, or a create that failed part way
@@ -67,39 +67,39 @@ struct KpbwBlob {
     }
 };
 
-// host-side staging of repacked tensors, for the nets' creates and kpb_lg_create alike (so its messages name the stage, not a caller); upload()
-// copies them into one device allocation, after which dev() resolves a staged name to its device pointer.  The stage lives inside a create function only: a network keeps the pointers, not the names.
+// host-side staging of repacked tensors, for the nets' creates and kpb_lg_create alike (so its messages name the stage, not a caller).  put() takes a tensor
+// together with the pointer member(s) it is to be read through; upload() copies the stage into one device allocation and then assigns every one of them.
+// The one rule: a destination is a member of the heap-allocated net or matcher object, which outlives the stage (&net->k2.w1pk, &L.w with L a reference into
+// net->L[i]) -- never a member of a local copy, whose address upload() would write through after it is gone.
 struct WeightStage {
+    struct Bind {
+        const float** f = nullptr;
+        const uint4** u = nullptr;
+        size_t off;
+        Bind(const float** d, size_t o) : f(d), off(o) {}
+        Bind(const uint4** d, size_t o) : u(d), off(o) {}
+    };
     std::vector<float> host;
-    std::map<std::string, size_t> off;
-    const float* wdev = nullptr;
-    std::string missing;        // the first name dev() did not find
-    void put(const std::string& name, const std::vector<float>& v)
+    std::vector<Bind> binds;    // (destination, offset into host) of every put
+    template <class D0, class... D> void put(const std::vector<float>& v, D0 d0, D... d)     // destinations: const float** or const uint4**, at least one
     {
         while (host.size() % 64) host.push_back(0.0f);   // 256-byte alignment for scalar/vector loads
-        off[name] = host.size();
+        binds.emplace_back(d0, host.size());
+        (binds.emplace_back(d, host.size()), ...);
         host.insert(host.end(), v.begin(), v.end());
     }
-    void put_raw(const std::string& name, const float* p, size_t n) { put(name, std::vector<float>(p, p + n)); }
-    int upload(kpb_ctx* ctx, float** owner)       // *owner (kpb_net::wdev, kpb_lg::wdev) frees the allocation, also when the upload or the binding fails
+    template <class... D> void put_raw(const float* p, size_t n, D... d) { put(std::vector<float>(p, p + n), d...); }
+    int upload(kpb_ctx* ctx, float** owner)       // *owner (kpb_net::wdev, kpb_lg::wdev) frees the allocation, also when the upload fails
     {
         if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(owner, host.size() * sizeof(float)) != hipSuccess)
             return kpb_fail(ctx, KPB_E_NOMEM, "WeightStage::upload: weight allocation failed");
         if (hipMemcpy(*owner, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
             return kpb_fail(ctx, KPB_E_HIP, "WeightStage::upload: weight copy to the device failed");
-        wdev = *owner;
+        for (const Bind& b : binds) {
+            if (b.f) *b.f = *owner + b.off;
+            else *b.u = reinterpret_cast<const uint4*>(*owner + b.off);
+        }
         return KPB_OK;
-    }
-    template <class T = float> const T* dev(const std::string& name)
-    {
-        auto it = off.find(name);
-        if (it != off.end()) return reinterpret_cast<const T*>(wdev + it->second);
-        if (missing.empty()) missing = name;
-        return nullptr;
-    }
-    int bound(kpb_ctx* ctx) const      // after the last dev(): a name that did not resolve is a refused create, not a null pointer in a kernel's arguments
-    {
-        return missing.empty() ? KPB_OK : kpb_fail(ctx, KPB_E_WEIGHTS, "WeightStage::bound: no staged tensor %s to bind", missing.c_str());
     }
 };
 

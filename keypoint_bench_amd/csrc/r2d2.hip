@@ -145,6 +145,7 @@ int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     for (int i = 0; i < 9; ++i) {
         const R2Layer& L = R2D2_PLAN[i];
         const std::string n = L.name;
+        R2d2Net::Bound& dst = net->lay[i];
         const float* w = bl.get((n + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
         const float* b = bl.get((n + ".b").c_str(), {(uint32_t)L.cout});
         if (!w || !b) return bad(L.name);
@@ -153,16 +154,16 @@ int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             for (int o = 0; o < 32; ++o)
                 for (int c = 0; c < 3; ++c)
                     for (int t = 0; t < 9; ++t) p[(t * 3 + c) * 32 + o] = w[(o * 3 + c) * 9 + t];
-            ws.put(n + ".w", p);
-            ws.put_raw(n + ".b", b, 32);
+            ws.put(p, &dst.w);
+            ws.put_raw(b, 32, &dst.b);
         } else if (conv_mfma_use_h16()) {      // tap-major fragments, two n-tiles per workgroup: the same pack serves the halo form and the tap-gathered one
             const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * L.ks * L.ks);
-            ws.put(n + ".w", pack_mfma_h(w, L.cout, L.cin, L.ks, 32, 2, sc));
-            net->lay[i].unscale = 1.0f / sc;
-            ws.put(n + ".b", pad_bias(b, L.cout, 64));
+            ws.put(pack_mfma_h(w, L.cout, L.cin, L.ks, 32, 2, sc), &dst.w);
+            dst.unscale = 1.0f / sc;
+            ws.put(pad_bias(b, L.cout, 64), &dst.b);
         } else {
-            ws.put(n + ".w", pack_mfma(w, L.cout, L.cin, L.ks, r2_cc_fp32(L), r2_ntb_fp32(L)));
-            ws.put(n + ".b", pad_bias(b, L.cout, 64));
+            ws.put(pack_mfma(w, L.cout, L.cin, L.ks, r2_cc_fp32(L), r2_ntb_fp32(L)), &dst.w);
+            ws.put(pad_bias(b, L.cout, 64), &dst.b);
         }
     }
     const float* cw = bl.get("clf.w", {2, 128});
@@ -172,15 +173,9 @@ int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     if (!cw || !cb || !sw || !sb) return bad("clf / sal");
     std::vector<float> hw(cw, cw + 256), hb = {cb[0], cb[1], sb[0]};
     hw.insert(hw.end(), sw, sw + 128);
-    ws.put("head.w", hw);
-    ws.put("head.b", hb);
+    ws.put(hw, &net->head_w);
+    ws.put(hb, &net->head_b);
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
-    for (int i = 0; i < 9; ++i) {
-        const std::string n = R2D2_PLAN[i].name;
-        net->lay[i].w = ws.dev(n + ".w"); net->lay[i].b = ws.dev(n + ".b");
-    }
-    net->head_w = ws.dev("head.w"); net->head_b = ws.dev("head.b");
-    if (int rc = ws.bound(ctx)) return rc;
     *out = net.release();
     return KPB_OK;
 }
