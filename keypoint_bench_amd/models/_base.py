@@ -1,5 +1,6 @@
-"""Shared torch.nn.Module-shaped surface of the HIP-backed extractor nets (model_interface.py:43-86 uses
-load_state_dict / eval / __call__)."""
+"""What every HIP-backed model object shares: `NativeOwner`, the one owner of a packed blob and the native handle(s) made from it on
+one device (the extractor nets and LightGlue), and `HipNet`, the torch.nn.Module-shaped surface of the extractor nets
+(model_interface.py:43-86 uses load_state_dict / eval / __call__)."""
 import ctypes
 
 import torch
@@ -7,24 +8,67 @@ import torch
 from .._lib import Context, c_void_p, ptr
 
 
-class HipNet:
-    ARCH = 0
-    signed_scores = False       # the score map is a raw logit (any sign): detect on it with signed=True (utils/extracter.py), as the pipelines do
+class NativeOwner:
+    """A subclass says how one handle is made (`_create`), how it goes (`_destroy`) and how many there are (`_count`)."""
+    LOAD_FIRST = "load_state_dict() / load_packed() must be called before forward"
 
     def __init__(self):
-        self._handle = None
+        self._blob = None
+        self._handle = None         # handle 0 (a c_void_p), None while nothing is created
+        self._handles = []          # all of them
         self._ctx = None
         self._device = None
-        self._blob = None
-        self._forward_count = 0
-        self.training = False
 
-    # ---- torch.nn.Module surface
     def load_packed(self, blob: bytes):
+        """Load an already packed .kpbw blob; the native side is rebuilt at the next use."""
         self._blob = bytes(blob)
         self._release()
         return self
 
+    def _create(self, ctx):
+        raise NotImplementedError
+
+    def _destroy(self, lib, handle):
+        raise NotImplementedError
+
+    def _count(self):
+        return 1
+
+    def _ensure(self, device):
+        ctx = Context.get(device)       # every call: the context follows torch's CURRENT stream (torch.cuda.stream(s))
+        if self._handle is not None and self._device == device:
+            return
+        if self._blob is None:
+            raise RuntimeError("%s: %s" % (type(self).__name__, self.LOAD_FIRST))
+        self._release()
+        self._ctx = ctx
+        for _ in range(self._count()):      # a create that fails leaves _handle None; what was made before it goes at the next _release
+            self._handles.append(self._create(ctx))
+        self._handle, self._device = self._handles[0], device
+
+    def _release(self):
+        for h in self._handles:
+            self._destroy(self._ctx.lib, h)
+        self._handle, self._handles = None, []
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+
+class HipNet(NativeOwner):
+    ARCH = 0
+    signed_scores = False       # the score map is a raw logit (any sign): detect on it with signed=True (utils/extracter.py), as the pipelines do
+    dense_descriptors = True    # forward writes the descriptor map (ALNet can be built without: the pipelines then sample inside the net)
+
+    def __init__(self):
+        super().__init__()
+        self._forward_count = 0
+        self.training = False
+
+    # ---- torch.nn.Module surface
     def eval(self):
         self.training = False
         return self
@@ -38,32 +82,16 @@ class HipNet:
     def parameters(self):
         return iter(())
 
-    def _ensure(self, device):
-        ctx = Context.get(device)       # every forward: the context follows torch's CURRENT stream (torch.cuda.stream(s))
-        if self._handle is not None and self._device == device:
-            return
-        if self._blob is None:
-            raise RuntimeError("%s: load_state_dict() / load_packed() must be called before forward" % type(self).__name__)
-        self._release()
-        self._ctx = ctx
+    def _create(self, ctx):
         h = c_void_p()
-        self._ctx.check(self._ctx.lib.kpb_net_create(self._ctx.handle, self.ARCH, self._blob, len(self._blob), ctypes.byref(h)))
-        self._handle, self._device = h, device
-        self.dim = self._ctx.lib.kpb_net_desc_dim(h)
-        self.desc_div = self._ctx.lib.kpb_net_desc_div(h)
+        ctx.check(ctx.lib.kpb_net_create(ctx.handle, self.ARCH, self._blob, len(self._blob), ctypes.byref(h)))
+        self.dim, self.desc_div = ctx.lib.kpb_net_desc_dim(h), ctx.lib.kpb_net_desc_div(h)
+        return h
 
-    def _release(self):
-        if self._handle is not None:
-            self._ctx.lib.kpb_net_destroy(self._handle)
-            self._handle = None
+    def _destroy(self, lib, handle):
+        lib.kpb_net_destroy(handle)
 
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def _run(self, image: torch.Tensor, want_desc=True):
+    def _run(self, image: torch.Tensor, want_desc=True, slot=0):
         if not image.is_cuda:
             raise RuntimeError("keypoint_bench_amd.%s needs a CUDA/HIP tensor (MI355X); there is no CPU path" % type(self).__name__)
         if image.dim() != 4 or image.shape[1] != 3:
@@ -75,7 +103,7 @@ class HipNet:
         desc = None
         if want_desc:
             desc = torch.empty((B, H // self.desc_div, W // self.desc_div, self.dim), dtype=torch.float32, device=x.device)
-        self._ctx.check(self._ctx.lib.kpb_net_forward(self._handle, ptr(x), B, H, W, ptr(score), ptr(desc)))
+        self._ctx.check(self._ctx.lib.kpb_net_forward(self._handles[slot], ptr(x), B, H, W, ptr(score), ptr(desc)))
         self._forward_count += 1
         return score, desc
 

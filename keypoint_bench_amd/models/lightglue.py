@@ -11,13 +11,15 @@ import os
 import torch
 
 from .. import weights as _weights
-from .._lib import Context, LgParams, c_void_p, ptr
+from .._lib import LgParams, c_void_p, ptr
+from ._base import NativeOwner
 
 _FEATURES = {"superpoint": dict(weights="superpoint_lightglue", input_dim=256, desc_scale=8),     # lightglue.py:361-385, 405-408
              "disk": dict(weights="disk_lightglue", input_dim=128, desc_scale=1)}
 
 
-class LightGlue:
+class LightGlue(NativeOwner):
+    LOAD_FIRST = "load_state_dict() must be called first"
     default_conf = dict(depth_confidence=0.95, width_confidence=0.99, filter_threshold=0.1)       # lightglue.py:335-348
 
     def __init__(self, features="superpoint", weight_path="", desc_scale=None, prune_min_kpts=-1, attention="fp32", **conf):
@@ -31,10 +33,7 @@ class LightGlue:
         self.conf = dict(self.default_conf, **{k: v for k, v in conf.items() if k in self.default_conf})
         self.prune_min_kpts = int(prune_min_kpts)
         self.desc_scale = desc_scale
-        self._blob = None
-        self._handle = None
-        self._ctx = None
-        self._device = None
+        super().__init__()
         if features is not None:
             f = _FEATURES[features]
             self.desc_scale = f["desc_scale"]
@@ -42,8 +41,7 @@ class LightGlue:
             self.load_state_dict(torch.load(path, map_location="cpu"))
 
     def load_state_dict(self, state_dict, strict=False):
-        self._blob = _weights.pack(_weights.tensors_lightglue(state_dict), _weights.ARCH_LIGHTGLUE)
-        self._release()
+        self.load_packed(_weights.pack(_weights.tensors_lightglue(state_dict), _weights.ARCH_LIGHTGLUE))
         return "<All keys matched successfully>"
 
     def eval(self):
@@ -52,32 +50,17 @@ class LightGlue:
     def to(self, *a, **k):
         return self
 
-    def _release(self):
-        if self._handle is not None:
-            self._ctx.lib.kpb_lg_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def _ensure(self, device):
-        ctx = Context.get(device)       # follow torch's current stream on every call
-        if self._handle is not None and self._device == device:
-            return
-        if self._blob is None:
-            raise RuntimeError("LightGlue: load_state_dict() must be called first")
+    def _create(self, ctx):
         if self.desc_scale is None:
             raise RuntimeError("LightGlue(features=None): set desc_scale (8 for SuperPoint maps, 1 for DISK)")
-        self._release()
-        self._ctx = ctx
         h = c_void_p()
-        self._ctx.check(self._ctx.lib.kpb_lg_create(self._ctx.handle, self._blob, len(self._blob), float(self.desc_scale), ctypes.byref(h)))
-        self._handle, self._device = h, device
+        ctx.check(ctx.lib.kpb_lg_create(ctx.handle, self._blob, len(self._blob), float(self.desc_scale), ctypes.byref(h)))
         if self.attention == "f16":
-            self._ctx.check(self._ctx.lib.kpb_lg_set_attention(h, 1))
+            ctx.check(ctx.lib.kpb_lg_set_attention(h, 1))
+        return h
+
+    def _destroy(self, lib, handle):
+        lib.kpb_lg_destroy(handle)
 
     def match_indices(self, pts0, pts1, desc_map_0, desc_map_1, params):
         """Returns (pairs [K,2] int64, scores [K] float32, layers_run)."""

@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from ._lib import Context, DetectParams, MatchParams, ptr
+from ._lib import Context, DetectParams, LgParams, MatchParams, ptr
 
 
 PLACE_MIN_BYTES = 4 << 30       # descriptor maps below this are not worth placing (their forward is not bound by the map's stores)
@@ -19,16 +19,12 @@ PLACE_CANDIDATES = 4            # allocations compared (the first included), as 
 PLACE_HEADROOM = 12 << 30       # bytes that must stay free while the candidates exist (workspaces of the first forward, the caller's tensors)
 
 
-class PairPipeline:
-    def __init__(self, net, extractor_params, brute_force_params, batch, H, W, device="cuda:0", lightglue=None, match=True, place_map=None):
-        """match=False stops after detection (the repeatability task never matches: tasks/repeatability.py:95-122).
-        place_map: choose WHERE the dense descriptor map lives by measurement at the first run (`_place_map`); None = on unless
-        KPB_PLACE_MAP=0 (a host-side knob of this class: the library allocates nothing of the caller's)."""
-        import os
-        self.place_map = (os.environ.get("KPB_PLACE_MAP", "1") != "0") if place_map is None else bool(place_map)
-        self.placement = None       # the record of that choice (bench.py prints it in config.placement)
-        self.net, self.B, self.H, self.W = net, int(batch), int(H), int(W)
-        self.match = bool(match)
+class _Core:
+    """What the two pipelines share: the parameters, the facts of the net, the buffer set, and the three stages as methods over tensor
+    views and an image count.  The pipelines differ in slot layout only: [2B] split at B, against [F+1] shifted by one."""
+
+    def __init__(self, net, extractor_params, brute_force_params, H, W, device):
+        self.net, self.H, self.W = net, int(H), int(W)
         self.device = torch.device(device)
         self.ctx = Context.get(self.device)
         ep, bf = extractor_params, brute_force_params
@@ -39,24 +35,74 @@ class PairPipeline:
                                  float(ep["min_score"]))
         self.mprm = MatchParams(float(bf["max_distance"]), 1 if bf["cross_check"] else 0)
         net._ensure(self.device)
-        self.dense = getattr(net, "dense_descriptors", True)
-        self.div = getattr(net, "desc_div", 1)
-        B2, K, C = 2 * self.B, self.top_k, (net.param["dim"] if hasattr(net, "param") else net.dim)
-        dev = self.device
-        f32, i32 = torch.float32, torch.int32
-        self.score = torch.empty((B2, 1, H, W), dtype=f32, device=dev)
+        self.dense, self.div, self.C = net.dense_descriptors, net.desc_div, net.dim
         self.Hd, self.Wd = H // self.div, W // self.div
-        self.desc = torch.empty((B2, self.Hd, self.Wd, C), dtype=f32, device=dev) if self.dense else None
-        self.kps = torch.empty((B2, K, 3), dtype=f32, device=dev)
-        self.idx = torch.empty((B2, K), dtype=i32, device=dev)
-        self.n = torch.empty((B2,), dtype=i32, device=dev)
-        self.sdesc = torch.empty((B2, K, C), dtype=f32, device=dev)
-        self.pairs = torch.empty((self.B, K, 2), dtype=i32, device=dev)
-        self.dist = torch.empty((self.B, K), dtype=torch.float64, device=dev)
-        self.k = torch.empty((self.B,), dtype=i32, device=dev)
-        self.m0 = torch.empty((self.B, K, 3), dtype=f32, device=dev)
-        self.m1 = torch.empty((self.B, K, 3), dtype=f32, device=dev)
-        self.C = C
+        self.lg = None
+
+    def _buffers(self, images, slots, pairs, carried):
+        """images per forward, keypoint slots, pairs per match; `carried` (torch.empty or torch.zeros) makes what a slot carries over."""
+        K, C, H, W = self.top_k, self.C, self.H, self.W
+        dev, f32, i32 = self.device, torch.float32, torch.int32
+        self.score = torch.empty((images, 1, H, W), dtype=f32, device=dev)
+        self.desc = torch.empty((images, self.Hd, self.Wd, C), dtype=f32, device=dev) if self.dense else None
+        self.kps = carried((slots, K, 3), dtype=f32, device=dev)
+        self.idx = torch.empty((slots, K), dtype=i32, device=dev)
+        self.n = carried((slots,), dtype=i32, device=dev)
+        self.sdesc = carried((slots, K, C), dtype=f32, device=dev)
+        self.pairs = torch.empty((pairs, K, 2), dtype=i32, device=dev)
+        self.dist = torch.empty((pairs, K), dtype=torch.float64, device=dev)
+        self.k = carried((pairs,), dtype=i32, device=dev)
+        self.m0 = torch.empty((pairs, K, 3), dtype=f32, device=dev)
+        self.m1 = torch.empty((pairs, K, 3), dtype=f32, device=dev)
+
+    def _extract(self, images, count, kps, idx, n, sync):
+        """Net forward on `count` images, then detection on their score maps into the slot views kps / idx / n."""
+        ctx, L, net = self.ctx, self.ctx.lib, self.net
+        ctx.check(L.kpb_net_forward(net._handle, ptr(images), count, self.H, self.W, ptr(self.score), ptr(self.desc)))
+        net._forward_count += 1
+        with ctx.detect_signed(net.signed_scores):      # a pending detection (sync=0) keeps the setting until kpb_detect_check
+            ctx.check(L.kpb_detect(ctx.handle, ptr(self.score), count, self.H, self.W, ctypes.byref(self.dprm), ptr(kps), ptr(idx), ptr(n), sync))
+
+    def _describe(self, count, pts, cols, n, sdesc):
+        """Descriptors at the points of `count` images: utils/matcher.py:221-226 on the dense map (channels-last strides), or inside the net."""
+        ctx, L, K, C, Hd, Wd = self.ctx, self.ctx.lib, self.top_k, self.C, self.Hd, self.Wd
+        if self.desc is not None:
+            ctx.check(L.kpb_sample(ctx.handle, ptr(self.desc), count, C, Hd, Wd, Hd * Wd * C, 1, Wd * C, C, ptr(pts), cols, K, ptr(n), ptr(sdesc)))
+        else:
+            ctx.check(L.kpb_net_desc_at(self.net._handle, ptr(pts), cols, K, ptr(n), ptr(sdesc)))
+
+    def _match(self, count, second, pts, cols, n, m0, m1):
+        """Pair j = (slot j, slot second + j) for j < count: mutual brute-force match of the sampled descriptors, or LightGlue where one is
+        attached (FundamentalMatrix.py:132-133 / visual_odometer.py:60-61: matcher.match(kps0, kps1, desc0, desc1, {'w','h'})), then the
+        matched rows of `pts` into m0 / m1."""
+        ctx, L, K, C = self.ctx, self.ctx.lib, self.top_k, self.C
+        if self.lg is not None:
+            lg, Hd, Wd = self.lg, self.Hd, self.Wd
+            if cols != 3:
+                raise NotImplementedError("LightGlue consumes (x, y, score) rows (lightglue.py:451-452)")
+            prm = LgParams(float(lg.conf["depth_confidence"]), float(lg.conf["width_confidence"]), float(lg.conf["filter_threshold"]),
+                           lg.prune_min_kpts)
+            ctx.check(L.kpb_lg_match(lg._handle, ptr(pts), ptr(pts[second:]), ptr(n), ptr(n[second:]), count, K,
+                                     ptr(self.desc), ptr(self.desc[second:]), C, Hd, Wd, Hd * Wd * C, 1, Wd * C, C, self.W, self.H,
+                                     ctypes.byref(prm), ptr(self.pairs), ptr(self.lg_scores), ptr(self.k), ptr(self.lg_stop)))
+        else:
+            ctx.check(L.kpb_match(ctx.handle, ptr(self.sdesc), ptr(self.sdesc[second:]), count, C, K, K, ptr(n), ptr(n[second:]),
+                                  ctypes.byref(self.mprm), ptr(self.pairs), ptr(self.dist), ptr(self.k)))
+        ctx.check(L.kpb_gather_rows(ctx.handle, ptr(pts), count, K, cols, ptr(self.pairs), K, 2, 0, ptr(self.k), ptr(m0)))
+        ctx.check(L.kpb_gather_rows(ctx.handle, ptr(pts[second:]), count, K, cols, ptr(self.pairs), K, 2, 1, ptr(self.k), ptr(m1)))
+
+
+class PairPipeline(_Core):
+    def __init__(self, net, extractor_params, brute_force_params, batch, H, W, device="cuda:0", lightglue=None, match=True, place_map=None):
+        """match=False stops after detection (the repeatability task never matches: tasks/repeatability.py:95-122).
+        place_map: choose WHERE the dense descriptor map lives by measurement at the first run (`_place_map`); None = on unless
+        KPB_PLACE_MAP=0 (a host-side knob of this class: the library allocates nothing of the caller's)."""
+        import os
+        self.place_map = (os.environ.get("KPB_PLACE_MAP", "1") != "0") if place_map is None else bool(place_map)
+        self.placement = None       # the record of that choice (bench.py prints it in config.placement)
+        super().__init__(net, extractor_params, brute_force_params, H, W, device)
+        self.B, self.match = int(batch), bool(match)
+        self._buffers(2 * self.B, 2 * self.B, self.B, torch.empty)
         self.reruns = 0
         self._covis, self.cov, self.m0c, self.m1c = None, None, None, None
         self.lg = lightglue          # a keypoint_bench_amd.models.lightglue.LightGlue: replaces the brute-force matcher
@@ -64,9 +110,8 @@ class PairPipeline:
             if self.desc is None:
                 raise ValueError("the LightGlue matcher samples the dense descriptor map")
             self.lg._ensure(self.device)
-            self.lg_scores = torch.empty((self.B, K), dtype=f32, device=dev)
-            self.lg_stop = torch.empty((self.B,), dtype=i32, device=dev)
-        net._ensure(self.device)
+            self.lg_scores = torch.empty((self.B, self.top_k), dtype=torch.float32, device=self.device)
+            self.lg_stop = torch.empty((self.B,), dtype=torch.int32, device=self.device)
 
     def _place_map(self, images):
         """Where the descriptor map's pages are decides how fast the dense head stores it -- a property of the ALLOCATION, found in r06
@@ -122,17 +167,12 @@ class PairPipeline:
         covisibility warp (rows 0..B-1 with warp01, rows B..2B-1 with warp10) BEFORE sampling and matching, and the
         matcher sees the surviving (x, y) rows only."""
         self.ctx = Context.get(self.device)      # follows torch's current stream
-        ctx, L, net = self.ctx, self.ctx.lib, self.net
-        B, B2, K, C, H, W = self.B, 2 * self.B, self.top_k, self.C, self.H, self.W
-        assert images.shape == (B2, 3, H, W) and images.is_contiguous() and images.dtype == torch.float32
+        B2 = 2 * self.B
+        assert images.shape == (B2, 3, self.H, self.W) and images.is_contiguous() and images.dtype == torch.float32
         self._covis = covis
         if self.place_map:
             self._place_map(images)
-        ctx.check(L.kpb_net_forward(net._handle, ptr(images), B2, H, W, ptr(self.score), ptr(self.desc)))
-        net._forward_count += 1
-        with ctx.detect_signed(getattr(net, "signed_scores", False)):      # the pending detection keeps the setting until kpb_detect_check
-            ctx.check(L.kpb_detect(ctx.handle, ptr(self.score), B2, H, W, ctypes.byref(self.dprm), ptr(self.kps),
-                                   ptr(self.idx), ptr(self.n), 0))
+        self._extract(images, B2, self.kps, self.idx, self.n, 0)
         self._enqueue_match()
 
     def _enqueue_covis(self):
@@ -152,34 +192,15 @@ class PairPipeline:
             self._enqueue_covis()
         if not self.match:
             return
-        ctx, L, net = self.ctx, self.ctx.lib, self.net
-        B, B2, K, C, H, W = self.B, 2 * self.B, self.top_k, self.C, self.H, self.W
+        B, K = self.B, self.top_k
         pts, cols, n = (self.kps, 3, self.n) if self._covis is None else (self.cov["k0"], 2, self.cov["n"])
         if cols == 2 and self.m0c is None:
             self.m0c = torch.empty((B, K, 2), dtype=torch.float32, device=self.device)
             self.m1c = torch.empty((B, K, 2), dtype=torch.float32, device=self.device)
         m0, m1 = (self.m0, self.m1) if cols == 3 else (self.m0c, self.m1c)
-        if self.lg is not None:     # FundamentalMatrix.py:132-133 / visual_odometer.py:60-61: matcher.match(kps0, kps1, desc0, desc1, {'w','h'})
-            from ._lib import LgParams
-            lg, Hd, Wd = self.lg, self.Hd, self.Wd
-            if cols != 3:
-                raise NotImplementedError("LightGlue consumes (x, y, score) rows (lightglue.py:451-452)")
-            prm = LgParams(float(lg.conf["depth_confidence"]), float(lg.conf["width_confidence"]), float(lg.conf["filter_threshold"]),
-                           lg.prune_min_kpts)
-            ctx.check(L.kpb_lg_match(lg._handle, ptr(self.kps[:B]), ptr(self.kps[B:]), ptr(self.n[:B]), ptr(self.n[B:]), B, K,
-                                     ptr(self.desc[:B]), ptr(self.desc[B:]), C, Hd, Wd, Hd * Wd * C, 1, Wd * C, C, W, H, ctypes.byref(prm),
-                                     ptr(self.pairs), ptr(self.lg_scores), ptr(self.k), ptr(self.lg_stop)))
-        else:
-            if self.desc is not None:   # utils/matcher.py:221-226 on the dense map (channels-last strides)
-                Hd, Wd = self.Hd, self.Wd
-                ctx.check(L.kpb_sample(ctx.handle, ptr(self.desc), B2, C, Hd, Wd, Hd * Wd * C, 1, Wd * C, C, ptr(pts), cols, K,
-                                       ptr(n), ptr(self.sdesc)))
-            else:
-                ctx.check(L.kpb_net_desc_at(net._handle, ptr(pts), cols, K, ptr(n), ptr(self.sdesc)))
-            ctx.check(L.kpb_match(ctx.handle, ptr(self.sdesc[:B]), ptr(self.sdesc[B:]), B, C, K, K, ptr(n[:B]), ptr(n[B:]),
-                                  ctypes.byref(self.mprm), ptr(self.pairs), ptr(self.dist), ptr(self.k)))
-        ctx.check(L.kpb_gather_rows(ctx.handle, ptr(pts[:B]), B, K, cols, ptr(self.pairs), K, 2, 0, ptr(self.k), ptr(m0)))
-        ctx.check(L.kpb_gather_rows(ctx.handle, ptr(pts[B:]), B, K, cols, ptr(self.pairs), K, 2, 1, ptr(self.k), ptr(m1)))
+        if self.lg is None:
+            self._describe(2 * B, pts, cols, n, self.sdesc)
+        self._match(B, B, pts, cols, n, m0, m1)
 
     def finish(self):
         """Sync; re-runs NMS sweeps + everything downstream for the (rare) batch that had not converged."""
@@ -209,7 +230,7 @@ class PairPipeline:
                     m0=self.m0[b, :k].cpu().numpy(), m1=self.m1[b, :k].cpu().numpy())
 
 
-class SequencePipeline:
+class SequencePipeline(_Core):
     """Frames of one sequence dataset (model_interface.py:217-228): result i pairs frame i-1 with frame i, and the first
     frame with itself (`last_batch` starts as the batch).  The reference runs the net on the previous frame again for
     every step; here every frame goes through net -> detection -> descriptors-at-keypoints ONCE, and pair i matches
@@ -217,32 +238,9 @@ class SequencePipeline:
     pointers, so the shift is a pointer offset).  Slot 0 carries the last frame of the previous chunk."""
 
     def __init__(self, net, extractor_params, brute_force_params, frames, H, W, device="cuda:0"):
-        self.net, self.F, self.H, self.W = net, int(frames), int(H), int(W)
-        self.device = torch.device(device)
-        self.ctx = Context.get(self.device)
-        ep, bf = extractor_params, brute_force_params
-        if bf.get("metric", "euclidean") != "euclidean":
-            raise NotImplementedError("only metric='euclidean'")
-        self.top_k = min(int(ep["top_k"]), H * W)
-        self.dprm = DetectParams(int(ep["nms_dist"]), float(ep["threshold"]), int(ep["border_dist"]), self.top_k, float(ep["min_score"]))
-        self.mprm = MatchParams(float(bf["max_distance"]), 1 if bf["cross_check"] else 0)
-        net._ensure(self.device)
-        self.dense = getattr(net, "dense_descriptors", True)
-        self.div = getattr(net, "desc_div", 1)
-        F, K, C = self.F, self.top_k, (net.param["dim"] if hasattr(net, "param") else net.dim)
-        dev, f32, i32 = self.device, torch.float32, torch.int32
-        self.C, self.Hd, self.Wd = C, H // self.div, W // self.div
-        self.score = torch.empty((F, 1, H, W), dtype=f32, device=dev)
-        self.desc = torch.empty((F, self.Hd, self.Wd, C), dtype=f32, device=dev) if self.dense else None
-        self.kps = torch.zeros((F + 1, K, 3), dtype=f32, device=dev)
-        self.idx = torch.empty((F + 1, K), dtype=i32, device=dev)
-        self.n = torch.zeros((F + 1,), dtype=i32, device=dev)
-        self.sdesc = torch.zeros((F + 1, K, C), dtype=f32, device=dev)
-        self.pairs = torch.empty((F, K, 2), dtype=i32, device=dev)
-        self.dist = torch.empty((F, K), dtype=torch.float64, device=dev)
-        self.k = torch.zeros((F,), dtype=i32, device=dev)
-        self.m0 = torch.empty((F, K, 3), dtype=f32, device=dev)
-        self.m1 = torch.empty((F, K, 3), dtype=f32, device=dev)
+        super().__init__(net, extractor_params, brute_force_params, H, W, device)
+        self.F = int(frames)
+        self._buffers(self.F, self.F + 1, self.F, torch.zeros)      # slot 0 is read before it is ever written
         self._last = None       # slot that holds the newest frame of the previous chunk
 
     def run(self, images, first):
@@ -250,34 +248,20 @@ class SequencePipeline:
         (otherwise the previous call -- or `prime` -- supplied the frame before images[0]).  Leaves pair j =
         (frame before images[j], images[j]) in pairs/dist/k/m0/m1[j]."""
         self.ctx = Context.get(self.device)      # follows torch's current stream
-        ctx, L, net = self.ctx, self.ctx.lib, self.net
-        K, C, H, W = self.top_k, self.C, self.H, self.W
         f = images.shape[0]
-        assert 0 < f <= self.F and images.shape[1:] == (3, H, W) and images.is_contiguous() and images.dtype == torch.float32
+        assert 0 < f <= self.F and images.shape[1:] == (3, self.H, self.W) and images.is_contiguous() and images.dtype == torch.float32
         if not first:
             if self._last is None:
                 raise RuntimeError("SequencePipeline.run(first=False) needs the previous frame: call prime() or run() first")
             if self._last != 0:
                 for t in (self.kps, self.n, self.sdesc):
                     t[0].copy_(t[self._last])
-        ctx.check(L.kpb_net_forward(net._handle, ptr(images), f, H, W, ptr(self.score), ptr(self.desc)))
-        net._forward_count += 1
-        with ctx.detect_signed(getattr(net, "signed_scores", False)):
-            ctx.check(L.kpb_detect(ctx.handle, ptr(self.score), f, H, W, ctypes.byref(self.dprm), ptr(self.kps[1:]), ptr(self.idx[1:]),
-                                   ptr(self.n[1:]), 1))
-        if self.desc is not None:
-            Hd, Wd = self.Hd, self.Wd
-            ctx.check(L.kpb_sample(ctx.handle, ptr(self.desc), f, C, Hd, Wd, Hd * Wd * C, 1, Wd * C, C, ptr(self.kps[1:]), 3, K,
-                                   ptr(self.n[1:]), ptr(self.sdesc[1:])))
-        else:
-            ctx.check(L.kpb_net_desc_at(net._handle, ptr(self.kps[1:]), 3, K, ptr(self.n[1:]), ptr(self.sdesc[1:])))
+        self._extract(images, f, self.kps[1:], self.idx[1:], self.n[1:], 1)
+        self._describe(f, self.kps[1:], 3, self.n[1:], self.sdesc[1:])
         if first:
             for t in (self.kps, self.n, self.sdesc):
                 t[0].copy_(t[1])
-        ctx.check(L.kpb_match(ctx.handle, ptr(self.sdesc), ptr(self.sdesc[1:]), f, C, K, K, ptr(self.n), ptr(self.n[1:]),
-                              ctypes.byref(self.mprm), ptr(self.pairs), ptr(self.dist), ptr(self.k)))
-        ctx.check(L.kpb_gather_rows(ctx.handle, ptr(self.kps), f, K, 3, ptr(self.pairs), K, 2, 0, ptr(self.k), ptr(self.m0)))
-        ctx.check(L.kpb_gather_rows(ctx.handle, ptr(self.kps[1:]), f, K, 3, ptr(self.pairs), K, 2, 1, ptr(self.k), ptr(self.m1)))
+        self._match(f, 1, self.kps, 3, self.n, self.m0, self.m1)
         self._last = f
         return self
 

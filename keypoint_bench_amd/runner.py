@@ -39,48 +39,41 @@ def load_config(path):
     return params
 
 
+_NOT_SHIPPED = " (it is not shipped with the reference tree either)"
+# model_type -> (module under models/, constructor from (module, its params, dense_descriptors), params key, sub-key of the checkpoint that holds
+# the state dict, what follows "checkpoint %r not found").  No constructor: the checkpoint names its own (model_interface.py:69-73, from_checkpoint).
+# No text: the checkpoint shipped with the package (folded from the reference's weights/alike-t.pth) stands in for a missing file.
+_MODELS = {"Alike": ("ALike", lambda m, p, dense: m.ALNet(p, dense_descriptors=dense), "Alike_params", None, None),
+           "SuperPoint": ("SuperPoint", lambda m, p, dense: m.SuperPointNet(), "SuperPoint_params", None, _NOT_SHIPPED),
+           "XFeat": ("XFeat", lambda m, p, dense: m.XFeatModel(), "XFeat_params", None, _NOT_SHIPPED),
+           "DISK": ("disk", lambda m, p, dense: m.DISK(), "DISK_params", "extractor", _NOT_SHIPPED),
+           "r2d2": ("r2d2", None, "r2d2_params", None, ""),
+           "EdgePoint": ("EdgePoint", lambda m, p, dense: m.EdgePoint(p), "EdgePoint_params", None, "")}
+
+
 def build_model(params, dense_descriptors=True):
-    """model_interface.py:43-86 for the model types this package carries kernels for."""
+    """model_interface.py:43-86 for the model types this package carries kernels for: construct, find the checkpoint or refuse,
+    load_state_dict, eval."""
+    import importlib
     mt = params["model_type"]
-    if mt == "Alike":
-        from .models.ALike import ALNet
-        net = ALNet(params["Alike_params"], dense_descriptors=dense_descriptors)
-        w = params["Alike_params"].get("weight")
-        if w and os.path.exists(w):
-            net.load_state_dict(torch.load(w, map_location="cpu"))
-        else:   # the checkpoint shipped with the package (folded from the reference's weights/alike-t.pth)
-            here = os.path.dirname(os.path.abspath(__file__))
-            with open(os.path.join(here, "weights", "alike-t.kpbw"), "rb") as f:
-                net.load_packed(f.read())
-        return net.eval()
-    builders = {"SuperPoint": ("SuperPoint", "SuperPointNet", "SuperPoint_params", None),
-                "XFeat": ("XFeat", "XFeatModel", "XFeat_params", None),
-                "DISK": ("disk", "DISK", "DISK_params", "extractor")}
-    if mt in builders:   # model_interface.py:59-63, 67-69, 76-81
-        import importlib
-        mod, cls, pkey, sub = builders[mt]
-        net = getattr(importlib.import_module("keypoint_bench_amd.models." + mod), cls)()
-        w = (params.get(pkey) or {}).get("weight")
-        if not (w and os.path.exists(w)):
-            raise FileNotFoundError("%s checkpoint %r not found (it is not shipped with the reference tree either)" % (mt, w))
+    if mt not in _MODELS:
+        raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint)" % (mt,))
+    mod, make, pkey, sub, missing = _MODELS[mt]
+    mod = importlib.import_module("keypoint_bench_amd.models." + mod)
+    p = params.get(pkey) or {}
+    net = make(mod, p, dense_descriptors) if make else None
+    w = p.get("weight")
+    if w and os.path.exists(w):
         sd = torch.load(w, map_location="cpu")
-        net.load_state_dict(sd[sub] if sub else sd)
-        return net.eval()
-    if mt == "r2d2":     # model_interface.py:69-73: the checkpoint names its own constructor
-        from .models.r2d2 import from_checkpoint
-        w = (params.get("r2d2_params") or {}).get("weight")
-        if not (w and os.path.exists(w)):
-            raise FileNotFoundError("r2d2 checkpoint %r not found" % (w,))
-        return from_checkpoint(torch.load(w, map_location="cpu"))
-    if mt == "EdgePoint":    # model_interface.py:46-48
-        from .models.EdgePoint import EdgePoint
-        net = EdgePoint(params["EdgePoint_params"])
-        w = params["EdgePoint_params"].get("weight")
-        if not (w and os.path.exists(w)):
-            raise FileNotFoundError("EdgePoint checkpoint %r not found" % (w,))
-        net.load_state_dict(torch.load(w, map_location="cpu"))
-        return net.eval()
-    raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint)" % (mt,))
+        if net is None:
+            net = mod.from_checkpoint(sd)
+        else:
+            net.load_state_dict(sd[sub] if sub else sd)
+    elif missing is None:
+        net.load_packed(mod.packaged_blob())
+    else:
+        raise FileNotFoundError("%s checkpoint %r not found%s" % (mt, w, missing))
+    return net.eval()
 
 
 # ------------------------------------------------------------------------------------------ sharding
