@@ -198,7 +198,12 @@ int kpb_val_keypoints(kpb_ctx* ctx, const float* k0_dev, const float* k01_dev, c
  * unit_dev [n][2] = (cos, sin) of the random start angles the reference draws (matcher.py:55-56; the
  * caller draws them so that runs are reproducible).  Pyramid of `levels` (avg-pool 2i), `iterations`
  * Gauss-Newton steps per level on a win_size x win_size x C window.  out_pts_dev [n][2] in PIXELS of the
- * full image, as the reference returns them; out_err_dev [n] = min(|out - pts2|, 8). */
+ * full image, as the reference returns them; out_err_dev [n] = min(|out - pts2|, 8).  Rows past n are not written; n == 0
+ * returns KPB_OK without touching the point and output buffers.
+ * Limits: C >= 1, H > 20 and W > 20 (the start is clamped to [10, W-10] x [10, H-10]), pts_stride >= 2 (one stride for both point
+ * arrays), n >= 0, no null image or params pointer: KPB_E_INVALID otherwise.  win_size odd and in 1..31, levels in 1..4,
+ * iterations >= 0, and C * win_size^2 <= 4096 (a workgroup keeps the image-1 patches of its four keypoints in 64 KB of LDS):
+ * KPB_E_UNSUPPORTED otherwise. */
 typedef struct kpb_lk_params {
     float distance;
     int32_t win_size, levels, iterations;

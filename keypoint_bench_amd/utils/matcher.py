@@ -110,9 +110,14 @@ class OpticalFlow(object):
         dev = img1.device
         a = img1.detach().to(torch.float32).contiguous()
         b = img2.detach().to(torch.float32).contiguous()
-        p1 = pts1.detach().to(torch.float32).contiguous()
-        p2 = pts2.detach().to(torch.float32).contiguous()
+        if pts1.shape[-1] < 2 or pts2.shape[-1] < 2:
+            raise ValueError("points need (x, y) columns")
+        # the kernel takes one stride for both arrays: hand it the (x, y) columns of each, whatever else the rows carry
+        p1 = pts1.detach()[:, :2].to(torch.float32).contiguous()
+        p2 = pts2.detach()[:, :2].to(torch.float32).contiguous()
         n = p1.shape[0]
+        if p2.shape[0] != n:
+            raise ValueError("pts1 and pts2 must have one row per track")
         if random_angle is None:
             random_angle = torch.randn(n, device=dev) * 6.28                                             # 55
         unit = torch.stack([torch.cos(random_angle), torch.sin(random_angle)], dim=1).to(torch.float32).contiguous()   # 56
@@ -121,7 +126,7 @@ class OpticalFlow(object):
         if n:
             ctx = Context.get(dev)
             prm = LkParams(float(self.distance), int(self.win_size), int(self.levels), int(self.interation))
-            ctx.check(ctx.lib.kpb_lk_track(ctx.handle, ptr(a), ptr(b), C, H, W, ptr(p1), ptr(p2), p1.shape[1], ptr(unit), n,
+            ctx.check(ctx.lib.kpb_lk_track(ctx.handle, ptr(a), ptr(b), C, H, W, ptr(p1), ptr(p2), 2, ptr(unit), n,
                                            ctypes.byref(prm), ptr(out), ptr(err)))
         return out.unsqueeze(0), err.unsqueeze(0)
 

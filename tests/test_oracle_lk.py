@@ -30,3 +30,60 @@ def test_lk_oracle_matches_reference(c):
     np.testing.assert_allclose(out, want, rtol=0, atol=LK_ATOL_PX)
     np.testing.assert_allclose(err, want_err, rtol=0, atol=LK_ATOL_PX)
     assert (np.abs(out - want).max(1) == 0).mean() > 0.5        # most tracks are bit-identical
+
+
+# ---- the edges: fixtures of tests/golden/make_golden_lk_edges.py (whole [0,1]^2 with the corners, pts1 != pts2, image sizes the
+# pooling does not divide, four levels, gray).  `stable` marks the tracks the reference reproduces itself (within 2e-5 px) when
+# image 2 moves by one ulp; only those can be compared, and at most 5 % of a case may be anything else.
+GE = np.load(os.path.join(os.path.dirname(__file__), "golden", "lk_edges.npz"))
+EDGE_CASES = [str(s) for s in GE["names"]]
+UNSTABLE_CAP_PERCENT = 5
+
+
+def lk_edge_case(name):
+    """(v0, v1, pts1, pts2, unit, params, reference out, reference err, stable) of one case of lk_edges.npz."""
+    k = name + "_"
+    seed, H, W = (int(v) for v in GE[k + "image_pair"])
+    v0, v1 = synthetic.image_pair(seed, H, W)
+    gray = bool(GE[k + "gray"])
+    if gray:
+        v0, v1 = v0.mean(0, keepdims=True).astype(np.float32), v1.mean(0, keepdims=True).astype(np.float32)
+    d, w, l, it = (int(v) for v in GE[k + "prm"])
+    stable = GE[k + "stable"]
+    assert 100 * int((~stable).sum()) <= UNSTABLE_CAP_PERCENT * len(stable), (name, int((~stable).sum()))
+    return (v0, v1, GE[k + "pts1"], GE[k + "pts2"], GE[k + "unit"], dict(distance=d, win_size=w, levels=l, interation=it, gray=gray),
+            GE[k + "out"], GE[k + "err"], stable)
+
+
+def test_lk_edge_fixture_is_what_the_tests_assume():
+    assert EDGE_CASES == ["E%d" % i for i in range(7)]
+    for name in EDGE_CASES:
+        v0, _, pts1, pts2, unit, prm, want, _, stable = lk_edge_case(name)
+        assert len(pts1) == 200 and pts1.shape == pts2.shape == unit.shape == want.shape == (200, 2) and stable.shape == (200,)
+        assert v0.shape[0] == (1 if prm["gray"] else 3)
+        np.testing.assert_array_equal(pts1[:4], [(0, 0), (1, 1), (0, 1), (1, 0)])
+        assert pts1.min() >= 0 and pts1.max() <= 1 and pts2.min() >= 0 and pts2.max() <= 1
+        assert (np.abs(pts1 - pts2).max(1) > 0)[4:].all()          # (a corner may clip back onto itself)
+    # E1: the start clamp works on all four sides
+    _, _, _, pts2, unit, prm, _, _, _ = lk_edge_case("E1")
+    start = pts2 * np.array([95, 63], np.float32) + unit * np.float32(prm["distance"])
+    assert (start[:, 0] < 10).any() and (start[:, 0] > 86).any() and (start[:, 1] < 10).any() and (start[:, 1] > 54).any()
+
+
+@pytest.mark.parametrize("name", EDGE_CASES)
+def test_lk_oracle_matches_reference_at_the_edges(name):
+    v0, v1, pts1, pts2, unit, prm, want, want_err, stable = lk_edge_case(name)
+    out, err = oracle.lk_track(v0, v1, pts1, pts2, unit, prm["distance"], prm["win_size"], prm["levels"], prm["interation"])
+    print(name, "oracle vs reference on stable points: %.3g px (err %.3g)" % (np.abs(out - want)[stable].max(), np.abs(err - want_err)[stable].max()))
+    np.testing.assert_allclose(out[stable], want[stable], rtol=0, atol=LK_ATOL_PX)
+    np.testing.assert_allclose(err[stable], want_err[stable], rtol=0, atol=LK_ATOL_PX)
+
+
+@pytest.mark.parametrize("name", EDGE_CASES)
+def test_lk_edge_case_tells_pts1_from_pts2(name):
+    """Negative control on the data: a tracker that cut the image-1 patch at pts2 would move more than half the tracks."""
+    v0, v1, pts1, pts2, unit, prm, _, _, _ = lk_edge_case(name)
+    args = (unit, prm["distance"], prm["win_size"], prm["levels"], prm["interation"])
+    out, _ = oracle.lk_track(v0, v1, pts1, pts2, *args)
+    swapped, _ = oracle.lk_track(v0, v1, pts2, pts2, *args)
+    assert (np.abs(out - swapped).max(1) > 1e-3).mean() > 0.5
