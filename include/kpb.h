@@ -212,6 +212,23 @@ int kpb_lk_track(kpb_ctx* ctx, const float* img1_dev, const float* img2_dev, int
                  const float* pts1_dev, const float* pts2_dev, int pts_stride, const float* unit_dev,
                  int n, const kpb_lk_params* params, float* out_pts_dev, float* out_err_dev);
 
+/* The tracker for `batch` pairs in one call, on maps of any strides.  Pair j tracks from map1_dev + j sb into map2_dev + j sb; sb, sc, sh, sw are ELEMENT
+ * strides as kpb_sample takes them (planar: sc = H W, sh = W, sw = 1; channels-last: sc = 1, sh = W C, sw = C), so a net's descriptor map is tracked where
+ * it lies.  The two pointers may overlap: a sequence of batch + 1 consecutive maps passes map2_dev = map1_dev + sb.  pts1_dev / pts2_dev
+ * [batch][max_n][pts_stride] (they may be one buffer), unit_dev [batch][max_n][2], n_dev [batch] on the device or NULL (= max_n; read on the device, no
+ * host synchronisation; values are held to 0 .. max_n).  out_pts_dev [batch][max_n][2] in pixels, out_err_dev [batch][max_n].  Rows past n[j] are not
+ * written; a pair with n[j] == 0 writes nothing.
+ * Contract: every pair's rows equal, bit for bit, what kpb_lk_track returns for that pair's maps made planar-contiguous with the same points, units and
+ * parameters -- both entries run the same kernels; only level 0 reads through the strides, pooled and Sobel planes are planar workspace per pair.
+ * Limits and refusals as kpb_lk_track, plus batch in 1 .. 65535, max_n >= 0 and positive strides (KPB_E_INVALID; KPB_E_UNSUPPORTED past 65535 pairs, or
+ * when one pair's map spans 2^31 elements or more: offsets inside a map are 32-bit);
+ * messages begin "kpb_lk_track_batch:", and a refused call writes nothing. */
+int kpb_lk_track_batch(kpb_ctx* ctx, const float* map1_dev, const float* map2_dev, int batch, int C, int H, int W,
+                       int64_t sb, int64_t sc, int64_t sh, int64_t sw,
+                       const float* pts1_dev, const float* pts2_dev, int pts_stride, const float* unit_dev,
+                       int max_n, const int32_t* n_dev, const kpb_lk_params* params,
+                       float* out_pts_dev, float* out_err_dev);
+
 /* ---- configs[3]: epipolar residual of the matches, tasks/FundamentalMatrix.py:137-161 ------------------------------
  * kps0_dev [batch][max_k][cols0] matched rows of image 0, normalised (x, y, ...): scaled to pixels (x (W-1), y (H-1), 1);
  * kps1_dev [batch][max_k][cols1] matched rows of image 1 as the reference's matcher branch leaves them --
@@ -294,6 +311,7 @@ int kpb_preprocess(kpb_ctx* ctx, const uint8_t* src_dev, int batch, int Hs, int 
 #define KPB_ARCH_DISK 4         /* models/disk.py       DISK (thin U-Net, 5x5), H, W multiples of 16, not 16 x 16 (a 1 x 1 bottleneck has no instance norm) */
 #define KPB_ARCH_R2D2 6         /* models/r2d2.py       Quad_L2Net_ConfCFS (dilated, full resolution), BN folded; any H, W */
 #define KPB_ARCH_EDGEPOINT 7    /* models/EdgePoint.py  EdgePoint (ALIKE-t trunk, plan 8,16,32,64 / 64), BN folded; raw-logit score (KPB_OPT_DETECT_SIGNED), 64-channel map at H/8 x W/8 */
+#define KPB_ARCH_GOODPOINT 8    /* models/GoodPoint.py  GoodPoint (ALIKE-t's block 1, plan c0 = 3, c1 = 8), BN folded; H, W multiples of 32; sigmoid score and a sigmoid 3-channel map at full resolution, not normalised: the map the tracker follows (kpb_lk_track_batch); desc_out_dev 16-byte aligned */
 int kpb_net_create(kpb_ctx* ctx, int arch, const void* blob, size_t len, kpb_net** out);
 void kpb_net_destroy(kpb_net* net);
 int kpb_net_desc_dim(const kpb_net* net);   /* descriptor channels C */

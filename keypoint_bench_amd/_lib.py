@@ -66,6 +66,8 @@ SIGNATURES = {
                                   c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "kpb_lk_track": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                              c_void_p, c_void_p, c_void_p]),
+    "kpb_lk_track_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                   c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "kpb_epipolar_error": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                    c_float, c_void_p, c_void_p]),
     "kpb_find_homography": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_uint32,

@@ -2008,19 +2008,117 @@ __global__ __launch_bounds__(256) void edgepoint_desc(EpDescArgs a)           //
     }
 }
 
+// ------------------------------------------------------------------------------------------------ GoodPoint head
+// GoodPoint (models/GoodPoint.py:103-109) puts two heads on block 1's features x1, both at full resolution: score = sigmoid(conv_head2(x1)), 3 x 3, 8 -> 1, zero
+// padding 1, no bias; desc = sigmoid(conv_head1(x1)), 1 x 1, 8 -> 3, no bias, not normalised -- the 3-channel map the Lucas-Kanade tracker follows.
+// fp32 fmaf chains in one fixed order (score: ky, kx, c ascending from 0; desc: c ascending from 0), the same code in the split-f16 and the strict-fp32 build.
+// x1 outside the image is ZERO (the head's own padding): a zero operand leaves a chain's value as it is, so a pixel's bits depend on neither tile nor batch.
+// An HBM stream: 32 bytes of x1 read, 4 + 12 written per pixel for 96 multiply-adds.  A workgroup stages a 64 x 16 tile + halo once in LDS with 16-byte loads (a
+// row of the tile is 2 KB contiguous), as two planes of float4 -- channels 0..3 and 4..7 -- so that a wave's 16-byte LDS reads are dense.  A lane owns a column of
+// four pixels and walks its six input rows once: every loaded pixel feeds up to three output rows (4.5 LDS pixel reads per output instead of 9).
+// Descriptor rows are formed in LDS: a wave's 4 x 64 pixels x 3 channels are 4 rows of 768 contiguous bytes in the [B][H][W][3] map, stored as float4, a row piece per
+// 48 lanes.  Each wave owns its piece of `dst` and a wave's LDS operations execute in order: no barrier there (as edgepoint_desc).
+// w: conv_head2 as [ky][kx][c] (72), then conv_head1 [o][c] (24); wave-uniform and never written by a kernel: scalar loads through the constant address space.
+// Measured 1.74 ms per 512 images of 480 x 640, 0.54 of 8 TB/s: bound by vector issue (384 fmaf + 16 sigmoids + 160 lane moves of parked weights per column), DESIGN.md 4.
+constexpr int GP_TW = 64, GP_TH = 16, GP_RPT = 4, GP_WDESC = 72;
+struct GpHeadArgs { const float* x1; float* score; float* desc; const float* w; int H, W; };      // desc null: score only
+__global__ __launch_bounds__(256) void goodpoint_head(GpHeadArgs a)
+{
+    constexpr int LW = GP_TW + 2, LH = GP_TH + 2, NLD = 2 * LW * LH, NK = (NLD + 255) / 256;
+    static_assert(GP_TH == 4 * GP_RPT, "four waves, GP_RPT rows each");
+    __shared__ float4 xt[2][LH * LW];
+    __shared__ __attribute__((aligned(16))) float dst[4][GP_RPT * GP_TW * 3];
+    typedef const __attribute__((address_space(4))) float* cfp;
+    const cfp w = (cfp)a.w;
+    const int tx0 = blockIdx.x * GP_TW, ty0 = blockIdx.y * GP_TH, H = a.H, W = a.W;
+    const size_t img = (size_t)blockIdx.z * H * W;
+    {
+        float4 v[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int i = threadIdx.x + 256 * k, pix = i >> 1, py = pix / LW, px = pix - py * LW;
+            const int y = ty0 + py - 1, x = tx0 + px - 1;
+            v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (i < NLD && y >= 0 && y < H && x >= 0 && x < W) v[k] = *reinterpret_cast<const float4*>(a.x1 + (img + (size_t)y * W + x) * 8 + 4 * (i & 1));
+        }
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int i = threadIdx.x + 256 * k;
+            if (i < NLD) xt[i & 1][i >> 1] = v[k];
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float sc[GP_RPT], d[GP_RPT][3];
+#pragma unroll
+    for (int r = 0; r < GP_RPT; ++r) sc[r] = 0.0f;
+#pragma unroll
+    for (int iy = 0; iy < GP_RPT + 2; ++iy)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int li = (wv * GP_RPT + iy) * LW + lane + kx;
+            const float4 lo = xt[0][li], hi = xt[1][li];
+            const float x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+            for (int r = 0; r < GP_RPT; ++r) {
+                const int ky = iy - r;
+                if (ky < 0 || ky > 2) continue;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) sc[r] = fmaf(w[(ky * 3 + kx) * 8 + c], x[c], sc[r]);
+                if (ky == 1 && kx == 1) {
+#pragma unroll
+                    for (int o = 0; o < 3; ++o) {
+                        float acc = 0.0f;
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) acc = fmaf(w[GP_WDESC + o * 8 + c], x[c], acc);
+                        d[r][o] = __fdiv_rn(1.0f, 1.0f + expf(-acc));      // torch.sigmoid (GoodPoint.py:109)
+                    }
+                }
+            }
+        }
+    const int xo = tx0 + lane, yw = ty0 + wv * GP_RPT;
+#pragma unroll
+    for (int r = 0; r < GP_RPT; ++r)
+        if (xo < W && yw + r < H) a.score[img + (size_t)(yw + r) * W + xo] = __fdiv_rn(1.0f, 1.0f + expf(-sc[r]));      // (GoodPoint.py:108)
+    if (!a.desc) return;
+    float* ds = dst[wv];
+#pragma unroll
+    for (int r = 0; r < GP_RPT; ++r)
+#pragma unroll
+        for (int o = 0; o < 3; ++o) ds[r * (GP_TW * 3) + lane * 3 + o] = d[r][o];
+    __builtin_amdgcn_wave_barrier();
+    const int vw = min(GP_TW, W - tx0) * 3;      // floats of a row piece inside the image: W is a multiple of 32, so of 4 floats too
+#pragma unroll
+    for (int k = 0; k < GP_RPT * GP_TW * 3 / 4 / 64; ++k) {
+        const int f = k * 64 + lane, r = f / (GP_TW * 3 / 4), c4 = (f - r * (GP_TW * 3 / 4)) * 4;
+        if (c4 < vw && yw + r < H)
+            *reinterpret_cast<float4*>(a.desc + (img + (size_t)(yw + r) * W + tx0) * 3 + c4) = *reinterpret_cast<const float4*>(ds + r * (GP_TW * 3) + c4);
+    }
+}
+
 }  // namespace
 
 // ================================================================================================ host side
 namespace {
 
-// The encoder ALIKE-t and EdgePoint share (ALike.py:137-150, EdgePoint.py:146-158): block 1 .. block 4 and the aggregations 2 .. 4, in all three regimes (split-f16 batch
-// path with the fused tails from 16 images on, latency path below, strict fp32).  A net derives from it and adds its head.
-struct AlikeTrunk : kpb_net {
-    float *x1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr;      // the maps of the last forward that the heads and desc_at read
+// Block 1 (ALike.py:137-138, EdgePoint.py:146-147, GoodPoint.py:103: ConvBlock(3, 8)) as every net built on it runs it: the split-f16 kernel with its per-image
+// maxima, or the strict fp32 kernel (KPB_FP32_MATRIX=1).  A net carves x1 and the pieces of B1Bufs from its arena and calls block1().
+struct AlikeBlock1 : kpb_net {
+    float* x1 = nullptr;        // [B][H][W][8], the map of the last forward that the heads and desc_at read
     // What forward needs of the staged weights, bound once at create: device pointers, and the host scalars of the split-f16 form -- reciprocal power-of-two
     // weight scales of the custom packs, and the L1 norms / bias maxima behind the bounds the fused kernels scale their intermediate maps by (conv_mfma.h,
     // cm_scale_of).  One struct per fused kernel; the members carry the names of the kernel arguments they fill.
     struct { const float *w1, *b1, *w2, *b2; const uint4 *w1pk, *w2pk; float inv_ws1, inv_ws2, l1_c1, bmax_c1; } k1 = {};       // Block1Args, Block1HArgs
+    // p1 [B][H/2][W/2][8]: max_pool2d(x1, 2), always written; split-f16 form only: wmax_x1 [B][b1_waves], every wave's largest x1 value, and amax_x1 [B], their fold
+    struct B1Bufs { float *p1, *wmax_x1; unsigned* amax_x1; };
+    static int b1_waves(int H, int W) { return cdiv(W, B1_TW) * cdiv(H, B1H_TH) * 4; }
+    void block1(const float* img_dev, int batch, int H, int W, const B1Bufs& b);
+};
+
+// The encoder ALIKE-t and EdgePoint share (ALike.py:137-150, EdgePoint.py:146-158): block 1 .. block 4 and the aggregations 2 .. 4, in all three regimes (split-f16 batch
+// path with the fused tails from 16 images on, latency path below, strict fp32).  A net derives from it and adds its head.
+struct AlikeTrunk : AlikeBlock1 {
+    float *a2 = nullptr, *a3 = nullptr, *a4 = nullptr;      // with x1: the maps of the last forward that the heads and desc_at read
     struct { const uint4 *w1pk, *w2pk, *wapk; const float *b1, *bsum; float inv_ws1, inv_ws2, inv_wsa, l1_c1, bmax_c1, l1_c2, l1_ds, bmax_sum; } k2 = {};   // Block2Args
     // blocks 2 .. 4 as strict fp32 sees them (ConvArgs: w1 .. dsb).  Blocks 3 / 4 keep conv2 as an MFMA pack in both forms (w2p, b2p, un2) and, in the
     // split-f16 form, conv1 + the identity branch as one pack (w1h, b1h, un1); prof1 / prof2 are the profile names of their conv1 / conv2
@@ -2109,6 +2207,18 @@ __global__ __launch_bounds__(256) void maxpool4_nhwc(const float* __restrict__ i
     *reinterpret_cast<float4*>(out + ((b * Ho + y) * (size_t)Wo + x) * C + c) = m;
 }
 
+void AlikeBlock1::block1(const float* img_dev, int batch, int H, int W, const B1Bufs& b)
+{
+    hipStream_t st = ctx->stream;
+    Block1Args b1{img_dev, x1, b.p1, k1.w1, k1.b1, k1.w2, k1.b2, H, W};
+    if (conv_mfma_use_h16()) {
+        Block1HArgs hb{b1, k1.w1pk, k1.w2pk, k1.inv_ws1, k1.inv_ws2, k1.l1_c1, k1.bmax_c1, b.wmax_x1, 0};       // XCD-aware map: +4 % on block 1 (not bound by its halo re-reads), off
+        KPB_LAUNCH(ctx, "alike_block1", alike_block1_h, dim3(cdiv(W, B1_TW), cdiv(H, B1H_TH), batch), dim3(256), 0, st, hb);
+        KPB_LAUNCH(ctx, "amax_reduce", amax_reduce, dim3(batch), dim3(256), 0, st, b.wmax_x1, b1_waves(H, W), b.amax_x1);
+    } else
+        KPB_LAUNCH(ctx, "alike_block1", alike_block1, dim3(cdiv(W, B1_TW), cdiv(H, B1_TH), batch), dim3(256), 0, st, b1);
+}
+
 // H and W are multiples of 32 (the nets' forwards check, each under its own name)
 int AlikeTrunk::trunk(const float* img_dev, int batch, int H, int W, bool dense, Maps& mo)
 {
@@ -2116,7 +2226,7 @@ int AlikeTrunk::trunk(const float* img_dev, int batch, int H, int W, bool dense,
     const bool h16 = conv_mfma_use_h16();       // the split-f16 matrix form (default) or the strict fp32 kernels (KPB_FP32_MATRIX=1)
     // blocks 3 / 4 finished inside their conv2 (CmForm::tail): x3 / x4 are not written, maxpool4_x3 and the two aggregations are not launched
     const bool fused = h16 && batch >= 16 && ctx->alike_coarse_fused;
-    const int nw1 = cdiv(W, B1_TW) * cdiv(H, B1H_TH) * 4, nw2 = cdiv(W / 2, 32) * cdiv(H / 2, 8) * 4;      // per-wave maxima of blocks 1 / 2
+    const int nw1 = b1_waves(H, W), nw2 = cdiv(W / 2, 32) * cdiv(H / 2, 8) * 4;      // per-wave maxima of blocks 1 / 2
     const size_t n_2 = B * (P / 4) * 16, n_3 = B * (P / 64) * 32, n_4 = B * (P / 1024) * 64;
     float *p1, *t2, *x2, *t3, *x3, *t4, *x4, *r3, *r4, *t3r3, *t4r4, *p2, *p3, *S2, *S3, *S4, *E3, *E4, *wmax_x1, *wmax_a2;
     unsigned *amax_x1, *amax_a2;
@@ -2147,12 +2257,9 @@ int AlikeTrunk::trunk(const float* img_dev, int batch, int H, int W, bool dense,
     this->B = batch; this->H = H; this->W = W;
     hipStream_t st = ctx->stream;
 
-    Block1Args b1{img_dev, x1, p1, k1.w1, k1.b1, k1.w2, k1.b2, H, W};
+    block1(img_dev, batch, H, W, B1Bufs{p1, wmax_x1, amax_x1});
     ConvArgs c;
     if (h16) {
-        Block1HArgs hb{b1, k1.w1pk, k1.w2pk, k1.inv_ws1, k1.inv_ws2, k1.l1_c1, k1.bmax_c1, wmax_x1, 0};       // XCD-aware map: +4 % on block 1 (not bound by its halo re-reads), off
-        KPB_LAUNCH(ctx, "alike_block1", alike_block1_h, dim3(cdiv(W, B1_TW), cdiv(H, B1H_TH), batch), dim3(256), 0, st, hb);
-        KPB_LAUNCH(ctx, "amax_reduce", amax_reduce, dim3(batch), dim3(256), 0, st, wmax_x1, nw1, amax_x1);
         // block2 @ H/2 (ALike.py:139-140) + agg2, fused; it hands block 3 the 4 x 4 max-pool of its output (141)
         Block2Args b2{p1, x2, a2, S2, p2, k2.w1pk, k2.w2pk, k2.wapk, k2.b1, k2.bsum, kh.wsc + 16, H / 2, W / 2,
                       k2.inv_ws1, k2.inv_ws2, k2.inv_wsa, k2.l1_c1, k2.bmax_c1, k2.l1_c2, k2.l1_ds, k2.bmax_sum, amax_x1, wmax_a2, 1};     // XCD-aware map: -5 % (profiles/r04_ab_knobs.txt)
@@ -2203,7 +2310,6 @@ int AlikeTrunk::trunk(const float* img_dev, int batch, int H, int W, bool dense,
             return launch_conv_mfma<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32}>(
                 ctx, r.prof2, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = c / 32}, m, batch);
         };
-        KPB_LAUNCH(ctx, "alike_block1", alike_block1, dim3(cdiv(W, B1_TW), cdiv(H, B1_TH), batch), dim3(256), 0, st, b1);
         c = ConvArgs{p1, t2, blk[2].w1, blk[2].b1, nullptr, nullptr, nullptr, nullptr, H / 2, W / 2};      // pooled by block1
         launch_conv<8, 16, 1, false, 4, 1>(ctx, "conv3x3_b2c1", st, c, batch);
         c = ConvArgs{t2, x2, blk[2].w2, blk[2].b2, p1, blk[2].dsw, blk[2].dsb, nullptr, H / 2, W / 2};
@@ -2307,8 +2413,8 @@ const char* first_missing(const KpbwBlob& bl, const std::vector<Need>& more)
 // the profile names of conv1 / conv2 of blocks 2 .. 4 (AlikeTrunk::Res::prof1, prof2)
 constexpr const char* RES_PROF[5][2] = {{}, {}, {"conv3x3_b2c1", "conv3x3_b2c2"}, {"conv3x3_b3c1", "conv3x3_b3c2"}, {"conv3x3_b4c1", "conv3x3_b4c2"}};
 
-// the trunk half of a create: repacks, h16 packs, L1 norms and bias maxima of blocks 1 .. 4 and the four aggregations, each staged with the members of *net it binds
-void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
+// block 1's weights as its two kernels read them, each staged with the member of net->k1 it binds
+void block1_stage(const KpbwBlob& bl, WeightStage& ws, AlikeBlock1* net)
 {
     std::vector<float> tmp;
     {   // block1 conv1: [co][ci][ky][kx] -> [(ci,ky,kx)][co]
@@ -2329,6 +2435,13 @@ void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
         }
         ws.put_raw(bl.get("b1c2.b", {c1}), 8, &net->k1.b2);
     }
+}
+
+// the trunk half of a create: repacks, h16 packs, L1 norms and bias maxima of blocks 1 .. 4 and the four aggregations, each staged with the members of *net it binds
+void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
+{
+    std::vector<float> tmp;
+    block1_stage(bl, ws, net);
     const uint32_t ch[5] = {0, c1, c2, c3, c4};
     for (int i = 2; i <= 4; ++i) {
         char nm[16];
@@ -2502,6 +2615,65 @@ int edgepoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             for (int k = 0; k < 16; ++k) tb[(3 + k) * 16 + j] = bl.get("ct4.b", {q})[j];
         }
         ws.put(tab, &net->ke.tab); ws.put(tb, &net->ke.tabb);
+    }
+    if (int rc = ws.upload(ctx, &net->wdev)) return rc;
+    *out = net.release();
+    return KPB_OK;
+}
+
+// ================================================================================================ GoodPoint: block 1, its own head
+namespace {
+
+struct GoodPointNet : AlikeBlock1 {
+    struct { const float* w; } kg = {};       // goodpoint_head's weights
+    int forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev) override;
+};
+
+int GoodPointNet::forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev)
+{
+    if ((H_ % 32) || (W_ % 32))     // block 1's contract (its 2 x 2 pooled output and tiles), as for ALIKE and EdgePoint
+        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: GoodPoint needs H and W multiples of 32 (got %dx%d)", H_, W_);
+    if (batch > 65535) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_net_forward: GoodPoint: at most 65535 images a call (got %d)", batch);
+    if (reinterpret_cast<uintptr_t>(desc_out_dev) & 15)     // goodpoint_head stores the map's rows as float4
+        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: GoodPoint: desc_out_dev must be 16-byte aligned");
+    const size_t P = (size_t)H_ * W_, B = batch;
+    const bool h16 = conv_mfma_use_h16();
+    B1Bufs b{};
+    if (int rc = kpb_carve(ctx, act, [&](Arena& a) {
+            x1 = a.take(B * P * 8);
+            b.p1 = a.take(B * (P / 4) * 8);
+            b.amax_x1 = h16 ? a.take<unsigned>(B) : nullptr;
+            b.wmax_x1 = h16 ? a.take(B * b1_waves(H_, W_)) : nullptr;
+        }))
+        return rc;
+    this->B = batch; this->H = H_; this->W = W_;
+    block1(img_dev, batch, H_, W_, b);
+    GpHeadArgs g{x1, score_out_dev, desc_out_dev, kg.w, H_, W_};      // (a null map: the repeatability task needs the score only)
+    KPB_LAUNCH(ctx, "goodpoint_head", goodpoint_head, dim3(cdiv(W_, GP_TW), cdiv(H_, GP_TH), batch), dim3(256), 0, ctx->stream, g);
+    KPB_HIP(ctx, hipGetLastError());
+    return KPB_OK;
+}
+
+}  // namespace
+
+int goodpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
+{
+    const std::vector<Need> need = {{"b1c1.w", {c1, 3, 3, 3}}, {"b1c1.b", {c1}}, {"b1c2.w", {c1, c1, 3, 3}}, {"b1c2.b", {c1}}, {"gp.desc.w", {3, c1}},
+                                    {"gp.score.w", {c1, 3, 3}}};
+    for (auto& nd : need)
+        if (!bl.get(nd.n, nd.d))
+            return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not GoodPoint shaped (this build supports c0 = 3, c1 = 8)", nd.n);
+    auto net = std::make_unique<GoodPointNet>();
+    net->ctx = ctx; net->arch = KPB_ARCH_GOODPOINT; net->dim = 3; net->desc_div = 1;
+    WeightStage ws;
+    block1_stage(bl, ws, net.get());
+    {   // goodpoint_head's weights: conv_head2 [c][ky][kx] -> [ky][kx][c], then conv_head1 [o][c] as it is
+        const float *wsr = bl.get("gp.score.w", {c1, 3, 3}), *wd = bl.get("gp.desc.w", {3, c1});
+        std::vector<float> tmp(GP_WDESC + 24);
+        for (int k = 0; k < 9; ++k)
+            for (int c = 0; c < 8; ++c) tmp[k * 8 + c] = wsr[c * 9 + k];
+        for (int i = 0; i < 24; ++i) tmp[GP_WDESC + i] = wd[i];
+        ws.put(tmp, &net->kg.w);
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     *out = net.release();

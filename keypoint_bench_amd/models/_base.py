@@ -62,6 +62,7 @@ class HipNet(NativeOwner):
     ARCH = 0
     signed_scores = False       # the score map is a raw logit (any sign): detect on it with signed=True (utils/extracter.py), as the pipelines do
     dense_descriptors = True    # forward writes the descriptor map (ALNet can be built without: the pipelines then sample inside the net)
+    tracked_maps = False        # with the optical_flow matcher the tracker follows the net's descriptor maps instead of the frames (model_interface.py:262-272)
 
     def __init__(self):
         super().__init__()

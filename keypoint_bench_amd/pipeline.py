@@ -237,16 +237,38 @@ class SequencePipeline(_Core):
     slot i against slot i+1 of the same buffers (kpb_match / kpb_gather_rows take the two sides as separate base
     pointers, so the shift is a pointer offset).  Slot 0 carries the last frame of the previous chunk."""
 
-    def __init__(self, net, extractor_params, brute_force_params, frames, H, W, device="cuda:0"):
+    def __init__(self, net, extractor_params, brute_force_params, frames, H, W, device="cuda:0", track=None):
+        """track = the matcher's optical_flow_params: pair j is TRACKED instead of matched (FundamentalMatrix.py:116-119) -- one kpb_lk_track_batch
+        call follows slot j's keypoints from slot j's map into slot j + 1's.  The maps are the net's descriptor maps when net.tracked_maps, the frames
+        themselves otherwise (model_interface.py:262-272); F + 1 of them are kept, slot 0 carried like kps and n.  brute_force_params may be None then."""
+        self.track = track
+        if track is not None and brute_force_params is None:
+            brute_force_params = dict(metric="euclidean", max_distance=float("inf"), cross_check=True)
         super().__init__(net, extractor_params, brute_force_params, H, W, device)
         self.F = int(frames)
+        if track is not None and net.tracked_maps and not (self.dense and self.div == 1):
+            raise ValueError("a net with tracked_maps writes a full-resolution descriptor map")
         self._buffers(self.F, self.F + 1, self.F, torch.zeros)      # slot 0 is read before it is ever written
         self._last = None       # slot that holds the newest frame of the previous chunk
+        if track is not None:
+            K, dev = self.top_k, self.device
+            if net.tracked_maps:        # the forward writes slots 1 .. F of the map buffer directly; viewed [F+1, C, H, W] over channels-last storage
+                self.maps_store = torch.zeros((self.F + 1, self.H, self.W, self.C), dtype=torch.float32, device=dev)
+                self.desc = self.maps_store[1:]
+                self.maps = self.maps_store.permute(0, 3, 1, 2)
+            else:                       # the frames are tracked (the forward stays the one the single-pair path runs: its score bits are the contract)
+                self.maps_store = self.maps = torch.zeros((self.F + 1, 3, self.H, self.W), dtype=torch.float32, device=dev)
+            self.tracked = torch.empty((self.F, K, 2), dtype=torch.float32, device=dev)
+            self.track_err = torch.empty((self.F, K), dtype=torch.float32, device=dev)
 
-    def run(self, images, first):
+    def _carried(self):
+        return (self.kps, self.n, self.maps_store) if self.track is not None else (self.kps, self.n, self.sdesc)
+
+    def run(self, images, first, angles=None):
         """images [f, 3, H, W], f <= F consecutive frames; first = the chunk starts at frame 0 of the whole sequence
         (otherwise the previous call -- or `prime` -- supplied the frame before images[0]).  Leaves pair j =
-        (frame before images[j], images[j]) in pairs/dist/k/m0/m1[j]."""
+        (frame before images[j], images[j]) in pairs/dist/k/m0/m1[j] -- or, with `track`, in tracked [F][K][2] (pixels), track_err [F][K] and
+        k = n[:f] (the keypoints of the pair's FIRST frame, all tracked).  angles [f, K]: the tracker's start angles (drawn when missing)."""
         self.ctx = Context.get(self.device)      # follows torch's current stream
         f = images.shape[0]
         assert 0 < f <= self.F and images.shape[1:] == (3, self.H, self.W) and images.is_contiguous() and images.dtype == torch.float32
@@ -254,12 +276,26 @@ class SequencePipeline(_Core):
             if self._last is None:
                 raise RuntimeError("SequencePipeline.run(first=False) needs the previous frame: call prime() or run() first")
             if self._last != 0:
-                for t in (self.kps, self.n, self.sdesc):
+                for t in self._carried():
                     t[0].copy_(t[self._last])
         self._extract(images, f, self.kps[1:], self.idx[1:], self.n[1:], 1)
+        if self.track is not None:
+            from .utils.matcher import optical_flow_batch
+            if not self.net.tracked_maps:
+                self.maps[1:f + 1].copy_(images)
+            if first:       # the first frame of a sequence is paired with itself
+                for t in self._carried():
+                    t[0].copy_(t[1])
+            ang = None if angles is None else angles[:f]
+            out, err = optical_flow_batch(self.maps[:f], self.maps[1:f + 1], self.kps[:f], self.kps[:f], self.n[:f], self.track, random_angle=ang)
+            self.tracked[:f].copy_(out)
+            self.track_err[:f].copy_(err)
+            self.k[:f].copy_(self.n[:f])
+            self._last = f
+            return self
         self._describe(f, self.kps[1:], 3, self.n[1:], self.sdesc[1:])
         if first:
-            for t in (self.kps, self.n, self.sdesc):
+            for t in self._carried():
                 t[0].copy_(t[1])
         self._match(f, 1, self.kps, 3, self.n, self.m0, self.m1)
         self._last = f

@@ -48,7 +48,8 @@ _MODELS = {"Alike": ("ALike", lambda m, p, dense: m.ALNet(p, dense_descriptors=d
            "XFeat": ("XFeat", lambda m, p, dense: m.XFeatModel(), "XFeat_params", None, _NOT_SHIPPED),
            "DISK": ("disk", lambda m, p, dense: m.DISK(), "DISK_params", "extractor", _NOT_SHIPPED),
            "r2d2": ("r2d2", None, "r2d2_params", None, ""),
-           "EdgePoint": ("EdgePoint", lambda m, p, dense: m.EdgePoint(p), "EdgePoint_params", None, "")}
+           "EdgePoint": ("EdgePoint", lambda m, p, dense: m.EdgePoint(p), "EdgePoint_params", None, ""),
+           "GoodPoint": ("GoodPoint", lambda m, p, dense: m.GoodPoint(p), "GoodPoint_params", None, "")}
 
 
 def build_model(params, dense_descriptors=True):
@@ -57,7 +58,7 @@ def build_model(params, dense_descriptors=True):
     import importlib
     mt = params["model_type"]
     if mt not in _MODELS:
-        raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint)" % (mt,))
+        raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint, GoodPoint)" % (mt,))
     mod, make, pkey, sub, missing = _MODELS[mt]
     mod = importlib.import_module("keypoint_bench_amd.models." + mod)
     p = params.get(pkey) or {}
@@ -467,8 +468,9 @@ class PairRunner:
             r = list(R.reshape(9)) + list(t.reshape(3)) + [step_length(cur)]
             self.results.append(r)
             return r
-        if mp["type"] == "optical_flow":      # 262-267: the tracker works on the two images
-            res = fundamental_matrix(idx, last_img, cur, s0, s1, last_img, cur["image0"], self.matcher, self.params)
+        if mp["type"] == "optical_flow":      # 262-272: the tracker works on the two images, or on the maps of a net that makes them for it
+            t0, t1 = (d0, d1) if getattr(self.model, "tracked_maps", False) else (last_img, cur["image0"])
+            res = fundamental_matrix(idx, last_img, cur, s0, s1, t0, t1, self.matcher, self.params)
         else:
             res = fundamental_matrix(idx, last_img, cur, s0, s1, d0, d1, self.matcher, self.params)
         r = [float(res["fundamental_error"]), float(res["fundamental_radio"]), float(res["fundamental_num"])]
@@ -739,13 +741,14 @@ class PairRunner:
                 fetched.close()
         return [out[i] for i in indices]
 
-    # ---- batched sequence (BASELINE configs[3]: brute-force branch)
+    # ---- batched sequence (BASELINE configs[3]: brute-force branch; config_fund.yaml: the tracker)
     def _run_sequence(self, dataset, indices, task_type="FundamentalMatrix"):
         from .pipeline import SequencePipeline
         from .tasks.FundamentalMatrix import epipolar_error
         mp = self.params["matcher_params"]
+        track = mp["type"] == "optical_flow" and task_type == "FundamentalMatrix"     # (visual_odometer + optical_flow is cv2's tracker: refused per frame)
         batched = (not self.user_task) and self.batch > 1 and hasattr(self.model, "_handle") and \
-            (mp["type"] == "brute_force" or (mp["type"] == "light_glue" and self.matcher is None))
+            (mp["type"] == "brute_force" or (mp["type"] == "light_glue" and self.matcher is None) or track)
         rows = []
         if not indices:
             return rows
@@ -762,7 +765,8 @@ class PairRunner:
         first = as_image(dataset[indices[0]]["image0"], self.device)
         H, W = first.shape[-2:]
         F = min(self.batch, len(indices))
-        pipe = SequencePipeline(self.model, self.params["extractor_params"], mp["brute_force_params"], F, H, W, device=self.device)
+        pipe = SequencePipeline(self.model, self.params["extractor_params"], mp.get("brute_force_params"), F, H, W, device=self.device,
+                                track=mp["optical_flow_params"] if track else None)
         images = torch.empty((F, 3, H, W), dtype=torch.float32, device=self.device)
         if indices[0] > 0:
             pipe.prime(as_image(dataset[indices[0] - 1]["image0"], self.device))
@@ -799,7 +803,10 @@ class PairRunner:
                 self.batched_pairs += f
                 continue
             fmat = torch.stack(fm).to(self.device)
-            _, stats = epipolar_error(pipe.m0[:f], pipe.m1[:f], fmat, W, H, 0, th, k_dev=pipe.k)      # FundamentalMatrix.py:120-122: mode 0
+            if track:       # FundamentalMatrix.py:116-119: every keypoint of the pair's first frame, against where it was tracked to (pixels: mode 2)
+                _, stats = epipolar_error(pipe.kps[:f], pipe.tracked[:f], fmat, W, H, 2, th, k_dev=pipe.n[:f])
+            else:
+                _, stats = epipolar_error(pipe.m0[:f], pipe.m1[:f], fmat, W, H, 0, th, k_dev=pipe.k)      # FundamentalMatrix.py:120-122: mode 0
             st, kk = stats.cpu().numpy(), pipe.k[:f].tolist()
             for j in range(f):
                 if kk[j] == 0:

@@ -135,3 +135,41 @@ def optical_flow_tensor(pts0, pts1, img0, img1, params=None):
     """utils/matcher.py:186-203."""
     pts1_, _ = OpticalFlow(params)(img0, img1, pts0, pts1)
     return pts1_
+
+
+def optical_flow_batch(maps1, maps2, pts1, pts2, n, params, random_angle=None):
+    """The tracker for B pairs in one kpb_lk_track_batch call: pair j follows pts (normalised rows, as OpticalFlow takes them) from maps1[j] into
+    maps2[j].  maps1 / maps2 [B,C,H,W] fp32 of ANY strides, both with the same ones -- a planar stack of frames, the channels-last storage behind a
+    net's [B,C,H,W] descriptor view, or two shifted views of one buffer (maps[:-1], maps[1:]): the strides are passed on, nothing is copied.
+    pts1 / pts2 [B,K,>=2] (the same tensor is fine), n [B] int32 on the device or None (= K), random_angle [B,K] (drawn as the reference draws them,
+    matcher.py:55, when missing).  Returns (points [B,K,2] in PIXELS, error [B,K]); rows past n[j] are left as allocated.  Every pair's rows are the
+    bits of OpticalFlow(params) on that pair."""
+    if params is None:
+        params = {"distance": 3, "win_size": 3, "levels": 1, "interation": 40, "gray": False}
+    if not maps1.is_cuda:
+        raise RuntimeError("keypoint_bench_amd needs CUDA/HIP tensors; there is no CPU path")
+    B, C, H, W = maps1.shape
+    if maps1.dtype != torch.float32 or maps2.dtype != torch.float32:
+        raise ValueError("maps must be float32")
+    if maps2.shape != maps1.shape or maps2.stride() != maps1.stride():
+        raise ValueError("maps1 and maps2 must have one shape and one set of strides")
+    if C != (1 if params["gray"] else 3):
+        raise ValueError("maps must have %d channel(s) for gray=%s" % (1 if params["gray"] else 3, params["gray"]))
+    if pts1.shape[-1] < 2 or pts2.shape[-1] < 2 or pts1.shape != pts2.shape or pts1.stride() != pts2.stride() or pts1.shape[0] != B:
+        raise ValueError("points need (x, y) columns, one [B,K,cols] layout for both arrays")
+    p1, p2 = pts1.detach(), pts2.detach()
+    if p1.dtype != torch.float32 or not p1.is_contiguous() or not p2.is_contiguous():
+        p1, p2 = p1.to(torch.float32).contiguous(), p2.to(torch.float32).contiguous()
+    K, dev = p1.shape[1], maps1.device
+    if random_angle is None:
+        random_angle = torch.randn((B, K), device=dev) * 6.28                                            # 55
+    unit = torch.stack([torch.cos(random_angle), torch.sin(random_angle)], dim=2).to(torch.float32).contiguous()   # 56
+    out = torch.empty((B, K, 2), dtype=torch.float32, device=dev)
+    err = torch.empty((B, K), dtype=torch.float32, device=dev)
+    if K:
+        ctx = Context.get(dev)
+        sb, sc, sh, sw = maps1.stride()
+        prm = LkParams(float(params["distance"]), int(params["win_size"]), int(params["levels"]), int(params["interation"]))
+        ctx.check(ctx.lib.kpb_lk_track_batch(ctx.handle, ptr(maps1), ptr(maps2), B, C, H, W, sb, sc, sh, sw, ptr(p1), ptr(p2), p1.shape[2], ptr(unit), K,
+                                             ptr(n), ctypes.byref(prm), ptr(out), ptr(err)))
+    return out, err

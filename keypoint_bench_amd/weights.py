@@ -19,6 +19,7 @@ ARCH_DISK = 4
 ARCH_LIGHTGLUE = 5
 ARCH_R2D2 = 6
 ARCH_EDGEPOINT = 7
+ARCH_GOODPOINT = 8
 _REC = struct.Struct("<40sI4II")
 
 
@@ -115,6 +116,31 @@ def fold_edgepoint(sd) -> dict:
     t["d8.w"], t["d8.b"] = f32("conv_8.weight").reshape(q, q), f32("conv_8.bias")
     t["d4.w"], t["d4.b"] = f32("conv_4.weight").reshape(q, q), f32("conv_4.bias")
     t["ct4.w"], t["ct4.b"] = f32("conv_transpose_4.weight"), f32("conv_transpose_4.bias")
+    return t
+
+
+GOODPOINT_PLAN = dict(c0=3, c1=8)
+
+
+def fold_goodpoint(sd) -> dict:
+    """state_dict of GoodPoint (models/GoodPoint.py:84-93) -> block 1 folded under the names fold_alike gives it (b1c1.w/.b, b1c2.w/.b: the reference's
+    ConvBlock(3, 8) is ALIKE-t's block 1, and csrc/alike.hip binds it the same way), plus the two heads: gp.desc.w [3][8] (conv_head1, 1 x 1, no bias)
+    and gp.score.w [8][3][3] (conv_head2, 3 x 3, one output channel, no bias).  Refused: a missing or mis-shaped tensor, any plan but c0 = 3, c1 = 8."""
+    c0, c1 = GOODPOINT_PLAN["c0"], GOODPOINT_PLAN["c1"]
+    need = {"block.conv1.weight": (c1, c0, 3, 3), "block.conv2.weight": (c1, c1, 3, 3), "conv_head1.weight": (3, c1, 1, 1), "conv_head2.weight": (1, c1, 3, 3)}
+    for bn in ("bn1", "bn2"):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            need["block.%s.%s" % (bn, leaf)] = (c1,)
+    for key, shape in need.items():
+        if key not in sd:
+            raise ValueError("GoodPoint state_dict: %s is missing" % key)
+        if tuple(sd[key].shape) != shape:
+            raise ValueError("GoodPoint state_dict: %s has shape %s, the supported plan (c0 = 3, c1 = 8) needs %s" % (key, tuple(sd[key].shape), shape))
+    t = {}
+    t["b1c1.w"], t["b1c1.b"] = _fold(sd, "block.conv1", "block.bn1")
+    t["b1c2.w"], t["b1c2.b"] = _fold(sd, "block.conv2", "block.bn2")
+    t["gp.desc.w"] = _np(sd["conv_head1.weight"]).astype(np.float32).reshape(3, c1)
+    t["gp.score.w"] = _np(sd["conv_head2.weight"]).astype(np.float32).reshape(c1, 3, 3)
     return t
 
 
