@@ -17,6 +17,7 @@ and the task is evaluated for a whole batch on the device; host-resident dataset
 ring (HostStager) so that their PCIe copy runs under the previous batch's kernels.
 """
 import contextlib
+import itertools
 import os
 
 import numpy as np
@@ -285,6 +286,14 @@ class HostStager:
                     np.copyto(dst[j], a.reshape(dst.shape[1:]))
         list(self.pool.map(chunk, range(min(self.workers, n))))
 
+    def upload(self, arrays, dst, stream):
+        """dst (a device tensor) <- arrays, synchronously: one pinned gather, one PCIe copy, waited for on `stream`."""
+        _, pinned = self.acquire(dst.shape, dst.dtype)
+        self.fill(pinned, arrays)
+        dst.copy_(pinned, non_blocking=True)
+        stream.synchronize()
+        self.release()
+
     def close(self):
         self.pool.shutdown(wait=True)
 
@@ -381,20 +390,94 @@ def _covis_tables(items, B, dev):
 BATCHED_TASKS = {"match_stats": (_batched_match_stats, True, False), "repeatability": (_batched_repeatability, False, False),
                  "MHA": (_batched_mha, True, True), "AUC": (_batched_auc, True, False),
                  "FundamentalMatrixRansac": (_batched_fund_ransac, True, False)}
+ANY_WARP_TASKS = ("AUC", "FundamentalMatrixRansac")      # their batched rows take se3 warps too; every other batched task needs homographies
+_STAGED_DTYPES = (np.dtype(np.uint8), np.dtype(np.float32))      # what the staging ring carries
 
 
 def _homo_only(item):
     return all(item.get(k, {}).get("mode", "homo") == "homo" for k in ("warp01_params", "warp10_params"))
 
 
+def _view_key(a):
+    """What the views of one batch share: (dtype, H, W) of a cropped view, fp32 [.., H, W] or decoded uint8 [H, W, 3]."""
+    s = a.shape
+    return (a.dtype, s[0], s[1]) if is_decoded_u8(a) else (a.dtype, s[-2], s[-1])
+
+
+def host_views(item):
+    """plan_pairs' `views` for host-resident items: None when an image is on a device or has a dtype the staging ring does not carry."""
+    a, b = _host_array(item["image0"]), _host_array(item["image1"])
+    if a is None or b is None or a.dtype not in _STAGED_DTYPES or b.dtype not in _STAGED_DTYPES:
+        return None
+    return crop32_host(a), crop32_host(b)
+
+
+def plan_pairs(items, task_type, batch, batched, views):
+    """THE routing and grouping rule of the pair loops, a pure function of the items and the task: consumes (i, item) in order, yields
+    ("single", i, item) for the one-pair path and ("batch", group) for the batched one, group = [(i, item, view0, view1)]: at most
+    `batch` consecutive pairs whose cropped views share one _view_key.  `views(item)` gives the two cropped views or None (not
+    batchable); it is all that differs by residency, and whatever touches a device happens inside it.  Single: nothing is batched, the
+    task needs homographies and the item has another warp, no views, or two views of different keys.  The open group is flushed when
+    the key changes, when it is full, before every single and at the end.  Lazy: the consumer acts on an event before the next item."""
+    group, key = [], None
+    for i, item in items:
+        v = views(item) if batched and (task_type in ANY_WARP_TASKS or _homo_only(item)) else None
+        k = _view_key(v[0]) if v is not None else None
+        if k is not None and k != _view_key(v[1]):
+            k = None
+        if group and k != key:
+            yield "batch", group
+            group = []
+        if k is None:
+            yield "single", i, item
+            continue
+        key = k
+        group.append((i, item, v[0], v[1]))
+        if len(group) == batch:
+            yield "batch", group
+            group = []
+    if group:
+        yield "batch", group
+
+
+class RowLedger:
+    """The rows of one run by pair index, each stored exactly once.  store(group, rows): one row per member of `group` (whose first fields
+    are the pair indices), at once -- or, given a zero-argument callable that computes them (a task's host half), when settle() runs it."""
+
+    def __init__(self):
+        self.out, self.late = {}, []
+
+    def store(self, group, rows):
+        if callable(rows):
+            self.late.append((group, rows))
+        else:
+            for g, r in zip(group, rows):
+                self.single(g[0], r)
+
+    def settle(self):
+        while self.late:
+            group, fn_rows = self.late.pop(0)
+            self.store(group, fn_rows())
+
+    def single(self, i, row):
+        assert i not in self.out, "pair %r has a row already" % (i,)
+        self.out[i] = row
+
+    def rows(self, indices):
+        return [self.out[i] for i in indices]
+
+
 class PairRunner:
     """Per-rank evaluation loop (MInterface.test_step / on_test_end, model_interface.py:119-299) over
 
     * a pair dataset: any indexable of dicts with 'image0', 'image1' and optionally 'warp01_params' / 'warp10_params', as
-      datasets/hpatches.py:74-83 returns them (numpy [C,H,W] images; tensors work too).  Pairs of equal cropped shape are
-      collected `batch` at a time and pushed through PairPipeline (net -> detection -> sampling -> match in one launch
-      wave), the task is evaluated on the whole batch on the device; ragged shapes, se3 warps and user-supplied
-      `task_fn`s take the single-pair path (`test_step`), whose rows the batched path reproduces bit for bit;
+      datasets/hpatches.py:74-83 returns them (numpy [C,H,W] images; tensors work too).  plan_pairs decides, in one place,
+      which pairs are collected `batch` at a time (equal cropped views) and pushed through PairPipeline (net -> detection ->
+      sampling -> match in one launch wave, the task evaluated on the whole batch on the device) and which take the single-pair
+      path (`test_step`: ragged views, se3 warps, every pair under a user `task_fn`), whose rows the batched path reproduces
+      bit for bit.  Two consumers run its events, each on its own schedule and with a RowLedger: `_run_pairs` inline for device
+      items (a batch in flight while the next is collected), `_run_pairs_staged` for host items (the planner on a producer
+      thread that fills the pinned ring, the copy of batch k + 1 under batch k's kernels);
     * a sequence dataset ('dataset' in Kitti / Euroc / TartanAir, items with 'image0' and 'fundamental'): the
       `last_batch` flow of model_interface.py:217-228 with the FundamentalMatrix task (261-276), frames sharded in
       contiguous chunks with a one-frame overlap."""
@@ -526,139 +609,73 @@ class PairRunner:
         self.batched_pairs += len(items)
         return rows
 
-    def _flush(self, group, task_type, staged=None, between=None):
-        """`_begin`, then `between()` (the previous batch's host-side row arithmetic, under this batch's kernels), then `_end`."""
-        token = self._begin(group, task_type, staged)
-        if between is not None:
-            between()
-        return self._end(token)
+    def _can_batch(self):
+        return (not self.user_task) and self.batch > 1 and hasattr(self.model, "_handle")
+
+    def _staging(self):
+        self._stager = self._stager or HostStager()
+        return self._stager
 
     def _run_pairs(self, dataset, indices, task_type):
-        batched = (not self.user_task) and task_type in BATCHED_TASKS and self.batch > 1 and hasattr(self.model, "_handle")
+        batched = self._can_batch() and task_type in BATCHED_TASKS
         if task_type == "FundamentalMatrixRansac":          # the batched rows are the brute-force branch without cv2 drawing
             mp = self.params["matcher_params"]
             batched = batched and mp["type"] == "brute_force" and not mp.get("save_result") and not self.params["extractor_params"].get("save_result")
-        out = {}
-        host = batched and len(indices) > 0 and _host_array(dataset[indices[0]]["image0"]) is not None
-        if host:
+        if batched and len(indices) > 0 and _host_array(dataset[indices[0]]["image0"]) is not None:
             return self._run_pairs_staged(dataset, indices, task_type)
-        group, shape = [], None
-        late = []               # [(group, callable)]: rows whose host half is still to run (under the next batch's kernels)
-        inflight = None         # (group, token): a batch whose kernels are running while the next group is being collected
-
-        def settle():
-            while late:
-                g, fn_rows = late.pop(0)
-                for (i, _, _, _), r in zip(g, fn_rows()):
-                    out[i] = r
+        ledger, inflight = RowLedger(), None         # (group, token): a batch whose kernels are running while the planner collects the next group
 
         def land():
             nonlocal inflight
             if inflight is not None:
                 g, token = inflight
                 inflight = None
-                res = self._end(token)
-                if callable(res):
-                    late.append((g, res))
-                else:
-                    for (i, _, _, _), r in zip(g, res):
-                        out[i] = r
+                ledger.store(g, self._end(token))
 
-        def flush():
-            nonlocal group, inflight
-            if group:
-                land()                                              # the pipeline's buffers are free again
-                inflight = (group, self._begin(group, task_type))
-                settle()                                            # host halves of the batch before, under this batch's kernels
-            group = []
-
-        def single(item, i):        # the drop-in path shares the context (one detection in flight at a time): land first
-            flush()
-            land()
-            settle()
-            out[i] = self.test_step(item, i)
-
-        for i in indices:
-            item = dataset[i]
-            if not batched or (task_type not in ("AUC", "FundamentalMatrixRansac") and not _homo_only(item)):
-                single(item, i)
-                continue
-            a, b = crop32(as_image(item["image0"], self.device)), crop32(as_image(item["image1"], self.device))
-            if a.shape[-2:] != b.shape[-2:]:                # the two views differ in size: single-pair path
-                single(item, i)
-                continue
-            if shape is not None and a.shape[-2:] != shape:
-                flush()
-            shape = a.shape[-2:]
-            group.append((i, item, a, b))
-            if len(group) == self.batch:
-                flush()
-        flush()
+        views = lambda item: (crop32(as_image(item["image0"], self.device)), crop32(as_image(item["image1"], self.device)))
+        for kind, *ev in plan_pairs(((i, dataset[i]) for i in indices), task_type, self.batch, batched, views):
+            land()                                                  # the pipeline's buffers are free again
+            if kind == "batch":
+                inflight = (ev[0], self._begin(ev[0], task_type))
+                ledger.settle()                                     # host halves of the batch before, under this batch's kernels
+            else:               # the drop-in path shares the context (one detection in flight at a time): it runs with nothing in flight
+                ledger.settle()
+                ledger.single(ev[0], self.test_step(ev[1], ev[0]))
         land()
-        settle()
-        return [out[i] for i in indices]
+        ledger.settle()
+        return ledger.rows(indices)
 
     def _run_pairs_staged(self, dataset, indices, task_type):
-        """The batched pair path for HOST-resident dataset items (numpy arrays / CPU tensors, fp32 CHW or decoded uint8 HWC):
-        a producer thread walks the dataset, groups pairs of equal cropped shape and gathers each group into a pinned
-        buffer of the HostStager while the main thread runs the previous group on the device.  Rows are those of the
-        device-resident path; pairs the batched path does not take (ragged views, se3 warps for the homography tasks) go
-        through `test_step` on the main thread, in order."""
+        """The batched pair path for HOST-resident dataset items (numpy arrays / CPU tensors, fp32 CHW or decoded uint8 HWC): a producer
+        thread runs plan_pairs over the dataset and gathers each group into a pinned buffer of the HostStager while the main thread runs
+        the previous group on the device.  Rows are those of the device-resident path; singles go through `test_step` here, in order."""
         import queue
         import threading
-        if self._stager is None:
-            self._stager = HostStager()
-        st = self._stager
+        st = self._staging()
         q = queue.Queue(maxsize=1)
-
-        def shape_of(a):
-            return tuple(a.shape[:2]) if is_decoded_u8(a) else tuple(a.shape[-2:])
-
         from .datasets import Prefetcher
         fetched = None              # created inside the try below, so that close() runs whatever fails in between
         stop = threading.Event()    # set when the consumer fails: the producer stops at its next item instead of staging the rest
 
+        def live(it):               # ends with the first item or event that arrives after `stop`
+            return itertools.takewhile(lambda _: not stop.is_set(), it)
+
         def produce():
-            try:
-                group, key = [], None
-
-                def emit():
-                    nonlocal group
-                    if group:
-                        u8 = is_decoded_u8(group[0][2])
-                        f = len(group)
-                        shp = (2 * f,) + (tuple(group[0][2].shape) if u8 else (3,) + shape_of(group[0][2]))
-                        _, pinned = st.acquire(shp, torch.uint8 if u8 else torch.float32)
-                        st.fill(pinned, [g[2] for g in group] + [g[3] for g in group])
-                        q.put(("batch", group, pinned))
-                    group = []
-
-                for i, item in fetched:       # dataset[i], decoded / read a few items ahead on a thread pool (datasets.Prefetcher)
-                    if stop.is_set():
-                        return
-                    a, b = _host_array(item["image0"]), _host_array(item["image1"])
-                    single = a is None or b is None or (task_type not in ("AUC", "FundamentalMatrixRansac") and not _homo_only(item))
-                    if not single:
-                        a, b = crop32_host(a), crop32_host(b)
-                        if a.dtype != b.dtype or shape_of(a) != shape_of(b) or (a.dtype != np.uint8 and a.dtype != np.float32):
-                            single = True
-                    if single:
-                        emit()
-                        q.put(("single", i, item))
-                        continue
-                    k = (a.dtype, shape_of(a))
-                    if key is not None and k != key:
-                        emit()
-                    key = k
-                    group.append((i, item, a, b))
-                    if len(group) == self.batch:
-                        emit()
-                emit()
-                q.put(("end", None, None))
+            try:    # items: dataset[i], decoded / read a few items ahead on a thread pool (datasets.Prefetcher)
+                for kind, *ev in live(plan_pairs(live(fetched), task_type, self.batch, True, host_views)):
+                    if kind == "batch":
+                        views = [g[2] for g in ev[0]] + [g[3] for g in ev[0]]       # views 0 first, then views 1 (_begin)
+                        u8 = is_decoded_u8(views[0])
+                        shp = (len(views),) + (tuple(views[0].shape) if u8 else (3,) + _view_key(views[0])[1:])
+                        ev.append(st.acquire(shp, torch.uint8 if u8 else torch.float32)[1])
+                        st.fill(ev[1], views)
+                    q.put((kind, *ev))
+                if not stop.is_set():
+                    q.put(("end", None, None))
             except BaseException as e:          # surfaces on the main thread
                 q.put(("error", e, None))
 
-        out = {}
+        ledger = RowLedger()
         copy_stream = None
         pending = None          # (group, device tensor, copy-done event): its PCIe copy runs under the previous group's kernels
         held = []               # copies whose pinned slot has not been given back yet (slot ownership, explicit)
@@ -674,25 +691,14 @@ class PairRunner:
             held.append(p)
             return p
 
-        late = []
-
-        def settle():
-            while late:
-                g, fn_rows = late.pop(0)
-                for (i, _, _, _), r in zip(g, fn_rows()):
-                    out[i] = r
-
         def finish(p):
             group, dev, ev = p
             ev.synchronize()        # the copy has left the pinned slot: the producer may refill it
             st.release()
             held.remove(p)          # from here on a failing task must not give the slot back a second time
-            res = self._flush(group, task_type, staged=dev, between=settle)
-            if callable(res):
-                late.append((group, res))
-            else:
-                for (i, _, _, _), r in zip(group, res):
-                    out[i] = r
+            token = self._begin(group, task_type, staged=dev)
+            ledger.settle()         # host halves of the batch before, under this batch's kernels
+            ledger.store(group, self._end(token))
 
         th = None
         try:
@@ -711,8 +717,8 @@ class PairRunner:
                 if kind == "end":
                     break
                 if kind == "single":
-                    out[x] = self.test_step(y, x)
-            settle()
+                    ledger.single(x, self.test_step(y, x))
+            ledger.settle()
         finally:
             for p in held:                      # only on an error path: slots whose copy was started but never consumed
                 try:
@@ -739,7 +745,7 @@ class PairRunner:
             drain()                             # the producer's LAST item may still sit in q (maxsize 1) after it has exited
             if fetched is not None:
                 fetched.close()
-        return [out[i] for i in indices]
+        return ledger.rows(indices)
 
     # ---- batched sequence (BASELINE configs[3]: brute-force branch; config_fund.yaml: the tracker)
     def _run_sequence(self, dataset, indices, task_type="FundamentalMatrix"):
@@ -747,8 +753,7 @@ class PairRunner:
         from .tasks.FundamentalMatrix import epipolar_error
         mp = self.params["matcher_params"]
         track = mp["type"] == "optical_flow" and task_type == "FundamentalMatrix"     # (visual_odometer + optical_flow is cv2's tracker: refused per frame)
-        batched = (not self.user_task) and self.batch > 1 and hasattr(self.model, "_handle") and \
-            (mp["type"] == "brute_force" or (mp["type"] == "light_glue" and self.matcher is None) or track)
+        batched = self._can_batch() and (mp["type"] == "brute_force" or (mp["type"] == "light_glue" and self.matcher is None) or track)
         rows = []
         if not indices:
             return rows
@@ -784,13 +789,7 @@ class PairRunner:
             frames = [it["image0"] for it in items]
             host = [_host_array(v) for v in frames]
             if all(h is not None and h.dtype == np.float32 for h in host):      # host frames: one pinned gather, one PCIe copy
-                if self._stager is None:
-                    self._stager = HostStager()
-                _, pinned = self._stager.acquire((f, 3, H, W), torch.float32)
-                self._stager.fill(pinned, host)
-                images[:f].copy_(pinned, non_blocking=True)
-                torch.cuda.current_stream(self.device).synchronize()
-                self._stager.release()
+                self._staging().upload(host, images[:f], torch.cuda.current_stream(self.device))
             elif all(torch.is_tensor(v) and v.is_cuda and v.dtype == torch.float32 for v in frames):    # device frames: one gather kernel
                 torch.stack([v.reshape(3, H, W) for v in frames], out=images[:f])
             else:

@@ -299,3 +299,28 @@ def test_hpatches_ppm_files_are_read_straight_into_the_staging_ring_and_give_the
     single = runner.PairRunner(params(task), device=DEV, batch=1)        # every pair through test_step: as_image reads the RawImages
     _, rows_single = single.run(files)
     assert np.array_equal(rows_single.view(np.uint64), rows_arr.view(np.uint64))
+
+
+def test_singles_between_batches_keep_rows_counts_and_staging_for_host_and_device_items():
+    """A stream in which the one-pair path interrupts the batched one twice -- a pair of unequal views and an se3-warp pair (repeatability
+    batches homographies only) -- over two shapes with batch=2: host numpy items and device tensors give the rows of batch=1 bit for bit,
+    every batchable pair is batched, and only the host items are staged."""
+    ds = pair_dataset(9, shapes=((96, 128), (96, 128), (64, 96), (64, 96), (64, 96), (64, 96), (96, 128), (96, 128), (96, 128)))
+    ds[3]["image1"] = synthetic.image_pair(103, 96, 128)[1]                    # unequal views: 64x96 against 96x128
+    ds[3]["warp01_params"].update(width=np.int64(128), height=np.int64(96), resize=np.int64(128))
+    K = np.array([[120.0, 0, 63.5], [0, 120.0, 47.5], [0, 0, 1]], np.float32)
+    for key, tx in (("warp01_params", 1.0), ("warp10_params", -1.0)):          # a fronto-parallel plane 50 away, the camera moved sideways
+        T = np.eye(4, dtype=np.float32)
+        T[0, 3] = tx
+        ds[6][key] = dict(mode="se3", intrinsics0=K, intrinsics1=K, pose01=T, bbox0=np.zeros(2, np.float32), bbox1=np.zeros(2, np.float32),
+                          depth0=np.full((96, 128), 50.0, np.float32), depth1=np.full((96, 128), 50.0, np.float32), width=128, height=96)
+    dev = [dict(it, image0=torch.from_numpy(it["image0"]).to(DEV), image1=torch.from_numpy(it["image1"]).to(DEV)) for it in ds]
+    single = runner.PairRunner(params("repeatability"), device=DEV, batch=1)
+    _, rows1 = single.run(ds)
+    assert single.batched_pairs == 0 and rows1[:, 0].min() > 20
+    for name, d in (("host", ds), ("dev", dev)):
+        r = runner.PairRunner(params("repeatability"), device=DEV, batch=2)
+        _, rows = r.run(d)
+        assert r.batched_pairs == 7, (name, r.batched_pairs)
+        assert (r.staged_batches == 0) == (name == "dev"), (name, r.staged_batches)
+        assert np.array_equal(rows.view(np.uint64), rows1.view(np.uint64)), (name, rows, rows1)

@@ -197,3 +197,123 @@ def test_generator_threads_share_the_cores():
     assert bench.generator_threads(1) == max(1, min(cores, 16))
     assert bench.generator_threads(8) == max(1, min(cores // 8, 16))
     assert bench.generator_threads(8) * 8 <= max(cores, 8)
+
+
+# ------------------------------------------------------------------------------------------------ the pair planner and the row ledger
+def _item(h, w, h1=None, w1=None, dtype=np.float32, dtype1=None, mode="homo"):
+    """A host pair as the datasets hand it out: fp32 / fp64 CHW, or -- uint8 -- a decoded HWC image."""
+    def img(h, w, dt):
+        return np.zeros((h, w, 3) if dt == np.uint8 else (3, h, w), dt)
+    return {"image0": img(h, w, dtype), "image1": img(h1 or h, w1 or w, dtype1 or dtype), "warp01_params": {"mode": mode}, "warp10_params": {"mode": mode}}
+
+
+def _plan(items, task="repeatability", batch=3, batched=True, indices=None):
+    """The planner's events over host items, as ("single", i) / ("batch", [i, ..]).  Checked for every case (i): the events' indices,
+    concatenated, are the input indices -- each exactly once, in order; every event carries its own item, and a group's views are the
+    x32 crops of its items' images."""
+    indices = list(indices if indices is not None else range(len(items)))
+    by_index = dict(zip(indices, items))
+    events = []
+    for kind, *ev in runner.plan_pairs(zip(indices, items), task, batch, batched, runner.host_views):
+        if kind == "single":
+            assert ev[1] is by_index[ev[0]]
+            events.append(("single", ev[0]))
+        else:
+            assert kind == "batch" and 0 < len(ev[0]) <= batch
+            for i, item, a, b in ev[0]:
+                assert item is by_index[i] and a.dtype == item["image0"].dtype and a.shape == b.shape
+                hw = a.shape[:2] if a.dtype == np.uint8 else a.shape[-2:]
+                assert hw == tuple(s - s % 32 for s in (item["image0"].shape[:2] if a.dtype == np.uint8 else item["image0"].shape[-2:]))
+            events.append(("batch", [g[0] for g in ev[0]]))
+    assert [i for kind, x in events for i in ([x] if kind == "single" else x)] == indices
+    return events
+
+
+def test_plan_groups_equal_shapes_batch_at_a_time():
+    assert _plan([_item(64, 96) for _ in range(7)]) == [("batch", [0, 1, 2]), ("batch", [3, 4, 5]), ("batch", [6])]                       # (a)
+    assert _plan([_item(64, 96) for _ in range(6)]) == [("batch", [0, 1, 2]), ("batch", [3, 4, 5])]       # no empty group at the end
+    assert _plan([]) == []
+
+
+def test_plan_flushes_on_a_change_of_shape_and_groups_by_cropped_shape():
+    items = [_item(64, 96), _item(64, 96), _item(96, 128), _item(96, 128), _item(64, 96)]
+    assert _plan(items) == [("batch", [0, 1]), ("batch", [2, 3]), ("batch", [4])]                                                         # (b)
+    items = [_item(96, 128), _item(100, 130), _item(96, 128), _item(100, 130)]
+    assert _plan(items, indices=[1, 3, 5, 7]) == [("batch", [1, 3, 5]), ("batch", [7])]                                                   # (c)
+
+
+def test_plan_sends_unequal_views_to_the_single_path_after_the_open_group():
+    items = [_item(64, 96), _item(64, 96), _item(64, 96, 96, 128), _item(64, 96), _item(96, 128, 64, 96)]
+    assert _plan(items) == [("batch", [0, 1]), ("single", 2), ("batch", [3]), ("single", 4)]                                              # (d)
+    assert _plan([_item(64, 96, 96, 128), _item(64, 96)]) == [("single", 0), ("batch", [1])]              # no group open: none emitted
+    assert _plan([_item(100, 130, 96, 128), _item(96, 128)]) == [("batch", [0, 1])]                       # unequal before the crop only
+
+
+@pytest.mark.parametrize("task,needs_homo", [("repeatability", True), ("MHA", True), ("match_stats", True), ("AUC", False), ("FundamentalMatrixRansac", False)])
+def test_plan_keeps_other_warps_off_the_batched_path_of_the_homography_tasks(task, needs_homo):
+    items = [_item(64, 96), _item(64, 96, mode="se3"), _item(64, 96), _item(64, 96)]                                                      # (e)
+    want = [("batch", [0]), ("single", 1), ("batch", [2, 3])] if needs_homo else [("batch", [0, 1, 2]), ("batch", [3])]
+    assert _plan(items, task=task) == want
+    assert set(runner.ANY_WARP_TASKS) == {"AUC", "FundamentalMatrixRansac"} and set(runner.ANY_WARP_TASKS) <= set(runner.BATCHED_TASKS)
+
+
+def test_plan_keys_groups_by_dtype_and_refuses_what_the_staging_ring_does_not_carry():
+    items = [_item(64, 96), _item(64, 96, dtype=np.uint8), _item(64, 96, dtype=np.uint8), _item(64, 96)]
+    assert _plan(items) == [("batch", [0]), ("batch", [1, 2]), ("batch", [3])]                                                            # (f)
+    items = [_item(64, 96), _item(64, 96, dtype=np.float64), _item(64, 96, dtype1=np.float64), _item(64, 96, dtype=np.uint8, dtype1=np.float32),
+             _item(64, 96)]
+    assert _plan(items) == [("batch", [0]), ("single", 1), ("single", 2), ("single", 3), ("batch", [4])]                                  # (g)
+    cpu, other = _item(64, 96), _item(64, 96)
+    cpu["image0"], cpu["image1"] = torch.zeros(3, 64, 96), torch.zeros(3, 64, 96)                        # CPU tensors are host items
+    other["image1"] = object()                                                                            # what is neither array nor CPU tensor is not
+    assert runner.host_views(other) is None
+    events = list(runner.plan_pairs(enumerate([cpu, _item(64, 96), other]), "repeatability", 3, True, runner.host_views))
+    assert [(e[0], [g[0] for g in e[1]] if e[0] == "batch" else e[1]) for e in events] == [("batch", [0, 1]), ("single", 2)]
+
+
+def test_plan_without_batching_is_all_singles_and_never_asks_for_views():
+    def views(item):
+        raise AssertionError("views() called for an item of the single-pair path")
+    items = [_item(64, 96), _item(96, 128), _item(64, 96, mode="se3")]
+    got = list(runner.plan_pairs(enumerate(items), "repeatability", 3, False, views))                                                     # (h)
+    assert got == [("single", 0, items[0]), ("single", 1, items[1]), ("single", 2, items[2])]
+    assert _plan(items, batched=False) == [("single", 0), ("single", 1), ("single", 2)]
+    assert list(runner.plan_pairs(enumerate(items[2:]), "MHA", 3, True, views)) == [("single", 0, items[2])]     # an se3 pair: routed before its views are made
+
+
+def test_plan_is_lazy_an_event_is_out_before_the_next_item_is_read():
+    """The device loop launches a full batch before it touches the next dataset item, and a group cut by a new shape after that item's views."""
+    read = []
+
+    def stream():
+        for i, it in enumerate([_item(64, 96), _item(64, 96), _item(96, 128)]):
+            read.append(i)
+            yield i, it
+    seen = [(kind, list(read)) for kind, *_ in runner.plan_pairs(stream(), "repeatability", 2, True, runner.host_views)]
+    assert seen == [("batch", [0, 1]), ("batch", [0, 1, 2])]
+
+
+def test_row_ledger_settles_in_order_never_overwrites_and_returns_rows_in_index_order():
+    led = runner.RowLedger()
+    order = []
+
+    def later(tag, rows):
+        def fn():
+            order.append(tag)
+            return rows
+        return fn
+    led.store([(4, "item"), (2, "item")], [[4.0], [2.0]])               # a group's members start with the pair index
+    led.store([(7,), (5,)], later("a", [[7.0], [5.0]]))
+    led.single(6, [6.0])
+    led.store([(1,)], later("b", [[1.0]]))
+    assert order == [] and sorted(led.out) == [2, 4, 6]                 # deferred rows wait for settle()
+    with pytest.raises(KeyError):
+        led.rows([1])
+    led.settle()
+    led.settle()                                                        # nothing left: the callables ran once
+    assert order == ["a", "b"] and led.late == []
+    assert led.rows([1, 2, 4, 5, 6, 7]) == [[1.0], [2.0], [4.0], [5.0], [6.0], [7.0]] and led.rows([7, 1]) == [[7.0], [1.0]]
+    for again in (lambda: led.single(6, [0.0]), lambda: led.store([(2,)], [[0.0]]), lambda: (led.store([(7,)], later("c", [[0.0]])), led.settle())):
+        with pytest.raises(AssertionError):
+            again()
+    assert led.rows([2, 6, 7]) == [[2.0], [6.0], [7.0]]                 # the first rows stand
