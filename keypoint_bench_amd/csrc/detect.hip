@@ -302,7 +302,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_sweep_r(NmsArgs a)
         // gx0 is a multiple of 4: whole float4s are inside or outside the image.  All loads of a thread go out before the first is used,
         // without a branch: a float4 outside the image is fetched from the image's first bytes and replaced by zeros (r05: the nine
         // exec-masked blocks and 64-bit address chains of the branchy form were a fifth of the sweep's instructions).  The image base is
-        // wave-uniform, the offset 32 bits (an image has < 2^30 pixels: nms_open checks).
+        // wave-uniform, the offset 32 bits (an image has < 2^30 pixels: nms_begin checks).
         constexpr int Q = PITCH / 4, NQ = ROWS * Q, PER = (NQ + NMS_THREADS - 1) / NMS_THREADS;
         float4 buf[PER];
         bool okk[PER];
@@ -1142,6 +1142,17 @@ __global__ __launch_bounds__(SEL_THREADS) void select_topk(SelArgs a)
     emit(a, img, sel, a.top_k, wsum);
 }
 
+// kpad * 8 bytes of dynamic LDS: 64 KB for top_k 4097 .. KPB_MAX_TOPK, and for the lists the two-phase form gathers behind the selection slots.
+// (Here, ahead of the NMS launchers: the first mention of a specialisation is its place in the code object.)
+int select_lds_attr(kpb_ctx* ctx)
+{
+    if (!(ctx->lds_attr_done & KPB_ATTR_SELECT))
+        for (const void* f : {reinterpret_cast<const void*>(select_topk<false>), reinterpret_cast<const void*>(select_topk<true>)})
+            KPB_HIP(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    ctx->lds_attr_done |= KPB_ATTR_SELECT;
+    return KPB_OK;
+}
+
 int next_pow2(int v)
 {
     int p = 1;
@@ -1195,7 +1206,7 @@ int nms_plan(kpb_ctx* ctx, int batch, int H, int W, int r, NmsPlan& p, int prune
     const bool big = (size_t)batch * H * W >= (size_t)192 * 480 * 640;
     const bool tail = r >= 1 && r <= 8 && (tiled == 0 || (tiled < 0 && big));
     const bool prune = tail && prune_k > 0 && prune_k < H * W && kpb_env_int("KPB_NMS_PRUNE", 1);
-    // ONE piece for what nms_open clears with one memset: lastchg[B] and negflag[B] -- adjacent, nms_status copies both back as 2 * batch ints -- then,
+    // ONE piece for what nms_open clears with one memset: lastchg[B] and negflag[B] -- adjacent, nms_poll copies both back as 2 * batch ints -- then,
     // from the next multiple of 16 bytes on (nms_tail reads them as uint4s; 2 * batch ints end on one for even batches only), the histograms
     const size_t head = (2 * (size_t)batch + 3) & ~(size_t)3;
     p.nclear = head + (prune ? (size_t)batch * NMS_HBINS : 0);
@@ -1224,10 +1235,6 @@ int nms_plan(kpb_ctx* ctx, int batch, int H, int W, int r, NmsPlan& p, int prune
     if (!(ctx->lds_attr_done & KPB_ATTR_NMS)) {
         KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(nms_sweep),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-        KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(select_topk<false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(select_topk<true>),     // kpad * 8 bytes: 64 KB for top_k 4097 .. KPB_MAX_TOPK
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
         ctx->lds_attr_done |= KPB_ATTR_NMS;
     }
     return KPB_OK;
@@ -1264,8 +1271,6 @@ int nms_launch(kpb_ctx* ctx, const NmsPlan& p, const float* src, float* cur, int
 // over, with every tile marked as changed).  Returns the number of sweeps the status check has to account for.
 int nms_open(kpb_ctx* ctx, const NmsPlan& p, const float* src, float* cur, int batch, int H, int W, int r, int chunk, int& sweeps_run)
 {
-    if ((size_t)H * W >= ((size_t)1 << 30))       // nms_sweep_r addresses a pixel by a 32-bit BYTE offset from its image
-        return kpb_fail(ctx, KPB_E_UNSUPPORTED, "NMS: a %d x %d map is too large (2^30 pixels per image at most)", H, W);
     KPB_HIP(ctx, hipMemsetAsync(p.lastchg, 0, p.nclear * sizeof(int), ctx->stream));
     if (!p.ulist) {
         sweeps_run = chunk;
@@ -1281,20 +1286,6 @@ int nms_open(kpb_ctx* ctx, const NmsPlan& p, const float* src, float* cur, int b
     return KPB_OK;
 }
 
-// reads lastchg/negflag back; returns number of images that changed in sweep (sweeps_run - 1), sets neg
-int nms_status(kpb_ctx* ctx, const NmsPlan& p, int batch, int sweeps_run, int& pending, int& neg)
-{
-    std::vector<int> h(2 * (size_t)batch);      // lastchg[B] and negflag[B]: adjacent in nms_plan's cleared piece
-    KPB_HIP(ctx, hipMemcpyAsync(h.data(), p.lastchg, h.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    pending = 0; neg = 0;
-    for (int b = 0; b < batch; ++b) {
-        pending += (h[b] >= sweeps_run);
-        neg |= h[batch + b];
-    }
-    return KPB_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ signed maps: the reference's rounds
 // KPB_OPT_DETECT_SIGNED (DESIGN.md "signed maps: the rounds, not the fixed point").  On a map with negative scores the reference's loop is no fixed-point
 // iteration: it stops as soon as the NUMBER of maxima repeats, and negative and zero maxima feed that number, so the stopping round -- and with it the
@@ -1305,6 +1296,8 @@ int nms_status(kpb_ctx* ctx, const NmsPlan& p, int batch, int sweeps_run, int& p
 //   map_k+1  the tile with every pixel zeroed that lies within r of a maximum other than itself, written to the OTHER buffer.
 // The stop decision needs all of count_k, so launch k+1 takes it: if count_k == count_k-1 every workgroup leaves without writing (map_k is intact in its
 // buffer) and fin[img] = k + 1 is recorded; later launches see fin and leave at once.  map_0 is the caller's map, map_k (k >= 1) lives in buf[k & 1].
+// On the host the rounds are one of NmsRun's schedules (below): how many are enqueued before and after a look, when to give up and what "undecided"
+// means are stated there once, and kpb_fast_nms and kpb_detect_check drive them with the loop that drives the sweeps.  They take no nms_plan.
 constexpr int RTH = 32, RTW = 64, ROUND_THREADS = 256;
 
 struct RoundArgs {
@@ -1410,7 +1403,6 @@ struct RoundPlan {
 
 int round_plan(kpb_ctx* ctx, int batch, int H, int W, int r, RoundPlan& p)
 {
-    if ((size_t)H * W >= ((size_t)1 << 30)) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "NMS: a %d x %d map is too large (2^30 pixels per image at most)", H, W);
     const int LH = RTH + 4 * r, LW = RTW + 4 * r;
     p.tiles_x = cdiv(W, RTW);
     p.ntiles = p.tiles_x * cdiv(H, RTH);
@@ -1447,9 +1439,99 @@ int round_launch(kpb_ctx* ctx, const RoundPlan& p, const float* src, int batch, 
 // rounds enqueued before the first look at the state / after each further look: an EdgePoint map stops at round 5 or 6, which launch 6 or 7 finds
 constexpr int ROUND_FIRST = 8, ROUND_MORE = 6;
 
-}  // namespace
+// ------------------------------------------------------------------------------------------------ an NMS in flight
+// What kpb_fast_nms and kpb_detect / kpb_detect_check drive: nms_begin enqueues the schedule's opening, the driver looks at every image's status word
+// (nms_poll's copy, or the mirror select_topk leaves in pinned memory) and calls nms_more while nms_undecided says so.  The chunk sizes, the give-up
+// limits and the meaning of a status word live here and nowhere else.
+enum NmsSchedule { NMS_NONE, NMS_SWEEPS, NMS_ROUNDS };    // nms_dist == 0 / the fixed-point sweeps / KPB_OPT_DETECT_SIGNED's rounds
 
-namespace {
+struct NmsRun {
+    NmsSchedule sched;
+    NmsPlan plan;           // NMS_SWEEPS
+    RoundPlan rplan;        // NMS_ROUNDS
+    const float* src;       // the caller's map
+    float* cur;             // the sweeps' working map (null otherwise: the rounds keep theirs in rplan.buf)
+    int batch, H, W, r;
+    int steps;              // sweeps or rounds enqueued so far
+};
+
+// The schedule is chosen here, from nms_dist and the context's option at the time of the call.  first_sweeps: the tiled sweeps enqueued before the first
+// look when there is no tail; cur: the sweeps' working map, or null to have it carved from ws_nms_map; prune_k / border / cmin: nms_plan's top-K pruning.
+int nms_begin(kpb_ctx* ctx, NmsRun& n, const float* src, float* cur, int batch, int H, int W, int r, int first_sweeps,
+              int prune_k = 0, int border = 0, float cmin = 0.0f)
+{
+    n.sched = r == 0 ? NMS_NONE : ctx->detect_signed ? NMS_ROUNDS : NMS_SWEEPS;
+    n.src = src; n.cur = nullptr; n.batch = batch; n.H = H; n.W = W; n.r = r; n.steps = 0;
+    if (r > 0 && (size_t)H * W >= ((size_t)1 << 30))       // nms_sweep_r addresses a pixel by a 32-bit BYTE offset from its image
+        return kpb_fail(ctx, KPB_E_UNSUPPORTED, "NMS: a %d x %d map is too large (2^30 pixels per image at most)", H, W);
+    if (n.sched == NMS_ROUNDS) {
+        if (int rc = round_plan(ctx, batch, H, W, r, n.rplan)) return rc;
+        n.steps = ROUND_FIRST;
+        return round_launch(ctx, n.rplan, src, batch, H, W, r, 0, ROUND_FIRST);
+    }
+    if (n.sched == NMS_SWEEPS) {
+        if (int rc = nms_plan(ctx, batch, H, W, r, n.plan, prune_k, border, cmin)) return rc;
+        if (int rc = cur ? KPB_OK : kpb_carve(ctx, ctx->ws_nms_map, [&](Arena& a) { cur = a.take((size_t)batch * H * W); })) return rc;
+        n.cur = cur;
+        return nms_open(ctx, n.plan, src, cur, batch, H, W, r, first_sweeps, n.steps);
+    }
+    return KPB_OK;
+}
+
+// the next chunk, or KPB_E_NOT_CONVERGED past the schedule's limit (who: the entry point's name for the message)
+int nms_more(kpb_ctx* ctx, NmsRun& n, const char* who)
+{
+    const bool rounds = n.sched == NMS_ROUNDS;
+    const int chunk = rounds ? ROUND_MORE : 6;
+    if (rounds ? (size_t)n.steps > (size_t)n.H * n.W + 2 : n.steps > 100000)
+        return kpb_fail(ctx, KPB_E_NOT_CONVERGED, rounds ? "%s: the count of maxima has not repeated after %d rounds" : "%s: no fixed point after %d sweeps",
+                        who, n.steps);
+    if (int rc = rounds ? round_launch(ctx, n.rplan, n.src, n.batch, n.H, n.W, n.r, n.steps, chunk)
+                        : nms_launch(ctx, n.plan, n.src, n.cur, n.batch, n.H, n.W, n.r, n.steps, chunk)) return rc;
+    n.steps += chunk;
+    return KPB_OK;
+}
+
+// An image's status word is what emit() mirrors into host_status[3 * img]: the last sweep that changed the image (sweeps), or whether the count of
+// maxima has yet to repeat (rounds: fin[img] == 0).  Undecided: a sweep of the last chunk still changed something / the rounds have not stopped.
+bool nms_undecided(const NmsRun& n, int word0)
+{
+    return n.sched == NMS_SWEEPS ? word0 >= n.steps : n.sched == NMS_ROUNDS ? word0 != 0 : false;
+}
+
+// kpb_fast_nms's look: the device's words copied back into h -- lastchg[B] and negflag[B] (adjacent in nms_plan's cleared piece), or the rounds' fin[B]
+int nms_poll(kpb_ctx* ctx, const NmsRun& n, std::vector<int>& h, int& pending, int& neg)
+{
+    const bool rounds = n.sched == NMS_ROUNDS;
+    h.resize((rounds ? 1 : 2) * (size_t)n.batch);
+    KPB_HIP(ctx, hipMemcpyAsync(h.data(), rounds ? n.rplan.fin : n.plan.lastchg, h.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    pending = 0; neg = 0;
+    for (int b = 0; b < n.batch; ++b) {
+        pending += nms_undecided(n, rounds ? h[b] == 0 : h[b]);
+        if (!rounds) neg |= h[n.batch + b];      // a negative score is no error on the rounds
+    }
+    return KPB_OK;
+}
+
+// where the selection finds the NMS's result and status
+void nms_bind(const NmsRun& n, float threshold, SelArgs& s)
+{
+    s.map = n.src; s.map1 = nullptr; s.rfin = nullptr; s.signed_map = 0; s.lastchg = nullptr; s.negflag = nullptr; s.cbits = nullptr; s.wb = 0;
+    if (n.sched == NMS_ROUNDS) {        // the rounds keep the scores as they are; fin names each image's plane
+        s.map = n.rplan.buf[0]; s.map1 = n.rplan.buf[1]; s.rfin = n.rplan.fin;
+    } else if (n.sched == NMS_SWEEPS) {
+        s.map = n.cur;
+        s.signed_map = n.r <= 8;        // the specialised sweep keeps confirmed maxima negated in its working map
+        s.lastchg = n.plan.lastchg; s.negflag = n.plan.negflag;
+        // the bitmap of confirmed maxima stands for the map right after sweep 0 + tail only (later sweeps do not keep it), and only at threshold 0 (or -0):
+        // every maximum passes it and no suppressed pixel does.  A negative threshold keeps the zeroed non-maxima as well (map > threshold after NMS), a
+        // NaN one keeps nothing: both read the map.
+        if (n.plan.cbits && n.steps == 1 && threshold == 0.0f && s.signed_map) s.cbits = reinterpret_cast<const unsigned*>(n.plan.cbits);
+        s.wb = n.plan.wb;
+    }
+}
+
 __global__ void abs_inplace(float* m, size_t n)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -1466,48 +1548,27 @@ extern "C" __attribute__((visibility("default"))) int kpb_fast_nms(kpb_ctx* ctx,
     if (nms_dist < 0 || nms_dist > KPB_MAX_NMS_DIST)
         return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_fast_nms: nms_dist %d outside 0..%d", nms_dist, KPB_MAX_NMS_DIST);
     KPB_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)batch * H * W * sizeof(float);
     if (nms_dist == 0) {  // extracter.py:40-41
-        KPB_HIP(ctx, hipMemcpyAsync(out_map_dev, score_dev, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        KPB_HIP(ctx, hipMemcpyAsync(out_map_dev, score_dev, (size_t)batch * H * W * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return KPB_OK;
     }
-    if (ctx->detect_signed) {      // the reference's rounds: image b's result is the map of the round it stopped at
-        RoundPlan rp;
-        if (int rc = round_plan(ctx, batch, H, W, nms_dist, rp)) return rc;
-        std::vector<int> fin((size_t)batch);
-        const size_t P = (size_t)H * W;
-        for (int run = 0, pending = 1; pending;) {
-            const int n = run == 0 ? ROUND_FIRST : ROUND_MORE;
-            if (int rc = round_launch(ctx, rp, score_dev, batch, H, W, nms_dist, run, n)) return rc;
-            run += n;
-            KPB_HIP(ctx, hipMemcpyAsync(fin.data(), rp.fin, fin.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            pending = 0;
-            for (int b = 0; b < batch; ++b) pending += fin[b] == 0;
-            if (pending && (size_t)run > P + 2) return kpb_fail(ctx, KPB_E_NOT_CONVERGED, "kpb_fast_nms: the count of maxima has not repeated after %d rounds", run);
-        }
-        for (int b = 0; b < batch; ++b)
-            KPB_HIP(ctx, hipMemcpyAsync(out_map_dev + b * P, rp.buf[(fin[b] - 1) & 1] + b * P, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return KPB_OK;
-    }
-    NmsPlan p;
-    if (int rc = nms_plan(ctx, batch, H, W, nms_dist, p)) return rc;
-    const int chunk = 6;
-    int run = 0, pending = 1, neg = 0;
-    while (pending) {
-        if (run == 0) {
-            if (int rc = nms_open(ctx, p, score_dev, out_map_dev, batch, H, W, nms_dist, chunk, run)) return rc;
-        } else {
-            if (int rc = nms_launch(ctx, p, score_dev, out_map_dev, batch, H, W, nms_dist, run, chunk)) return rc;
-            run += chunk;
-        }
-        if (int rc = nms_status(ctx, p, batch, run, pending, neg)) return rc;
+    NmsRun run;
+    if (int rc = nms_begin(ctx, run, score_dev, out_map_dev, batch, H, W, nms_dist, 6)) return rc;
+    std::vector<int> h;
+    for (;;) {
+        int pending, neg;
+        if (int rc = nms_poll(ctx, run, h, pending, neg)) return rc;
         if (neg) return kpb_fail(ctx, KPB_E_NEGATIVE, "kpb_fast_nms: negative scores are outside this path's contract");
-        if (run > 100000) return kpb_fail(ctx, KPB_E_NOT_CONVERGED, "kpb_fast_nms: no fixed point after %d sweeps", run);
+        if (!pending) break;
+        if (int rc = nms_more(ctx, run, "kpb_fast_nms")) return rc;
     }
-    if (nms_dist <= 8) {   // the specialised sweep keeps confirmed maxima negated in its working map
+    if (run.sched == NMS_ROUNDS) {      // image b's result is the map of the round it stopped at: h holds fin
+        const size_t P = (size_t)H * W;
+        for (int b = 0; b < batch; ++b)
+            KPB_HIP(ctx, hipMemcpyAsync(out_map_dev + b * P, run.rplan.buf[(h[b] - 1) & 1] + b * P, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    } else if (nms_dist <= 8) {         // the specialised sweep keeps confirmed maxima negated in its working map
         const size_t n = (size_t)batch * H * W;
         KPB_LAUNCH(ctx, "abs_inplace", abs_inplace, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, out_map_dev, n);
         KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1517,13 +1578,10 @@ extern "C" __attribute__((visibility("default"))) int kpb_fast_nms(kpb_ctx* ctx,
 
 namespace {
 struct DetState {
-    NmsPlan plan;
-    const float* score; float* cur; unsigned long long* cand;
-    int batch, H, W; kpb_detect_params prm;
+    NmsRun nms;         // the schedule chosen at the time of the call (KPB_OPT_DETECT_SIGNED may change before kpb_detect_check), its map, batch, H, W
+    unsigned long long* cand;
+    kpb_detect_params prm;
     float* out_kps; int* out_idx; int* out_n;
-    int sweeps_run;
-    int rounds;         // KPB_OPT_DETECT_SIGNED at the time of the call: the NMS is rplan's rounds, sweeps_run counts them
-    RoundPlan rplan;
 };
 
 DetState& det_state(kpb_ctx* ctx)
@@ -1537,41 +1595,33 @@ DetState& det_state(kpb_ctx* ctx)
 
 int det_select(kpb_ctx* ctx, const DetState& d)
 {
+    const int batch = d.nms.batch, H = d.nms.H, W = d.nms.W;
     SelArgs s;
-    s.map = d.prm.nms_dist == 0 ? d.score : d.cur;
-    const bool rounds = d.rounds && d.prm.nms_dist > 0;
-    s.rfin = rounds ? d.rplan.fin : nullptr; s.map1 = rounds ? d.rplan.buf[1] : nullptr;
-    if (rounds) s.map = d.rplan.buf[0];
+    nms_bind(d.nms, d.prm.threshold, s);
     s.cand = d.cand;
     s.out_kps = d.out_kps; s.out_idx = d.out_idx; s.out_n = d.out_n;
-    s.H = d.H; s.W = d.W; s.border = d.prm.border_dist; s.top_k = d.prm.top_k;
-    s.kpad = d.prm.top_k >= d.H * d.W ? 0 : next_pow2(d.prm.top_k);
+    s.H = H; s.W = W; s.border = d.prm.border_dist; s.top_k = d.prm.top_k;
+    s.kpad = d.prm.top_k >= H * W ? 0 : next_pow2(d.prm.top_k);
     s.threshold = d.prm.threshold; s.min_score = d.prm.min_score;
-    s.signed_map = (!rounds && d.prm.nms_dist >= 1 && d.prm.nms_dist <= 8) ? 1 : 0;       // the rounds keep the scores as they are
-    s.lastchg = d.prm.nms_dist > 0 ? d.plan.lastchg : nullptr; s.negflag = d.prm.nms_dist > 0 ? d.plan.negflag : nullptr;
-    if (ctx->host_det_cap < 3 * d.batch) {
+    if (ctx->host_det_cap < 3 * batch) {
         KPB_HIP(ctx, hipStreamSynchronize(ctx->stream));        // an earlier call's select_topk may still be writing the old mirror
         if (ctx->host_det) KPB_HIP(ctx, hipHostFree(ctx->host_det));
         ctx->host_det = nullptr; ctx->host_det_cap = 0;
-        KPB_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->host_det), (size_t)3 * d.batch * sizeof(int), hipHostMallocDefault));
-        ctx->host_det_cap = 3 * d.batch;
+        KPB_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->host_det), (size_t)3 * batch * sizeof(int), hipHostMallocDefault));
+        ctx->host_det_cap = 3 * batch;
     }
     s.host_status = ctx->host_det;
-    s.chunk_cnt = nullptr; s.nchunks = cdiv(d.H * d.W, SEL_CHUNK); s.lcap = 0;
-    // the bitmap of confirmed maxima stands for the map right after sweep 0 + tail only (later sweeps do not keep it), and only at threshold 0 (or -0):
-    // every maximum passes it and no suppressed pixel does.  A negative threshold keeps the zeroed non-maxima as well (map > threshold after NMS), a
-    // NaN one keeps nothing: both read the map.
-    const bool bits = !rounds && d.plan.cbits && d.sweeps_run == 1 && d.prm.threshold == 0.0f && s.signed_map;
-    s.cbits = bits ? reinterpret_cast<const unsigned*>(d.plan.cbits) : nullptr; s.wb = d.plan.wb;
+    s.chunk_cnt = nullptr; s.nchunks = cdiv(H * W, SEL_CHUNK); s.lcap = 0;
+    if (int rc = select_lds_attr(ctx)) return rc;
     size_t lds = (size_t)s.kpad * sizeof(unsigned long long);
-    if (d.batch < 64 && s.nchunks > 1) {       // too few images to fill the chip with one workgroup each: scan in (chunks x batch) workgroups first
-        if (int rc = kpb_carve(ctx, ctx->ws_sel, [&](Arena& a) { s.chunk_cnt = a.take<int>((size_t)d.batch * s.nchunks); })) return rc;
-        s.lcap = (int)((64 * 1024 - lds) / sizeof(unsigned long long));        // (the attribute set in nms_plan allows 64 KB)
+    if (batch < 64 && s.nchunks > 1) {       // too few images to fill the chip with one workgroup each: scan in (chunks x batch) workgroups first
+        if (int rc = kpb_carve(ctx, ctx->ws_sel, [&](Arena& a) { s.chunk_cnt = a.take<int>((size_t)batch * s.nchunks); })) return rc;
+        s.lcap = (int)((64 * 1024 - lds) / sizeof(unsigned long long));
         lds = 64 * 1024;
-        KPB_LAUNCH(ctx, "select_scan", select_scan, dim3(s.nchunks, d.batch), dim3(SEL_THREADS), 0, ctx->stream, s);
+        KPB_LAUNCH(ctx, "select_scan", select_scan, dim3(s.nchunks, batch), dim3(SEL_THREADS), 0, ctx->stream, s);
     }
-    if (bits && !s.chunk_cnt) KPB_LAUNCH(ctx, "select_topk", select_topk<true>, dim3(d.batch), dim3(SEL_THREADS), lds, ctx->stream, s);
-    else KPB_LAUNCH(ctx, "select_topk", select_topk<false>, dim3(d.batch), dim3(SEL_THREADS), lds, ctx->stream, s);
+    if (s.cbits && !s.chunk_cnt) KPB_LAUNCH(ctx, "select_topk", select_topk<true>, dim3(batch), dim3(SEL_THREADS), lds, ctx->stream, s);
+    else KPB_LAUNCH(ctx, "select_topk", select_topk<false>, dim3(batch), dim3(SEL_THREADS), lds, ctx->stream, s);
     KPB_HIP(ctx, hipGetLastError());
     return KPB_OK;
 }
@@ -1593,38 +1643,23 @@ extern "C" __attribute__((visibility("default"))) int kpb_detect(kpb_ctx* ctx, c
     if (ctx->det_pending)   // one DetState per context: a second enqueue would drop the first call's convergence / sign check
         return kpb_fail(ctx, KPB_E_INVALID, "kpb_detect: the previous kpb_detect(sync=0) has not been completed by kpb_detect_check "
                                             "(its score map and outputs must stay alive until then)");
-    const bool rounds = ctx->detect_signed && prm->nms_dist > 0;
-    if (rounds && prm->threshold < 0.0f)        // map > threshold would keep suppressed pixels, and the negative ones the rounds never touched
+    if (ctx->detect_signed && prm->nms_dist > 0 && prm->threshold < 0.0f)   // map > threshold would keep suppressed pixels, and the negative ones the rounds never touched
         return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_detect: KPB_OPT_DETECT_SIGNED takes a threshold >= 0 (got %g)", (double)prm->threshold);
     KPB_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t P = (size_t)H * W;
     DetState& d = det_state(ctx);
-    d.rounds = rounds;
-    d.score = score_dev; d.batch = batch; d.H = H; d.W = W; d.prm = *prm;
+    d.prm = *prm;
     if (d.prm.top_k > H * W) d.prm.top_k = H * W;   // N can never exceed H*W: same rows, smaller buffers
     d.out_kps = out_kps_dev; d.out_idx = out_idx_dev; d.out_n = out_n_dev;
-    if (int rc = kpb_carve(ctx, ctx->ws_cand, [&](Arena& a) { d.cand = a.take<unsigned long long>((size_t)batch * P); })) return rc;
-    {   // a confirmed maximum counts toward the pruning bound only if the detection could output it
-        const float cmin = std::max(prm->threshold, prm->min_score > 0.0f ? prm->min_score : prm->threshold);
-        const int border = std::max(prm->border_dist, 0);
-        if (int rc = nms_plan(ctx, batch, H, W, prm->nms_dist, d.plan, d.prm.top_k, border, cmin)) return rc;
-    }
-    d.sweeps_run = 0;
-    d.cur = nullptr;
-    if (rounds) {
-        if (int rc = round_plan(ctx, batch, H, W, prm->nms_dist, d.rplan)) return rc;
-        if (int rc = round_launch(ctx, d.rplan, score_dev, batch, H, W, prm->nms_dist, 0, ROUND_FIRST)) return rc;
-        d.sweeps_run = ROUND_FIRST;
-    } else if (prm->nms_dist > 0) {
-        if (int rc = kpb_carve(ctx, ctx->ws_nms_map, [&](Arena& a) { d.cur = a.take((size_t)batch * P); })) return rc;
-        // tiled sweeps enqueued before the first look at the status: an ALIKE map is at its fixed point after 3-4 of them; a sweep
-        // with nothing to do still costs its launch (5 us each on the single map of the drop-in path), an early look costs a
-        // synchronisation -- 6 for batches (amortised), 4 when a few images are all there is
-        // (r04, 96 single maps -- synthetic pairs and warped views: none is confirmed at its fixed point by three sweeps, 86 are by
-        //  four, the other 10 take a second chunk)
-        const int chunk = batch >= 16 ? 6 : 4;
-        if (int rc = nms_open(ctx, d.plan, score_dev, d.cur, batch, H, W, prm->nms_dist, chunk, d.sweeps_run)) return rc;
-    }
+    if (int rc = kpb_carve(ctx, ctx->ws_cand, [&](Arena& a) { d.cand = a.take<unsigned long long>((size_t)batch * H * W); })) return rc;
+    // tiled sweeps enqueued before the first look at the status: an ALIKE map is at its fixed point after 3-4 of them; a sweep
+    // with nothing to do still costs its launch (5 us each on the single map of the drop-in path), an early look costs a
+    // synchronisation -- 6 for batches (amortised), 4 when a few images are all there is
+    // (r04, 96 single maps -- synthetic pairs and warped views: none is confirmed at its fixed point by three sweeps, 86 are by
+    //  four, the other 10 take a second chunk)
+    const int first_sweeps = batch >= 16 ? 6 : 4;
+    // a confirmed maximum counts toward the pruning bound only if the detection could output it
+    const float cmin = std::max(prm->threshold, prm->min_score > 0.0f ? prm->min_score : prm->threshold);
+    if (int rc = nms_begin(ctx, d.nms, score_dev, nullptr, batch, H, W, prm->nms_dist, first_sweeps, d.prm.top_k, std::max(prm->border_dist, 0), cmin)) return rc;
     if (int rc = det_select(ctx, d)) return rc;
     ctx->det_pending = 1;
     if (!sync) return KPB_OK;
@@ -1638,49 +1673,26 @@ extern "C" __attribute__((visibility("default"))) int kpb_detect_check(kpb_ctx* 
     if (!ctx->det_pending) return KPB_OK;
     DetState& d = det_state(ctx);
     KPB_HIP(ctx, hipSetDevice(ctx->device));
-    if (d.prm.nms_dist == 0) {
-        KPB_HIP(ctx, kpb_wait_stream(ctx, d.batch < 16));
-        ctx->det_pending = 0;
-        ctx->det_counts_valid = 1;
-        return KPB_OK;
-    }
-    const int chunk = 6;
+    // every way out from here on ends the pending detection: the context takes a new kpb_detect, and only a completed one leaves counts
+    const auto done = [ctx](int rc, int counts_valid) { ctx->det_pending = 0; ctx->det_counts_valid = counts_valid; return rc; };
     int rerun = 0;
     for (;;) {
         int pending = 0, neg = 0;
-        KPB_HIP(ctx, kpb_wait_stream(ctx, d.batch < 16));        // select_topk has written every image's status to pinned host memory
-        for (int b = 0; b < d.batch; ++b) {
-            pending += d.rounds ? (ctx->host_det[3 * b] != 0) : (ctx->host_det[3 * b] >= d.sweeps_run);
+        const hipError_t e = kpb_wait_stream(ctx, d.nms.batch < 16);    // select_topk has written every image's status to pinned host memory
+        if (e != hipSuccess) return done(kpb_fail(ctx, KPB_E_HIP, "kpb_detect_check: waiting for the stream failed: %s", hipGetErrorString(e)), 0);
+        for (int b = 0; b < d.nms.batch; ++b) {
+            pending += nms_undecided(d.nms, ctx->host_det[3 * b]);
             neg |= ctx->host_det[3 * b + 1];
         }
-        if (neg) {
-            ctx->det_pending = 0;
-            return kpb_fail(ctx, KPB_E_NEGATIVE, "kpb_detect: negative scores are outside this path's contract "
-                                                 "(the reference's zero padding makes them data dependent)");
-        }
+        if (neg)
+            return done(kpb_fail(ctx, KPB_E_NEGATIVE, "kpb_detect: negative scores are outside this path's contract "
+                                                      "(the reference's zero padding makes them data dependent)"), 0);
         if (!pending) break;
         rerun = 1;
-        if (d.rounds) {     // word 0 of the mirror = undecided: more rounds, then the selection again
-            if ((size_t)d.sweeps_run > (size_t)d.H * d.W + 2) {
-                ctx->det_pending = 0;
-                return kpb_fail(ctx, KPB_E_NOT_CONVERGED, "kpb_detect: the count of maxima has not repeated after %d rounds", d.sweeps_run);
-            }
-            if (int rc = round_launch(ctx, d.rplan, d.score, d.batch, d.H, d.W, d.prm.nms_dist, d.sweeps_run, ROUND_MORE)) return rc;
-            d.sweeps_run += ROUND_MORE;
-            if (int rc = det_select(ctx, d)) return rc;
-            continue;
-        }
-        if (d.sweeps_run > 100000) {
-            ctx->det_pending = 0;
-            return kpb_fail(ctx, KPB_E_NOT_CONVERGED, "kpb_detect: NMS did not converge");
-        }
-        if (int rc = nms_launch(ctx, d.plan, d.score, d.cur, d.batch, d.H, d.W, d.prm.nms_dist, d.sweeps_run, chunk)) return rc;
-        d.sweeps_run += chunk;
-        if (int rc = det_select(ctx, d)) return rc;
+        if (int rc = nms_more(ctx, d.nms, "kpb_detect")) return done(rc, 0);
+        if (int rc = det_select(ctx, d)) return done(rc, 0);
     }
-    ctx->det_pending = 0;
-    ctx->det_counts_valid = 1;
-    return rerun;   // 1: the outputs were rewritten after extra sweeps (the loop's last synchronisation covers them)
+    return done(rerun, 1);      // 1: the outputs were rewritten after extra sweeps or rounds (the loop's last synchronisation covers them)
 }
 
 extern "C" __attribute__((visibility("default"))) int kpb_detect_counts(kpb_ctx* ctx, int32_t* out_n_host, int batch)
@@ -1690,8 +1702,8 @@ extern "C" __attribute__((visibility("default"))) int kpb_detect_counts(kpb_ctx*
     if (ctx->det_pending) return kpb_fail(ctx, KPB_E_INVALID, "kpb_detect_counts: the last kpb_detect has not been completed (kpb_detect_check)");
     if (!ctx->det_state || !ctx->host_det || !ctx->det_counts_valid)
         return kpb_fail(ctx, KPB_E_INVALID, "kpb_detect_counts: no completed detection (the last kpb_detect failed, was rejected, or none has run)");
-    const DetState& d = det_state(ctx);
-    if (batch != d.batch) return kpb_fail(ctx, KPB_E_INVALID, "kpb_detect_counts: the last kpb_detect had %d images, not %d", d.batch, batch);
+    const int had = det_state(ctx).nms.batch;
+    if (batch != had) return kpb_fail(ctx, KPB_E_INVALID, "kpb_detect_counts: the last kpb_detect had %d images, not %d", had, batch);
     for (int b = 0; b < batch; ++b) out_n_host[b] = ctx->host_det[3 * b + 2];
     return KPB_OK;
 }

@@ -177,7 +177,7 @@ struct kpb_ctx {
     int alike_coarse_fused = 1;                     // KPB_OPT_ALIKE_COARSE_FUSED
     int detect_signed = 0;                          // KPB_OPT_DETECT_SIGNED
 };
-enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u, KPB_ATTR_NMS_ROUND = 16u };
+enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u, KPB_ATTR_NMS_ROUND = 16u, KPB_ATTR_SELECT = 32u };
 
 extern char g_kpb_err[512];
 
