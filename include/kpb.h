@@ -229,6 +229,20 @@ int kpb_lk_track_batch(kpb_ctx* ctx, const float* map1_dev, const float* map2_de
                        int max_n, const int32_t* n_dev, const kpb_lk_params* params,
                        float* out_pts_dev, float* out_err_dev);
 
+/* ---- the tracking error of tasks/VisualizeTrackingError.py:45-46 for `batch` pairs:
+ *     kps01_wh = kps01 * tensor([w - 1, h - 1]);  error = torch.norm(kps01_wh - kps1, dim=2)[0];  torch.mean(error)
+ * kps01_dev [batch][max_n][pts_stride] normalised (x, y, ...): the keypoints of view 0 warped into view 1; tracked_dev [batch][max_n][2] in pixels, as
+ * kpb_lk_track_batch returns them (its own out_err cannot serve: it is clamped at 8, matcher.py:73); n_dev [batch] on the device or NULL (= max_n; held to
+ * 0 .. max_n); scale_dev [batch][2] = (w - 1, h - 1) of the image the task was handed.
+ * out_err_dev [batch][max_n] = sqrt(dx dx + dy dy), dx = kps01.x * scale.x - tracked.x, every operation rounded to fp32 on its own; out_mean_dev [batch]
+ * float64 = the mean of the first n[j] errors, accumulated in float64 in one order that depends on n[j] only (one wave per pair: lane l sums rows l, l + 64,
+ * ... ascending, then a butterfly over the distances 32 .. 1), so a pair's bits are the same in any batch.  Rows past n[j] are not written; n[j] == 0 writes
+ * NaN as the mean (torch.mean of an empty tensor) and no error row.  No atomics, no workspace, asynchronous.
+ * Refusals: a null context, scale or mean pointer, a null point or error buffer with max_n > 0, pts_stride < 2, batch < 1, max_n < 0 (KPB_E_INVALID); more than
+ * 65535 pairs (KPB_E_UNSUPPORTED).  Messages begin "kpb_track_error:", and a refused call writes nothing. */
+int kpb_track_error(kpb_ctx* ctx, const float* kps01_dev, int pts_stride, const float* tracked_dev, int batch, int max_n,
+                    const int32_t* n_dev, const float* scale_dev, float* out_err_dev, double* out_mean_dev);
+
 /* ---- configs[3]: epipolar residual of the matches, tasks/FundamentalMatrix.py:137-161 ------------------------------
  * kps0_dev [batch][max_k][cols0] matched rows of image 0, normalised (x, y, ...): scaled to pixels (x (W-1), y (H-1), 1);
  * kps1_dev [batch][max_k][cols1] matched rows of image 1 as the reference's matcher branch leaves them --
@@ -312,6 +326,7 @@ int kpb_preprocess(kpb_ctx* ctx, const uint8_t* src_dev, int batch, int Hs, int 
 #define KPB_ARCH_R2D2 6         /* models/r2d2.py       Quad_L2Net_ConfCFS (dilated, full resolution), BN folded; any H, W */
 #define KPB_ARCH_EDGEPOINT 7    /* models/EdgePoint.py  EdgePoint (ALIKE-t trunk, plan 8,16,32,64 / 64), BN folded; raw-logit score (KPB_OPT_DETECT_SIGNED), 64-channel map at H/8 x W/8 */
 #define KPB_ARCH_GOODPOINT 8    /* models/GoodPoint.py  GoodPoint (ALIKE-t's block 1, plan c0 = 3, c1 = 8), BN folded; H, W multiples of 32; sigmoid score and a sigmoid 3-channel map at full resolution, not normalised: the map the tracker follows (kpb_lk_track_batch); desc_out_dev 16-byte aligned */
+#define KPB_ARCH_LETNET 9       /* models/LETNet.py     LETNet(c1 = 8, c2 = 16, grayscale = False) (ALIKE-t's block 1, then two 1 x 1 convolutions, 8 -> 16 -> 4), BN folded; H, W multiples of 32; the sigmoid of channels 0..2 is the 3-channel map at full resolution the tracker follows, that of channel 3 the score; desc_out_dev 16-byte aligned, NULL gives the score only */
 int kpb_net_create(kpb_ctx* ctx, int arch, const void* blob, size_t len, kpb_net** out);
 void kpb_net_destroy(kpb_net* net);
 int kpb_net_desc_dim(const kpb_net* net);   /* descriptor channels C */

@@ -68,6 +68,7 @@ SIGNATURES = {
                              c_void_p, c_void_p, c_void_p]),
     "kpb_lk_track_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                    c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "kpb_track_error": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "kpb_epipolar_error": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                    c_float, c_void_p, c_void_p]),
     "kpb_find_homography": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_uint32,

@@ -2096,6 +2096,66 @@ __global__ __launch_bounds__(256) void goodpoint_head(GpHeadArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ LETNet head
+// LETNet (models/LETNet.py:47-52) puts two 1 x 1 convolutions without bias on block 1's features x1: t = relu(conv1(x1)), 8 -> 16, z = conv_head(t), 16 -> 4;
+// map = sigmoid(z[0..2]), score = sigmoid(z[3]) -- the score is channel 3 of the vector the map is cut from, so z is computed once.  fp32 fmaf chains in one fixed
+// order (input channel ascending from 0 in both layers: z takes t[o] as soon as it exists), the same code in the split-f16 and the strict-fp32 build; a pixel reads
+// nothing but itself, so its bits depend on neither tile nor batch.
+// A pure HBM stream without halo: 32 bytes of x1 read, 4 + 12 written per pixel (goodpoint_head's bytes) for 192 multiply-adds (twice its 96).  Nothing is staged: a
+// lane loads its pixel's two float4 directly (a wave's row of 64 pixels is 2 KB contiguous), four rows a wave with all eight loads issued before the arithmetic.
+// The tile, the four-waves-by-four-rows split and the map's way out are goodpoint_head's: rows formed in the wave's own piece of `dst`, stored as float4 row pieces
+// into [B][H][W][3] behind a wave barrier.
+// w: conv1 [o][c] (128), then conv_head [k][o] (64); wave-uniform and never written by a kernel: scalar loads through the constant address space.  Measured 1.44 ms per 512 images of 480 x 640 beside goodpoint_head's 1.67 in one process (5.2 TB/s; 57 registers, no scratch), DESIGN.md 5.
+constexpr int LET_WHEAD = 128;
+struct LetHeadArgs { const float* x1; float* score; float* desc; const float* w; int H, W; };     // desc null: score only
+__global__ __launch_bounds__(256) void letnet_head(LetHeadArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float dst[4][GP_RPT * GP_TW * 3];
+    typedef const __attribute__((address_space(4))) float* cfp;
+    const cfp w = (cfp)a.w;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, H = a.H, W = a.W;
+    const int tx0 = blockIdx.x * GP_TW, xo = tx0 + lane, yw = blockIdx.y * GP_TH + wv * GP_RPT;
+    const size_t img = (size_t)blockIdx.z * H * W;
+    float4 lo[GP_RPT], hi[GP_RPT];
+#pragma unroll
+    for (int r = 0; r < GP_RPT; ++r) {
+        lo[r] = hi[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (xo < W && yw + r < H) {
+            const float4* p = reinterpret_cast<const float4*>(a.x1 + (img + (size_t)(yw + r) * W + xo) * 8);
+            lo[r] = p[0]; hi[r] = p[1];
+        }
+    }
+    float* ds = dst[wv];
+#pragma unroll
+    for (int r = 0; r < GP_RPT; ++r) {
+        const float x[8] = {lo[r].x, lo[r].y, lo[r].z, lo[r].w, hi[r].x, hi[r].y, hi[r].z, hi[r].w};
+        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int o = 0; o < 16; ++o) {
+            float t = 0.0f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) t = fmaf(w[o * 8 + c], x[c], t);
+            t = fmaxf(t, 0.0f);                                         // (LETNet.py:47)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) z[k] = fmaf(w[LET_WHEAD + k * 16 + o], t, z[k]);
+        }
+        if (xo < W && yw + r < H) a.score[img + (size_t)(yw + r) * W + xo] = __fdiv_rn(1.0f, 1.0f + expf(-z[3]));      // torch.sigmoid (LETNet.py:50)
+        if (a.desc) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ds[r * (GP_TW * 3) + lane * 3 + k] = __fdiv_rn(1.0f, 1.0f + expf(-z[k]));      // (LETNet.py:51)
+        }
+    }
+    if (!a.desc) return;
+    __builtin_amdgcn_wave_barrier();
+    const int vw = min(GP_TW, W - tx0) * 3;      // floats of a row piece inside the image: W is a multiple of 32, so of 4 floats too
+#pragma unroll
+    for (int k = 0; k < GP_RPT * GP_TW * 3 / 4 / 64; ++k) {
+        const int f = k * 64 + lane, r = f / (GP_TW * 3 / 4), c4 = (f - r * (GP_TW * 3 / 4)) * 4;
+        if (c4 < vw && yw + r < H)
+            *reinterpret_cast<float4*>(a.desc + (img + (size_t)(yw + r) * W + tx0) * 3 + c4) = *reinterpret_cast<const float4*>(ds + r * (GP_TW * 3) + c4);
+    }
+}
+
 }  // namespace
 
 // ================================================================================================ host side
@@ -2674,6 +2734,64 @@ int goodpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
             for (int c = 0; c < 8; ++c) tmp[k * 8 + c] = wsr[c * 9 + k];
         for (int i = 0; i < 24; ++i) tmp[GP_WDESC + i] = wd[i];
         ws.put(tmp, &net->kg.w);
+    }
+    if (int rc = ws.upload(ctx, &net->wdev)) return rc;
+    *out = net.release();
+    return KPB_OK;
+}
+
+// ================================================================================================ LETNet: block 1, its own head
+namespace {
+
+struct LetNet : AlikeBlock1 {
+    struct { const float* w; } kl = {};       // letnet_head's weights
+    int forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev) override;
+};
+
+// GoodPointNet::forward with another head launch
+int LetNet::forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev)
+{
+    if ((H_ % 32) || (W_ % 32))     // block 1's contract (its 2 x 2 pooled output and tiles), as for ALIKE, EdgePoint and GoodPoint
+        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: LETNet needs H and W multiples of 32 (got %dx%d)", H_, W_);
+    if (batch > 65535) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_net_forward: LETNet: at most 65535 images a call (got %d)", batch);
+    if (reinterpret_cast<uintptr_t>(desc_out_dev) & 15)     // letnet_head stores the map's rows as float4
+        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: LETNet: desc_out_dev must be 16-byte aligned");
+    const size_t P = (size_t)H_ * W_, B = batch;
+    const bool h16 = conv_mfma_use_h16();
+    B1Bufs b{};
+    if (int rc = kpb_carve(ctx, act, [&](Arena& a) {
+            x1 = a.take(B * P * 8);
+            b.p1 = a.take(B * (P / 4) * 8);
+            b.amax_x1 = h16 ? a.take<unsigned>(B) : nullptr;
+            b.wmax_x1 = h16 ? a.take(B * b1_waves(H_, W_)) : nullptr;
+        }))
+        return rc;
+    this->B = batch; this->H = H_; this->W = W_;
+    block1(img_dev, batch, H_, W_, b);
+    LetHeadArgs g{x1, score_out_dev, desc_out_dev, kl.w, H_, W_};     // (a null map: the repeatability task needs the score only)
+    KPB_LAUNCH(ctx, "letnet_head", letnet_head, dim3(cdiv(W_, GP_TW), cdiv(H_, GP_TH), batch), dim3(256), 0, ctx->stream, g);
+    KPB_HIP(ctx, hipGetLastError());
+    return KPB_OK;
+}
+
+}  // namespace
+
+int letnet_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
+{
+    const std::vector<Need> need = {{"b1c1.w", {c1, 3, 3, 3}}, {"b1c1.b", {c1}}, {"b1c2.w", {c1, c1, 3, 3}}, {"b1c2.b", {c1}}, {"let.conv1.w", {16, c1}},
+                                    {"let.head.w", {4, 16}}};
+    for (auto& nd : need)
+        if (!bl.get(nd.n, nd.d))
+            return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not LETNet shaped (this build supports c1 = 8, c2 = 16, colour input)", nd.n);
+    auto net = std::make_unique<LetNet>();
+    net->ctx = ctx; net->arch = KPB_ARCH_LETNET; net->dim = 3; net->desc_div = 1;
+    WeightStage ws;
+    block1_stage(bl, ws, net.get());
+    {   // letnet_head's weights: conv1 [o][c], then conv_head [k][o], both as they are
+        const float *w1 = bl.get("let.conv1.w", {16, c1}), *w2 = bl.get("let.head.w", {4, 16});
+        std::vector<float> tmp(w1, w1 + LET_WHEAD);
+        tmp.insert(tmp.end(), w2, w2 + 64);
+        ws.put(tmp, &net->kl.w);
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     *out = net.release();

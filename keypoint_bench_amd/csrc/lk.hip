@@ -229,7 +229,44 @@ int lk_run(kpb_ctx* ctx, const char* who, const float* map1_dev, const float* ma
     return KPB_OK;
 }
 
+// kpb_track_error: one wave per pair (blockIdx.x).  The error of a row is the reference's three fp32 tensor operations (VisualizeTrackingError.py:45-46: a
+// multiply, a subtraction, the norm of two components), each rounded on its own -- nothing contracted into an fma.  The mean is a float64 sum in one fixed order:
+// lane l adds rows l, l + 64, ... ascending, then the butterfly 32 .. 1 (a + b is commutative, so every lane ends with the same bits).
+__global__ __launch_bounds__(64) void lk_track_error(const float* __restrict__ kps01, int stride, const float* __restrict__ tracked, const int32_t* n_dev, int max_n,
+                                                     const float* __restrict__ scale, float* __restrict__ out_err, double* __restrict__ out_mean)
+{
+    const int lane = threadIdx.x, j = blockIdx.x, n = pair_n(n_dev, j, max_n);
+    const float sx = scale[2 * j], sy = scale[2 * j + 1];
+    double s = 0.0;
+    for (int i = lane; i < n; i += 64) {
+        const size_t r = (size_t)j * max_n + i;
+        const float dx = __fsub_rn(__fmul_rn(kps01[r * stride], sx), tracked[2 * r]);
+        const float dy = __fsub_rn(__fmul_rn(kps01[r * stride + 1], sy), tracked[2 * r + 1]);
+        const float e = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));       // sqrtf: correctly rounded (__fsqrt_rn is the 1-ulp native root here)
+        out_err[r] = e;
+        s += (double)e;
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) out_mean[j] = n > 0 ? s / (double)n : __longlong_as_double(0x7ff8000000000000ll);
+}
+
 }  // namespace
+
+extern "C" __attribute__((visibility("default"))) int kpb_track_error(
+    kpb_ctx* ctx, const float* kps01_dev, int pts_stride, const float* tracked_dev, int batch, int max_n, const int32_t* n_dev, const float* scale_dev,
+    float* out_err_dev, double* out_mean_dev)
+{
+    if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_track_error: null context");
+    if (!scale_dev || !out_mean_dev || pts_stride < 2 || batch <= 0 || max_n < 0) return kpb_fail(ctx, KPB_E_INVALID, "kpb_track_error: bad argument");
+    if (max_n > 0 && (!kps01_dev || !tracked_dev || !out_err_dev)) return kpb_fail(ctx, KPB_E_INVALID, "kpb_track_error: null buffer");
+    if (batch > 65535) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_track_error: at most 65535 pairs a call (got %d)", batch);
+    KPB_HIP(ctx, hipSetDevice(ctx->device));
+    KPB_LAUNCH(ctx, "lk_track_error", lk_track_error, dim3(batch), dim3(64), 0, ctx->stream, kps01_dev, pts_stride, tracked_dev, n_dev, max_n, scale_dev,
+               out_err_dev, out_mean_dev);
+    KPB_HIP(ctx, hipGetLastError());
+    return KPB_OK;
+}
 
 extern "C" __attribute__((visibility("default"))) int kpb_lk_track(
     kpb_ctx* ctx, const float* img1_dev, const float* img2_dev, int C, int H, int W, const float* pts1_dev, const float* pts2_dev,

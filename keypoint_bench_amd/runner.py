@@ -8,7 +8,7 @@ all-gather (RCCL on GPUs, gloo in the CPU tests) moves the rows; rank 0 reduces 
 on_test_end would.  There is no other communication: weights are replicated and pairs are independent.
 
 Tasks (`task_type`): ``repeatability``, ``MHA``, ``AUC``, ``FundamentalMatrix``, ``FundamentalMatrixRansac`` and
-``visual_odometer`` run on the device end to end, the robust-geometry stages included (csrc/geometry.hip restates the
+``visual_odometer`` and ``VisualizeTrackingError`` run on the device end to end, the robust-geometry stages included (csrc/geometry.hip restates the
 OpenCV calls of the reference's tasks; parity unpinned, see utils/mvg.py); ``match_stats`` is a dependency-free task used
 by bench.py and the tests: it returns [n_kps0, n_kps1, n_matches].  Any other metric function can be passed in through
 ``task_fn`` (it then runs pair by pair), and ``install()`` swaps this package's kernels under an importable reference
@@ -50,7 +50,8 @@ _MODELS = {"Alike": ("ALike", lambda m, p, dense: m.ALNet(p, dense_descriptors=d
            "DISK": ("disk", lambda m, p, dense: m.DISK(), "DISK_params", "extractor", _NOT_SHIPPED),
            "r2d2": ("r2d2", None, "r2d2_params", None, ""),
            "EdgePoint": ("EdgePoint", lambda m, p, dense: m.EdgePoint(p), "EdgePoint_params", None, ""),
-           "GoodPoint": ("GoodPoint", lambda m, p, dense: m.GoodPoint(p), "GoodPoint_params", None, "")}
+           "GoodPoint": ("GoodPoint", lambda m, p, dense: m.GoodPoint(p), "GoodPoint_params", None, ""),
+           "LETNet": ("LETNet", lambda m, p, dense: m.LETNet(c1=8, c2=16, grayscale=False), "LETNet_params", None, "")}      # model_interface.py:57
 
 
 def build_model(params, dense_descriptors=True):
@@ -59,7 +60,7 @@ def build_model(params, dense_descriptors=True):
     import importlib
     mt = params["model_type"]
     if mt not in _MODELS:
-        raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint, GoodPoint)" % (mt,))
+        raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint, GoodPoint, LETNet)" % (mt,))
     mod, make, pkey, sub, missing = _MODELS[mt]
     mod = importlib.import_module("keypoint_bench_amd.models." + mod)
     p = params.get(pkey) or {}
@@ -171,6 +172,8 @@ def aggregate(task_type, rows, params=None):
         from .tasks.visual_odometer import compose
         r_est, t_est = compose(rows[:, :13])
         return {"r_est": r_est, "t_est": t_est}
+    if task_type == "VisualizeTrackingError":     # rows: [track_error, tracked points] (model_interface.py:146-150)
+        return {"track_error": float(np.mean(rows[:, 0]))}
     if task_type == "match_stats":        # rows: [n0, n1, matches]
         return {"mean_kps": float(rows[:, :2].mean()), "mean_matches": float(rows[:, 2].mean())}
     raise NotImplementedError(task_type)
@@ -342,8 +345,17 @@ def fund_ransac_row(idx, img0, score0, desc0, img1, score1, desc1, warp01, warp1
     return [float(r["fundamental_error"]), float(r["fundamental_radio"]), float(r["fundamental_num"])]
 
 
+def tracking_error_row(idx, img0, score0, desc0, img1, score1, desc1, warp01, warp10, params, tracked_maps=False):
+    """model_interface.py:231-241: [track_error, tracked points].  The tracker follows the net's maps when the net makes them for it (`tracked_maps`:
+    LETNet, GoodPoint), the two images the task was handed otherwise; img0 scales the warped keypoints either way."""
+    from .tasks.VisualizeTrackingError import visualize_tracking_error
+    m0, m1 = (desc0, desc1) if tracked_maps else (img0, img1)
+    r = visualize_tracking_error(idx, img0, score0, m0, m1, params, warp01)
+    return [float(r["track_error"]), float(r["kps0"].shape[0])]
+
+
 TASKS = {"repeatability": repeatability_row, "MHA": mha_row, "AUC": auc_row, "match_stats": match_stats,
-         "FundamentalMatrixRansac": fund_ransac_row}
+         "FundamentalMatrixRansac": fund_ransac_row, "VisualizeTrackingError": tracking_error_row}
 
 
 # ---- the same tasks over a whole PairPipeline batch (rows equal to the single-pair functions above)
@@ -377,6 +389,11 @@ def _batched_fund_ransac(pipe, items, params, indices=None):
     return fundamental_ransac_batch(pipe, items, params, indices)
 
 
+def _batched_tracking_error(pipe, items, params, indices=None):
+    from .tasks.VisualizeTrackingError import tracking_error_batch
+    return tracking_error_batch(pipe, items, params, indices)
+
+
 def _covis_tables(items, B, dev):
     """(hmat [2B,9], wh [2B,2]) of the MHA flow: rows 0..B-1 warp01 of each pair, B..2B-1 warp10 (padded by repetition)."""
     from .tasks.repeatability import homography_tables
@@ -389,13 +406,23 @@ def _covis_tables(items, B, dev):
 # task -> (rows function, pipeline needs the match stage, keypoints are covisibility-filtered before matching)
 BATCHED_TASKS = {"match_stats": (_batched_match_stats, True, False), "repeatability": (_batched_repeatability, False, False),
                  "MHA": (_batched_mha, True, True), "AUC": (_batched_auc, True, False),
-                 "FundamentalMatrixRansac": (_batched_fund_ransac, True, False)}
+                 "FundamentalMatrixRansac": (_batched_fund_ransac, True, False),
+                 "VisualizeTrackingError": (_batched_tracking_error, False, False)}      # (its pipeline tracks instead: PairPipeline(track=...))
 ANY_WARP_TASKS = ("AUC", "FundamentalMatrixRansac")      # their batched rows take se3 warps too; every other batched task needs homographies
+TRACK_TASK = "VisualizeTrackingError"
 _STAGED_DTYPES = (np.dtype(np.uint8), np.dtype(np.float32))      # what the staging ring carries
 
 
 def _homo_only(item):
     return all(item.get(k, {}).get("mode", "homo") == "homo" for k in ("warp01_params", "warp10_params"))
+
+
+def _trackable(item, v):
+    """TRACK_TASK batches a pair only when it CARRIES a homography warp01 (without one the task tracks kps0 onto itself: the single-pair path) and its views
+    need no crop: the task is handed the uncropped images (model_interface.py:234-240) -- they scale the warped keypoints, and a net without tracked_maps is
+    tracked on them."""
+    from .tasks.MHA import _raw_hw
+    return bool(item.get("warp01_params")) and all(_raw_hw(item[k]) == tuple(_view_key(c)[1:]) for k, c in (("image0", v[0]), ("image1", v[1])))
 
 
 def _view_key(a):
@@ -418,10 +445,13 @@ def plan_pairs(items, task_type, batch, batched, views):
     `batch` consecutive pairs whose cropped views share one _view_key.  `views(item)` gives the two cropped views or None (not
     batchable); it is all that differs by residency, and whatever touches a device happens inside it.  Single: nothing is batched, the
     task needs homographies and the item has another warp, no views, or two views of different keys.  The open group is flushed when
-    the key changes, when it is full, before every single and at the end.  Lazy: the consumer acts on an event before the next item."""
+    the key changes, when it is full, before every single and at the end.  Lazy: the consumer acts on an event before the next item.
+    Under TRACK_TASK a pair is single as well when it carries no warp01 or a view would be cropped (_trackable)."""
     group, key = [], None
     for i, item in items:
         v = views(item) if batched and (task_type in ANY_WARP_TASKS or _homo_only(item)) else None
+        if v is not None and task_type == TRACK_TASK and not _trackable(item, v):
+            v = None
         k = _view_key(v[0]) if v is not None else None
         if k is not None and k != _view_key(v[1]):
             k = None
@@ -508,6 +538,8 @@ class PairRunner:
             s0, d0 = self.model(img0)     # model_interface.py:205-207
             s1, d1 = self.model(img1)
         kw = {"matcher": self.matcher} if self.task_fn is fund_ransac_row else {}
+        if self.task_fn is tracking_error_row:      # model_interface.py:233-240: the net's maps for the nets that make them for the tracker, the images otherwise
+            kw = {"tracked_maps": bool(getattr(self.model, "tracked_maps", False))}
         # the tasks get the UNCROPPED images, as model_interface.py:242-259 hands batch['image0'] / batch['image1'] over
         # (MHA.py:59-60 takes its resize factors from their shape)
         with self._signed_scope():
@@ -561,14 +593,14 @@ class PairRunner:
         return r
 
     # ---- batched pairs
-    def _pipe(self, B, H, W, match, lightglue=None):
+    def _pipe(self, B, H, W, match, lightglue=None, track=None):
         from .pipeline import PairPipeline
-        key = (B, H, W, match)
+        key = (B, H, W, match) if track is None else (B, H, W, match, "track")
         if key not in self._pipes:
             self._pipes = {k: v for k, v in self._pipes.items() if k[1:3] == (H, W)}      # one resolution resident at a time
             mp = self.params.get("matcher_params", {})
             bf = mp.get("brute_force_params", dict(metric="euclidean", max_distance=float("inf"), cross_check=True))
-            self._pipes[key] = (PairPipeline(self.model, self.params["extractor_params"], bf, B, H, W, device=self.device, match=match),
+            self._pipes[key] = (PairPipeline(self.model, self.params["extractor_params"], bf, B, H, W, device=self.device, match=match, track=track),
                                 torch.empty((2 * B, 3, H, W), dtype=torch.float32, device=self.device))
         return self._pipes[key]
 
@@ -581,7 +613,8 @@ class PairRunner:
         u8 = is_decoded_u8(group[0][2])
         H, W = group[0][2].shape[:2] if u8 else group[0][2].shape[-2:]
         B = self.batch if f > self.batch // 2 else f        # a short tail gets a pipeline of its own size
-        pipe, images = self._pipe(B, H, W, match)
+        track = self.params["matcher_params"]["optical_flow_params"] if task_type == TRACK_TASK else None
+        pipe, images = self._pipe(B, H, W, match, track=track)
         if staged is not None:      # the group's images, already on the device (copied on the staging stream)
             if u8:                  # decoded bytes: the datasets' transform on the device
                 from .utils.preprocess import to_tensor_resized
@@ -596,7 +629,11 @@ class PairRunner:
             images[j].copy_(images[f - 1])
             images[B + j].copy_(images[B + f - 1])
         items = [g[1] for g in group]
-        pipe.enqueue(images, _covis_tables(items, B, self.device) if covis else None)
+        if track is not None:       # warp01 of every pair (padded by repetition): the tracker's targets
+            from .tasks.repeatability import homography_tables
+            pipe.enqueue(images, homography_tables([it["warp01_params"] for it in items] + [items[-1]["warp01_params"]] * (B - f), self.device)[:2])
+        else:
+            pipe.enqueue(images, _covis_tables(items, B, self.device) if covis else None)
         return fn, pipe, items, [g[0] for g in group]
 
     def _end(self, token):
@@ -621,6 +658,8 @@ class PairRunner:
         if task_type == "FundamentalMatrixRansac":          # the batched rows are the brute-force branch without cv2 drawing
             mp = self.params["matcher_params"]
             batched = batched and mp["type"] == "brute_force" and not mp.get("save_result") and not self.params["extractor_params"].get("save_result")
+        if task_type == TRACK_TASK:                         # the batched rows are the tensor tracker's (the single-pair path refuses every other matcher)
+            batched = batched and self.params["matcher_params"]["type"] == "optical_flow"
         if batched and len(indices) > 0 and _host_array(dataset[indices[0]]["image0"]) is not None:
             return self._run_pairs_staged(dataset, indices, task_type)
         ledger, inflight = RowLedger(), None         # (group, token): a batch whose kernels are running while the planner collects the next group
@@ -825,6 +864,8 @@ class PairRunner:
         sequence = n > 0 and is_sequence_item(dataset[0])
         shard = shard_chunk if sequence else shard_indices
         indices = shard(n, rank, world)
+        if sequence and task_type == TRACK_TASK:
+            raise NotImplementedError("VisualizeTrackingError measures pair datasets (a ground-truth warp01 per pair); a sequence item carries none")
         if sequence:
             self.results = self._run_sequence(dataset, indices, "visual_odometer" if task_type == "visual_odometer" else "FundamentalMatrix")
         else:

@@ -131,10 +131,31 @@ class OpticalFlow(object):
         return out.unsqueeze(0), err.unsqueeze(0)
 
 
-def optical_flow_tensor(pts0, pts1, img0, img1, params=None):
-    """utils/matcher.py:186-203."""
-    pts1_, _ = OpticalFlow(params)(img0, img1, pts0, pts1)
+def optical_flow_tensor(pts0, pts1, img0, img1, params=None, random_angle=None):
+    """utils/matcher.py:186-203.  random_angle [n]: the tracker's start angles (drawn as the reference draws them when missing)."""
+    pts1_, _ = OpticalFlow(params)(img0, img1, pts0, pts1, random_angle=random_angle)
     return pts1_
+
+
+def track_error(kps01, tracked, scale, n=None):
+    """tasks/VisualizeTrackingError.py:45-46 for B pairs in one kpb_track_error call: kps01 [B,K,>=2] normalised warped keypoints, tracked [B,K,2] pixels (what
+    optical_flow_batch returns), scale [B,2] = (w - 1, h - 1), n [B] int32 on the device or None (= K).  Returns (error [B,K] fp32, mean [B] float64); rows past
+    n[j] are left as allocated, a pair without rows has a NaN mean."""
+    if not tracked.is_cuda:
+        raise RuntimeError("keypoint_bench_amd needs CUDA/HIP tensors; there is no CPU path")
+    if kps01.dim() != 3 or kps01.shape[-1] < 2 or tracked.shape != kps01.shape[:2] + (2,) or scale.shape != (kps01.shape[0], 2):
+        raise ValueError("kps01 [B,K,>=2], tracked [B,K,2], scale [B,2]")
+    dev = tracked.device
+    a = kps01.detach().to(torch.float32).contiguous()
+    b = tracked.detach().to(torch.float32).contiguous()
+    s = scale.detach().to(torch.float32).contiguous()
+    B, K = a.shape[:2]
+    err = torch.empty((B, K), dtype=torch.float32, device=dev)
+    mean = torch.empty((B,), dtype=torch.float64, device=dev)
+    if B:
+        ctx = Context.get(dev)
+        ctx.check(ctx.lib.kpb_track_error(ctx.handle, ptr(a), a.shape[2], ptr(b), B, K, ptr(n), ptr(s), ptr(err), ptr(mean)))
+    return err, mean
 
 
 def optical_flow_batch(maps1, maps2, pts1, pts2, n, params, random_angle=None):

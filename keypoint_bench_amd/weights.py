@@ -20,6 +20,7 @@ ARCH_LIGHTGLUE = 5
 ARCH_R2D2 = 6
 ARCH_EDGEPOINT = 7
 ARCH_GOODPOINT = 8
+ARCH_LETNET = 9
 _REC = struct.Struct("<40sI4II")
 
 
@@ -141,6 +142,31 @@ def fold_goodpoint(sd) -> dict:
     t["b1c2.w"], t["b1c2.b"] = _fold(sd, "block.conv2", "block.bn2")
     t["gp.desc.w"] = _np(sd["conv_head1.weight"]).astype(np.float32).reshape(3, c1)
     t["gp.score.w"] = _np(sd["conv_head2.weight"]).astype(np.float32).reshape(c1, 3, 3)
+    return t
+
+
+LETNET_PLAN = dict(c1=8, c2=16, grayscale=False)
+
+
+def fold_letnet(sd) -> dict:
+    """state_dict of LETNet (models/LETNet.py:31-42) -> block 1 folded under the names fold_alike gives it (b1c1.w/.b, b1c2.w/.b: the reference's ConvBlock(3, 8)
+    is ALIKE-t's block 1 once more), plus the two 1 x 1 convolutions as they are: let.conv1.w [16][8] (conv1, no bias) and let.head.w [4][16] (conv_head, no bias;
+    rows 0..2 the map, row 3 the score).  Refused: a missing or mis-shaped tensor, any plan but c1 = 8, c2 = 16 on colour input."""
+    c1, c2 = LETNET_PLAN["c1"], LETNET_PLAN["c2"]
+    need = {"block1.conv1.weight": (c1, 3, 3, 3), "block1.conv2.weight": (c1, c1, 3, 3), "conv1.weight": (c2, c1, 1, 1), "conv_head.weight": (4, c2, 1, 1)}
+    for bn in ("bn1", "bn2"):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            need["block1.%s.%s" % (bn, leaf)] = (c1,)
+    for key, shape in need.items():
+        if key not in sd:
+            raise ValueError("LETNet state_dict: %s is missing" % key)
+        if tuple(sd[key].shape) != shape:
+            raise ValueError("LETNet state_dict: %s has shape %s, the supported plan (c1 = 8, c2 = 16, grayscale = False) needs %s" % (key, tuple(sd[key].shape), shape))
+    t = {}
+    t["b1c1.w"], t["b1c1.b"] = _fold(sd, "block1.conv1", "block1.bn1")
+    t["b1c2.w"], t["b1c2.b"] = _fold(sd, "block1.conv2", "block1.bn2")
+    t["let.conv1.w"] = _np(sd["conv1.weight"]).astype(np.float32).reshape(c2, c1)
+    t["let.head.w"] = _np(sd["conv_head.weight"]).astype(np.float32).reshape(4, c2)
     return t
 
 
