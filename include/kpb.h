@@ -327,6 +327,7 @@ int kpb_preprocess(kpb_ctx* ctx, const uint8_t* src_dev, int batch, int Hs, int 
 #define KPB_ARCH_EDGEPOINT 7    /* models/EdgePoint.py  EdgePoint (ALIKE-t trunk, plan 8,16,32,64 / 64), BN folded; raw-logit score (KPB_OPT_DETECT_SIGNED), 64-channel map at H/8 x W/8 */
 #define KPB_ARCH_GOODPOINT 8    /* models/GoodPoint.py  GoodPoint (ALIKE-t's block 1, plan c0 = 3, c1 = 8), BN folded; H, W multiples of 32; sigmoid score and a sigmoid 3-channel map at full resolution, not normalised: the map the tracker follows (kpb_lk_track_batch); desc_out_dev 16-byte aligned */
 #define KPB_ARCH_LETNET 9       /* models/LETNet.py     LETNet(c1 = 8, c2 = 16, grayscale = False) (ALIKE-t's block 1, then two 1 x 1 convolutions, 8 -> 16 -> 4), BN folded; H, W multiples of 32; the sigmoid of channels 0..2 is the 3-channel map at full resolution the tracker follows, that of channel 3 the score; desc_out_dev 16-byte aligned, NULL gives the score only */
+#define KPB_ARCH_KEYNET 10      /* models/KeyNet.py     KeyNet(num_filters = 8, num_levels = 3, kernel_size = 5): a detector -- three pyramid levels (1.2 x), ten handcrafted gradient features and three 5 x 5 layers per level (BN folded), a 24 -> 1 fusion layer; any H, W >= 16; non-negative UNBOUNDED score, no descriptors (dim 0): desc_out_dev is ignored and may be NULL */
 int kpb_net_create(kpb_ctx* ctx, int arch, const void* blob, size_t len, kpb_net** out);
 void kpb_net_destroy(kpb_net* net);
 int kpb_net_desc_dim(const kpb_net* net);   /* descriptor channels C */

@@ -112,3 +112,4 @@ int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int edgepoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int goodpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int letnet_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
+int keynet_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);

@@ -19,6 +19,12 @@ PLACE_CANDIDATES = 4            # allocations compared (the first included), as 
 PLACE_HEADROOM = 12 << 30       # bytes that must stay free while the candidates exist (workspaces of the first forward, the caller's tensors)
 
 
+def no_descriptors(net, what):
+    """The refusal of everything that matches descriptors for a net that has none (Key.Net: dim = 0) -- raised before any kernel is asked for a zero-width match."""
+    return ValueError("%s has no descriptors (dim = 0): %s needs them; such a net feeds detection, the repeatability task (match=False) and the "
+                      "Lucas-Kanade tracker on the frames (track=...)" % (type(net).__name__, what))
+
+
 class _Core:
     """What the two pipelines share: the parameters, the facts of the net, the buffer set, and the three stages as methods over tensor
     views and an image count.  The pipelines differ in slot layout only: [2B] split at B, against [F+1] shifted by one."""
@@ -110,6 +116,8 @@ class PairPipeline(_Core):
             brute_force_params = dict(metric="euclidean", max_distance=float("inf"), cross_check=True)
         super().__init__(net, extractor_params, brute_force_params, H, W, device)
         self.B, self.match = int(batch), bool(match) and track is None
+        if self.match and self.C == 0:
+            raise no_descriptors(net, "PairPipeline with matching on")
         if track is not None and net.tracked_maps and not (self.dense and self.div == 1):
             raise ValueError("a net with tracked_maps writes a full-resolution descriptor map")
         self._buffers(2 * self.B, 2 * self.B, self.B, torch.empty)
@@ -284,6 +292,8 @@ class SequencePipeline(_Core):
             brute_force_params = dict(metric="euclidean", max_distance=float("inf"), cross_check=True)
         super().__init__(net, extractor_params, brute_force_params, H, W, device)
         self.F = int(frames)
+        if track is None and self.C == 0:
+            raise no_descriptors(net, "SequencePipeline without track=...")
         if track is not None and net.tracked_maps and not (self.dense and self.div == 1):
             raise ValueError("a net with tracked_maps writes a full-resolution descriptor map")
         self._buffers(self.F, self.F + 1, self.F, torch.zeros)      # slot 0 is read before it is ever written

@@ -51,7 +51,10 @@ _MODELS = {"Alike": ("ALike", lambda m, p, dense: m.ALNet(p, dense_descriptors=d
            "r2d2": ("r2d2", None, "r2d2_params", None, ""),
            "EdgePoint": ("EdgePoint", lambda m, p, dense: m.EdgePoint(p), "EdgePoint_params", None, ""),
            "GoodPoint": ("GoodPoint", lambda m, p, dense: m.GoodPoint(p), "GoodPoint_params", None, ""),
-           "LETNet": ("LETNet", lambda m, p, dense: m.LETNet(c1=8, c2=16, grayscale=False), "LETNet_params", None, "")}      # model_interface.py:57
+           "LETNet": ("LETNet", lambda m, p, dense: m.LETNet(c1=8, c2=16, grayscale=False), "LETNet_params", None, ""),      # model_interface.py:57
+           # the checkpoint is {'state_dict', 'optimizer'}; the three plan keys sit beside `weight` in KeyNet_params
+           "KeyNet": ("KeyNet", lambda m, p, dense: m.KeyNet({k: p[k] for k in ("num_filters", "num_levels", "kernel_size") if k in p} or None), "KeyNet_params",
+                      "state_dict", "")}
 
 
 def build_model(params, dense_descriptors=True):
@@ -60,7 +63,7 @@ def build_model(params, dense_descriptors=True):
     import importlib
     mt = params["model_type"]
     if mt not in _MODELS:
-        raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint, GoodPoint, LETNet)" % (mt,))
+        raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint, GoodPoint, LETNet, KeyNet)" % (mt,))
     mod, make, pkey, sub, missing = _MODELS[mt]
     mod = importlib.import_module("keypoint_bench_amd.models." + mod)
     p = params.get(pkey) or {}
@@ -534,6 +537,9 @@ class PairRunner:
         if raw0.dim() == 3:
             raw0, raw1 = raw0[None], raw1[None]
         img0, img1 = crop32(raw0), crop32(raw1)
+        if getattr(self.model, "dim", None) == 0 and not self.user_task and self.task_fn not in (repeatability_row, tracking_error_row):
+            from .pipeline import no_descriptors
+            raise no_descriptors(self.model, "task %r" % (self.params.get("task_type", "match_stats"),))
         with torch.no_grad():
             s0, d0 = self.model(img0)     # model_interface.py:205-207
             s1, d1 = self.model(img1)
@@ -577,6 +583,9 @@ class PairRunner:
     def _sequence_task(self, idx, task_type, last_img, cur, s0, s1, d0, d1):
         from .tasks.FundamentalMatrix import fundamental_matrix
         mp = self.params["matcher_params"]
+        if d0 is None and mp["type"] != "optical_flow":       # a net without descriptors (Key.Net) can only be tracked
+            from .pipeline import no_descriptors
+            raise no_descriptors(self.model, "task %r with the %s matcher" % (task_type, mp["type"]))
         if task_type == "visual_odometer":    # 283-298: the per-frame motion; the chain is composed from the gathered rows
             from .tasks.visual_odometer import relative_motion, step_length
             R, t = relative_motion(idx, last_img, cur, s0, s1, d0, d1, self.matcher, self.params)

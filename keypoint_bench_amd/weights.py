@@ -21,6 +21,7 @@ ARCH_R2D2 = 6
 ARCH_EDGEPOINT = 7
 ARCH_GOODPOINT = 8
 ARCH_LETNET = 9
+ARCH_KEYNET = 10
 _REC = struct.Struct("<40sI4II")
 
 
@@ -168,6 +169,48 @@ def fold_letnet(sd) -> dict:
     t["let.conv1.w"] = _np(sd["conv1.weight"]).astype(np.float32).reshape(c2, c1)
     t["let.head.w"] = _np(sd["conv_head.weight"]).astype(np.float32).reshape(4, c2)
     return t
+
+
+KEYNET_PLAN = dict(num_filters=8, num_levels=3, kernel_size=5)
+
+
+def fold_keynet(sd, eps=1e-5) -> dict:
+    """state_dict of KeyNet (models/KeyNet.py:99-114; the checkpoint keeps it under 'state_dict') -> the folded tensors csrc/keynet.hip expects: l0 / l1 / l2
+    (.w [8][10 or 8][5][5], .b [8]) are the learnable block's Conv2d(bias) + eval-mode BatchNorm2d, w' = w g / sqrt(var + eps) and
+    b' = (b - mean) g / sqrt(var + eps) + beta per output channel, and last.w [1][24][5][5] / last.b [1] the fusion layer as it is (input channels
+    [level 0 | level 1 | level 2]).  num_batches_tracked is dropped.  Refused: a missing or mis-shaped tensor, any plan but 8 filters, 3 levels, 5 x 5."""
+    nf, nl, ks = (KEYNET_PLAN[k] for k in ("num_filters", "num_levels", "kernel_size"))
+    need = {"last_conv.0.weight": (1, nf * nl, ks, ks), "last_conv.0.bias": (1,)}
+    for i, cin in enumerate((10, nf, nf)):
+        p = "feature_extractor.lb_block.conv%d." % i
+        need.update({p + "0.weight": (nf, cin, ks, ks), p + "0.bias": (nf,)})
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            need[p + "1." + leaf] = (nf,)
+    for key, shape in need.items():
+        if key not in sd:
+            raise ValueError("KeyNet state_dict: %s is missing" % key)
+        if tuple(sd[key].shape) != shape:
+            raise ValueError("KeyNet state_dict: %s has shape %s, the supported plan (num_filters = 8, num_levels = 3, kernel_size = 5) needs %s"
+                             % (key, tuple(sd[key].shape), shape))
+    t = {}
+    for i in range(3):
+        p = "feature_extractor.lb_block.conv%d." % i
+        s = _np(sd[p + "1.weight"]) / np.sqrt(_np(sd[p + "1.running_var"]) + eps)
+        t["l%d.w" % i] = (_np(sd[p + "0.weight"]) * s[:, None, None, None]).astype(np.float32)
+        t["l%d.b" % i] = ((_np(sd[p + "0.bias"]) - _np(sd[p + "1.running_mean"])) * s + _np(sd[p + "1.bias"])).astype(np.float32)
+    t["last.w"] = _np(sd["last_conv.0.weight"]).astype(np.float32)
+    t["last.b"] = _np(sd["last_conv.0.bias"]).astype(np.float32)
+    return t
+
+
+def keynet_level_sizes(H, W, levels=3):
+    """[(h, w)] of the pyramid of models/KeyNet.py:85-96, 122-126: level l + 1 is (int(h // 1.2), int(w // 1.2)) of level l -- Python's float floor division,
+    which csrc/keynet.hip restates as floor(h / 1.2) in double (equal for every size from 8 to 8192: tests/test_keynet_cpu.py)."""
+    out = [(int(H), int(W))]
+    for _ in range(levels - 1):
+        h, w = out[-1]
+        out.append((int(h // 1.2), int(w // 1.2)))
+    return out
 
 
 def load_alike_t():
