@@ -85,10 +85,14 @@ int kpb_sync(kpb_ctx* ctx);
  *                              counts them -- and never return KPB_E_NEGATIVE: exact detection on raw logits and other signed responses.  On a non-negative map both
  *                              give the same rows; the rounds are slower.  With the option on, nms_dist > 0 and threshold < 0 are KPB_E_UNSUPPORTED (-0.0 is zero);
  *                              nms_dist == 0 is unchanged.  A kpb_detect(sync = 0) keeps the setting it was enqueued under.  Any other value is invalid.
+ *   KPB_OPT_SFD2_PROBE         0 (default).  A test hook: with 1 or 2 an SFD2 forward stops behind the grouped 3 x 3 layer of conv4's first ResBlock and leaves channels
+ *                              0..127 (1) or 128..255 (2) of that layer's output [B][H/4][W/4][256] in desc_out_dev, unnormalised; score_out_dev is not written
+ *                              (tests/test_gpu_sfd2.py: groups do not leak).  Any other value is invalid.
  * Returns KPB_E_INVALID for an unknown option or a negative value. */
 #define KPB_OPT_COVIS_STORE_BYTES 1
 #define KPB_OPT_ALIKE_COARSE_FUSED 2
 #define KPB_OPT_DETECT_SIGNED 3
+#define KPB_OPT_SFD2_PROBE 4
 int kpb_ctx_set_option(kpb_ctx* ctx, int option, int64_t value);
 
 /* Per-kernel timing for bench.py's roofline leg: when enabled every kernel launch is bracketed by two
@@ -328,6 +332,7 @@ int kpb_preprocess(kpb_ctx* ctx, const uint8_t* src_dev, int batch, int Hs, int 
 #define KPB_ARCH_GOODPOINT 8    /* models/GoodPoint.py  GoodPoint (ALIKE-t's block 1, plan c0 = 3, c1 = 8), BN folded; H, W multiples of 32; sigmoid score and a sigmoid 3-channel map at full resolution, not normalised: the map the tracker follows (kpb_lk_track_batch); desc_out_dev 16-byte aligned */
 #define KPB_ARCH_LETNET 9       /* models/LETNet.py     LETNet(c1 = 8, c2 = 16, grayscale = False) (ALIKE-t's block 1, then two 1 x 1 convolutions, 8 -> 16 -> 4), BN folded; H, W multiples of 32; the sigmoid of channels 0..2 is the 3-channel map at full resolution the tracker follows, that of channel 3 the score; desc_out_dev 16-byte aligned, NULL gives the score only */
 #define KPB_ARCH_KEYNET 10      /* models/KeyNet.py     KeyNet(num_filters = 8, num_levels = 3, kernel_size = 5): a detector -- three pyramid levels (1.2 x), ten handcrafted gradient features and three 5 x 5 layers per level (BN folded), a 24 -> 1 fusion layer; any H, W >= 16; non-negative UNBOUNDED score, no descriptors (dim 0): desc_out_dev is ignored and may be NULL */
+#define KPB_ARCH_SFD2 11        /* models/sfd2.py       ResSegNetV2(outdim = 128, require_stability = True), BN folded: conv1a .. conv3b (3 x 3, two of them stride 2), three ResBlocks at H/4 x W/4 (1 x 1, 3 x 3 in 32 groups of 8, 1 x 1 + identity), convPa / convPb -> 65 logits per 8 x 8 cell, convDa / convDb -> descriptors, ConvSta -> 3 stability logits; score = exp(logit) / (sum of the 65 + 1e-5), depth-to-space, times 0.1 / 0.5 / 1.0 by the argmax of the x 4 bilinearly upsampled stability logits; H, W multiples of 8; dim 128, desc_div 4: an L2-normalised 128-channel map at H/4 x W/4; desc_out_dev is required */
 int kpb_net_create(kpb_ctx* ctx, int arch, const void* blob, size_t len, kpb_net** out);
 void kpb_net_destroy(kpb_net* net);
 int kpb_net_desc_dim(const kpb_net* net);   /* descriptor channels C */

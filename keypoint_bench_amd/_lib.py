@@ -167,6 +167,7 @@ class Context:
     OPT_COVIS_STORE_BYTES = 1       # KPB_OPT_COVIS_STORE_BYTES
     OPT_ALIKE_COARSE_FUSED = 2      # KPB_OPT_ALIKE_COARSE_FUSED
     OPT_DETECT_SIGNED = 3           # KPB_OPT_DETECT_SIGNED
+    OPT_SFD2_PROBE = 4              # KPB_OPT_SFD2_PROBE (a test hook)
 
     def set_option(self, option: int, value: int):
         """kpb_ctx_set_option (include/kpb.h): a limit of this context, e.g. OPT_COVIS_STORE_BYTES."""

@@ -69,7 +69,9 @@ constexpr int CM_ESTRIDE = 68;          // floats of a projected pixel: 64 descr
 // (aux0, aux1) = (cos, sin) [row][32] and all three go out head-major as float2 (lightglue.py:71-78, 179-183).
 // GE_SPLIT2: output tiles from column 256 on go to out1 (two Linears over the same input as one product).
 // GE_L2NORM: COUT = 64 = the workgroup's two tiles, so a wave holds whole rows: out = v / max(||v||_2, xb) (F.normalize, XFeat.py:136).
-enum { GE_PLAIN = 0, GE_RESIDUAL = 1, GE_ROTARY = 2, GE_SPLIT2 = 3, GE_L2NORM = 4 };
+// GE_RES_RELU: out = relu(res + (W x + b)), the identity tile of a ResBlock added BEFORE the ReLU (sfd2.py:41-45; the strict-fp32 counterpart is ConvM::res of
+// conv_mfma); `res` has the output's layout, rows rstride floats apart, and any row count (rows past the end are not read); ConvM::relu is not consulted.
+enum { GE_PLAIN = 0, GE_RESIDUAL = 1, GE_ROTARY = 2, GE_SPLIT2 = 3, GE_L2NORM = 4, GE_RES_RELU = 5 };
 
 // A form of conv_mfma_h, named field by field: conv_mfma_h<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2}>.  The strict-fp32 conv_mfma has the
 // first seven fields; the others stay at their defaults.  launch_conv_mfma(_h) (below the kernels) launch a form on the grid its 16 x tile_h() tile needs.
@@ -1042,7 +1044,7 @@ template <int NTB, int MT = 2, int EPI = GE_PLAIN, bool UNFOLD = false, int TAPK
 //  workgroups per CU), help only that same form and by the same amount (it is the spills, not the bytes): ffn3 +18 %, to_out / out_proj +14 %, ffn0 +3 %.
 //  profiles/r06_gemm_forms_ab.txt)
 // (TAPK: the pixel coordinates of the staged rows are eight more registers; at four waves per SIMD two registers spill, at three none do.)
-__global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY || TAPK ? 3 : 4) : 2) void gemm_h(ConvM a)
+__global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY || EPI == GE_RES_RELU || TAPK ? 3 : 4) : 2) void gemm_h(ConvM a)
 {
     // r03: a wave stages exactly the 32 MT rows it multiplies, so its slice of the LDS buffers is private to it (a wave's LDS
     // operations execute in order: no barrier anywhere in the kernel) and the activation scale is chosen PER WAVE from the
@@ -1145,7 +1147,7 @@ __global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY || TAPK ? 3 : 4) :
     // (Also requesting the next slab's weight fragments a slab ahead costs 94 more VGPRs and the second wave per SIMD: 1.7x slower.)
     // what the fused epilogues read per output element is requested ahead of the LAST slab's products (in the epilogue each load
     // was an exposed round trip: ffn3 + residual 0.83 -> 1.10 ms per 18 launches)
-    constexpr int NX = EPI == GE_RESIDUAL ? NTB : (EPI == GE_ROTARY ? 2 : 0);
+    constexpr int NX = EPI == GE_RESIDUAL || EPI == GE_RES_RELU ? NTB : (EPI == GE_ROTARY ? 2 : 0);
     float xv[MT][NX ? NX : 1][16];
     auto fetch_epilogue = [&]() {
         if constexpr (EPI == GE_RESIDUAL) {
@@ -1158,6 +1160,17 @@ __global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY || TAPK ? 3 : 4) :
                     for (int r = 0; r < 16; ++r) {
                         const int row = r0 + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * h;        // < nrows_all: see the check at the top
                         xv[m][n][r] = res[(size_t)row * a.rstride + (nt0 + n) * 32 + p];
+                    }
+        } else if constexpr (EPI == GE_RES_RELU) {
+            const float* res = a.res + (size_t)b * nrows_all * a.rstride;
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int n = 0; n < NTB; ++n)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = r0 + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * h, co = (nt0 + n) * 32 + p;
+                        xv[m][n][r] = (row < nrows && co < a.COUT) ? res[(size_t)row * a.rstride + co] : 0.0f;
                     }
         } else if constexpr (EPI == GE_ROTARY) {
             const float* cs = a.aux0 + (size_t)b * nrows_all * 32 + p;
@@ -1267,9 +1280,10 @@ __global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY || TAPK ? 3 : 4) :
             for (int r = 0; r < 16; ++r) {
                 const int row = r0 + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * h;
                 float v = fmaf(acc[m][n][r], unscale, bias);
-                if (a.relu) v = relu(v);
+                if (EPI != GE_RES_RELU && a.relu) v = relu(v);
                 if (row < nrows) {
                     if constexpr (EPI == GE_RESIDUAL) v = xv[m][n][r] + v;
+                    if constexpr (EPI == GE_RES_RELU) v = relu(v + xv[m][n][r]);
                     o[(size_t)row * a.ostride + co] = v;
                 }
             }

@@ -878,6 +878,12 @@ struct SuperPointNet : kpb_net {
 
 }  // namespace
 
+void launch_l2norm_nhwc(kpb_ctx* ctx, const char* tag, float* desc, int C, size_t npix, float eps_clamp)
+{
+    const size_t per_block = C == 64 ? 4 * PXW : 4;
+    KPB_LAUNCH(ctx, tag, l2norm_nhwc, dim3((unsigned)((npix + per_block - 1) / per_block)), dim3(256), 0, ctx->stream, desc, C, npix, eps_clamp);
+}
+
 int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
     // name, cin, cout, ks, stride, mfma, relu, pool_out: conv1b, conv2b and conv3b are max-pooled 2 x 2; convPb and convDb have no ReLU

@@ -176,6 +176,7 @@ struct kpb_ctx {
     size_t covis_store_bytes = (size_t)4 << 30;     // KPB_OPT_COVIS_STORE_BYTES (kpb_ctx_set_option)
     int alike_coarse_fused = 1;                     // KPB_OPT_ALIKE_COARSE_FUSED
     int detect_signed = 0;                          // KPB_OPT_DETECT_SIGNED
+    int sfd2_probe = 0;                             // KPB_OPT_SFD2_PROBE
 };
 enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u, KPB_ATTR_NMS_ROUND = 16u, KPB_ATTR_SELECT = 32u };
 

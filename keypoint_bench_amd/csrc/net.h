@@ -103,6 +103,10 @@ struct WeightStage {
     }
 };
 
+// convnet.hip's l2norm_nhwc for the nets of other translation units: every C-channel row of an NHWC map divided by its L2 norm in place, the norm clamped from
+// below at eps_clamp when that is > 0 (F.normalize)
+void launch_l2norm_nhwc(kpb_ctx* ctx, const char* tag, float* desc, int C, size_t npix, float eps_clamp);
+
 // factories, one per architecture
 int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
@@ -113,3 +117,4 @@ int edgepoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int goodpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int letnet_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int keynet_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
+int sfd2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);

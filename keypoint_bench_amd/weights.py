@@ -22,6 +22,7 @@ ARCH_EDGEPOINT = 7
 ARCH_GOODPOINT = 8
 ARCH_LETNET = 9
 ARCH_KEYNET = 10
+ARCH_SFD2 = 11
 _REC = struct.Struct("<40sI4II")
 
 
@@ -211,6 +212,79 @@ def keynet_level_sizes(H, W, levels=3):
         h, w = out[-1]
         out.append((int(h // 1.2), int(w // 1.2)))
     return out
+
+
+SFD2_PLAN = dict(outdim=128, require_feature=False, require_stability=True, ms_detector=True)
+# ResSegNetV2 (models/sfd2.py:90-134) as (folded name, convolution key, BatchNorm key or None, affine, (cout, cin per group, k), conv bias).  The folded names
+# are those csrc/sfd2.hip reads; `res<i>.c2` is the grouped 3 x 3 (32 groups of 8): its weight is [256][8][3][3].
+_SFD2_LAYERS = (("conv1a", "conv1a.0", "conv1a.1", False, (64, 3, 3), True), ("conv1b", "conv1b.0", "bn1b.0", False, (64, 64, 3), True),
+                ("conv2a", "conv2a.0", "conv2a.1", False, (128, 64, 3), True), ("conv2b", "conv2b.0", "bn2b.0", False, (128, 128, 3), True),
+                ("conv3a", "conv3a.0", "conv3a.1", False, (256, 128, 3), True), ("conv3b", "conv3b.0", "bn3b.0", False, (256, 256, 3), True)) + tuple(
+    ("res%d.c%d" % (i, j), "conv4.%d.conv%d" % (i, j), "conv4.%d.bn%d" % (i, j), True, (256, 8 if j == 2 else 256, 3 if j == 2 else 1), False)
+    for i in range(3) for j in (1, 2, 3)) + (
+    ("convPa0", "convPa.0", "convPa.1", True, (256, 256, 3), True), ("convPa3", "convPa.3", None, False, (256, 256, 3), True),
+    ("convPb", "convPb", None, False, (65, 256, 1), True),
+    ("convDa0", "convDa.0", "convDa.1", True, (256, 256, 3), True), ("convDa3", "convDa.3", None, False, (256, 256, 3), True),
+    ("convDb", "convDb", None, False, (128, 256, 1), True), ("sta", "ConvSta", None, False, (3, 256, 1), True))
+
+
+def _sfd2_need():
+    need = {}
+    for name, conv, bn, affine, (co, ci, k), bias in _SFD2_LAYERS:
+        need[conv + ".weight"] = (co, ci, k, k)
+        if bias:
+            need[conv + ".bias"] = (co,)
+        if bn:
+            for leaf in ("running_mean", "running_var") + (("weight", "bias") if affine else ()):
+                need[bn + "." + leaf] = (co,)
+    return need
+
+
+def fold_sfd2(sd, eps=1e-5) -> dict:
+    """state_dict of ResSegNetV2(outdim = 128, require_stability = True) (models/sfd2.py:90-134; the checkpoint keeps it under 'model', which the caller
+    strips) -> the folded tensors csrc/sfd2.hip expects, `<name>.w` [cout][cin per group][k][k] and `<name>.b` [cout] per layer of _SFD2_LAYERS: every eval-mode
+    BatchNorm (eps 1e-5; weight and bias only where it is affine) goes into the convolution in front of it, w' = w g / sqrt(var + eps) and
+    b' = (b - mean) g / sqrt(var + eps) + beta per output channel (b = 0 for the ResBlocks' bias-free convolutions).  Keys the forward does not use
+    (num_batches_tracked, heads of other variants) are ignored, as the reference's load_state_dict(strict=False) ignores them.  Refused: a missing or
+    mis-shaped tensor."""
+    for key, shape in _sfd2_need().items():
+        if key not in sd:
+            raise ValueError("SFD2 state_dict: %s is missing" % key)
+        if tuple(sd[key].shape) != shape:
+            raise ValueError("SFD2 state_dict: %s has shape %s, ResSegNetV2(outdim = 128, require_stability = True) needs %s" % (key, tuple(sd[key].shape), shape))
+    t = {}
+    for name, conv, bn, affine, (co, ci, k), bias in _SFD2_LAYERS:
+        w = _np(sd[conv + ".weight"])
+        b = _np(sd[conv + ".bias"]) if bias else np.zeros(co)
+        if bn:
+            s = 1.0 / np.sqrt(_np(sd[bn + ".running_var"]) + eps)
+            if affine:
+                s = s * _np(sd[bn + ".weight"])
+            w, b = w * s[:, None, None, None], (b - _np(sd[bn + ".running_mean"])) * s
+            if affine:
+                b = b + _np(sd[bn + ".bias"])
+        t[name + ".w"], t[name + ".b"] = w.astype(np.float32), b.astype(np.float32)
+    return t
+
+
+def random_sfd2_state_dict(seed: int) -> dict:
+    """Seeded stand-in for the absent weights/sfd2.pth (.MISSING_LARGE_BLOBS), drawn from numpy so the same seed gives the same tensors on every machine:
+    conv weights N(0, 2 / fan_in) with fan_in = shape[1] k^2, conv biases and BatchNorm biases / running means N(0, 0.1^2), BatchNorm weights and running
+    variances U(0.75, 1.25); num_batches_tracked as the reference's BatchNorms keep it."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for name, conv, bn, affine, (co, ci, k), bias in _SFD2_LAYERS:
+        sd[conv + ".weight"] = rng.normal(0.0, np.sqrt(2.0 / (ci * k * k)), size=(co, ci, k, k)).astype(np.float32)
+        if bias:
+            sd[conv + ".bias"] = rng.normal(0.0, 0.1, size=(co,)).astype(np.float32)
+        if bn:
+            if affine:
+                sd[bn + ".weight"] = rng.uniform(0.75, 1.25, size=(co,)).astype(np.float32)
+                sd[bn + ".bias"] = rng.normal(0.0, 0.1, size=(co,)).astype(np.float32)
+            sd[bn + ".running_mean"] = rng.normal(0.0, 0.1, size=(co,)).astype(np.float32)
+            sd[bn + ".running_var"] = rng.uniform(0.75, 1.25, size=(co,)).astype(np.float32)
+            sd[bn + ".num_batches_tracked"] = np.array(0, np.int64)
+    return sd
 
 
 def load_alike_t():
