@@ -9,8 +9,7 @@
 //     neighbours clamped at the edge --, argmax over the three (the first maximum wins), classes 0 / 1 / 2 -> 0.1 / 0.5 / 1.0; score = semi_norm x stability.
 //     H and W must be multiples of 8: the reference's own product fails on mismatched shapes otherwise.
 // Kernels:
-//   sfd2_conv1a        3 -> 64 at full resolution on the vector ALU from the planar image (27 taps; conv1a_c64's column walk).  Its 64-channel map is written
-//                      and read back once (2 x 79 MB per 480 x 640 image): generating it inside conv1b's staging, as SuperPoint does, is not built.
+//   conv1a_rgb64       (conv1a_rgb.h, shared with D2-Net) 3 -> 64 at full resolution on the vector ALU from the planar image
 //   conv_mfma_h        the 3 x 3 layers at stride 1 and 2 (SuperPoint's forms); KPB_FP32_MATRIX=1: conv_mfma
 //   gemm_h             the 1 x 1 layers; <GE_RES_RELU> adds the ResBlock's identity tile before the ReLU.  KPB_FP32_MATRIX=1: conv_mfma's 1 x 1 form with ConvM::res
 //   sfd2_gconv_f32     the grouped 3 x 3 as strict fp32 fmaf chains: a thread takes one pixel and four groups in turn, the 9 x 8 x 8 weights of a group wave-uniform
@@ -20,55 +19,11 @@
 //   sfd2_score         one wave per 8 x 8 cell: exp, guarded sum, depth-to-space, the x 4 bilinear of the three stability logits, argmax and the product; no
 //                      full-resolution stability map is written
 //   l2norm_nhwc        (convnet.hip) F.normalize of the 128-channel rows in place, eps_clamp 1e-12
-#include "conv_mfma.h"
+#include "conv1a_rgb.h"
 
 namespace {
 
 typedef float sf_f4 __attribute__((ext_vector_type(4)));
-
-// ------------------------------------------------------------------------------------------------ conv1a
-// 16 lanes share a pixel, each keeps the 27 taps of its 4 output channels in registers and walks down a column; a wave store is 4 whole 256-byte pixels.
-// Every output is bias, then the taps in (kx, channel) order of rows y - 1, y, y + 1 interleaved, an fma each; a tap outside the image is zero.
-__global__ __launch_bounds__(256) void sfd2_conv1a(const float* __restrict__ img, float* __restrict__ out, const float* __restrict__ w /*[3 ky][3 kx][3 c][64]*/,
-                                                    const float* __restrict__ bias, int H, int W, int rows_per_block)
-{
-    const int b = blockIdx.z, lane16 = threadIdx.x & 15, c4 = lane16 * 4;
-    const int x = blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (x >= W) return;
-    float wr[27][4], bv[4];
-#pragma unroll
-    for (int t = 0; t < 27; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) wr[t][j] = w[t * 64 + c4 + j];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bv[j] = bias[c4 + j];
-    const size_t P = (size_t)H * W;
-    const float* im = img + (size_t)b * 3 * P;
-    auto ld = [&](int yy, int k) {      // k = 3 kx + channel
-        const int xx = x - 1 + k / 3;
-        return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? im[(size_t)(k % 3) * P + (size_t)yy * W + xx] : 0.0f;
-    };
-    const int y0 = blockIdx.y * rows_per_block, y1 = min(y0 + rows_per_block, H);
-    float r0[9], r1[9], r2[9], r3[9];       // the row below is requested one iteration before it is used
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { r0[k] = ld(y0 - 1, k); r1[k] = ld(y0, k); r2[k] = ld(y0 + 1, k); }
-    for (int y = y0; y < y1; ++y) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) r3[k] = ld(y + 2, k);
-        float acc[4] = {bv[0], bv[1], bv[2], bv[3]};
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc[j] = fmaf(r0[k], wr[k][j], acc[j]);
-                acc[j] = fmaf(r1[k], wr[9 + k][j], acc[j]);
-                acc[j] = fmaf(r2[k], wr[18 + k][j], acc[j]);
-            }
-        *reinterpret_cast<float4*>(out + (((size_t)b * H + y) * W + x) * 64 + c4) = make_float4(relu(acc[0]), relu(acc[1]), relu(acc[2]), relu(acc[3]));
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { r0[k] = r1[k]; r1[k] = r2[k]; r2[k] = r3[k]; }
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ the grouped 3 x 3 layer (256 channels, 32 groups of 8 -> 8)
 struct SfGcArgs {
@@ -339,7 +294,7 @@ struct Sfd2Net : kpb_net {
         this->B = batch; this->H = H; this->W = W;
         hipStream_t st = ctx->stream;
         int rc;
-        KPB_LAUNCH(ctx, lay[SF_1A].prof.c_str(), sfd2_conv1a, dim3(cdiv(W, 16), cdiv(H, 32), batch), dim3(256), 0, st, img, x1a, lay[SF_1A].w, lay[SF_1A].b, H, W, 32);
+        launch_conv1a_rgb64(ctx, lay[SF_1A].prof.c_str(), img, x1a, lay[SF_1A].w, lay[SF_1A].b, batch, H, W);
         if ((rc = conv(SF_1B, x1a, x1b, batch, H, W))) return rc;
         if ((rc = conv(SF_2A, x1b, x2a, batch, H2, W2))) return rc;
         if ((rc = conv(SF_2B, x2a, x2b, batch, H2, W2))) return rc;
@@ -392,12 +347,8 @@ int sfd2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         if (!w) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SFD2 tensor %s.w missing or mis-shaped", L.name);
         if (!b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SFD2 tensor %s.b missing or mis-shaped", L.name);
         const size_t cnt = (size_t)L.cout * L.cin * L.ks * L.ks;
-        if (i == SF_1A) {       // [ky][kx][c][64]
-            std::vector<float> p(27 * 64);
-            for (int o = 0; o < 64; ++o)
-                for (int c = 0; c < 3; ++c)
-                    for (int t = 0; t < 9; ++t) p[(t * 3 + c) * 64 + o] = w[(o * 3 + c) * 9 + t];
-            ws.put(p, &dst.w);
+        if (i == SF_1A) {
+            ws.put(pack_conv1a_rgb64(w), &dst.w);
             ws.put_raw(b, 64, &dst.b);
         } else if (L.grouped) {
             if (net->h16) {

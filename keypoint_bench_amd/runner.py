@@ -56,7 +56,9 @@ _MODELS = {"Alike": ("ALike", lambda m, p, dense: m.ALNet(p, dense_descriptors=d
            "KeyNet": ("KeyNet", lambda m, p, dense: m.KeyNet({k: p[k] for k in ("num_filters", "num_levels", "kernel_size") if k in p} or None), "KeyNet_params",
                       "state_dict", ""),
            # model_interface.py:74-76: ResSegNetV2(outdim=128, require_stability=True), the checkpoint's 'model' entry loaded with strict=False
-           "sfd2": ("sfd2", lambda m, p, dense: m.ResSegNetV2(outdim=128, require_stability=True), "sfd2_params", "model", _NOT_SHIPPED)}
+           "sfd2": ("sfd2", lambda m, p, dense: m.ResSegNetV2(outdim=128, require_stability=True), "sfd2_params", "model", _NOT_SHIPPED),
+           # model_interface.py:64-65: D2Net(model_file=weight) loads the checkpoint's 'model' entry itself; here the file is looked for first
+           "D2Net": ("D2_Net", lambda m, p, dense: m.D2Net(), "D2Net_params", "model", _NOT_SHIPPED)}
 
 
 def build_model(params, dense_descriptors=True):
@@ -65,7 +67,7 @@ def build_model(params, dense_descriptors=True):
     import importlib
     mt = params["model_type"]
     if mt not in _MODELS:
-        raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint, GoodPoint, LETNet, KeyNet, sfd2)" % (mt,))
+        raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint, GoodPoint, LETNet, KeyNet, sfd2, D2Net)" % (mt,))
     mod, make, pkey, sub, missing = _MODELS[mt]
     mod = importlib.import_module("keypoint_bench_amd.models." + mod)
     p = params.get(pkey) or {}

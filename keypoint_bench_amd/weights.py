@@ -23,6 +23,7 @@ ARCH_GOODPOINT = 8
 ARCH_LETNET = 9
 ARCH_KEYNET = 10
 ARCH_SFD2 = 11
+ARCH_D2NET = 12
 _REC = struct.Struct("<40sI4II")
 
 
@@ -284,6 +285,41 @@ def random_sfd2_state_dict(seed: int) -> dict:
             sd[bn + ".running_mean"] = rng.normal(0.0, 0.1, size=(co,)).astype(np.float32)
             sd[bn + ".running_var"] = rng.uniform(0.75, 1.25, size=(co,)).astype(np.float32)
             sd[bn + ".num_batches_tracked"] = np.array(0, np.int64)
+    return sd
+
+
+# D2-Net's trunk (models/D2_Net.py:10-46) = torchvision's vgg16().features[:22] as (folded name, index in that Sequential, (cout, cin)): ten 3 x 3 layers with
+# bias and no BatchNorm; a 2 x 2 max-pool follows conv1_2, conv2_2 and conv3_3, a ReLU every layer but conv4_3.  The folded names are those csrc/d2net.hip reads.
+_D2NET_LAYERS = (("conv1_1", 0, (64, 3)), ("conv1_2", 2, (64, 64)), ("conv2_1", 5, (128, 64)), ("conv2_2", 7, (128, 128)),
+                 ("conv3_1", 10, (256, 128)), ("conv3_2", 12, (256, 256)), ("conv3_3", 14, (256, 256)),
+                 ("conv4_1", 17, (512, 256)), ("conv4_2", 19, (512, 512)), ("conv4_3", 21, (512, 512)))
+_D2NET_KEY = "dense_feature_extraction.model.%d."
+
+
+def fold_d2net(sd) -> dict:
+    """state_dict of D2Net (models/D2_Net.py:84-96; the checkpoint keeps it under 'model', which the caller strips) -> the tensors csrc/d2net.hip expects,
+    `<name>.w` [cout][cin][3][3] and `<name>.b` [cout] per layer of _D2NET_LAYERS.  There is nothing to fold (no BatchNorm): the ten pairs are renamed.  Keys the
+    forward does not read are ignored.  Refused: a missing or mis-shaped tensor (ValueError names the key and the shape it needs)."""
+    t = {}
+    for name, idx, (co, ci) in _D2NET_LAYERS:
+        for leaf, out, shape in (("weight", ".w", (co, ci, 3, 3)), ("bias", ".b", (co,))):
+            key = _D2NET_KEY % idx + leaf
+            if key not in sd:
+                raise ValueError("D2Net state_dict: %s is missing (needs shape %s)" % (key, shape))
+            if tuple(sd[key].shape) != shape:
+                raise ValueError("D2Net state_dict: %s has shape %s, D2Net needs %s" % (key, tuple(sd[key].shape), shape))
+            t[name + out] = _np(sd[key]).astype(np.float32)
+    return t
+
+
+def random_d2net_state_dict(seed: int) -> dict:
+    """Seeded stand-in for the absent weights/d2_tf.pth (.MISSING_LARGE_BLOBS), drawn from numpy so the same seed gives the same tensors on every machine:
+    He-scaled weights N(0, 2 / (9 cin)), biases N(0, 0.05^2)."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for name, idx, (co, ci) in _D2NET_LAYERS:
+        sd[_D2NET_KEY % idx + "weight"] = rng.normal(0.0, np.sqrt(2.0 / (9 * ci)), size=(co, ci, 3, 3)).astype(np.float32)
+        sd[_D2NET_KEY % idx + "bias"] = rng.normal(0.0, 0.05, size=(co,)).astype(np.float32)
     return sd
 
 
