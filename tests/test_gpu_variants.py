@@ -58,12 +58,12 @@ def test_strict_fp32_kernels_pass_the_goldens():
 
 @pytest.mark.timeout(900)
 def test_exact_match_kernel_without_the_prefilter_passes_the_goldens():
-    _child({"KPB_MATCH_PREFILTER": "0"}, ["tests/test_gpu_match.py", "tests/test_gpu_fuzz.py", "tests/test_gpu_pipeline.py"])
+    _child({"KPB_MATCH_PREFILTER": "0"}, ["tests/test_gpu_match.py", "tests/test_gpu_fuzz.py", "tests/test_gpu_pipeline.py", "tests/test_gpu_match_prefilter.py"])
 
 
 @pytest.mark.timeout(900)
 def test_prefilter_forced_on_single_pairs_passes_the_goldens():
-    _child({"KPB_MATCH_PREFILTER": "2"}, ["tests/test_gpu_match.py", "tests/test_gpu_fuzz.py", "tests/test_gpu_range.py", "tests/test_gpu_pipeline.py"])
+    _child({"KPB_MATCH_PREFILTER": "2"}, ["tests/test_gpu_match.py", "tests/test_gpu_fuzz.py", "tests/test_gpu_range.py", "tests/test_gpu_pipeline.py", "tests/test_gpu_match_prefilter.py"])
 
 
 def test_no_other_environment_knob_selects_a_kernel():
