@@ -148,7 +148,16 @@ int kpb_match(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch,
               int max_m, const int32_t* n_dev, const int32_t* m_dev, const kpb_match_params* params,
               int32_t* out_pairs_dev, double* out_dist_dev, int32_t* out_k_dev);
 
-/* Match counts of the last kpb_match as host integers: waits for the context's stream, then hands over what match_finalize left in
+/* kpb_match followed by skimage's third filter, max_ratio (Lowe's ratio test, skimage >= 0.16), on the rows that survived the cross-check
+ * and max_distance:  second = min over j != j* of D[i][j] (numpy's argmin after D[i][j*] = inf: a NaN wins), second = 2^-52 where it is 0,
+ * and the row is kept when best / second < max_ratio in float64 (strict; a NaN ratio -- inf / inf, a NaN distance -- drops the row; one
+ * column leaves second = inf, ratio 0).  The second nearest is the exact float64 one.  max_ratio >= 1 (inf included) turns the step off:
+ * the call is kpb_match, launch for launch.  A NaN max_ratio is KPB_E_INVALID.  kpb_match_counts serves this call as well. */
+int kpb_match_ratio(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch, int C, int max_n,
+                    int max_m, const int32_t* n_dev, const int32_t* m_dev, const kpb_match_params* params, double max_ratio,
+                    int32_t* out_pairs_dev, double* out_dist_dev, int32_t* out_k_dev);
+
+/* Match counts of the last kpb_match / kpb_match_ratio as host integers: waits for the context's stream, then hands over what match_finalize left in
  * pinned host memory -- the `K` of skimage's `matches` array [K, 2] (utils/matcher.py:227-230) without a device read-back of its own.
  * out_k_host [batch] is host memory; batch must be the batch of that call. */
 int kpb_match_counts(kpb_ctx* ctx, int32_t* out_k_host, int batch);

@@ -56,6 +56,8 @@ SIGNATURES = {
                            c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "kpb_match": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                           ctypes.POINTER(MatchParams), c_void_p, c_void_p, c_void_p]),
+    "kpb_match_ratio": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                ctypes.POINTER(MatchParams), c_double, c_void_p, c_void_p, c_void_p]),
     "kpb_gather_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
                                 c_void_p]),
     "kpb_warp_homography": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

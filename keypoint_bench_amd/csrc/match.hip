@@ -88,10 +88,15 @@ constexpr int MTI = 16 * TM, MTJ = 16 * TN, KC = 16, MATCH_THREADS = 256;
 struct MatchArgs {
     const int* only;                 // optional [B]: run only for pairs whose flag is set (the prefilter's exact fallback)
     const float* d0; const float* d1; const int* n; const int* m;
-    double* rpart_s; int* rpart_j;   // [B][tiles_j][max_n]
+    double* rpart_s; int* rpart_j;   // [B][rdepth][max_n]
     double* cpart_s; int* cpart_i;   // [B][tiles_i][max_m]
-    int C, max_n, max_m, tiles_i, tiles_j;
+    int C, max_n, max_m, tiles_i, rdepth;       // rdepth: row slots per pair -- tiles_j, or row_depth(tiles_j) with the ratio test on (two per column tile)
 };
+
+// Row slots of a pair with the ratio test on: every column tile of match_tile hands over its TWO best entries, and the prefilter files a row's
+// candidates (the nearest, the second nearest and whatever the filter cannot tell from them: usually three or four) in the same array, at
+// least eight deep so that a pair of up to 256 columns does not overflow on an ordinary row.
+__host__ __device__ constexpr int row_depth(int tiles_j) { return 2 * tiles_j > 8 ? 2 * tiles_j : 8; }
 
 // One MTI x MTJ tile of the distance matrix per workgroup, TM x TN of it per thread: every float64 operand read from LDS
 // feeds TN (TM) subtract / multiply / add triples, which keeps the LDS pipe far below the vector ALUs' rate.
@@ -101,6 +106,9 @@ struct MatchArgs {
 // slots (r01: lanes 64 bytes apart -> every group on 4 bank sets, 67 % conflict cycles).  Row pitches are padded by two
 // doubles so that the k-major staging writes of a float4 (four k rows) fall on different banks pairwise.
 #define COLJ(c, q) (2 * (c) + 32 * ((q) >> 1) + ((q) & 1))
+// RATIO: the tile hands over its two best (sum, column) per row, in slots 2 tj and 2 tj + 1 (the second one empty -- column INT_MAX -- in a
+// tile of one valid column); the k loop is the same, the extra compares are in the epilogue.
+template <bool RATIO>
 __global__ __launch_bounds__(MATCH_THREADS) void match_tile(MatchArgs a)
 {
     constexpr int PA = MTI + 2, PB = MTJ + 2;                             // padded pitches (doubles)
@@ -169,21 +177,36 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_tile(MatchArgs a)
     for (int p = 0; p < TM; ++p) {
         double bs = __longlong_as_double(0x7FF0000000000000LL);
         int bj = 0x7FFFFFFF;
+        double ss = bs;             // RATIO: the runner-up, (inf, INT_MAX) while there is none
+        int sj = bj;
 #pragma unroll
         for (int q = 0; q < TN; ++q) {
             const int j = j0 + COLJ(c, q);
-            if (j < m && precedes(acc[p][q], j, bs, bj)) { bs = acc[p][q]; bj = j; }
+            if (j < m) {
+                if (precedes(acc[p][q], j, bs, bj)) {
+                    if (RATIO) { ss = bs; sj = bj; }
+                    bs = acc[p][q]; bj = j;
+                } else if (RATIO && precedes(acc[p][q], j, ss, sj)) { ss = acc[p][q]; sj = j; }
+            }
         }
 #pragma unroll
-        for (int d = 1; d < 16; d <<= 1) {
+        for (int d = 1; d < 16; d <<= 1) {      // (the two lanes of an exchange hold disjoint column sets)
             const double os = __shfl_xor(bs, d, 64);
             const int oj = __shfl_xor(bj, d, 64);
-            if (precedes(os, oj, bs, bj)) { bs = os; bj = oj; }
+            if (RATIO) {
+                const double os2 = __shfl_xor(ss, d, 64);
+                const int oj2 = __shfl_xor(sj, d, 64);
+                if (precedes(os, oj, bs, bj)) {           // the other best leads: the runner-up is this best or the other runner-up
+                    if (precedes(os2, oj2, bs, bj)) { ss = os2; sj = oj2; } else { ss = bs; sj = bj; }
+                    bs = os; bj = oj;
+                } else if (precedes(os, oj, ss, sj)) { ss = os; sj = oj; }
+            } else if (precedes(os, oj, bs, bj)) { bs = os; bj = oj; }
         }
         const int i = i0 + TM * r + p;
         if ((lane & 15) == 0 && i < n) {
-            const size_t o = ((size_t)b * a.tiles_j + tj) * a.max_n + i;
+            const size_t o = ((size_t)b * a.rdepth + (RATIO ? 2 * tj : tj)) * a.max_n + i;
             a.rpart_s[o] = bs; a.rpart_j[o] = bj;
+            if (RATIO) { a.rpart_s[o + a.max_n] = ss; a.rpart_j[o + a.max_n] = sj; }
         }
     }
     // column minima over this tile's rows: TM local rows, then across the 16 row groups through LDS (the operand
@@ -221,10 +244,17 @@ struct FinArgs {
     const int* n; const int* m;
     int* out_pairs; double* out_dist; int* out_k;
     int* host_k;        // pinned host mirror of out_k (kpb_match_counts), written by the kernel
-    int max_n, max_m, tiles_i, tiles_j, cross_check;
+    int max_n, max_m, tiles_i, rdepth, cross_check;
     double max_distance;
+    const int* exact;   // RATIO, prefilter: [B] the pair's fallback flag (match_tile filled its slots), or NULL = match_tile served every pair
+    double max_ratio;   // RATIO
 };
 
+// RATIO: skimage's max_ratio step on the rows that survived the cross-check and max_distance: the row's second nearest distance is the entry
+// that precedes all the others once the best is taken out (numpy's argmin after D[i, j*] = inf: the first NaN wins, then the smallest
+// rooted value), 0 becomes eps, and the row is kept when best / second < max_ratio in float64 (a NaN ratio -- inf / inf, a NaN distance --
+// compares false and drops the row; m = 1 leaves second = inf and ratio 0).
+template <bool RATIO>
 __global__ __launch_bounds__(FIN_THREADS) void match_finalize(FinArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -232,7 +262,10 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize(FinArgs a)
     __shared__ int wsum[FIN_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int n = a.n ? min(a.n[b], a.max_n) : a.max_n, m = a.m ? min(a.m[b], a.max_m) : a.max_m;
-    const int tiles_i = (n + MTI - 1) / MTI, tiles_j = (m + MTJ - 1) / MTJ;
+    const int tiles_i = (n + MTI - 1) / MTI;
+    // row slots to read: one per column tile of the pair; RATIO: two per column tile where match_tile wrote them, the whole depth where
+    // match_exact filed the row's candidates (slots past a row's count keep the INT_MAX of the fill)
+    const int rslots = !RATIO ? (m + MTJ - 1) / MTJ : (a.exact && !a.exact[b]) ? a.rdepth : 2 * ((m + MTJ - 1) / MTJ);
     for (int j = tid; j < m; j += FIN_THREADS) {   // argmin(distances, axis=0)
         double bs = __longlong_as_double(0x7FF0000000000000LL);
         int bi = 0x7FFFFFFF;
@@ -253,14 +286,27 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize(FinArgs a)
         if (i < n && m > 0) {
             double bs = __longlong_as_double(0x7FF0000000000000LL);
             bj = 0x7FFFFFFF;
-            for (int t = 0; t < tiles_j; ++t) {
-                const size_t o = ((size_t)b * a.tiles_j + t) * a.max_n + i;
+            int bt = 0;
+            for (int t = 0; t < rslots; ++t) {
+                const size_t o = ((size_t)b * a.rdepth + t) * a.max_n + i;
                 const double s = a.rpart_s[o]; const int j = a.rpart_j[o];
-                if (j != 0x7FFFFFFF && precedes(s, j, bs, bj)) { bs = s; bj = j; }
+                if (j != 0x7FFFFFFF && precedes(s, j, bs, bj)) { bs = s; bj = j; bt = t; }
             }
             dist = sqrt(bs);
             // skimage filters on distance only `if max_distance < np.inf`: inf / nan distances survive max_distance = inf
             keep = (!a.cross_check || colarg[bj] == i) && (!(a.max_distance < __longlong_as_double(0x7FF0000000000000LL)) || dist < a.max_distance);
+            if (RATIO && keep) {
+                double ss = __longlong_as_double(0x7FF0000000000000LL);
+                int sj = 0x7FFFFFFF;
+                for (int t = 0; t < rslots; ++t) {     // every slot holds another column: leaving out the best's slot leaves out the best
+                    const size_t o = ((size_t)b * a.rdepth + t) * a.max_n + i;
+                    const double s = a.rpart_s[o]; const int j = a.rpart_j[o];
+                    if (t != bt && j != 0x7FFFFFFF && precedes(s, j, ss, sj)) { ss = s; sj = j; }
+                }
+                double second = sqrt(ss);
+                if (second == 0.0) second = 2.220446049250313e-16;      // np.finfo(np.double).eps
+                keep = __ddiv_rn(dist, second) < a.max_ratio;
+            }
         }
         // ordered compaction (rows stay sorted by i, as numpy boolean masking leaves them)
         const unsigned long long bal = __ballot(keep);
@@ -296,10 +342,17 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize(FinArgs a)
 //      satisfies D~_ij* <= D_ij* + delta_ij* <= D_ij' + delta_ij* <= rowmin_i + delta_ij' + delta_ij* (j' the approximate
 //      arg-minimum), so mr_i = 2.5 x delta evaluated with the LARGEST column norm of the pair covers it with a quarter to
 //      spare, for every exact tie as well; mc_j likewise with the largest row norm;
+//      RATIO TEST (kpb_match_ratio with max_ratio < 1): match_finalize also needs the exact SECOND nearest of a row, so pass 0 keeps the two
+//      smallest approximate distances of every row (by rank: a tie counts twice) and a.rowmin receives the second, rowmin2~_i; pass 1 lists
+//      (i, j) as a row candidate when D~_ij <= rowmin2~_i + mr_i.  Bound: the two approximately smallest columns have exact distances
+//      <= rowmin2~_i + delta, so the exact second-smallest VALUE of the row is <= rowmin2~_i + delta; the column j2 that holds it has
+//      D~_ij2 <= D_ij2 + delta <= rowmin2~_i + 2 delta.  The same 2.5 x delta margin therefore covers the exact second nearest, every column
+//      tied with it, and (its distance is no larger) the exact nearest and its ties.  Column candidates are unchanged.  A row of m = 1 has
+//      rowmin2~ = +inf and lists its one column;
 //   4. match_exact: scipy's float64 sum for the listed pairs only (same order, no FMA), filed under their row and column
 //      in the slots match_finalize reads (the per-tile partial arrays of match_tile, one slot per column / row tile).
 // A pair whose descriptors are not finite or reach 2^15 in magnitude (the split would saturate), or that needs more slots than
-// there are tiles (massive exact ties), raises a flag: match_tile then runs for that pair alone (it returns at once for the others) and overwrites the slots.  Results
+// there are tiles (massive exact ties; with the ratio test on: more row candidates than row_depth, eight or two per column tile), raises a flag: match_tile then runs for that pair alone (it returns at once for the others) and overwrites the slots.  Results
 // are bit-identical to match_tile's by construction; tests/test_gpu_match.py checks them on the goldens and the tie / NaN cases.
 typedef _Float16 mh8 __attribute__((ext_vector_type(8)));
 typedef float mf4 __attribute__((ext_vector_type(4)));
@@ -386,9 +439,12 @@ struct ApxArgs {
 // A wave owns RT 16-row tiles (all columns); KB = C / 32 k-blocks.  PASS 0: minima.  PASS 1: candidate list.
 constexpr int CBUF = 192;       // candidates a wave collects in LDS before it reserves room in the pair's list with ONE global atomic
 
-template <int KB, int RT, int PASS>
+// RATIO (PASS 0 only): a.rowmin receives the row's SECOND smallest approximate distance by rank (a tie counts twice; +inf for m = 1), so
+// that PASS 1 -- the same code -- lists the row's candidates against rowmin2_i + mr_i.
+template <int KB, int RT, int PASS, bool RATIO = false>
 __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
 {
+    static_assert(PASS == 0 || !RATIO, "the candidate pass is the same with the ratio test on");
     __shared__ int2 cbuf[PASS == 1 ? 4 : 1][PASS == 1 ? CBUF : 1];
     int wcnt = 0;                   // wave-uniform: every append goes through a ballot
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -429,6 +485,13 @@ __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
     }
     const float namax = __uint_as_float(a.nmax[2 * b]), nbmax = __uint_as_float(a.nmax[2 * b + 1]);
     float rmin[RT][4];        // PASS 1: rowmin_i + mr_i
+    float rmin2[RATIO ? RT : 1][4];      // RATIO: the second smallest so far (each row belongs to one wave: registers, no atomics)
+    if (RATIO) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) rmin2[RATIO ? rt : 0][r] = __uint_as_float(INF_BITS);
+    }
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -461,7 +524,10 @@ __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
                 dd[r] = fmaxf(__fadd_rn(__fadd_rn(na[rt][r], nb), -2.0f * acc[r]), 0.0f) + 0.0f;
             if (PASS == 0) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { rmin[rt][r] = fminf(rmin[rt][r], dd[r]); cm = fminf(cm, dd[r]); }
+                for (int r = 0; r < 4; ++r) {
+                    if (RATIO) rmin2[RATIO ? rt : 0][r] = fminf(rmin2[RATIO ? rt : 0][r], fmaxf(rmin[rt][r], dd[r]));
+                    rmin[rt][r] = fminf(rmin[rt][r], dd[r]); cm = fminf(cm, dd[r]);
+                }
             } else {
                 unsigned rowc = 0, colc = 0;
 #pragma unroll
@@ -499,8 +565,17 @@ __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float v = rmin[rt][r];
-                v = fminf(v, kpb_shfl_xor<1>(v)); v = fminf(v, kpb_shfl_xor<2>(v));
-                v = fminf(v, kpb_shfl_xor<4>(v)); v = fminf(v, kpb_shfl_xor<8>(v));
+                if (RATIO) {        // two smallest of the union: min(max of the two smallest, min of the two second smallest)
+                    float w = rmin2[RATIO ? rt : 0][r], ov, ow;
+                    ov = kpb_shfl_xor<1>(v); ow = kpb_shfl_xor<1>(w); w = fminf(fmaxf(v, ov), fminf(w, ow)); v = fminf(v, ov);
+                    ov = kpb_shfl_xor<2>(v); ow = kpb_shfl_xor<2>(w); w = fminf(fmaxf(v, ov), fminf(w, ow)); v = fminf(v, ov);
+                    ov = kpb_shfl_xor<4>(v); ow = kpb_shfl_xor<4>(w); w = fminf(fmaxf(v, ov), fminf(w, ow)); v = fminf(v, ov);
+                    ov = kpb_shfl_xor<8>(v); ow = kpb_shfl_xor<8>(w); w = fminf(fmaxf(v, ov), fminf(w, ow));
+                    v = w;
+                } else {
+                    v = fminf(v, kpb_shfl_xor<1>(v)); v = fminf(v, kpb_shfl_xor<2>(v));
+                    v = fminf(v, kpb_shfl_xor<4>(v)); v = fminf(v, kpb_shfl_xor<8>(v));
+                }
                 const int i = i0 + 16 * rt + 4 * g + r;
                 if (c16 == 0 && i < n) a.rowmin[(size_t)b * a.max_n + i] = __float_as_uint(v);
             }
@@ -509,7 +584,8 @@ __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
 
 struct ExactArgs {
     const float* d0; const float* d1; const int2* cand; const int* ncand; int cap, C, max_n, max_m;
-    int* rcnt; int* ccnt; double* rs; int* rj; double* cs; int* ci; int tiles_i, tiles_j; const int* m; const int* n; int* flag;
+    int* rcnt; int* ccnt; double* rs; int* rj; double* cs; int* ci; int tiles_i, rdepth; const int* m; const int* n; int* flag;
+    int ratio;      // the ratio test is on: a row has rdepth slots (match_finalize<true> reads them all), not one per column tile
 };
 
 // scipy's float64 sum (ascending k, no FMA: the same three instructions as match_tile) for the listed pairs only
@@ -531,10 +607,10 @@ __global__ __launch_bounds__(256) void match_exact(ExactArgs a)
         d = __dsub_rn((double)u.w, (double)v.w); s = __dadd_rn(s, __dmul_rn(d, d));
     }
     const int n = a.n ? min(a.n[b], a.max_n) : a.max_n, m = a.m ? min(a.m[b], a.max_m) : a.max_m;
-    const int slots_r = (m + MTJ - 1) / MTJ, slots_c = (n + MTI - 1) / MTI;      // what match_finalize reads for this pair
+    const int slots_r = a.ratio ? a.rdepth : (m + MTJ - 1) / MTJ, slots_c = (n + MTI - 1) / MTI;      // what match_finalize reads for this pair
     if (c.x & (1 << 30)) {
         const int t = atomicAdd(&a.rcnt[(size_t)b * a.max_n + i], 1);
-        if (t < slots_r) { const size_t o = ((size_t)b * a.tiles_j + t) * a.max_n + i; a.rs[o] = s; a.rj[o] = j; }
+        if (t < slots_r) { const size_t o = ((size_t)b * a.rdepth + t) * a.max_n + i; a.rs[o] = s; a.rj[o] = j; }
         else a.flag[b] = 1;
     }
     if (c.x & (1 << 29)) {
@@ -574,11 +650,12 @@ extern "C" __attribute__((visibility("default"))) int kpb_sample(kpb_ctx* ctx, c
     return KPB_OK;
 }
 
-extern "C" __attribute__((visibility("default"))) int kpb_match(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch, int C, int max_n,
-                         int max_m, const int32_t* n_dev, const int32_t* m_dev, const kpb_match_params* prm,
-                         int32_t* out_pairs_dev, double* out_dist_dev, int32_t* out_k_dev)
+// kpb_match and kpb_match_ratio.  ratio: max_ratio < 1, the ratio test is on; off, every launch, grid and workspace size is what kpb_match
+// has always enqueued (the <false> instantiations are that code).
+static int match_impl(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch, int C, int max_n, int max_m, const int32_t* n_dev,
+                      const int32_t* m_dev, const kpb_match_params* prm, double max_ratio, int32_t* out_pairs_dev, double* out_dist_dev, int32_t* out_k_dev)
 {
-    if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_match: null context");
+    const bool ratio = max_ratio < 1.0;
     ctx->match_counts_valid = 0;        // set again only when everything of this call has been enqueued
     if (!prm || !out_k_dev || batch <= 0 || C <= 0 || max_n < 0 || max_m < 0)
         return kpb_fail(ctx, KPB_E_INVALID, "kpb_match: bad argument");
@@ -601,7 +678,8 @@ extern "C" __attribute__((visibility("default"))) int kpb_match(kpb_ctx* ctx, co
     if (!d0_dev || !d1_dev || !out_pairs_dev) return kpb_fail(ctx, KPB_E_INVALID, "kpb_match: null buffer");
     if (max_m > 16384) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_match: max_m %d > 16384", max_m);
     const int tiles_i = cdiv(max_n, MTI), tiles_j = cdiv(max_m, MTJ);
-    const size_t nr = (size_t)batch * tiles_j * max_n, nc = (size_t)batch * tiles_i * max_m;
+    const int rdepth = ratio ? row_depth(tiles_j) : tiles_j;        // row slots per pair
+    const size_t nr = (size_t)batch * rdepth * max_n, nc = (size_t)batch * tiles_i * max_m;
     double *rs = nullptr, *cs = nullptr;
     int* rj = nullptr;          // rj[nr] and ci[nc] in ONE piece: the prefilter marks both empty with one 32-bit fill
     if (int rc = kpb_carve(ctx, ctx->ws_match, [&](Arena& a) { rs = a.take<double>(nr); cs = a.take<double>(nc); rj = a.take<int>(nr + nc); })) return rc;
@@ -639,24 +717,50 @@ extern "C" __attribute__((visibility("default"))) int kpb_match(kpb_ctx* ctx, co
 #define KPB_APX(KB_, RT_)                                                                                                                   \
         {                                                                                                                                       \
             const dim3 grid(cdiv(max_n, 64 * RT_), batch);                                                                                      \
-            KPB_LAUNCH(ctx, "match_approx_min", (match_approx<KB_, RT_, 0>), grid, dim3(256), 0, ctx->stream, xa);                              \
+            if (ratio) KPB_LAUNCH(ctx, "match_approx_min2", (match_approx<KB_, RT_, 0, true>), grid, dim3(256), 0, ctx->stream, xa);            \
+            else KPB_LAUNCH(ctx, "match_approx_min", (match_approx<KB_, RT_, 0>), grid, dim3(256), 0, ctx->stream, xa);                         \
             KPB_LAUNCH(ctx, "match_approx_cand", (match_approx<KB_, RT_, 1>), grid, dim3(256), 0, ctx->stream, xa);                             \
         }
         if (KB == 1) KPB_APX(1, 4) else if (KB == 2) KPB_APX(2, 4) else if (KB == 3) KPB_APX(3, 2) else if (KB == 4) KPB_APX(4, 2)
         else if (KB == 5) KPB_APX(5, 1) else if (KB == 6) KPB_APX(6, 1) else if (KB == 7) KPB_APX(7, 1) else KPB_APX(8, 1)
 #undef KPB_APX
-        ExactArgs ea{d0_dev, d1_dev, cand, ncand, cap, C, max_n, max_m, rcnt, ccnt, rs, rj, cs, ci, tiles_i, tiles_j, m_dev, n_dev, flag};
+        ExactArgs ea{d0_dev, d1_dev, cand, ncand, cap, C, max_n, max_m, rcnt, ccnt, rs, rj, cs, ci, tiles_i, rdepth, m_dev, n_dev, flag, ratio ? 1 : 0};
         KPB_LAUNCH(ctx, "match_exact", match_exact, dim3(cdiv(cap, 256), batch), dim3(256), 0, ctx->stream, ea);
         only = flag;
     }
-    MatchArgs a{only, d0_dev, d1_dev, n_dev, m_dev, rs, rj, cs, ci, C, max_n, max_m, tiles_i, tiles_j};
-    KPB_LAUNCH(ctx, "match_tile", match_tile, dim3(tiles_j, tiles_i, batch), dim3(MATCH_THREADS), 0, ctx->stream, a);
+    MatchArgs a{only, d0_dev, d1_dev, n_dev, m_dev, rs, rj, cs, ci, C, max_n, max_m, tiles_i, rdepth};
     FinArgs f{rs, rj, cs, ci, n_dev, m_dev, out_pairs_dev, out_dist_dev, out_k_dev, ctx->host_match,
-              max_n, max_m, tiles_i, tiles_j, prm->cross_check, prm->max_distance};
-    KPB_LAUNCH(ctx, "match_finalize", match_finalize, dim3(batch), dim3(FIN_THREADS), (size_t)max_m * sizeof(int), ctx->stream, f);
+              max_n, max_m, tiles_i, rdepth, prm->cross_check, prm->max_distance, only, max_ratio};
+    if (ratio) {
+        KPB_LAUNCH(ctx, "match_tile2", match_tile<true>, dim3(tiles_j, tiles_i, batch), dim3(MATCH_THREADS), 0, ctx->stream, a);
+        KPB_LAUNCH(ctx, "match_finalize_ratio", match_finalize<true>, dim3(batch), dim3(FIN_THREADS), (size_t)max_m * sizeof(int), ctx->stream, f);
+    } else {
+        KPB_LAUNCH(ctx, "match_tile", match_tile<false>, dim3(tiles_j, tiles_i, batch), dim3(MATCH_THREADS), 0, ctx->stream, a);
+        KPB_LAUNCH(ctx, "match_finalize", match_finalize<false>, dim3(batch), dim3(FIN_THREADS), (size_t)max_m * sizeof(int), ctx->stream, f);
+    }
     KPB_HIP(ctx, hipGetLastError());
     ctx->match_counts_valid = 1;
     return KPB_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) int kpb_match(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch, int C, int max_n,
+                         int max_m, const int32_t* n_dev, const int32_t* m_dev, const kpb_match_params* prm,
+                         int32_t* out_pairs_dev, double* out_dist_dev, int32_t* out_k_dev)
+{
+    if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_match: null context");
+    return match_impl(ctx, d0_dev, d1_dev, batch, C, max_n, max_m, n_dev, m_dev, prm, 1.0, out_pairs_dev, out_dist_dev, out_k_dev);
+}
+
+extern "C" __attribute__((visibility("default"))) int kpb_match_ratio(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch, int C, int max_n,
+                               int max_m, const int32_t* n_dev, const int32_t* m_dev, const kpb_match_params* prm, double max_ratio,
+                               int32_t* out_pairs_dev, double* out_dist_dev, int32_t* out_k_dev)
+{
+    if (max_ratio != max_ratio) {       // refused before anything touches a device (ctx may be NULL)
+        if (ctx) ctx->match_counts_valid = 0;
+        return kpb_fail(ctx, KPB_E_INVALID, "kpb_match_ratio: max_ratio is NaN");
+    }
+    if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_match_ratio: null context");
+    return match_impl(ctx, d0_dev, d1_dev, batch, C, max_n, max_m, n_dev, m_dev, prm, max_ratio, out_pairs_dev, out_dist_dev, out_k_dev);
 }
 
 extern "C" __attribute__((visibility("default"))) int kpb_match_counts(kpb_ctx* ctx, int32_t* out_k_host, int batch)

@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from ._lib import Context, DetectParams, LgParams, MatchParams, ptr
+from .utils.matcher import match_ratio_of
 
 
 PLACE_MIN_BYTES = 4 << 30       # descriptor maps below this are not worth placing (their forward is not bound by the map's stores)
@@ -40,6 +41,7 @@ class _Core:
         self.dprm = DetectParams(int(ep["nms_dist"]), float(ep["threshold"]), int(ep["border_dist"]), self.top_k,
                                  float(ep["min_score"]))
         self.mprm = MatchParams(float(bf["max_distance"]), 1 if bf["cross_check"] else 0)
+        self.max_ratio = match_ratio_of(bf)         # the optional max_ratio key: absent = 1.0 = off (the call is then kpb_match, launch for launch)
         net._ensure(self.device)
         self.dense, self.div, self.C = net.dense_descriptors, net.desc_div, net.dim
         self.Hd, self.Wd = H // self.div, W // self.div
@@ -92,8 +94,8 @@ class _Core:
                                      ptr(self.desc), ptr(self.desc[second:]), C, Hd, Wd, Hd * Wd * C, 1, Wd * C, C, self.W, self.H,
                                      ctypes.byref(prm), ptr(self.pairs), ptr(self.lg_scores), ptr(self.k), ptr(self.lg_stop)))
         else:
-            ctx.check(L.kpb_match(ctx.handle, ptr(self.sdesc), ptr(self.sdesc[second:]), count, C, K, K, ptr(n), ptr(n[second:]),
-                                  ctypes.byref(self.mprm), ptr(self.pairs), ptr(self.dist), ptr(self.k)))
+            ctx.check(L.kpb_match_ratio(ctx.handle, ptr(self.sdesc), ptr(self.sdesc[second:]), count, C, K, K, ptr(n), ptr(n[second:]),
+                                        ctypes.byref(self.mprm), self.max_ratio, ptr(self.pairs), ptr(self.dist), ptr(self.k)))
         ctx.check(L.kpb_gather_rows(ctx.handle, ptr(pts), count, K, cols, ptr(self.pairs), K, 2, 0, ptr(self.k), ptr(m0)))
         ctx.check(L.kpb_gather_rows(ctx.handle, ptr(pts[second:]), count, K, cols, ptr(self.pairs), K, 2, 1, ptr(self.k), ptr(m1)))
 

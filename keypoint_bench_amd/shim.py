@@ -11,6 +11,9 @@ never from oracle/) and routes to it whatever lies outside the library's contrac
   * arguments the kernels do not carry (fast_nms max_iter / min_value, a non-euclidean metric, nms_dist > 16, more matches
     than a RANSAC kernel holds, ALIKE channel plans other than -t, DISK variants): KPB_E_UNSUPPORTED / NotImplementedError.
 
+One thing is refused instead of routed: a brute-force call whose ``brute_force_params`` carry ``max_ratio`` < 1.  The reference's own
+``brute_force_matcher`` does not read that key, so handing it the call would drop the filter without a word: ValueError.
+
 Nothing else falls through: KPB_E_INVALID (a malformed call) and every other library error RAISE -- an in-contract call that
 starts failing must not turn into a silent thousandfold slowdown on the reference's CPU code.
 
@@ -40,16 +43,37 @@ def _note(name, why):
     warnings.warn("keypoint_bench_amd: %s handled by the reference's own code (%s)" % (name, why), RuntimeWarning, stacklevel=3)
 
 
-def guarded(name, hip_fn, ref_fn, in_contract):
-    """hip_fn where the call is inside the library's contract, ref_fn (the reference's original) elsewhere."""
+def ratio_refusal(*a, **k):
+    """Why the reference's own code cannot take this call: a max_ratio < 1 that its brute_force_matcher would ignore.  Looks at every dict among the
+    arguments: brute_force_params itself, or the task parameters whose matcher is the brute-force one."""
+    for d in list(a) + list(k.values()):
+        if not isinstance(d, dict):
+            continue
+        mp = d.get("matcher_params")
+        if isinstance(mp, dict):
+            d = mp.get("brute_force_params") if mp.get("type", "brute_force") == "brute_force" else None
+        if isinstance(d, dict) and d.get("max_ratio") is not None and not float(d["max_ratio"]) >= 1.0:
+            return "max_ratio = %r: the reference's brute_force_matcher ignores the key" % (d["max_ratio"],)
+    return None
+
+
+def guarded(name, hip_fn, ref_fn, in_contract, refuse=None):
+    """hip_fn where the call is inside the library's contract, ref_fn (the reference's original) elsewhere -- unless refuse(*a, **k) names a
+    reason why the original would compute something else than was asked for: then the call raises ValueError instead of being routed."""
+
+    def to_reference(why, *a, **k):
+        no = refuse(*a, **k) if refuse is not None else None
+        if no is not None:
+            raise ValueError("keypoint_bench_amd: %s cannot be handed to the reference's own code (%s): %s" % (name, why, no))
+        call.fallbacks += 1
+        return ref_fn(*a, **k)
 
     def call(*a, **k):
         if ref_fn is None:
             return hip_fn(*a, **k)
         why = in_contract(*a, **k)
         if why is not None:
-            call.fallbacks += 1
-            return ref_fn(*a, **k)
+            return to_reference(why, *a, **k)
         try:
             return hip_fn(*a, **k)
         except KpbError as e:
@@ -58,10 +82,9 @@ def guarded(name, hip_fn, ref_fn, in_contract):
             why = "negative scores" if e.code == KPB_E_NEGATIVE else str(e)
         except NotImplementedError as e:
             why = str(e)
-        if call.fallbacks == 0:
+        if call.fallbacks == 0 and (refuse is None or refuse(*a, **k) is None):
             _note(name, why)
-        call.fallbacks += 1
-        return ref_fn(*a, **k)
+        return to_reference(why, *a, **k)
 
     call.__name__ = getattr(hip_fn, "__name__", name)
     call.__doc__ = hip_fn.__doc__
@@ -208,6 +231,10 @@ def _c_vkp(kps0, kps1, warp01, warp10, th=3):
     return None if _on_device(kps0, kps1) else "keypoints are not on a HIP device"
 
 
+# the swapped functions through which a brute-force match can reach the reference's own brute_force_matcher
+RATIO_ROUTES = ("brute_force_matcher", "fundamental_matrix", "fundamental_matrix_ransac", "visual_odometry")
+
+
 def _table():
     from .models.ALike import ALNet
     from .models.SuperPoint import SuperPointNet
@@ -264,7 +291,7 @@ def install():
         ref = getattr(mod, attr)
         _state["originals"][full] = ref
         if kind == "fn":
-            new = guarded(full, hip, ref, contract)
+            new = guarded(full, hip, ref, contract, refuse=ratio_refusal if attr in RATIO_ROUTES else None)
         elif kind == "lk":
             new = _lk_factory(hip, ref)
         elif kind == "matcher":
