@@ -1,0 +1,119 @@
+// conv_layer.hip -- stage_layer and launch_mfma (conv_layer.h): the one place where the generic forms of conv_mfma_h, conv_mfma and gemm_h that the six
+// networks launch are instantiated.  A network that needs a new form adds it to the lists here.
+#include "conv_layer.h"
+#include "conv_mfma.h"
+
+namespace {
+
+// OIHW -> conv_valu's [tap][cin][COUT8] (convnet.hip)
+std::vector<float> pack_valu(const float* w, int COUT, int CIN, int KS)
+{
+    const int T = KS * KS, C8 = ((COUT + 7) / 8) * 8;
+    std::vector<float> out((size_t)T * CIN * C8, 0.0f);
+    for (int o = 0; o < COUT; ++o)
+        for (int c = 0; c < CIN; ++c)
+            for (int t = 0; t < T; ++t) out[((size_t)t * CIN + c) * C8 + o] = w[((size_t)o * CIN + c) * T + t];
+    return out;
+}
+
+}  // namespace
+
+int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const MfmaOpt& o)
+{
+    const int S = L.stride, CC = L.cc, HALO = (L.ks - 1) * L.dil, PAD = HALO / 2;       // CmForm::dil: the output keeps the input's extent at stride 1 for odd and even ks
+    const char* name = L.prof.c_str();
+    ConvM a{.in = in, .out = out, .wp = L.w, .bias = L.b, .xf = o.xf, .res = o.res,
+            .Hi = Hi, .Wi = Wi, .H = (Hi + 2 * PAD - HALO - 1) / S + 1, .W = (Wi + 2 * PAD - HALO - 1) / S + 1, .CIN = L.cin, .COUT = L.cout, .NCH = L.cin / CC,
+            .relu = o.res ? 0 : L.relu, .nblk = (L.cout + 32 * L.ntb - 1) / (32 * L.ntb), .istride = L.cin, .ostride = L.cout, .rstride = o.res ? L.cout : 0,
+            .aux0 = reinterpret_cast<const float*>(o.unfold_mr), .unfold_w = o.unfold_w};
+    if (o.unfold_w && !(conv_mfma_use_h16() && L.ks == 1 && S == 1 && CC == 32 && !L.pool_out && !o.xf && L.cin == 64))
+        return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: the unfolded input exists for 64-channel 1x1 layers of the split-f16 form only");
+    if (o.res && (L.ks != 1 || L.cout % 64)) return kpb_fail(ctx, KPB_E_INVALID, "SFD2 %s: the identity branch joins 1x1 layers of whole 64-channel tiles", L.name.c_str());
+    hipStream_t st = ctx->stream;
+    const bool x = o.xf != nullptr;
+    if (conv_mfma_use_h16()) {
+        a.unscale = L.unscale;
+        if (L.ks == 1 && S == 1 && CC == 32 && !L.pool_out && !x && !o.pre) {     // 1x1: gemm_h
+            const dim3 grid(cdiv(a.H * a.W, 128), 1, B * a.nblk), block(256);
+            if (o.l2_eps > 0.0f) {
+                if (L.cout != 64 || L.ntb != 2) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: the fused L2 norm needs a 64-channel layer");
+                a.xb = o.l2_eps;
+                KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_L2NORM>), grid, block, 0, st, a);
+            }
+            else if (o.unfold_w) KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_PLAIN, true>), grid, block, 0, st, a);
+            else if (o.res) KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_RES_RELU>), grid, block, 0, st, a);
+            else KPB_LAUNCH(ctx, name, (gemm_h<2, 1>), grid, block, 0, st, a);
+            return KPB_OK;
+        }
+        if (L.ks == 2) {        // tap-gathered product (R2D2's dilated 2 x 2 layers): K = 4 taps x cin, 128 pixels x 64 output channels per workgroup
+            a.NCH = 4 * (L.cin / 32); a.tap_dil = L.dil;
+            KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_PLAIN, false, 2>), dim3(cdiv(a.H * a.W, 128), 1, B * a.nblk), dim3(256), 0, st, a);
+            return KPB_OK;
+        }
+        // split-f16 form: stride-1 layers on 16-row workgroup tiles; with two n-tiles per workgroup the waves form 2 row groups x 2 n-tiles
+        // (four M tiles and one n-tile per wave)
+        CmForm f{.ks = L.ks, .s = S, .cc = CC, .pool_out = L.pool_out, .xf = x, .ntb = 1, .mt = 4, .wn = 2, .dil = L.dil};
+        // one-tile layers (cout <= 32) are bound by per-workgroup latency: 8-row tiles (one M tile per wave, 28 KB of LDS, five
+        // workgroups per CU) measured 8-16 % faster; layers with two output tiles lose the fragment reuse that way (+8 % time)
+        if (L.ntb == 1) f.mt = f.wn = 1;
+        if (S == 2) f.mt = 2;           // stride 2: 8-row tiles
+        if (L.dil == 4) f.mt = 2;       // dilation 4: 8-row tiles -- the 24-pixel-wide tile would not fit 16 rows into the LDS window
+        if (const PreSplit* pre = o.pre) {      // the input arrives already split (ConvM::pre_amax), generated while the tile is staged from the one-channel image the layer in front reads
+            if (!pre->gen_w) return kpb_fail(ctx, KPB_E_INVALID, "conv_mfma_h: no generated-input instance for %s", L.name.c_str());
+            a.pre_amax = pre->amax; a.pre_l1 = pre->l1; a.pre_bmax = pre->bmax; a.gen_w = pre->gen_w; a.gen_b = pre->gen_b; a.istride = 1;
+            f.pre = f.gen = true;
+        }
+        if (const UpSrc* up = o.up) {       // [up(bottom) | horizontal] evaluated while staging (ConvM::up_src); `in` holds the channels behind the upsampled ones
+            if (up->c % CC || up->c >= L.cin || (Hi % 2) || (Wi % 2)) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: bad upsampled-input split for %s", L.name.c_str());
+            a.up_src = up->src; a.up_c = up->c; a.istride = L.cin - up->c;
+            f.up = true;
+        }
+        if (L.ntb == 5) {
+            // 129 = 4 x 32 + 1 (DISK up_3): four MFMA tiles (two workgroups of two: 64 accumulator registers, three waves per SIMD)
+            // and the score channel on the VALU of the first workgroup
+            a.nblk = 2; a.xw = L.xw; a.xb = L.xb; a.xun = L.xun; a.xco = L.cout - 1;
+            f.xc = true;
+        }
+        return launch_conv_mfma_h<
+            CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
+            CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .pre = true, .wn = 2, .gen = true},
+            CmForm{.ks = 3, .s = 2, .cc = 16, .ntb = 1, .mt = 2, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .wn = 2},
+            CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2, .up = true},
+            CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .xc = true, .wn = 2, .up = true},
+            CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .dil = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 2, .wn = 2, .dil = 4}>(ctx, name, f, a, B);
+    }
+    return launch_conv_mfma<
+        CmForm{.ks = 1, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1},
+        CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true}, CmForm{.ks = 3, .s = 2, .cc = 16},
+        CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 5},
+        CmForm{.ks = 3, .s = 1, .cc = 32, .dil = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .dil = 4},
+        CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 4}, CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 8}, CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 16}>(
+        ctx, name, CmForm{.ks = L.ks, .s = S, .cc = CC, .pool_out = L.pool_out, .xf = x, .ntb = L.ntb, .dil = L.dil}, a, B);
+}
+
+void stage_layer(WeightStage& ws, Layer& L, const char* prefix, const float* w, const float* b)
+{
+    L.prof = prefix + L.name;
+    if (L.mfma) {
+        if (conv_mfma_use_h16() && L.ntb == 5) {       // cout = 4 x 32 + 1: the last channel goes to the VALU side of conv_mfma_h<XC>
+            const int T = L.ks * L.ks, co = L.cout - 1;
+            const float sc = weight_scale_h(w, (size_t)co * L.cin * T);
+            ws.put(pack_mfma_h(w, co, L.cin, L.ks, L.cc, 2, sc), &L.w);
+            L.unscale = 1.0f / sc;
+            const float xs = weight_scale_h(w + (size_t)co * L.cin * T, (size_t)L.cin * T);
+            ws.put(pack_xc_pairs(w + (size_t)co * L.cin * T, L.cin, T, xs), &L.xw);
+            L.xun = 1.0f / xs;
+            L.xb = b ? b[co] : 0.0f;
+        } else if (conv_mfma_use_h16()) {       // tap-major fragments: the same pack serves the halo form, the 1 x 1 product and the tap-gathered one
+            const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * L.ks * L.ks);
+            ws.put(pack_mfma_h(w, L.cout, L.cin, L.ks, L.cc, L.ntb, sc), &L.w);
+            L.unscale = 1.0f / sc;
+        } else {
+            ws.put(pack_mfma(w, L.cout, L.cin, L.ks, L.cc, L.ntb), &L.w);
+        }
+        ws.put(pad_bias(b, L.cout, 32 * L.ntb), &L.b);
+    } else {
+        ws.put(pack_valu(w, L.cout, L.cin, L.ks), &L.w);
+        ws.put(pad_bias(b, L.cout, 8), &L.b);
+    }
+}

@@ -1347,7 +1347,7 @@ inline std::vector<float> pack_win3x4_h16(const float* w, float scale)
 
 // OIHW -> conv_mfma_h fragment order [ntile][tap][chunk][kb][hi/lo][h][32] x 8 halves, scaled by `scale`; the result
 // has exactly the byte count of pack_mfma's, and is returned in a float vector so that it travels the same way
-std::vector<float> pack_mfma_h(const float* w, int COUT, int CIN, int KS, int CC, int NTB, float scale)
+inline std::vector<float> pack_mfma_h(const float* w, int COUT, int CIN, int KS, int CC, int NTB, float scale)
 {
     const int KC = CC / 2, NKB = CC / 16, T = KS * KS, NCH = CIN / CC, NT = ((COUT + 32 * NTB - 1) / (32 * NTB)) * NTB;
     H16Frags fr((size_t)NT * T * NCH * NKB * 4 * 32 * 8);
@@ -1389,7 +1389,7 @@ inline bool conv_mfma_use_h16()
 }
 
 // OIHW [COUT][CIN][KS][KS] -> conv_mfma fragment order [ntile][tap][chunk][h][32][KC]
-std::vector<float> pack_mfma(const float* w, int COUT, int CIN, int KS, int CC, int NTB)
+inline std::vector<float> pack_mfma(const float* w, int COUT, int CIN, int KS, int CC, int NTB)
 {
     const int KC = CC / 2, T = KS * KS, NCH = CIN / CC, NT = ((COUT + 32 * NTB - 1) / (32 * NTB)) * NTB;
     std::vector<float> out((size_t)NT * T * NCH * 2 * 32 * KC, 0.0f);
@@ -1406,7 +1406,7 @@ std::vector<float> pack_mfma(const float* w, int COUT, int CIN, int KS, int CC, 
     return out;
 }
 
-std::vector<float> pad_bias(const float* b, int COUT, int mult)
+inline std::vector<float> pad_bias(const float* b, int COUT, int mult)
 {
     std::vector<float> out(((COUT + mult - 1) / mult) * mult, 0.0f);
     if (b) for (int i = 0; i < COUT; ++i) out[i] = b[i];

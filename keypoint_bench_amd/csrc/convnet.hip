@@ -9,6 +9,7 @@
 // weights are pre-packed in exactly that fragment order so B is CC/8 global float4 loads per 32-wide tile.
 // The 2x2 max-pools of the VGG trunk are fused: on the input read (POOL_IN) or lane-locally on the
 // accumulators (POOL_OUT: the four pixels of a pool window live in registers r, r+1, r+8, r+9 of one lane).
+#include "conv_layer.h"
 #include "conv_mfma.h"
 
 namespace {
@@ -660,108 +661,6 @@ __global__ void unfold8(const float* gray, float* out, int H, int W)       // fo
 }
 
 // ------------------------------------------------------------------------------------------------ host helpers
-// OIHW -> [tap][cin][COUT8]
-std::vector<float> pack_valu(const float* w, int COUT, int CIN, int KS)
-{
-    const int T = KS * KS, C8 = ((COUT + 7) / 8) * 8;
-    std::vector<float> out((size_t)T * CIN * C8, 0.0f);
-    for (int o = 0; o < COUT; ++o)
-        for (int c = 0; c < CIN; ++c)
-            for (int t = 0; t < T; ++t) out[((size_t)t * CIN + c) * C8 + o] = w[((size_t)o * CIN + c) * T + t];
-    return out;
-}
-
-struct Layer {      // one convolution of a network plan
-    std::string name;
-    int cin, cout, ks, stride;
-    bool mfma;
-    bool relu = true;           // ReLU on the output
-    bool pool_out = false;      // the output max-pooled 2 x 2 (SuperPoint's MaxPool2d after conv1b / 2b / 3b)
-    int cc = 32;    // channels per LDS chunk of conv_mfma (32, or 16 for stride 2 / CIN not a multiple of 32)
-    int ntb = 2;    // 32-wide output tiles per workgroup
-    // what a launch needs of the staged weights, bound once at create by stage_layer: host scalars, device pointers and the profile name
-    float unscale = 1.0f;               // split-f16 form: 1 / the power-of-two scale the pack was made with (conv_mfma_h)
-    float xb = 0.0f, xun = 1.0f;        // ntb == 5 (DISK up_3): the score channel's bias and 1 / the scale of its pack
-    const float *w = nullptr, *b = nullptr, *xw = nullptr;
-    const float* slope = nullptr;       // DISK: the PReLU slopes of the layer's input
-    std::string prof;                   // profile name of its launch
-};
-
-struct UpSrc { const float* src; int c; };      // ConvM::up_src, up_c
-struct PreSplit { const unsigned* amax = nullptr; float l1 = 0.0f, bmax = 0.0f; const float* gen_w = nullptr; const float* gen_b = nullptr; };     // ConvM::pre_*, gen_*
-
-// What one launch_mfma call adds to its layer, by designated initialisers: launch_mfma(..., {.xf = xf, .up = &up})
-struct MfmaOpt {
-    const float* xf = nullptr;          // ConvM::xf: DISK's InstanceNorm + PReLU of the input, applied while it is staged
-    const PreSplit* pre = nullptr;      // SuperPoint conv1b: its input generated from the grey image while the tile is staged
-    const UpSrc* up = nullptr;          // DISK up2 / up3: the upsampled input channels evaluated while the tile is staged
-    int unfold_w = 0;                   // XFeat keypoint_head.0: the 8 x 8 cells of a [B][8 H][unfold_w] image read in place (ConvM::unfold_w),
-    const float2* unfold_mr = nullptr;  // normalised by the per-image (mean, 1 / std) as they are read
-    float l2_eps = 0.0f;                // > 0: F.normalize(eps = l2_eps) of every output row in the epilogue (XFeat block_fusion.2, split-f16 form)
-};
-
-int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const MfmaOpt& o = {})
-{
-    const int S = L.stride, CC = L.cc, PAD = L.ks / 2;
-    const char* name = L.prof.c_str();
-    ConvM a{.in = in, .out = out, .wp = L.w, .bias = L.b, .xf = o.xf,
-            .Hi = Hi, .Wi = Wi, .H = (Hi + 2 * PAD - L.ks) / S + 1, .W = (Wi + 2 * PAD - L.ks) / S + 1, .CIN = L.cin, .COUT = L.cout, .NCH = L.cin / CC,
-            .relu = L.relu, .nblk = (L.cout + 32 * L.ntb - 1) / (32 * L.ntb), .istride = L.cin, .ostride = L.cout,
-            .aux0 = reinterpret_cast<const float*>(o.unfold_mr), .unfold_w = o.unfold_w};
-    if (o.unfold_w && !(conv_mfma_use_h16() && L.ks == 1 && S == 1 && CC == 32 && !L.pool_out && !o.xf && L.cin == 64))
-        return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: the unfolded input exists for 64-channel 1x1 layers of the split-f16 form only");
-    hipStream_t st = ctx->stream;
-    const bool x = o.xf != nullptr;
-    if (conv_mfma_use_h16()) {
-        a.unscale = L.unscale;
-        if (L.ks == 1 && S == 1 && CC == 32 && !L.pool_out && !x && !o.pre) {     // 1x1: gemm_h
-            const dim3 grid(cdiv(a.H * a.W, 128), 1, B * a.nblk), block(256);
-            if (o.l2_eps > 0.0f) {
-                if (L.cout != 64 || L.ntb != 2) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: the fused L2 norm needs a 64-channel layer");
-                a.xb = o.l2_eps;
-                KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_L2NORM>), grid, block, 0, st, a);
-            }
-            else if (o.unfold_w) KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_PLAIN, true>), grid, block, 0, st, a);
-            else KPB_LAUNCH(ctx, name, (gemm_h<2, 1>), grid, block, 0, st, a);
-            return KPB_OK;
-        }
-        // split-f16 form: stride-1 layers on 16-row workgroup tiles; with two n-tiles per workgroup the waves form 2 row groups x 2 n-tiles
-        // (four M tiles and one n-tile per wave)
-        CmForm f{.ks = L.ks, .s = S, .cc = CC, .pool_out = L.pool_out, .xf = x, .ntb = 1, .mt = 4, .wn = 2};
-        // one-tile layers (cout <= 32) are bound by per-workgroup latency: 8-row tiles (one M tile per wave, 28 KB of LDS, five
-        // workgroups per CU) measured 8-16 % faster; layers with two output tiles lose the fragment reuse that way (+8 % time)
-        if (L.ntb == 1) f.mt = f.wn = 1;
-        if (S == 2) f.mt = 2;           // stride 2: 8-row tiles
-        if (const PreSplit* pre = o.pre) {      // the input arrives already split (ConvM::pre_amax), generated while the tile is staged from the one-channel image the layer in front reads
-            if (!pre->gen_w) return kpb_fail(ctx, KPB_E_INVALID, "conv_mfma_h: no generated-input instance for %s", L.name.c_str());
-            a.pre_amax = pre->amax; a.pre_l1 = pre->l1; a.pre_bmax = pre->bmax; a.gen_w = pre->gen_w; a.gen_b = pre->gen_b; a.istride = 1;
-            f.pre = f.gen = true;
-        }
-        if (const UpSrc* up = o.up) {       // [up(bottom) | horizontal] evaluated while staging (ConvM::up_src); `in` holds the channels behind the upsampled ones
-            if (up->c % CC || up->c >= L.cin || (Hi % 2) || (Wi % 2)) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: bad upsampled-input split for %s", L.name.c_str());
-            a.up_src = up->src; a.up_c = up->c; a.istride = L.cin - up->c;
-            f.up = true;
-        }
-        if (L.ntb == 5) {
-            // 129 = 4 x 32 + 1 (DISK up_3): four MFMA tiles (two workgroups of two: 64 accumulator registers, three waves per SIMD)
-            // and the score channel on the VALU of the first workgroup
-            a.nblk = 2; a.xw = L.xw; a.xb = L.xb; a.xun = L.xun; a.xco = L.cout - 1;
-            f.xc = true;
-        }
-        return launch_conv_mfma_h<
-            CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
-            CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .pre = true, .wn = 2, .gen = true},
-            CmForm{.ks = 3, .s = 2, .cc = 16, .ntb = 1, .mt = 2, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .wn = 2},
-            CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2, .up = true},
-            CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .xc = true, .wn = 2, .up = true}>(ctx, name, f, a, B);
-    }
-    return launch_conv_mfma<
-        CmForm{.ks = 1, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1},
-        CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true}, CmForm{.ks = 3, .s = 2, .cc = 16},
-        CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 5}>(
-        ctx, name, CmForm{.ks = L.ks, .s = S, .cc = CC, .pool_out = L.pool_out, .xf = x, .ntb = L.ntb}, a, B);
-}
-
 struct ValuSkip { const float* gray = nullptr; const float* w = nullptr; const float* b = nullptr; int n = 0; };     // ConvV::gray, skw, skb, skn
 
 int launch_valu(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const ValuSkip& skip = {})
@@ -792,34 +691,6 @@ int launch_valu(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B
         KPB_LAUNCH(ctx, name, conv_valu, grid, block, 0, st, a);
     }
     return KPB_OK;
-}
-
-// L is the net's own Layer (net->L[i]): the stage binds its pointers at the upload.  Profile name = prefix + layer name: "sp_conv1b", "xf_block2.0", "disk_up3"
-void stage_layer(WeightStage& ws, Layer& L, const char* prefix, const float* w, const float* b)
-{
-    L.prof = prefix + L.name;
-    if (L.mfma) {
-        if (conv_mfma_use_h16() && L.ntb == 5) {       // cout = 4 x 32 + 1: the last channel goes to the VALU side of conv_mfma_h<XC>
-            const int T = L.ks * L.ks, co = L.cout - 1;
-            const float sc = weight_scale_h(w, (size_t)co * L.cin * T);
-            ws.put(pack_mfma_h(w, co, L.cin, L.ks, L.cc, 2, sc), &L.w);
-            L.unscale = 1.0f / sc;
-            const float xs = weight_scale_h(w + (size_t)co * L.cin * T, (size_t)L.cin * T);
-            ws.put(pack_xc_pairs(w + (size_t)co * L.cin * T, L.cin, T, xs), &L.xw);
-            L.xun = 1.0f / xs;
-            L.xb = b ? b[co] : 0.0f;
-        } else if (conv_mfma_use_h16()) {
-            const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * L.ks * L.ks);
-            ws.put(pack_mfma_h(w, L.cout, L.cin, L.ks, L.cc, L.ntb, sc), &L.w);
-            L.unscale = 1.0f / sc;
-        } else {
-            ws.put(pack_mfma(w, L.cout, L.cin, L.ks, L.cc, L.ntb), &L.w);
-        }
-        ws.put(pad_bias(b, L.cout, 32 * L.ntb), &L.b);
-    } else {
-        ws.put(pack_valu(w, L.cout, L.cin, L.ks), &L.w);
-        ws.put(pad_bias(b, L.cout, 8), &L.b);
-    }
 }
 
 // ================================================================================================ SuperPoint

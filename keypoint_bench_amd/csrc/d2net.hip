@@ -21,6 +21,7 @@
 //   d2_sum             one workgroup per image: every thread adds its strided elements in index order, then a fixed tree -- the same bits every run, alone or
 //                      in a batch; no float atomics
 //   d2_upsample        one thread per output pixel: the four taps each divided by the image's sum (a true division), mixed as torch mixes them
+#include "conv_layer.h"
 #include "conv1a_rgb.h"
 
 namespace {
@@ -157,32 +158,10 @@ __global__ __launch_bounds__(256) void d2_upsample(const float* __restrict__ s, 
 }
 
 // ------------------------------------------------------------------------------------------------ host
-struct D2Layer { const char* name; int cin, cout; bool relu, pool_out; };
-enum { D2_11, D2_12, D2_21, D2_22, D2_31, D2_32, D2_33, D2_41, D2_42, D2_43, D2_LAYERS };
-// (folded tensor name, cin, cout, ReLU, 2 x 2 max-pool behind it); all 3 x 3, padding 1, bias
-constexpr D2Layer D2_PLAN[D2_LAYERS] = {
-    {"conv1_1", 3, 64, true, false}, {"conv1_2", 64, 64, true, true}, {"conv2_1", 64, 128, true, false}, {"conv2_2", 128, 128, true, true},
-    {"conv3_1", 128, 256, true, false}, {"conv3_2", 256, 256, true, false}, {"conv3_3", 256, 256, true, true},
-    {"conv4_1", 256, 512, true, false}, {"conv4_2", 512, 512, true, false}, {"conv4_3", 512, 512, false, false}};
+enum { D2_11, D2_12, D2_21, D2_22, D2_31, D2_32, D2_33, D2_41, D2_42, D2_43, D2_LAYERS };        // d2net_create's plan order
 
 struct D2Net : kpb_net {
-    struct Bound { const float* w = nullptr; const float* b = nullptr; float unscale = 1.0f; std::string prof; } lay[D2_LAYERS];
-    bool h16 = true;
-
-    // one 3 x 3 layer on the matrix cores at (Hi, Wi); `out` is (Hi, Wi) / 2 for the pooled layers
-    int conv(int i, const float* in, float* out, int batch, int Hi, int Wi)
-    {
-        const D2Layer& L = D2_PLAN[i];
-        const char* tag = lay[i].prof.c_str();
-        ConvM a{.in = in, .out = out, .wp = lay[i].w, .bias = lay[i].b, .Hi = Hi, .Wi = Wi, .H = Hi, .W = Wi, .CIN = L.cin, .COUT = L.cout, .NCH = L.cin / 32,
-                .relu = L.relu, .nblk = cdiv(L.cout, 64), .istride = L.cin, .ostride = L.cout};
-        if (!h16)
-            return launch_conv_mfma<CmForm{.ks = 3, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true}>(
-                ctx, tag, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = L.pool_out}, a, batch);
-        a.unscale = lay[i].unscale;
-        return launch_conv_mfma_h<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true, .ntb = 1, .mt = 4, .wn = 2}>(
-            ctx, tag, CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = L.pool_out, .ntb = 1, .mt = 4, .wn = 2}, a, batch);      // SuperPoint's forms: 16-row tiles
-    }
+    Layer L[D2_LAYERS];         // conv1_1 is conv1a_rgb64: its Layer carries the pointers only
 
     int forward(const float* img, int batch, int H, int W, float* score_out, float* desc_out) override
     {
@@ -203,17 +182,17 @@ struct D2Net : kpb_net {
         this->B = batch; this->H = H; this->W = W;
         hipStream_t st = ctx->stream;
         int rc;
-        launch_conv1a_rgb64(ctx, lay[D2_11].prof.c_str(), img, x11, lay[D2_11].w, lay[D2_11].b, batch, H, W);
-        if ((rc = conv(D2_12, x11, x12, batch, H, W))) return rc;
-        if ((rc = conv(D2_21, x12, x21, batch, H2, W2))) return rc;
-        if ((rc = conv(D2_22, x21, x22, batch, H2, W2))) return rc;
-        if ((rc = conv(D2_31, x22, x31, batch, H4, W4))) return rc;
-        if ((rc = conv(D2_32, x31, x32, batch, H4, W4))) return rc;
-        if ((rc = conv(D2_33, x32, x33, batch, H4, W4))) return rc;
-        if ((rc = conv(D2_41, x33, x41, batch, h, w))) return rc;
-        if ((rc = conv(D2_42, x41, x42, batch, h, w))) return rc;
+        launch_conv1a_rgb64(ctx, L[D2_11].prof.c_str(), img, x11, L[D2_11].w, L[D2_11].b, batch, H, W);
+        if ((rc = launch_mfma(ctx, L[D2_12], x11, x12, batch, H, W))) return rc;
+        if ((rc = launch_mfma(ctx, L[D2_21], x12, x21, batch, H2, W2))) return rc;
+        if ((rc = launch_mfma(ctx, L[D2_22], x21, x22, batch, H2, W2))) return rc;
+        if ((rc = launch_mfma(ctx, L[D2_31], x22, x31, batch, H4, W4))) return rc;
+        if ((rc = launch_mfma(ctx, L[D2_32], x31, x32, batch, H4, W4))) return rc;
+        if ((rc = launch_mfma(ctx, L[D2_33], x32, x33, batch, H4, W4))) return rc;
+        if ((rc = launch_mfma(ctx, L[D2_41], x33, x41, batch, h, w))) return rc;
+        if ((rc = launch_mfma(ctx, L[D2_42], x41, x42, batch, h, w))) return rc;
         float* feat = desc_out;         // the pre-ReLU conv4_3 map: read by the head, then normalised in place
-        if ((rc = conv(D2_43, x42, feat, batch, h, w))) return rc;
+        if ((rc = launch_mfma(ctx, L[D2_43], x42, feat, batch, h, w))) return rc;
         KPB_HIP(ctx, hipMemsetAsync(umax, 0, B * sizeof(unsigned), st));
         KPB_LAUNCH(ctx, "d2_max", d2_max, dim3(cdiv(h * w, D2_MAXPIX), batch), dim3(256), 0, st, feat, dw, umax, h * w);
         KPB_LAUNCH(ctx, "d2_softdetect", d2_softdetect, dim3(cdiv(w, D2_T), cdiv(h, D2_T), batch), dim3(256), 0, st, feat, dw, umax, s, h, w);
@@ -229,30 +208,27 @@ struct D2Net : kpb_net {
 
 int d2net_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
+    // folded tensor name, cin, cout, ks, stride, mfma, relu, pool_out (the 2 x 2 max-pool behind conv1_2 / 2_2 / 3_3); all 3 x 3, padding 1, bias
+    const Layer plan[] = {
+        {"conv1_1", 3, 64, 3, 1, false}, {"conv1_2", 64, 64, 3, 1, true, true, true}, {"conv2_1", 64, 128, 3, 1, true}, {"conv2_2", 128, 128, 3, 1, true, true, true},
+        {"conv3_1", 128, 256, 3, 1, true}, {"conv3_2", 256, 256, 3, 1, true}, {"conv3_3", 256, 256, 3, 1, true, true, true},
+        {"conv4_1", 256, 512, 3, 1, true}, {"conv4_2", 512, 512, 3, 1, true}, {"conv4_3", 512, 512, 3, 1, true, false}};
+    static_assert(sizeof(plan) / sizeof(plan[0]) == D2_LAYERS, "one plan entry per D2_* index");
     auto net = std::make_unique<D2Net>();
     net->ctx = ctx; net->arch = KPB_ARCH_D2NET; net->dim = D2_C; net->desc_div = 8;
-    net->h16 = conv_mfma_use_h16();
     WeightStage ws;
     for (int i = 0; i < D2_LAYERS; ++i) {
-        const D2Layer& L = D2_PLAN[i];
-        D2Net::Bound& dst = net->lay[i];
-        const std::string n = L.name;
-        dst.prof = "d2_" + n;
-        const float* w = bl.get((n + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, 3u, 3u});
-        const float* b = bl.get((n + ".b").c_str(), {(uint32_t)L.cout});
-        if (!w) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: D2Net tensor %s.w missing or mis-shaped", L.name);
-        if (!b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: D2Net tensor %s.b missing or mis-shaped", L.name);
+        Layer& L = net->L[i] = plan[i];
+        const float* w = bl.get((L.name + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, 3u, 3u});
+        const float* b = bl.get((L.name + ".b").c_str(), {(uint32_t)L.cout});
+        if (!w) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: D2Net tensor %s.w missing or mis-shaped", L.name.c_str());
+        if (!b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: D2Net tensor %s.b missing or mis-shaped", L.name.c_str());
         if (i == D2_11) {
-            ws.put(pack_conv1a_rgb64(w), &dst.w);
-            ws.put_raw(b, 64, &dst.b);
-        } else if (net->h16) {
-            const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * 9);
-            ws.put(pack_mfma_h(w, L.cout, L.cin, 3, 32, 2, sc), &dst.w);
-            dst.unscale = 1.0f / sc;
-            ws.put(pad_bias(b, L.cout, 64), &dst.b);
+            L.prof = "d2_" + L.name;
+            ws.put(pack_conv1a_rgb64(w), &L.w);
+            ws.put_raw(b, 64, &L.b);
         } else {
-            ws.put(pack_mfma(w, L.cout, L.cin, 3, 32, 2), &dst.w);
-            ws.put(pad_bias(b, L.cout, 64), &dst.b);
+            stage_layer(ws, L, "d2_", w, b);
         }
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;

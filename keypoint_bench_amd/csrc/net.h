@@ -103,9 +103,7 @@ struct WeightStage {
     }
 };
 
-// convnet.hip's l2norm_nhwc for the nets of other translation units: every C-channel row of an NHWC map divided by its L2 norm in place, the norm clamped from
-// below at eps_clamp when that is > 0 (F.normalize)
-void launch_l2norm_nhwc(kpb_ctx* ctx, const char* tag, float* desc, int C, size_t npix, float eps_clamp);
+// (what the conv_mfma networks lend each other -- Layer, stage_layer, launch_mfma, launch_l2norm_nhwc -- is declared in conv_layer.h)
 
 // factories, one per architecture
 int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);

@@ -7,7 +7,8 @@
 //   conv6 .. 8     gemm_h<.., TAPK = 2>: four taps x 128 channels gathered at (+-d / 2, +-d / 2) -- no halo in LDS
 //   r2d2_head      one pass over the 128-channel map: score and the normalised descriptor row
 // KPB_FP32_MATRIX=1: conv1 .. 8 on conv_mfma (fp32 MFMA) with the same dilation field.
-#include "conv_mfma.h"
+#include "conv_layer.h"
+#include "conv_mfma.h"      // relu
 
 namespace {
 
@@ -76,44 +77,12 @@ __global__ __launch_bounds__(256) void r2d2_head(float* __restrict__ desc, float
     }
 }
 
-struct R2Layer { const char* name; int cin, cout, ks, dil; bool relu; };
-// r2d2.py:105-117 with dilated = True: the strides of Quad_L2Net became the dilation of every layer behind them
-constexpr R2Layer R2D2_PLAN[9] = {{"conv0", 3, 32, 3, 1, true}, {"conv1", 32, 32, 3, 1, true}, {"conv2", 32, 64, 3, 1, true}, {"conv3", 64, 64, 3, 2, true},
-                                  {"conv4", 64, 128, 3, 2, true}, {"conv5", 128, 128, 3, 4, true}, {"conv6", 128, 128, 2, 4, false}, {"conv7", 128, 128, 2, 8, false},
-                                  {"conv8", 128, 128, 2, 16, false}};
-constexpr int r2_cc_fp32(const R2Layer& L) { return L.ks == 2 ? 16 : 32; }       // strict fp32: the 2 x 2, dilation-16 tile fits the LDS window in 16-channel slabs
-constexpr int r2_ntb_fp32(const R2Layer& L) { return L.cout == 32 ? 1 : 2; }
+enum { R2_C0, R2_C1, R2_C2, R2_C3, R2_C4, R2_C5, R2_C6, R2_C7, R2_C8, R2_LAYERS };       // r2d2_create's plan order
 
 struct R2d2Net : kpb_net {
-    struct Bound { const float* w; const float* b; float unscale = 1.0f; } lay[9];      // R2D2_PLAN's layers: packed weights, bias, 1 / the split-f16 pack's scale
+    Layer L[R2_LAYERS];         // conv0 is a kernel of its own: its Layer carries the pointers only
     const float* head_w = nullptr;
     const float* head_b = nullptr;
-    int conv(int i, const float* in, float* out, int batch, int H, int W)
-    {
-        const R2Layer& L = R2D2_PLAN[i];
-        ConvM a{.in = in, .out = out, .wp = lay[i].w, .bias = lay[i].b, .Hi = H, .Wi = W, .H = H, .W = W, .CIN = L.cin, .COUT = L.cout,
-                .NCH = L.cin / 32, .relu = L.relu, .nblk = cdiv(L.cout, 64), .istride = L.cin, .ostride = L.cout};
-        if (!conv_mfma_use_h16()) {
-            const int cc = r2_cc_fp32(L), ntb = r2_ntb_fp32(L);
-            a.NCH = L.cin / cc; a.nblk = cdiv(L.cout, 32 * ntb);
-            return launch_conv_mfma<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32, .dil = 2},
-                                    CmForm{.ks = 3, .s = 1, .cc = 32, .dil = 4}, CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 4}, CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 8},
-                                    CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 16}>(ctx, L.name, CmForm{.ks = L.ks, .s = 1, .cc = cc, .ntb = ntb, .dil = L.dil}, a, batch);
-        }
-        a.unscale = lay[i].unscale;
-        if (L.ks == 2) {        // tap-gathered product: K = 4 taps x cin, 128 pixels x 64 output channels per workgroup
-            a.NCH = 4 * (L.cin / 32); a.tap_dil = L.dil;
-            KPB_LAUNCH(ctx, L.name, (gemm_h<2, 1, GE_PLAIN, false, 2>), dim3(cdiv(H * W, 128), 1, batch * a.nblk), dim3(256), 0, ctx->stream, a);
-            return KPB_OK;
-        }
-        // halo tiles: 16 x 16 outputs (8 x 16 for the one-tile layer and for dilation 4, whose 24-pixel-wide tile would not fit 16 rows into the LDS window)
-        CmForm f{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .dil = L.dil};
-        if (L.cout == 32) f.mt = f.wn = 1;
-        if (L.dil == 4) f.mt = 2;
-        return launch_conv_mfma_h<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
-                                  CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .dil = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 2, .wn = 2, .dil = 4}>(
-            ctx, L.name, f, a, batch);
-    }
     int forward(const float* img, int batch, int H, int W, float* score_out, float* desc_out) override
     {
         if (!desc_out) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: R2D2 writes its 128 x H x W descriptor map; desc_out_dev is required");
@@ -125,9 +94,9 @@ struct R2d2Net : kpb_net {
         if (int rc = kpb_carve(ctx, act, [&](Arena& a) { for (float*& q : pp) q = a.take(B * P * 128); })) return rc;
         this->B = batch; this->H = H; this->W = W;
         hipStream_t st = ctx->stream;
-        KPB_LAUNCH(ctx, "r2d2_conv0", r2d2_conv0, dim3((unsigned)((P + 255) / 256), 4, batch), dim3(256), 0, st, img, pp[0], lay[0].w, lay[0].b, H, W);
-        for (int i = 1; i < 9; ++i)
-            if (int rc = conv(i, pp[(i - 1) & 1], i == 8 ? desc_out : pp[i & 1], batch, H, W)) return rc;
+        KPB_LAUNCH(ctx, "r2d2_conv0", r2d2_conv0, dim3((unsigned)((P + 255) / 256), 4, batch), dim3(256), 0, st, img, pp[0], L[R2_C0].w, L[R2_C0].b, H, W);
+        for (int i = R2_C1; i <= R2_C8; ++i)
+            if (int rc = launch_mfma(ctx, L[i], pp[(i - 1) & 1], i == R2_C8 ? desc_out : pp[i & 1], batch, H, W)) return rc;
         KPB_LAUNCH(ctx, "r2d2_head", r2d2_head, dim3((unsigned)((B * P + 15) / 16)), dim3(256), 0, st, desc_out, score_out, head_w, head_b, B * P);
         KPB_HIP(ctx, hipGetLastError());
         return KPB_OK;
@@ -138,33 +107,34 @@ struct R2d2Net : kpb_net {
 
 int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
+    // name, cin, cout, ks, stride, mfma, relu, pool_out, dil -- r2d2.py:105-117 with dilated = True: the strides of Quad_L2Net became the dilation of every layer behind them
+    const Layer plan[] = {
+        {"conv0", 3, 32, 3, 1, false}, {"conv1", 32, 32, 3, 1, true}, {"conv2", 32, 64, 3, 1, true}, {"conv3", 64, 64, 3, 1, true, true, false, 2},
+        {"conv4", 64, 128, 3, 1, true, true, false, 2}, {"conv5", 128, 128, 3, 1, true, true, false, 4}, {"conv6", 128, 128, 2, 1, true, false, false, 4},
+        {"conv7", 128, 128, 2, 1, true, false, false, 8}, {"conv8", 128, 128, 2, 1, true, false, false, 16}};
+    static_assert(sizeof(plan) / sizeof(plan[0]) == R2_LAYERS, "one plan entry per R2_* index");
     auto net = std::make_unique<R2d2Net>();
     net->ctx = ctx; net->arch = KPB_ARCH_R2D2; net->dim = 128; net->desc_div = 1;
     WeightStage ws;
     auto bad = [&](const char* what) { return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: R2D2 tensor %s missing or mis-shaped", what); };
-    for (int i = 0; i < 9; ++i) {
-        const R2Layer& L = R2D2_PLAN[i];
-        const std::string n = L.name;
-        R2d2Net::Bound& dst = net->lay[i];
-        const float* w = bl.get((n + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
-        const float* b = bl.get((n + ".b").c_str(), {(uint32_t)L.cout});
-        if (!w || !b) return bad(L.name);
-        if (L.cin == 3) {       // conv0: [tap][cin][32]
+    for (int i = 0; i < R2_LAYERS; ++i) {
+        Layer& L = net->L[i] = plan[i];
+        const float* w = bl.get((L.name + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
+        const float* b = bl.get((L.name + ".b").c_str(), {(uint32_t)L.cout});
+        if (!w || !b) return bad(L.name.c_str());
+        if (i == R2_C0) {       // conv0: [tap][cin][32]
             std::vector<float> p(27 * 32);
             for (int o = 0; o < 32; ++o)
                 for (int c = 0; c < 3; ++c)
                     for (int t = 0; t < 9; ++t) p[(t * 3 + c) * 32 + o] = w[(o * 3 + c) * 9 + t];
-            ws.put(p, &dst.w);
-            ws.put_raw(b, 32, &dst.b);
-        } else if (conv_mfma_use_h16()) {      // tap-major fragments, two n-tiles per workgroup: the same pack serves the halo form and the tap-gathered one
-            const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * L.ks * L.ks);
-            ws.put(pack_mfma_h(w, L.cout, L.cin, L.ks, 32, 2, sc), &dst.w);
-            dst.unscale = 1.0f / sc;
-            ws.put(pad_bias(b, L.cout, 64), &dst.b);
-        } else {
-            ws.put(pack_mfma(w, L.cout, L.cin, L.ks, r2_cc_fp32(L), r2_ntb_fp32(L)), &dst.w);
-            ws.put(pad_bias(b, L.cout, 64), &dst.b);
+            ws.put(p, &L.w);
+            ws.put_raw(b, 32, &L.b);
+            continue;
         }
+        // strict fp32: the 2 x 2, dilation-16 tile fits the LDS window in 16-channel slabs; the tap-gathered split-f16 product reads 32-channel slabs
+        L.cc = (L.ks == 2 && !conv_mfma_use_h16()) ? 16 : 32;
+        L.ntb = L.cout == 32 ? 1 : 2;       // conv1 owns one n-tile: the packs are n-tile-major, so its fragments sit where a two-tile pack had them and no second tile is fetched
+        stage_layer(ws, L, "", w, b);
     }
     const float* cw = bl.get("clf.w", {2, 128});
     const float* cb = bl.get("clf.b", {2});

@@ -19,6 +19,8 @@
 //   sfd2_score         one wave per 8 x 8 cell: exp, guarded sum, depth-to-space, the x 4 bilinear of the three stability logits, argmax and the product; no
 //                      full-resolution stability map is written
 //   l2norm_nhwc        (convnet.hip) F.normalize of the 128-channel rows in place, eps_clamp 1e-12
+// The dense layers are Layers staged and launched by conv_layer.h's stage_layer / launch_mfma; conv_mfma.h is here for cm_split4 and friends of the grouped kernel.
+#include "conv_layer.h"
 #include "conv1a_rgb.h"
 
 namespace {
@@ -207,19 +209,7 @@ __global__ void sfd2_take128(const float* __restrict__ src, float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------ host
-struct SfLayer { const char* name; int cin, cout, ks, stride; bool relu; bool grouped; };
-enum { SF_1A, SF_1B, SF_2A, SF_2B, SF_3A, SF_3B, SF_R0, SF_PA0 = SF_R0 + 9, SF_PA3, SF_PB, SF_DA0, SF_DA3, SF_DB, SF_STA, SF_LAYERS };
-// (folded tensor name, cin -- per group for the grouped layers --, cout, kernel, stride, ReLU, grouped); the third layer of a ResBlock gets its ReLU behind the sum
-constexpr SfLayer SFD2_PLAN[SF_LAYERS] = {
-    {"conv1a", 3, 64, 3, 1, true, false}, {"conv1b", 64, 64, 3, 2, true, false}, {"conv2a", 64, 128, 3, 1, true, false}, {"conv2b", 128, 128, 3, 2, true, false},
-    {"conv3a", 128, 256, 3, 1, true, false}, {"conv3b", 256, 256, 3, 1, true, false},
-    {"res0.c1", 256, 256, 1, 1, true, false}, {"res0.c2", 8, 256, 3, 1, true, true}, {"res0.c3", 256, 256, 1, 1, true, false},
-    {"res1.c1", 256, 256, 1, 1, true, false}, {"res1.c2", 8, 256, 3, 1, true, true}, {"res1.c3", 256, 256, 1, 1, true, false},
-    {"res2.c1", 256, 256, 1, 1, true, false}, {"res2.c2", 8, 256, 3, 1, true, true}, {"res2.c3", 256, 256, 1, 1, true, false},
-    {"convPa0", 256, 256, 3, 2, true, false}, {"convPa3", 256, 256, 3, 1, false, false}, {"convPb", 256, 65, 1, 1, false, false},
-    {"convDa0", 256, 256, 3, 1, true, false}, {"convDa3", 256, 256, 3, 1, false, false}, {"convDb", 256, 128, 1, 1, false, false},
-    {"sta", 256, 3, 1, 1, false, false}};
-constexpr int sf_cc(const SfLayer& L) { return L.stride == 2 ? 16 : 32; }       // input channels per LDS slab
+enum { SF_1A, SF_1B, SF_2A, SF_2B, SF_3A, SF_3B, SF_R0, SF_PA0 = SF_R0 + 9, SF_PA3, SF_PB, SF_DA0, SF_DA3, SF_DB, SF_STA, SF_LAYERS };      // sfd2_create's plan order
 
 // OIHW [256][8][3][3] -> sfd2_gconv_f32's [32 groups][9 taps][8 cin][8 cout]
 std::vector<float> sf_pack_gconv_f32(const float* w)
@@ -243,36 +233,14 @@ std::vector<float> sf_pack_gconv_h16(const float* w, float scale)
 }
 
 struct Sfd2Net : kpb_net {
-    struct Bound { const float* w = nullptr; const float* b = nullptr; const uint4* gw = nullptr; float unscale = 1.0f; std::string prof; } lay[SF_LAYERS];
+    Layer L[SF_LAYERS];             // conv1a and the grouped layers (mfma = false) are kernels of this file: their Layers carry the pointers only
+    const uint4* gw[3] = {};        // split-f16: the grouped layers' fragments (sf_pack_gconv_h16), per ResBlock
     bool h16 = true;
-
-    // one dense layer on the matrix cores: (Hi, Wi) -> (Hi, Wi) / stride; res: the identity map added before the ReLU (1 x 1 layers only)
-    int conv(int i, const float* in, float* out, int batch, int Hi, int Wi, const float* res = nullptr)
-    {
-        const SfLayer& L = SFD2_PLAN[i];
-        const int S = L.stride, PAD = L.ks / 2, cc = sf_cc(L), H = (Hi + 2 * PAD - L.ks) / S + 1, W = (Wi + 2 * PAD - L.ks) / S + 1;
-        const char* tag = lay[i].prof.c_str();
-        ConvM a{.in = in, .out = out, .wp = lay[i].w, .bias = lay[i].b, .res = res, .Hi = Hi, .Wi = Wi, .H = H, .W = W, .CIN = L.cin, .COUT = L.cout,
-                .NCH = L.cin / cc, .relu = res ? 0 : L.relu, .nblk = cdiv(L.cout, 64), .istride = L.cin, .ostride = L.cout, .rstride = L.cout};
-        if (res && (L.ks != 1 || L.cout % 64)) return kpb_fail(ctx, KPB_E_INVALID, "SFD2 %s: the identity branch joins 1x1 layers of whole 64-channel tiles", L.name);
-        if (!h16)
-            return launch_conv_mfma<CmForm{.ks = 1, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 2, .cc = 16}>(
-                ctx, tag, CmForm{.ks = L.ks, .s = S, .cc = cc}, a, batch);
-        a.unscale = lay[i].unscale;
-        if (L.ks == 1) {
-            const dim3 grid(cdiv(H * W, 128), 1, batch * a.nblk), block(256);
-            if (res) KPB_LAUNCH(ctx, tag, (gemm_h<2, 1, GE_RES_RELU>), grid, block, 0, ctx->stream, a);
-            else KPB_LAUNCH(ctx, tag, (gemm_h<2, 1>), grid, block, 0, ctx->stream, a);
-            return KPB_OK;
-        }
-        CmForm f{.ks = 3, .s = S, .cc = cc, .ntb = 1, .mt = S == 2 ? 2 : 4, .wn = 2};      // SuperPoint's forms: 16-row tiles at stride 1, 8-row tiles at stride 2
-        return launch_conv_mfma_h<CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 3, .s = 2, .cc = 16, .ntb = 1, .mt = 2, .wn = 2}>(ctx, tag, f, a, batch);
-    }
 
     void gconv(int i, const float* in, float* out, int batch, int H, int W)
     {
-        SfGcArgs a{in, out, lay[i].w, lay[i].gw, lay[i].b, lay[i].unscale, H, W};
-        const char* tag = lay[i].prof.c_str();
+        SfGcArgs a{in, out, L[i].w, gw[(i - SF_R0) / 3], L[i].b, L[i].unscale, H, W};
+        const char* tag = L[i].prof.c_str();
         if (h16) KPB_LAUNCH(ctx, tag, sfd2_gconv_h, dim3(cdiv(W, GC_T), cdiv(H, GC_T), batch * 8), dim3(256), 0, ctx->stream, a);
         else KPB_LAUNCH(ctx, tag, sfd2_gconv_f32, dim3(cdiv(H * W, 256), 8, batch), dim3(256), 0, ctx->stream, a);
     }
@@ -294,16 +262,16 @@ struct Sfd2Net : kpb_net {
         this->B = batch; this->H = H; this->W = W;
         hipStream_t st = ctx->stream;
         int rc;
-        launch_conv1a_rgb64(ctx, lay[SF_1A].prof.c_str(), img, x1a, lay[SF_1A].w, lay[SF_1A].b, batch, H, W);
-        if ((rc = conv(SF_1B, x1a, x1b, batch, H, W))) return rc;
-        if ((rc = conv(SF_2A, x1b, x2a, batch, H2, W2))) return rc;
-        if ((rc = conv(SF_2B, x2a, x2b, batch, H2, W2))) return rc;
-        if ((rc = conv(SF_3A, x2b, q[0], batch, H4, W4))) return rc;
-        if ((rc = conv(SF_3B, q[0], q[1], batch, H4, W4))) return rc;
+        launch_conv1a_rgb64(ctx, L[SF_1A].prof.c_str(), img, x1a, L[SF_1A].w, L[SF_1A].b, batch, H, W);
+        if ((rc = launch_mfma(ctx, L[SF_1B], x1a, x1b, batch, H, W))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_2A], x1b, x2a, batch, H2, W2))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_2B], x2a, x2b, batch, H2, W2))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_3A], x2b, q[0], batch, H4, W4))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_3B], q[0], q[1], batch, H4, W4))) return rc;
         float *x = q[1], *y = q[0];       // conv4: block k reads x and leaves its output in y
         for (int k = 0; k < 3; ++k) {
             const int i = SF_R0 + 3 * k;
-            if ((rc = conv(i, x, q[2], batch, H4, W4))) return rc;
+            if ((rc = launch_mfma(ctx, L[i], x, q[2], batch, H4, W4))) return rc;
             gconv(i + 1, q[2], q[3], batch, H4, W4);
             if (k == 0 && ctx->sfd2_probe) {      // the test hook: the first grouped layer's output, half of its channels, instead of the descriptor map
                 KPB_LAUNCH(ctx, "sfd2_probe", sfd2_take128, dim3((unsigned)((B * H4 * W4 * 32 + 255) / 256)), dim3(256), 0, st, q[3], desc_out, B * H4 * W4,
@@ -311,17 +279,17 @@ struct Sfd2Net : kpb_net {
                 KPB_HIP(ctx, hipGetLastError());
                 return KPB_OK;
             }
-            if ((rc = conv(i + 2, q[3], y, batch, H4, W4, x))) return rc;
+            if ((rc = launch_mfma(ctx, L[i + 2], q[3], y, batch, H4, W4, {.res = x}))) return rc;
             std::swap(x, y);
         }
         const float* out4 = x;          // = q[0]; q[1] .. q[3] are free again
-        if ((rc = conv(SF_PA0, out4, cpa0, batch, H4, W4))) return rc;
-        if ((rc = conv(SF_PA3, cpa0, cpa3, batch, Hc, Wc))) return rc;
-        if ((rc = conv(SF_PB, cpa3, semi, batch, Hc, Wc))) return rc;
-        if ((rc = conv(SF_STA, out4, sta, batch, H4, W4))) return rc;
-        if ((rc = conv(SF_DA0, out4, q[2], batch, H4, W4))) return rc;
-        if ((rc = conv(SF_DA3, q[2], q[3], batch, H4, W4))) return rc;
-        if ((rc = conv(SF_DB, q[3], desc_out, batch, H4, W4))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_PA0], out4, cpa0, batch, H4, W4))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_PA3], cpa0, cpa3, batch, Hc, Wc))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_PB], cpa3, semi, batch, Hc, Wc))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_STA], out4, sta, batch, H4, W4))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_DA0], out4, q[2], batch, H4, W4))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_DA3], q[2], q[3], batch, H4, W4))) return rc;
+        if ((rc = launch_mfma(ctx, L[SF_DB], q[3], desc_out, batch, H4, W4))) return rc;
         launch_l2norm_nhwc(ctx, "sfd2_l2norm", desc_out, 128, B * H4 * W4, 1e-12f);       // F.normalize
         KPB_LAUNCH(ctx, "sfd2_score", sfd2_score, dim3(cdiv(Hc * Wc, 4 * SF_PXW), batch), dim3(256), 0, st, semi, sta, score_out, Hc, Wc);
         KPB_HIP(ctx, hipGetLastError());
@@ -333,40 +301,46 @@ struct Sfd2Net : kpb_net {
 
 int sfd2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
+    // folded tensor name, cin (per group for the grouped layers), cout, ks, stride, mfma, relu: conv1a and the grouped res*.c2 are kernels of this file; the third
+    // layer of a ResBlock gets its ReLU behind the sum
+    const Layer plan[] = {
+        {"conv1a", 3, 64, 3, 1, false}, {"conv1b", 64, 64, 3, 2, true}, {"conv2a", 64, 128, 3, 1, true}, {"conv2b", 128, 128, 3, 2, true},
+        {"conv3a", 128, 256, 3, 1, true}, {"conv3b", 256, 256, 3, 1, true},
+        {"res0.c1", 256, 256, 1, 1, true}, {"res0.c2", 8, 256, 3, 1, false}, {"res0.c3", 256, 256, 1, 1, true},
+        {"res1.c1", 256, 256, 1, 1, true}, {"res1.c2", 8, 256, 3, 1, false}, {"res1.c3", 256, 256, 1, 1, true},
+        {"res2.c1", 256, 256, 1, 1, true}, {"res2.c2", 8, 256, 3, 1, false}, {"res2.c3", 256, 256, 1, 1, true},
+        {"convPa0", 256, 256, 3, 2, true}, {"convPa3", 256, 256, 3, 1, true, false}, {"convPb", 256, 65, 1, 1, true, false},
+        {"convDa0", 256, 256, 3, 1, true}, {"convDa3", 256, 256, 3, 1, true, false}, {"convDb", 256, 128, 1, 1, true, false},
+        {"sta", 256, 3, 1, 1, true, false}};
+    static_assert(sizeof(plan) / sizeof(plan[0]) == SF_LAYERS, "one plan entry per SF_* index");
     auto net = std::make_unique<Sfd2Net>();
     net->ctx = ctx; net->arch = KPB_ARCH_SFD2; net->dim = 128; net->desc_div = 4;
     net->h16 = conv_mfma_use_h16();
     WeightStage ws;
     for (int i = 0; i < SF_LAYERS; ++i) {
-        const SfLayer& L = SFD2_PLAN[i];
-        Sfd2Net::Bound& dst = net->lay[i];
-        const std::string n = L.name;
-        dst.prof = "sfd2_" + n;
-        const float* w = bl.get((n + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
-        const float* b = bl.get((n + ".b").c_str(), {(uint32_t)L.cout});
-        if (!w) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SFD2 tensor %s.w missing or mis-shaped", L.name);
-        if (!b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SFD2 tensor %s.b missing or mis-shaped", L.name);
-        const size_t cnt = (size_t)L.cout * L.cin * L.ks * L.ks;
+        Layer& L = net->L[i] = plan[i];
+        const float* w = bl.get((L.name + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
+        const float* b = bl.get((L.name + ".b").c_str(), {(uint32_t)L.cout});
+        if (!w) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SFD2 tensor %s.w missing or mis-shaped", L.name.c_str());
+        if (!b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SFD2 tensor %s.b missing or mis-shaped", L.name.c_str());
+        if (L.mfma) {
+            L.cc = L.stride == 2 ? 16 : 32;
+            stage_layer(ws, L, "sfd2_", w, b);
+            continue;
+        }
+        L.prof = "sfd2_" + L.name;
         if (i == SF_1A) {
-            ws.put(pack_conv1a_rgb64(w), &dst.w);
-            ws.put_raw(b, 64, &dst.b);
-        } else if (L.grouped) {
+            ws.put(pack_conv1a_rgb64(w), &L.w);
+            ws.put_raw(b, 64, &L.b);
+        } else {        // the grouped 3 x 3 of a ResBlock
             if (net->h16) {
-                const float sc = weight_scale_h(w, cnt);
-                ws.put(sf_pack_gconv_h16(w, sc), &dst.gw);
-                dst.unscale = 1.0f / sc;
+                const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * 9);
+                ws.put(sf_pack_gconv_h16(w, sc), &net->gw[(i - SF_R0) / 3]);
+                L.unscale = 1.0f / sc;
             } else {
-                ws.put(sf_pack_gconv_f32(w), &dst.w);
+                ws.put(sf_pack_gconv_f32(w), &L.w);
             }
-            ws.put_raw(b, 256, &dst.b);
-        } else if (net->h16) {
-            const float sc = weight_scale_h(w, cnt);
-            ws.put(pack_mfma_h(w, L.cout, L.cin, L.ks, sf_cc(L), 2, sc), &dst.w);
-            dst.unscale = 1.0f / sc;
-            ws.put(pad_bias(b, L.cout, 64), &dst.b);
-        } else {
-            ws.put(pack_mfma(w, L.cout, L.cin, L.ks, sf_cc(L), 2), &dst.w);
-            ws.put(pad_bias(b, L.cout, 64), &dst.b);
+            ws.put_raw(b, 256, &L.b);
         }
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;

@@ -1,4 +1,4 @@
-"""GPU parity of N4 (DISK, csrc/convnet.hip through the C ABI) against the reference's outputs on seeded random
+"""GPU parity of N4 (DISK, csrc/convnet.hip + csrc/conv_layer.hip through the C ABI) against the reference's outputs on seeded random
 weights (disk.pth is absent from the reference tree) and against the torch-fp32 oracle."""
 import numpy as np
 import pytest

@@ -1,6 +1,6 @@
 """Every image shape and batch kpb_net_forward accepts for SuperPoint, DISK and XFeat, not only the multiples of 32 the other files run.
 
-The three nets share conv_mfma_h / gemm_h / conv_valu_t (csrc/conv_mfma.h, csrc/convnet.hip) and accept H, W multiples of 8 (SuperPoint), 16 (DISK) and 32
+The three nets share conv_mfma_h / gemm_h / conv_valu_t (csrc/conv_mfma.h, launched by csrc/conv_layer.hip and csrc/convnet.hip) and accept H, W multiples of 8 (SuperPoint), 16 (DISK) and 32
 (XFeat).  Heights that are not multiples of 16 end in half a workgroup tile (the generated-input form of SuperPoint's conv1b must treat the rows below the image
 as conv1b's zero padding, not as relu(bias) of conv1a); DISK's lower levels are smaller than one 16 x 16 tile and its fused upsampling then stages a clamped
 source tile that covers the whole source; XFeat at 32 x 32 has one pixel at 1/32 and fewer rows than a gemm_h workgroup.  Each test compares the FULL maps with
@@ -159,7 +159,7 @@ def test_xfeat_shape_sweep_against_oracle(shape):
                          ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
 def test_a_batch_of_different_images_equals_the_oracle_and_the_single_images(name, B, shape):
     """Every image of the batch against the oracle, and images 0, B // 2, B - 1 against the net run on that image alone -- BIT FOR BIT, for all three nets.
-    The launch plans of csrc/convnet.hip choose their forms and tiles from the layer and from H, W only (launch_mfma / launch_valu have no batch-size branch; the
+    The launch plans choose their forms and tiles from the layer and from H, W only (launch_mfma of csrc/conv_layer.hip / launch_valu of csrc/convnet.hip have no batch-size branch; the
     batch is blockIdx.z / nblk or a grid dimension of its own), and everything per image is reduced per image in a fixed order: SuperPoint's pre_amax
     (plane_abs_max: one workgroup per image), XFeat's (mean, 1 / std) (gray_mean_stats: XF_STAT_BLOCKS partials per image, folded in block order), DISK's
     statistics and xf tables (chan_sums / up_chan_sums: SUM_BLOCKS partials per image, folded in block order by make_xf), gemm_h's per-wave operand scale (a

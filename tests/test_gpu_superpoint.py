@@ -1,4 +1,4 @@
-"""GPU parity of N2 (SuperPoint, csrc/convnet.hip through the C ABI) against the reference's outputs on seeded
+"""GPU parity of N2 (SuperPoint, csrc/convnet.hip + csrc/conv_layer.hip through the C ABI) against the reference's outputs on seeded
 random weights (the reference checkpoint is absent from its tree) and against the torch-fp32 oracle."""
 import numpy as np
 import pytest
