@@ -36,8 +36,9 @@ def detect_params(nms_dist, top_k):
     return dict(nms_dist=int(nms_dist), threshold=0.0, border_dist=8, top_k=int(top_k), min_score=0.0)
 
 
-def chain(t, img):
-    """(score [B,1,H,W], desc [B,128,H/4,W/4]) from the folded tensors `t` (weights.fold_sfd2): sfd2.py:144-182 with every BatchNorm already in its convolution."""
+def chain(t, img, margin=False):
+    """(score [B,1,H,W], desc [B,128,H/4,W/4]) from the folded tensors `t` (weights.fold_sfd2): sfd2.py:144-182 with every BatchNorm already in its convolution.
+    margin=True: a third result [B,H,W], the difference between the two largest upsampled stability logits per pixel (MARGIN is meant for the float64 chain's)."""
     import torch
     import torch.nn.functional as F
     tt = lambda a: torch.from_numpy(np.ascontiguousarray(a))
@@ -60,4 +61,7 @@ def chain(t, img):
     desc = F.normalize(conv(conv(conv(x, "convDa0"), "convDa3", relu=False), "convDb", relu=False), dim=1)
     logits = F.interpolate(conv(x, "sta", relu=False), size=img.shape[2:], mode="bilinear", align_corners=False)
     stab = torch.tensor([0.1, 0.5, 1.0])[logits.argmax(1, keepdim=True)]
+    if margin:
+        top2 = torch.topk(logits, 2, dim=1).values
+        return score * stab, desc, top2[:, 0] - top2[:, 1]
     return score * stab, desc
