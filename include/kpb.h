@@ -343,6 +343,7 @@ int kpb_preprocess(kpb_ctx* ctx, const uint8_t* src_dev, int batch, int Hs, int 
 #define KPB_ARCH_KEYNET 10      /* models/KeyNet.py     KeyNet(num_filters = 8, num_levels = 3, kernel_size = 5): a detector -- three pyramid levels (1.2 x), ten handcrafted gradient features and three 5 x 5 layers per level (BN folded), a 24 -> 1 fusion layer; any H, W >= 16; non-negative UNBOUNDED score, no descriptors (dim 0): desc_out_dev is ignored and may be NULL */
 #define KPB_ARCH_SFD2 11        /* models/sfd2.py       ResSegNetV2(outdim = 128, require_stability = True), BN folded: conv1a .. conv3b (3 x 3, two of them stride 2), three ResBlocks at H/4 x W/4 (1 x 1, 3 x 3 in 32 groups of 8, 1 x 1 + identity), convPa / convPb -> 65 logits per 8 x 8 cell, convDa / convDb -> descriptors, ConvSta -> 3 stability logits; score = exp(logit) / (sum of the 65 + 1e-5), depth-to-space, times 0.1 / 0.5 / 1.0 by the argmax of the x 4 bilinearly upsampled stability logits; H, W multiples of 8; dim 128, desc_div 4: an L2-normalised 128-channel map at H/4 x W/4; desc_out_dev is required */
 #define KPB_ARCH_D2NET 12       /* models/D2_Net.py     D2Net: torchvision vgg16().features[:22] (ten 3 x 3 layers with bias, 3 -> 64 -> 64 / pool / 128 -> 128 / pool / 256 -> 256 -> 256 / pool / 512 -> 512 -> 512, no ReLU behind the last), soft detection on the 512 x H/8 x W/8 map (exp(x / image maximum), 3 x 3 sum with out-of-map taps 1, ratio to the channel maximum, maximum over channels, divided by the image sum -- per image, the same bits alone or in a batch), upsampled bilinearly with align_corners = True; NO guard on a pixel without a positive channel: the map is NaN then, as the reference's; H, W multiples of 8 and >= 8; dim 512, desc_div 8: the L2-normalised pre-ReLU map; desc_out_dev is required */
+#define KPB_ARCH_HARRIS 13      /* models/Harris.py     Harris(params): no weights -- the blob carries ONE tensor, harris.plan = [block_size, ksize, k] as fp32 (missing or not 3 values: KPB_E_WEIGHTS; ksize != 3, block_size outside 2 .. 6 or not an integer, k not finite: KPB_E_UNSUPPORTED).  The response of cv2.cornerHarris on the uint8 plane ((c0 + c1) + c2) * 255 (fp32, truncated, low 8 bits: sums above 1 wrap), defined as the CORRECTLY ROUNDED value of the formula cv2's float32 chain approximates: integer 3 x 3 Sobel over reflect-101, integer block_size x block_size sums of the three products (anchor block_size / 2, reflect-101 of the product planes), then ((double)(A C - B B) - (double)(float)k * (double)(A + C)^2) * (1 / (4 block_size 255))^4 in float64, rounded once to fp32 -- bit-equal to a numpy restatement, the same bits alone or in a batch; any H, W >= 8 (KPB_E_INVALID below); SIGNED score (KPB_OPT_DETECT_SIGNED), no descriptors (dim 0, div 1): desc_out_dev is ignored and may be NULL, kpb_net_desc_at refuses */
 int kpb_net_create(kpb_ctx* ctx, int arch, const void* blob, size_t len, kpb_net** out);
 void kpb_net_destroy(kpb_net* net);
 int kpb_net_desc_dim(const kpb_net* net);   /* descriptor channels C */

@@ -117,3 +117,4 @@ int letnet_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int keynet_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int sfd2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int d2net_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
+int harris_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);

@@ -22,6 +22,7 @@ KPB_API int kpb_net_create(kpb_ctx* ctx, int arch, const void* blob, size_t len,
         case KPB_ARCH_KEYNET: return keynet_create(ctx, bl, out);
         case KPB_ARCH_SFD2: return sfd2_create(ctx, bl, out);
         case KPB_ARCH_D2NET: return d2net_create(ctx, bl, out);
+        case KPB_ARCH_HARRIS: return harris_create(ctx, bl, out);
         default: return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_create: unknown arch %d", arch);
         }
     });

@@ -58,19 +58,28 @@ _MODELS = {"Alike": ("ALike", lambda m, p, dense: m.ALNet(p, dense_descriptors=d
            # model_interface.py:74-76: ResSegNetV2(outdim=128, require_stability=True), the checkpoint's 'model' entry loaded with strict=False
            "sfd2": ("sfd2", lambda m, p, dense: m.ResSegNetV2(outdim=128, require_stability=True), "sfd2_params", "model", _NOT_SHIPPED),
            # model_interface.py:64-65: D2Net(model_file=weight) loads the checkpoint's 'model' entry itself; here the file is looked for first
-           "D2Net": ("D2_Net", lambda m, p, dense: m.D2Net(), "D2Net_params", "model", _NOT_SHIPPED)}
+           "D2Net": ("D2_Net", lambda m, p, dense: m.D2Net(), "D2Net_params", "model", _NOT_SHIPPED),
+           # model_interface.py:82-83: Harris(params['Harris_params']) -- no weights, so no checkpoint is looked for (_NO_CHECKPOINT)
+           "Harris": ("Harris", lambda m, p, dense: m.Harris(p), "Harris_params", None, None)}
+_NO_CHECKPOINT = ("Harris",)    # built from their params alone, and refused without them (the reference's constructor call raises KeyError there)
+_MODEL_NAMES = "Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint, GoodPoint, LETNet, KeyNet, sfd2, D2Net, Harris"
 
 
 def build_model(params, dense_descriptors=True):
     """model_interface.py:43-86 for the model types this package carries kernels for: construct, find the checkpoint or refuse,
-    load_state_dict, eval."""
+    load_state_dict, eval.  Harris has no weights: it is built from `Harris_params` alone, and refused when they are missing."""
     import importlib
     mt = params["model_type"]
     if mt not in _MODELS:
-        raise NotImplementedError("model_type %r: no MI355X kernels in this build (Alike, SuperPoint, XFeat, DISK, r2d2, EdgePoint, GoodPoint, LETNet, KeyNet, sfd2, D2Net)" % (mt,))
+        raise NotImplementedError("model_type %r: no MI355X kernels in this build (%s)" % (mt, _MODEL_NAMES))
     mod, make, pkey, sub, missing = _MODELS[mt]
-    mod = importlib.import_module("keypoint_bench_amd.models." + mod)
     p = params.get(pkey) or {}
+    if mt in _NO_CHECKPOINT:
+        if not p:
+            raise NotImplementedError("model_type %r without %s cannot be built (the reference's own constructor call fails there); the model types of this "
+                                      "build: %s" % (mt, pkey, _MODEL_NAMES))
+        return make(importlib.import_module("keypoint_bench_amd.models." + mod), p, dense_descriptors).eval()
+    mod = importlib.import_module("keypoint_bench_amd.models." + mod)
     net = make(mod, p, dense_descriptors) if make else None
     w = p.get("weight")
     if w and os.path.exists(w):

@@ -24,6 +24,7 @@ ARCH_LETNET = 9
 ARCH_KEYNET = 10
 ARCH_SFD2 = 11
 ARCH_D2NET = 12
+ARCH_HARRIS = 13
 _REC = struct.Struct("<40sI4II")
 
 
@@ -213,6 +214,25 @@ def keynet_level_sizes(H, W, levels=3):
         h, w = out[-1]
         out.append((int(h // 1.2), int(w // 1.2)))
     return out
+
+
+HARRIS_BLOCK_SIZES = (2, 3, 4, 5, 6)      # from 7 on (A + C)^2 can pass 2^53: the float64 response of csrc/harris.hip would no longer be exact up to its last line
+
+
+def harris_plan(params) -> dict:
+    """The reference's Harris constructor argument (models/Harris.py:16-18: block_size, ksize, k, each read with []) -> the one tensor csrc/harris.hip
+    expects: harris.plan = [block_size, ksize, float32(k)], all three exact in fp32.  Refused (NotImplementedError, what kpb_net_create answers with
+    KPB_E_UNSUPPORTED): any ksize but 3, a block_size outside 2 .. 6 or not an integer, a k that is not finite in fp32."""
+    bs, ks, k = params["block_size"], params["ksize"], params["k"]
+    if ks != 3:
+        raise NotImplementedError("this build carries the Harris response with the 3 x 3 Sobel (ksize = 3) only; got ksize = %r" % (ks,))
+    if bs not in HARRIS_BLOCK_SIZES:
+        raise NotImplementedError("this build carries the Harris response for block_size 2 .. 6 only (from 7 on its integer terms pass 2^53); got %r" % (bs,))
+    with np.errstate(over="ignore"):
+        k32 = np.float32(k)
+    if not np.isfinite(k32):
+        raise NotImplementedError("Harris: k = %r is not finite in float32" % (k,))
+    return {"harris.plan": np.array([bs, ks, k32], np.float32)}
 
 
 SFD2_PLAN = dict(outdim=128, require_feature=False, require_stability=True, ms_detector=True)

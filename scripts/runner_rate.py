@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--dense", action="store_true")
     ap.add_argument("--tasks", nargs="+", default=["match_stats", "repeatability", "MHA", "AUC"])
     ap.add_argument("--sequence", action="store_true", help="a sequence dataset instead (frames sliding over one canvas): FundamentalMatrix and visual_odometer tasks")
-    ap.add_argument("--model", default="Alike", choices=["Alike", "XFeat"])
+    ap.add_argument("--model", default="Alike", choices=["Alike", "XFeat", "Harris"])
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -91,7 +91,7 @@ def main():
            "decode_pool_alone_pairs_per_s": decode_only,
            "descriptors": "dense-map" if args.dense else "keypoint-only"}
     for task in args.tasks:
-        params = {"model_type": args.model, "task_type": task, "XFeat_params": {}, "FundamentalMatrix_params": {"th": 3.0}, "Alike_params": dict(c1=8, c2=16, c3=32, c4=64, dim=64),
+        params = {"model_type": args.model, "task_type": task, "XFeat_params": {}, "Harris_params": dict(block_size=5, ksize=3, k=0.04), "FundamentalMatrix_params": {"th": 3.0}, "Alike_params": dict(c1=8, c2=16, c3=32, c4=64, dim=64),
                   "extractor_params": dict(nms_dist=6, threshold=0.0, border_dist=8, top_k=1000, min_score=0.0),
                   "matcher_params": {"type": "brute_force", "brute_force_params": dict(metric="euclidean", max_distance=5, cross_check=True)},
                   "repeatability_params": {"th": 3}, "MHA_params": {"th": [3, 5, 7]}, "AUC_params": {"th": [5, 10, 20]}}
