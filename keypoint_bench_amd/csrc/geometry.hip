@@ -1,10 +1,24 @@
 // geometry.hip -- the metric side of tasks/*.py that consumes the matched keypoints (SURVEY 8(f) rank 3 and the
 // FundamentalMatrix task of BASELINE configs[3]), gfx950 only.
 //
-//   epipolar_error   tasks/FundamentalMatrix.py:137-161   |x1^T F x0| / |(F x0)_xy| per match + mean / ratio / count
+//   epipolar_error      tasks/FundamentalMatrix.py:137-161   |x1^T F x0| / |(F x0)_xy| per match + mean / ratio / count
+//   ransac_homography   tasks/MHA.py:45-47    cv2.findHomography(RANSAC): 4-point samples, refit on the inliers (DLT + LM)
+//   ransac_essential    tasks/AUC.py:50-58    cv2.findEssentialMat(RANSAC): 5-point samples, up to 10 models each
+//   recover_pose        tasks/AUC.py:60-64    cv2.recoverPose: SVD of E, the (R, t) with the most points in front
+//   ransac_fundamental  utils/mvg.py:16       cv2.findFundamentalMat(FM_RANSAC): 7-point samples, up to 3 models each; the
+//                                             least-median registrator below 15 matches
 //
 // One workgroup per image pair; a pair's matches (<= top_k rows) are a few KB, so everything after the loads lives in
 // registers and LDS and the launch is latency-bound by construction.
+//
+// The file in order: epipolar_error; OpenCV's sampler (CvRng, gen_round), the two registrator rules (CountInliers,
+// LeastMedian) with the scan that applies them (scan_round), and the search loop that the essential matrix, the fundamental
+// matrix and its least-median branch share (load_matches, search, write_mask / write_result); then each estimator under its
+// own heading: minimal solver, error function, the struct that describes it to the search, its kernel (recover_pose follows
+// the essential matrix); last the host wrappers with their one launch helper.  ransac_homography shares the sampler, the
+// rule and the scan but keeps its own loader, round loop and epilogue: its round is bound by thread 0's sampler, whose pace
+// was 0.8 to 3.9 % slower with every other arrangement of the kernel that was measured (profiles/geometry_ransac_ab.txt), so
+// its code is left as it was.
 #include "kpb_common.h"
 
 namespace {
@@ -128,7 +142,7 @@ constexpr int FM_LMEDS_BELOW = 15;        // cv::findFundamentalMat: FM_RANSAC w
 
 // thread 0 only.  s_idx[j][0..M) = the subset of hypothesis j of this round; s_ok[j] = 0 from the first getSubset failure on.
 template <int M, class Check>
-__device__ void gen_round(CvRng& rng, int n, unsigned short* s_idx, unsigned char* s_ok, bool& alive, Check check, int attempts = GETSUBSET_ATTEMPTS)
+__device__ void gen_round(CvRng& rng, int n, unsigned short* s_idx, unsigned char* s_ok, bool& alive, Check check, int attempts)
 {
     for (int j = 0; j < 256; ++j) {
         int idx[M];
@@ -159,31 +173,218 @@ __device__ void gen_round(CvRng& rng, int n, unsigned short* s_idx, unsigned cha
     }
 }
 
-struct RsState { int niters, max_good, iters, stop, failed; };
+__device__ int update_iters(double conf, double outlier_ratio, int m, int max_iters)
+{
+    const double p = fmin(fmax(conf, 0.0), 1.0), ep = fmin(fmax(outlier_ratio, 0.0), 1.0);
+    double num = fmax(1.0 - p, 2.2250738585072014e-308);
+    double denom = 1.0 - pow(1.0 - ep, (double)m);
+    if (denom < 2.2250738585072014e-308) return 0;
+    num = log(num); denom = log(denom);
+    return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
+}
 
-__device__ int update_iters(double conf, double outlier_ratio, int m, int max_iters);
+// ---- the search the estimators share (the homography: rule and scan only).  An estimator is a struct (EssentialEst, FundamentalEst, each after
+// its solver below) with
+//   M, NM            sample size, models per sample
+//   Point            a match in LDS: .x .y its point in image 0, .z .w in image 1
+//   Err              the type an error is compared with the squared threshold in
+//   check(x1, x2)    the estimator's checkSubset on a gathered sample (x1 / x2: M points, u v interleaved)
+//   solve(x1, x2, model, valid)   the minimal solver: up to NM models, valid[s] says which slots hold one
+//   error(model, p)  the error of one match
+// and a registrator rule (CountInliers, LeastMedian) says how a model is scored against all matches and when it is kept.
+struct RansacArgs {
+    const float* m0; int cols0; const float* m1; int cols1;
+    int max_k; const int32_t* k_dev; const float* scale;      // [B][4] = (sx0, sy0, sx1, sy1): normalised -> pixels, fp32
+    const uint32_t* seed_dev; uint32_t seed;
+    double threshold, confidence; int max_iters, refine;
+    double* model; uint8_t* mask; int32_t* info;              // [B][9], [B][max_k], [B][4] = (found, inliers, hypotheses, least-median)
+};
 
-// thread 0 only: RANSACPointSetRegistrator::run's keep / niters rule over one round, in iteration order.  s_cnt[j][s] = inliers
-// of model s of hypothesis j (0 for a void model).  Returns the (hypothesis, slot) kept LAST in this round, or -1.
-template <int M, int NM>
-__device__ int scan_round(const int* s_cnt, const unsigned char* s_ok, int base, int n, double conf, RsState& st)
+struct Pt4d { double x, y, z, w; };
+
+// this workgroup's pair once load_matches has parked its matches in LDS
+struct Pair { int n; uint32_t seed; double* model; uint8_t* mask; int32_t* info; };
+
+// Scales the pair's rows to pixels in fp32 (MHA.py:41-42, AUC.py:125-126, FundamentalMatrix.py:76-77), parks what `conv` makes of
+// each in pts[i], clears the pair's mask.  Ends in a barrier every thread reaches.
+template <class Point, class Conv>
+__device__ __forceinline__ Pair load_matches(const RansacArgs& a, Point* pts, Conv conv)
+{
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = a.k_dev ? min(a.k_dev[b], a.max_k) : a.max_k;
+    const float* sc = a.scale + 4 * b;
+    for (int i = tid; i < n; i += RS_THREADS) {
+        const float* p0 = a.m0 + ((size_t)b * a.max_k + i) * a.cols0;
+        const float* p1 = a.m1 + ((size_t)b * a.max_k + i) * a.cols1;
+        pts[i] = conv(i, p0[0] * sc[0], p0[1] * sc[1], p1[0] * sc[2], p1[1] * sc[3]);      // fp32 products
+    }
+    uint8_t* mask = a.mask + (size_t)b * a.max_k;
+    for (int i = tid; i < a.max_k; i += RS_THREADS) mask[i] = 0;
+    __syncthreads();
+    return Pair{n, a.seed_dev ? a.seed_dev[b] : a.seed, a.model + 9 * b, mask, a.info + 4 * b};
+}
+
+// The pair's result: the model (zeros when nothing was found) and info = (found, inliers, hypotheses, least-median branch).
+// inliers / iters are thread 0's.
+__device__ __forceinline__ void write_result(const Pair& p, bool found, const double* model, int inliers, int iters, int lmeds)
+{
+    const int tid = threadIdx.x;
+    if (tid < 9) p.model[tid] = found ? model[tid] : 0.0;
+    if (tid == 0) { p.info[0] = found; p.info[1] = inliers; p.info[2] = iters; p.info[3] = lmeds; }
+}
+
+__device__ __forceinline__ void nothing_found(const Pair& p, int iters, int lmeds) { write_result(p, false, nullptr, 0, iters, lmeds); }
+
+// mask[i] = the match is an inlier of `model`; returns how many of this thread's rows are
+template <class Est>
+__device__ __forceinline__ int write_mask(const Pair& p, const typename Est::Point* pts, const double* model, typename Est::Err t2)
+{
+    int mine = 0;
+    for (int i = threadIdx.x; i < p.n; i += RS_THREADS) {
+        const int in = Est::error(model, pts[i]) <= t2;
+        p.mask[i] = (uint8_t)in;
+        mine += in;
+    }
+    return mine;
+}
+
+template <int M, class Point, class Index>
+__device__ __forceinline__ void gather(const Point* pts, const Index* idx, double* x1, double* x2)
+{
+#pragma unroll
+    for (int j = 0; j < M; ++j) { const Point p = pts[idx[j]]; x1[2 * j] = p.x; x1[2 * j + 1] = p.y; x2[2 * j] = p.z; x2[2 * j + 1] = p.w; }
+}
+
+// thread 0's view of the loop: RANSACPointSetRegistrator::run's niters / maxGoodCount, LMeDSPointSetRegistrator::run's minMedian
+struct RsState { int niters, iters, stop, max_good; double min_med; };
+
+// RANSACPointSetRegistrator (ptsetreg.cpp): a model's score is its inlier count; a model with more inliers than any earlier one
+// is kept and RANSACUpdateNumIters shrinks niters after every kept model.  10 000 getSubset attempts.
+template <class Est>
+struct CountInliers {
+    static constexpr int ATTEMPTS = GETSUBSET_ATTEMPTS, LMEDS = 0;
+    typename Est::Err t2; double conf;
+    __device__ __forceinline__ int start(int max_iters) const { return max_iters; }
+    __device__ __forceinline__ int score(const double* model, bool valid, const typename Est::Point* pts, int n) const
+    {
+        int cnt = 0;
+        if (valid)
+            for (int i = 0; i < n; ++i) cnt += Est::error(model, pts[i]) <= t2;
+        return cnt;                                                              // 0 for a void model
+    }
+    __device__ __forceinline__ bool keep(int c, int n, RsState& st) const
+    {
+        if (!(c > max(st.max_good, Est::M - 1))) return false;
+        st.max_good = c;
+        st.niters = update_iters(conf, (double)(n - c) / n, Est::M, st.niters);
+        return true;
+    }
+};
+
+// LMeDSPointSetRegistrator (ptsetreg.cpp): niters = max(RANSACUpdateNumIters(confidence, 0.45, M, maxIters), 3) fixed up front, the
+// same RNG / getSubset (1000 attempts) / checkSubset stream, every model scored by the median of its float32 errors (element
+// n / 2 in sorted order), the strictly smallest median kept.  Only cv::findFundamentalMat comes here (FM_LMEDS_BELOW).
+template <class Est>
+struct LeastMedian {
+    static constexpr int ATTEMPTS = 1000, LMEDS = 1;
+    double conf;
+    __device__ __forceinline__ int start(int max_iters) const { return max(update_iters(conf, 0.45, Est::M, max_iters), 3); }
+    __device__ __forceinline__ int score(const double* model, bool valid, const typename Est::Point* pts, int n) const
+    {
+        const int k = n / 2;
+        float med = INFINITY;
+        bool got = false;
+        if (valid)
+            for (int i = 0; i < n; ++i) {               // the k-th smallest without an array: n <= 14
+                const float ei = Est::error(model, pts[i]);
+                int less = 0, leq = 0;
+                for (int j = 0; j < n; ++j) { const float ej = Est::error(model, pts[j]); less += ej < ei; leq += ej <= ei; }
+                if (less <= k && k < leq) { med = ei; got = true; }
+            }
+        return got ? __float_as_int(med) : -1;          // errors are non-negative: their bit patterns are too
+    }
+    __device__ __forceinline__ bool keep(int c, int, RsState& st) const
+    {
+        if (!(c >= 0 && (double)__int_as_float(c) < st.min_med)) return false;
+        st.min_med = (double)__int_as_float(c);
+        return true;
+    }
+};
+
+// thread 0 only: the registrator's loop body over one round, in iteration order.  s_cnt[j][s] = the rule's score of model s of
+// hypothesis j.  Returns the (hypothesis, slot) kept LAST in this round, or -1.
+template <int NM, class Rule>
+__device__ int scan_round(const int* s_cnt, const unsigned char* s_ok, int base, int n, const Rule& rule, RsState& st)
 {
     int best = -1;
     for (int j = 0; j < 256; ++j) {
         const int it = base + j;
-        if (it >= st.niters) { st.stop = 1; break; }
-        if (!s_ok[j]) { st.failed = it == 0; st.stop = 1; break; }        // `if (iter == 0) return false; break;`
-        for (int sl = 0; sl < NM; ++sl) {
-            const int c = s_cnt[j * NM + sl];
-            if (c > max(st.max_good, M - 1)) {
-                best = j * NM + sl;
-                st.max_good = c;
-                st.niters = update_iters(conf, (double)(n - c) / n, M, st.niters);
-            }
-        }
+        if (it >= st.niters || !s_ok[j]) { st.stop = 1; break; }          // a dead subset: `if (iter == 0) return false; break;`
+        for (int sl = 0; sl < NM; ++sl)
+            if (rule.keep(s_cnt[j * NM + sl], n, st)) best = j * NM + sl;
         st.iters = it + 1;
     }
     return best;
+}
+
+// what a round leaves in LDS
+template <class Est>
+struct alignas(16) RoundLds {
+    unsigned short idx[RS_THREADS * Est::M];      // the subsets: indices < n
+    unsigned char ok[RS_THREADS];
+    int cnt[RS_THREADS * Est::NM];
+    int ctl[3];                                   // niters, stop, kept (hypothesis * NM + slot of this round, -1: none)
+};
+
+// The registrator's loop, 256 hypotheses a round: thread 0 draws the round's subsets, every thread gathers its sample, solves
+// and scores each model against ALL matches (LDS broadcast reads), thread 0 applies the rule in iteration order and publishes
+// ctl, the owning thread parks the kept model in best[9].  Every thread returns whether a model was kept; st is thread 0's.
+// n >= M.  Every barrier is reached by all threads: the loop's exit is read from ctl between two barriers.
+template <class Est, class Rule>
+__device__ __forceinline__ bool search(const typename Est::Point* pts, const Pair& p, int max_iters, const Rule& rule, RoundLds<Est>& s, double* best,
+                                       RsState& st)
+{
+    constexpr int M = Est::M, NM = Est::NM;
+    const int tid = threadIdx.x, n = p.n;
+    CvRng rng{rng_state(p.seed)};
+    st = RsState{rule.start(max(max_iters, 1)), 0, 0, 0, INFINITY};
+    bool alive = true, have = false;
+    int base = 0;
+    for (;;) {
+        if (tid == 0) {
+            if (n == M) {       // `count == modelPoints`: the one sample, no loop and no checkSubset
+                for (int j = 0; j < RS_THREADS; ++j) { s.ok[j] = j == 0; for (int i = 0; i < M; ++i) s.idx[j * M + i] = (unsigned short)i; }
+                st.niters = 1;
+            } else
+                gen_round<M>(rng, n, s.idx, s.ok, alive, [&](const int* idx) {
+                    double x1[2 * M], x2[2 * M];
+                    gather<M>(pts, idx, x1, x2);
+                    return Est::check(x1, x2);
+                }, Rule::ATTEMPTS);
+        }
+        __syncthreads();
+        double x1[2 * M], x2[2 * M], model[NM][9];
+        bool valid[NM];
+#pragma unroll
+        for (int sl = 0; sl < NM; ++sl) valid[sl] = false;
+        gather<M>(pts, s.idx + tid * M, x1, x2);
+        if (s.ok[tid]) Est::solve(x1, x2, model, valid);
+        for (int sl = 0; sl < NM; ++sl) s.cnt[tid * NM + sl] = rule.score(model[sl], valid[sl], pts, n);
+        __syncthreads();
+        if (tid == 0) {
+            const int kept = scan_round<NM>(s.cnt, s.ok, base, n, rule, st);
+            s.ctl[0] = st.niters; s.ctl[1] = st.stop; s.ctl[2] = kept;
+        }
+        __syncthreads();
+        const int kept = s.ctl[2];
+        if (kept >= 0 && kept / NM == tid) for (int e = 0; e < 9; ++e) best[e] = model[kept % NM][e];
+        have = have || kept >= 0;
+        base += RS_THREADS;
+        const bool more = !s.ctl[1] && base < s.ctl[0];
+        __syncthreads();
+        if (!more) break;
+    }
+    return have;
 }
 
 // OpenCV's haveCollinearPoints(m, count): the LAST of `count` points against every pair of earlier ones (FLT_EPSILON test)
@@ -290,15 +491,13 @@ __device__ __forceinline__ double reproj_err2(const double* H, double x, double 
     return dx * dx + dy * dy;
 }
 
-__device__ int update_iters(double conf, double outlier_ratio, int m, int max_iters)
-{
-    const double p = fmin(fmax(conf, 0.0), 1.0), ep = fmin(fmax(outlier_ratio, 0.0), 1.0);
-    double num = fmax(1.0 - p, 2.2250738585072014e-308);
-    double denom = 1.0 - pow(1.0 - ep, (double)m);
-    if (denom < 2.2250738585072014e-308) return 0;
-    num = log(num); denom = log(denom);
-    return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
-}
+// The homography kernel keeps its own round loop (below): of this, the shared rule uses the sample size and the threshold's type.
+struct HomographyEst {
+    static constexpr int M = 4;
+    using Point = float4;                         // (x, y, u, v) pixels
+    using Err = double;
+    static __device__ __forceinline__ double error(const double* H, const float4& p) { return reproj_err2(H, p.x, p.y, p.z, p.w); }
+};
 
 // sums N per-thread doubles over the workgroup; every thread gets the totals back in v
 template <int N>
@@ -346,14 +545,6 @@ __device__ bool solve_small(double* a /* [n][n+1] augmented */, int n)
     return true;
 }
 
-struct RansacArgs {
-    const float* m0; int cols0; const float* m1; int cols1;
-    int max_k; const int32_t* k_dev; const float* scale;      // [B][4] = (sx0, sy0, sx1, sy1): normalised -> pixels
-    const uint32_t* seed_dev; uint32_t seed;
-    double threshold, confidence; int max_iters, refine;
-    double* H; uint8_t* mask; int32_t* info;                  // [B][9], [B][max_k], [B][4] = (found, inliers, iterations, 0)
-};
-
 // accumulates the upper triangle of J^T J (36), J^T r (8) for one 2-row block of an 8-parameter problem
 __device__ __forceinline__ void acc_rows(double* acc, const double* j0, double r0, const double* j1, double r1)
 {
@@ -395,7 +586,7 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_homography(RansacArgs a)
     if (tid == 0) s_flag = 0;
     __syncthreads();
     int32_t* info = a.info + 4 * b;
-    double* Hout = a.H + 9 * b;
+    double* Hout = a.model + 9 * b;
     if (n < 4) {
         if (tid < 9) Hout[tid] = 0.0;
         if (tid == 0) { info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0; }
@@ -416,9 +607,12 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_homography(RansacArgs a)
     __shared__ unsigned short s_idx[RS_THREADS * 4];
     __shared__ unsigned char s_ok[RS_THREADS];
     __shared__ int s_cnt[RS_THREADS];
-    __shared__ int s_ctl[4];            // niters, stop, kept (hypothesis of this round, -1: none), failed
+    // niters, stop, kept (hypothesis of this round, -1: none).  The fourth is never touched: it held the flag this change removed, and
+    // dropping it changes nothing but the LDS layout, which then is no longer the layout that was timed.
+    __shared__ int s_ctl[4];
     CvRng rng{rng_state(seed)};
-    RsState st{max(a.max_iters, 1), 0, 0, 0, 0};
+    RsState st{max(a.max_iters, 1), 0, 0, 0, INFINITY};
+    const CountInliers<HomographyEst> rule{t2, a.confidence};
     bool alive = true;
     int base = 0;
     bool have = false;
@@ -428,7 +622,7 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_homography(RansacArgs a)
                 double s[8], d[8];
                 for (int j = 0; j < 4; ++j) { const float4 p = pts[idx[j]]; s[2 * j] = p.x; s[2 * j + 1] = p.y; d[2 * j] = p.z; d[2 * j + 1] = p.w; }
                 return check_subset_h(s, d);
-            });
+            }, GETSUBSET_ATTEMPTS);
         __syncthreads();
         double s[8], d[8], H[9];
 #pragma unroll
@@ -442,8 +636,8 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_homography(RansacArgs a)
         s_cnt[tid] = ok ? cnt : 0;
         __syncthreads();
         if (tid == 0) {
-            const int kept = scan_round<4, 1>(s_cnt, s_ok, base, n, a.confidence, st);
-            s_ctl[0] = st.niters; s_ctl[1] = st.stop; s_ctl[2] = kept; s_ctl[3] = st.failed;
+            const int kept = scan_round<1>(s_cnt, s_ok, base, n, rule, st);
+            s_ctl[0] = st.niters; s_ctl[1] = st.stop; s_ctl[2] = kept;
         }
         __syncthreads();
         if (s_ctl[2] == tid) for (int i = 0; i < 9; ++i) bestH[i] = H[i];
@@ -566,31 +760,6 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_homography(RansacArgs a)
     if (tid == 0) { info[0] = 1; info[1] = best_inliers; info[2] = st.iters; info[3] = 0; }
 }
 
-}  // namespace
-
-extern "C" __attribute__((visibility("default"))) int kpb_find_homography(
-    kpb_ctx* ctx, const float* m0_dev, int cols0, const float* m1_dev, int cols1, int batch, int max_k, const int32_t* k_dev,
-    const float* scale_dev, const uint32_t* seed_dev, uint32_t seed, const kpb_ransac_params* prm, double* out_h_dev, uint8_t* out_mask_dev,
-    int32_t* out_info_dev)
-{
-    if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_find_homography: null context");
-    if (batch <= 0 || max_k < 0 || cols0 < 2 || cols1 < 2 || !scale_dev || !prm || !out_h_dev || !out_info_dev || (max_k && (!m0_dev || !m1_dev || !out_mask_dev)))
-        return kpb_fail(ctx, KPB_E_INVALID, "kpb_find_homography: bad argument");
-    if ((size_t)max_k * sizeof(float4) > 128 * 1024)
-        return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_find_homography: at most %d matches per pair", (int)(128 * 1024 / sizeof(float4)));
-    if (!(prm->threshold > 0.0) || prm->max_iters < 1) return kpb_fail(ctx, KPB_E_INVALID, "kpb_find_homography: bad parameters");
-    KPB_HIP(ctx, hipSetDevice(ctx->device));
-    RansacArgs a{m0_dev, cols0, m1_dev, cols1, max_k, k_dev, scale_dev, seed_dev, seed, prm->threshold, prm->confidence, prm->max_iters, prm->refine,
-                 out_h_dev, out_mask_dev, out_info_dev};
-    const size_t lds = (size_t)max_k * sizeof(float4);
-    if (!(ctx->lds_attr_done & KPB_ATTR_HOMOGRAPHY)) {
-        KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(ransac_homography), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        ctx->lds_attr_done |= KPB_ATTR_HOMOGRAPHY;
-    }
-    KPB_LAUNCH(ctx, "ransac_homography", ransac_homography, dim3(batch), dim3(RS_THREADS), lds, ctx->stream, a);
-    KPB_HIP(ctx, hipGetLastError());
-    return KPB_OK;
-}
 
 // ================================================================================================ RANSAC essential matrix
 // cv2.findEssentialMat(k0, k1, eye(3), threshold, prob, RANSAC) + cv2.recoverPose as tasks/AUC.py:50-64 calls them (maxIters
@@ -601,7 +770,6 @@ extern "C" __attribute__((visibility("default"))) int kpb_find_homography(
 // (tables below), Gauss-Jordan on the ten leading monomials, det B(z) (degree 10), its roots by Aberth-Ehrlich iteration,
 // up to ten candidate matrices, each scored against ALL matches (LDS broadcast reads).  The solver's small matrices are
 // thread-private (scratch): this stage is a few milliseconds per 256 pairs next to a 30 ms extraction step.
-namespace {
 
 // products of the monomial bases: linear (x, y, z, 1) x linear -> quadratic DEG2; quadratic x linear -> MONO (Nister's order:
 // x3 y3 x2y xy2 x2z x2 y2z y2 xyz xy | xz2 xz x yz2 yz y z3 z2 z 1)
@@ -823,34 +991,37 @@ __device__ __forceinline__ double sampson_err(const double* E, double u1, double
     return x2tEx1 * x2tEx1 / den;
 }
 
+struct EssentialEst {
+    static constexpr int M = 5, NM = 10;
+    using Point = Pt4d;                           // (u1, v1, u2, v2) normalised
+    using Err = double;
+    // EMEstimatorCallback has no checkSubset
+    static __device__ __forceinline__ bool check(const double*, const double*) { return true; }
+    static __device__ __forceinline__ void solve(const double* x1, const double* x2, double (*E)[9], bool* valid)
+    {
+        essential_5pt(x1, x2, E, valid);
+    }
+    static __device__ __forceinline__ double error(const double* E, const Pt4d& p) { return sampson_err(E, p.x, p.y, p.z, p.w); }
+};
+
 struct EssArgs {
-    const float* m0; int cols0; const float* m1; int cols1;
-    int max_k; const int32_t* k_dev;
-    const float* scale;       // [B][4]: normalised (x, y) -> pixels, fp32 as AUC.py:125-126
+    RansacArgs r;             // threshold and refine unused; confidence = prob
     const double* cam;        // [B][8]: cx0 cy0 fx0 fy0 cx1 cy1 fx1 fy1 (AUC.py:47-48: (k - c) / f)
     int cam_f32;              // the intrinsics are float32 (datasets/megadepth.py:341-342): numpy then normalises in float32
     const double* thr;        // [B]: norm_thresh = thresh / f_mean
-    const uint32_t* seed_dev; uint32_t seed;
-    double prob; int max_iters;
-    double* E; uint8_t* mask; int32_t* info;      // [B][9], [B][max_k], [B][4] = (found, inliers, hypotheses, 0)
-    double* pts;                                   // [B][max_k][4] normalised coordinates (u1 v1 u2 v2), kept for kpb_recover_pose
+    double* pts;              // [B][max_k][4] normalised coordinates (u1 v1 u2 v2), kept for kpb_recover_pose
 };
 
 __global__ __launch_bounds__(RS_THREADS) void ransac_essential(EssArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double* P = reinterpret_cast<double*>(smem);                     // [n][4]
+    Pt4d* P = reinterpret_cast<Pt4d*>(smem);                         // [n]
     __shared__ double bestE[9];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = a.k_dev ? min(a.k_dev[b], a.max_k) : a.max_k;
-    const uint32_t seed = a.seed_dev ? a.seed_dev[b] : a.seed;
-    const float* sc = a.scale + 4 * b;
+    __shared__ RoundLds<EssentialEst> s_round;
+    const int b = blockIdx.x;
     const double* cam = a.cam + 8 * b;
-    double* gp = a.pts + (size_t)b * a.max_k * 4;
-    for (int i = tid; i < n; i += RS_THREADS) {
-        const float* p0 = a.m0 + ((size_t)b * a.max_k + i) * a.cols0;
-        const float* p1 = a.m1 + ((size_t)b * a.max_k + i) * a.cols1;
-        const float x0 = p0[0] * sc[0], y0 = p0[1] * sc[1], x1 = p1[0] * sc[2], y1 = p1[1] * sc[3];      // fp32 pixel products (AUC.py:125-126)
+    Pt4d* gp = reinterpret_cast<Pt4d*>(a.pts) + (size_t)b * a.r.max_k;
+    const Pair pr = load_matches(a.r, P, [&](int i, float x0, float y0, float x1, float y1) {
         double u1, v1, u2, v2;
         if (a.cam_f32) {
             u1 = (double)__fdiv_rn(x0 - (float)cam[0], (float)cam[2]); v1 = (double)__fdiv_rn(y0 - (float)cam[1], (float)cam[3]);
@@ -859,72 +1030,23 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_essential(EssArgs a)
             u1 = ((double)x0 - cam[0]) / cam[2]; v1 = ((double)y0 - cam[1]) / cam[3];
             u2 = ((double)x1 - cam[4]) / cam[6]; v2 = ((double)y1 - cam[5]) / cam[7];
         }
-        P[4 * i] = u1; P[4 * i + 1] = v1; P[4 * i + 2] = u2; P[4 * i + 3] = v2;
-        gp[4 * i] = u1; gp[4 * i + 1] = v1; gp[4 * i + 2] = u2; gp[4 * i + 3] = v2;
-    }
-    uint8_t* mask = a.mask + (size_t)b * a.max_k;
-    for (int i = tid; i < a.max_k; i += RS_THREADS) mask[i] = 0;
-    __syncthreads();
-    int32_t* info = a.info + 4 * b;
-    double* Eout = a.E + 9 * b;
-    if (n < 5) {
-        if (tid < 9) Eout[tid] = 0.0;
-        if (tid == 0) { info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0; }
+        return gp[i] = Pt4d{u1, v1, u2, v2};
+    });
+    if (pr.n < 5) {
+        nothing_found(pr, 0, 0);
         return;
     }
     const double t2 = a.thr[b] * a.thr[b];
-    __shared__ unsigned short s_idx[RS_THREADS * 5];
-    __shared__ unsigned char s_ok[RS_THREADS];
-    __shared__ int s_cnt[RS_THREADS * 10];
-    __shared__ int s_ctl[4];            // niters, stop, kept (hypothesis * 10 + root slot of this round, -1: none), failed
-    CvRng rng{rng_state(seed)};
-    RsState st{max(a.max_iters, 1), 0, 0, 0, 0};
-    bool alive = true, have = false;
-    int base = 0;
-    for (;;) {
-        if (tid == 0) {
-            if (n == 5) {       // `count == modelPoints`: the one sample, no loop (EMEstimatorCallback has no checkSubset)
-                for (int j = 0; j < RS_THREADS; ++j) { s_ok[j] = j == 0; for (int i = 0; i < 5; ++i) s_idx[j * 5 + i] = (unsigned short)i; }
-                st.niters = 1;
-            } else
-                gen_round<5>(rng, n, s_idx, s_ok, alive, [](const int*) { return true; });
-        }
-        __syncthreads();
-        double x1[10], x2[10];
-        for (int j = 0; j < 5; ++j) { const int q = s_idx[tid * 5 + j]; x1[2 * j] = P[4 * q]; x1[2 * j + 1] = P[4 * q + 1]; x2[2 * j] = P[4 * q + 2]; x2[2 * j + 1] = P[4 * q + 3]; }
-        double E[10][9];
-        bool valid[10];
-        int nv = 0;
-        if (s_ok[tid]) nv = essential_5pt(x1, x2, E, valid);
-        for (int s = 0; s < 10; ++s) {
-            int cnt = 0;
-            if (nv && valid[s])
-                for (int i = 0; i < n; ++i) cnt += sampson_err(E[s], P[4 * i], P[4 * i + 1], P[4 * i + 2], P[4 * i + 3]) <= t2;
-            s_cnt[tid * 10 + s] = cnt;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const int kept = scan_round<5, 10>(s_cnt, s_ok, base, n, a.prob, st);
-            s_ctl[0] = st.niters; s_ctl[1] = st.stop; s_ctl[2] = kept; s_ctl[3] = st.failed;
-        }
-        __syncthreads();
-        if (s_ctl[2] >= 0 && s_ctl[2] / 10 == tid) for (int e = 0; e < 9; ++e) bestE[e] = E[s_ctl[2] % 10][e];
-        have = have || s_ctl[2] >= 0;
-        base += RS_THREADS;
-        const bool more = !s_ctl[1] && base < s_ctl[0];
-        __syncthreads();
-        if (!more) break;
-    }
-    if (!have) {
-        if (tid < 9) Eout[tid] = 0.0;
-        if (tid == 0) { info[0] = 0; info[1] = 0; info[2] = st.iters; info[3] = 0; }
+    RsState st;
+    const CountInliers<EssentialEst> rule{t2, a.r.confidence};
+    if (!search(P, pr, a.r.max_iters, rule, s_round, bestE, st)) {
+        nothing_found(pr, st.iters, 0);
         return;
     }
     double Eb[9];
     for (int e = 0; e < 9; ++e) Eb[e] = bestE[e];
-    for (int i = tid; i < n; i += RS_THREADS) mask[i] = sampson_err(Eb, P[4 * i], P[4 * i + 1], P[4 * i + 2], P[4 * i + 3]) <= t2;
-    if (tid < 9) Eout[tid] = Eb[tid];
-    if (tid == 0) { info[0] = 1; info[1] = st.max_good; info[2] = st.iters; info[3] = 0; }
+    write_mask<EssentialEst>(pr, P, Eb, t2);
+    write_result(pr, true, Eb, st.max_good, st.iters, 0);
 }
 
 // ---- recoverPose: SVD of E (Jacobi on E^T E), the four (R, t), depth signs of the masked points, the best combination
@@ -1120,195 +1242,126 @@ __device__ __forceinline__ float fm_err(const double* F, double u1, double v1, d
     return (float)fmax(d1 * d1 * s1, d2 * d2 * s2);
 }
 
-struct FundArgs {
-    const float* m0; int cols0; const float* m1; int cols1;
-    int max_k; const int32_t* k_dev; const float* scale;      // [B][4]: normalised -> pixels, fp32 (FundamentalMatrix.py:76-77)
-    const uint32_t* seed_dev; uint32_t seed;
-    double threshold, confidence; int max_iters;
-    double* F; uint8_t* mask; int32_t* info;                  // [B][9], [B][max_k], [B][4] = (found, inliers, hypotheses, 0)
+struct FundamentalEst {
+    static constexpr int M = 7, NM = 3;
+    using Point = float4;                         // (u1, v1, u2, v2) pixels
+    using Err = float;
+    // FMEstimatorCallback::checkSubset
+    static __device__ __forceinline__ bool check(const double* x1, const double* x2)
+    {
+        return !last_collinear<7>(x1) && !last_collinear<7>(x2);
+    }
+    static __device__ __forceinline__ void solve(const double* x1, const double* x2, double (*F)[9], bool* valid)
+    {
+        fundamental_7pt(x1, x2, F, valid);
+    }
+    static __device__ __forceinline__ float error(const double* F, const float4& p) { return fm_err(F, p.x, p.y, p.z, p.w); }
 };
 
-__global__ __launch_bounds__(RS_THREADS) void ransac_fundamental(FundArgs a)
+__global__ __launch_bounds__(RS_THREADS) void ransac_fundamental(RansacArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float4* pts = reinterpret_cast<float4*>(smem);                       // [n] (u1, v1, u2, v2) pixels
     __shared__ double bestF[9];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = a.k_dev ? min(a.k_dev[b], a.max_k) : a.max_k;
-    const uint32_t seed = a.seed_dev ? a.seed_dev[b] : a.seed;
-    const float* sc = a.scale + 4 * b;
-    for (int i = tid; i < n; i += RS_THREADS) {
-        const float* p0 = a.m0 + ((size_t)b * a.max_k + i) * a.cols0;
-        const float* p1 = a.m1 + ((size_t)b * a.max_k + i) * a.cols1;
-        pts[i] = make_float4(p0[0] * sc[0], p0[1] * sc[1], p1[0] * sc[2], p1[1] * sc[3]);
-    }
-    uint8_t* mask = a.mask + (size_t)b * a.max_k;
-    for (int i = tid; i < a.max_k; i += RS_THREADS) mask[i] = 0;
-    __syncthreads();
-    int32_t* info = a.info + 4 * b;
-    double* Fout = a.F + 9 * b;
+    __shared__ RoundLds<FundamentalEst> s_round;
+    const int tid = threadIdx.x;
+    const Pair pr = load_matches(a, pts, [](int, float x, float y, float u, float v) { return make_float4(x, y, u, v); });
+    const int n = pr.n;
     if (n < 8) {        // utils/mvg.py:13-15 never calls cv2 below eight matches
-        if (tid < 9) Fout[tid] = 0.0;
-        if (tid == 0) { info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0; }
+        nothing_found(pr, 0, 0);
+        return;
+    }
+    RsState st;
+    double Fb[9];
+    if (n < FM_LMEDS_BELOW) {
+        // cv::findFundamentalMat (OpenCV 4.9 fundam.cpp): `(method & ~3) == FM_RANSAC && npoints >= 15` runs the RANSAC registrator,
+        // FEWER THAN 15 correspondences go to the least-median one whatever the method.  LMeDSPointSetRegistrator::run
+        // (the LeastMedian rule), then: inliers = error <= sigma^2 with sigma = max(2.5 * 1.4826 * (1 + 5 / (n - 7)) * sqrt(median), 0.001);
+        // the model stands when at least 7 points are inliers.  info[3] = 1 marks the branch.  PARITY UNPINNED (see the top of this file).
+        __shared__ double s_minmed;
+        __shared__ int s_good;
+        const bool have = search(pts, pr, a.max_iters, LeastMedian<FundamentalEst>{a.confidence}, s_round, bestF, st);
+        if (!have) {
+            nothing_found(pr, st.iters, 1);
+            return;
+        }
+        if (tid == 0) { s_minmed = st.min_med; s_good = 0; }
+        __syncthreads();
+        for (int e = 0; e < 9; ++e) Fb[e] = bestF[e];
+        const double sigma = fmax(2.5 * 1.4826 * (1.0 + 5.0 / (n - 7)) * sqrt(s_minmed), 0.001);
+        const int mine = write_mask<FundamentalEst>(pr, pts, Fb, (float)(sigma * sigma));
+        if (mine) atomicAdd(&s_good, mine);
+        __syncthreads();
+        const int good = s_good;
+        write_result(pr, good >= 7, Fb, good, st.iters, 1);
         return;
     }
     const float t2 = (float)(a.threshold * a.threshold);
-    __shared__ unsigned short s_idx[RS_THREADS * 7];
-    __shared__ unsigned char s_ok[RS_THREADS];
-    __shared__ int s_cnt[RS_THREADS * 3];
-    __shared__ int s_ctl[4];            // niters, stop, kept (hypothesis * 3 + root slot of this round, -1: none), failed
-    CvRng rng{rng_state(seed)};
-    RsState st{max(a.max_iters, 1), 0, 0, 0, 0};
-    bool alive = true, have = false;
-    int base = 0;
-    auto check = [&](const int* idx) {       // FMEstimatorCallback::checkSubset
-        double x1[14], x2[14];
-        for (int j = 0; j < 7; ++j) { const float4 q = pts[idx[j]]; x1[2 * j] = q.x; x1[2 * j + 1] = q.y; x2[2 * j] = q.z; x2[2 * j + 1] = q.w; }
-        return !last_collinear<7>(x1) && !last_collinear<7>(x2);
-    };
-    if (n < FM_LMEDS_BELOW) {
-        // cv::findFundamentalMat (OpenCV 4.9 fundam.cpp): `(method & ~3) == FM_RANSAC && npoints >= 15` runs the RANSAC registrator,
-        // FEWER THAN 15 correspondences go to the least-median one whatever the method.  LMeDSPointSetRegistrator::run:
-        // niters = max(RANSACUpdateNumIters(confidence, 0.45, 7, maxIters), 3), the same RNG / getSubset (1000 attempts) / checkSubset
-        // stream, every model scored by the median of its float32 errors (element n / 2 in sorted order), the strictly smallest
-        // median kept; inliers = error <= sigma^2 with sigma = max(2.5 * 1.4826 * (1 + 5 / (n - 7)) * sqrt(median), 0.001); the model
-        // stands when at least 7 points are inliers.  info[3] = 1 marks the branch.  PARITY UNPINNED (see the top of this file).
-        const int niters = max(update_iters(a.confidence, 0.45, 7, max(a.max_iters, 1)), 3);
-        __shared__ double s_minmed;
-        __shared__ int s_good;
-        if (tid == 0) { s_minmed = INFINITY; s_good = 0; }
-        int iters = 0;
-        for (;;) {
-            if (tid == 0) gen_round<7>(rng, n, s_idx, s_ok, alive, check, 1000);
-            __syncthreads();
-            double x1[14], x2[14];
-            for (int j = 0; j < 7; ++j) { const float4 q = pts[s_idx[tid * 7 + j]]; x1[2 * j] = q.x; x1[2 * j + 1] = q.y; x2[2 * j] = q.z; x2[2 * j + 1] = q.w; }
-            double F[3][9];
-            bool valid[3] = {false, false, false};
-            int nv = 0;
-            if (s_ok[tid]) nv = fundamental_7pt(x1, x2, F, valid);
-            const int k = n / 2;
-            for (int s = 0; s < 3; ++s) {
-                float med = INFINITY;
-                bool got = false;
-                if (nv && valid[s])
-                    for (int i = 0; i < n; ++i) {               // the k-th smallest without an array: n <= 14
-                        const float4 qi = pts[i];
-                        const float ei = fm_err(F[s], qi.x, qi.y, qi.z, qi.w);
-                        int less = 0, leq = 0;
-                        for (int j = 0; j < n; ++j) { const float4 q = pts[j]; const float ej = fm_err(F[s], q.x, q.y, q.z, q.w); less += ej < ei; leq += ej <= ei; }
-                        if (less <= k && k < leq) { med = ei; got = true; }
-                    }
-                s_cnt[tid * 3 + s] = got ? __float_as_int(med) : -1;      // errors are non-negative: their bit patterns are too
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int kept = -1, stop = 0;
-                double mm = s_minmed;
-                for (int j = 0; j < 256; ++j) {
-                    const int it = base + j;
-                    if (it >= niters || !s_ok[j]) { stop = 1; break; }        // `if (iter == 0) return false; break;`
-                    for (int sl = 0; sl < 3; ++sl) {
-                        const int c = s_cnt[j * 3 + sl];
-                        if (c >= 0 && (double)__int_as_float(c) < mm) { mm = (double)__int_as_float(c); kept = j * 3 + sl; }
-                    }
-                    iters = it + 1;
-                }
-                s_minmed = mm; s_ctl[0] = iters; s_ctl[1] = stop; s_ctl[2] = kept;
-            }
-            __syncthreads();
-            if (s_ctl[2] >= 0 && s_ctl[2] / 3 == tid) for (int e = 0; e < 9; ++e) bestF[e] = F[s_ctl[2] % 3][e];
-            have = have || s_ctl[2] >= 0;
-            base += RS_THREADS;
-            const bool more = !s_ctl[1] && base < niters;
-            __syncthreads();
-            if (!more) break;
-        }
-        iters = s_ctl[0];
-        if (!have) {
-            if (tid < 9) Fout[tid] = 0.0;
-            if (tid == 0) { info[0] = 0; info[1] = 0; info[2] = iters; info[3] = 1; }
-            return;
-        }
-        double Fb[9];
-        for (int e = 0; e < 9; ++e) Fb[e] = bestF[e];
-        const double sigma = fmax(2.5 * 1.4826 * (1.0 + 5.0 / (n - 7)) * sqrt(s_minmed), 0.001);
-        const float ts = (float)(sigma * sigma);
-        for (int i = tid; i < n; i += RS_THREADS) {
-            const float4 q = pts[i];
-            const int in = fm_err(Fb, q.x, q.y, q.z, q.w) <= ts;
-            mask[i] = (uint8_t)in;
-            if (in) atomicAdd(&s_good, 1);
-        }
-        __syncthreads();
-        const int good = s_good, found = good >= 7;
-        if (tid < 9) Fout[tid] = found ? Fb[tid] : 0.0;
-        if (tid == 0) { info[0] = found; info[1] = good; info[2] = iters; info[3] = 1; }
+    if (!search(pts, pr, a.max_iters, CountInliers<FundamentalEst>{t2, a.confidence}, s_round, bestF, st)) {
+        nothing_found(pr, st.iters, 0);
         return;
     }
-    for (;;) {
-        if (tid == 0) gen_round<7>(rng, n, s_idx, s_ok, alive, check);
-        __syncthreads();
-        double x1[14], x2[14];
-        for (int j = 0; j < 7; ++j) { const float4 q = pts[s_idx[tid * 7 + j]]; x1[2 * j] = q.x; x1[2 * j + 1] = q.y; x2[2 * j] = q.z; x2[2 * j + 1] = q.w; }
-        double F[3][9];
-        bool valid[3] = {false, false, false};
-        int nv = 0;
-        if (s_ok[tid]) nv = fundamental_7pt(x1, x2, F, valid);
-        for (int s = 0; s < 3; ++s) {
-            int cnt = 0;
-            if (nv && valid[s])
-                for (int i = 0; i < n; ++i) { const float4 q = pts[i]; cnt += fm_err(F[s], q.x, q.y, q.z, q.w) <= t2; }
-            s_cnt[tid * 3 + s] = cnt;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const int kept = scan_round<7, 3>(s_cnt, s_ok, base, n, a.confidence, st);
-            s_ctl[0] = st.niters; s_ctl[1] = st.stop; s_ctl[2] = kept; s_ctl[3] = st.failed;
-        }
-        __syncthreads();
-        if (s_ctl[2] >= 0 && s_ctl[2] / 3 == tid) for (int e = 0; e < 9; ++e) bestF[e] = F[s_ctl[2] % 3][e];
-        have = have || s_ctl[2] >= 0;
-        base += RS_THREADS;
-        const bool more = !s_ctl[1] && base < s_ctl[0];
-        __syncthreads();
-        if (!more) break;
-    }
-    if (!have) {
-        if (tid < 9) Fout[tid] = 0.0;
-        if (tid == 0) { info[0] = 0; info[1] = 0; info[2] = st.iters; info[3] = 0; }
-        return;
-    }
-    double Fb[9];
     for (int e = 0; e < 9; ++e) Fb[e] = bestF[e];
-    for (int i = tid; i < n; i += RS_THREADS) { const float4 q = pts[i]; mask[i] = fm_err(Fb, q.x, q.y, q.z, q.w) <= t2; }
-    if (tid < 9) Fout[tid] = Fb[tid];
-    if (tid == 0) { info[0] = 1; info[1] = st.max_good; info[2] = st.iters; info[3] = 0; }
+    write_mask<FundamentalEst>(pr, pts, Fb, t2);
+    write_result(pr, true, Fb, st.max_good, st.iters, 0);
 }
 
+// What a kpb_find_* wrapper is to the launch helper: its name for the messages, the profile name, its kernel and KPB_ATTR_* bit, the
+// bytes a match takes in LDS, and its message above the LDS limit (two %d: the limit, max_k; the second may go unused).
+template <class Args>
+struct RansacLaunch { const char* fn; const char* name; void (*kernel)(Args); unsigned attr; size_t point; const char* limit_fmt; };
+
+// One launch path for the three kpb_find_* wrappers: the arguments they share (r, inside a), the LDS limit (128 KB of matches), the
+// dynamic-LDS attribute once per kernel and context, the launch.  own_ok / params_ok: the wrapper's own argument and parameter checks.
+template <class Args>
+int launch_ransac(kpb_ctx* ctx, const RansacLaunch<Args>& k, const Args& a, const RansacArgs& r, int batch, bool own_ok, bool params_ok)
+{
+    if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "%s: null context", k.fn);
+    if (batch <= 0 || r.max_k < 0 || r.cols0 < 2 || r.cols1 < 2 || !r.scale || !r.model || !r.info || (r.max_k && (!r.m0 || !r.m1 || !r.mask)) || !own_ok)
+        return kpb_fail(ctx, KPB_E_INVALID, "%s: bad argument", k.fn);
+    const size_t lds = (size_t)r.max_k * k.point;
+    if (lds > 128 * 1024)      // the matches live in LDS for the whole search (config_vo.yaml's top_k 2000 needs 64 KB of doubles)
+        return kpb_fail(ctx, KPB_E_UNSUPPORTED, k.limit_fmt, (int)(128 * 1024 / k.point), r.max_k);
+    if (!params_ok) return kpb_fail(ctx, KPB_E_INVALID, "%s: bad parameters", k.fn);
+    KPB_HIP(ctx, hipSetDevice(ctx->device));
+    if (!(ctx->lds_attr_done & k.attr)) {
+        KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        ctx->lds_attr_done |= k.attr;
+    }
+    KPB_LAUNCH(ctx, k.name, k.kernel, dim3(batch), dim3(RS_THREADS), lds, ctx->stream, a);
+    KPB_HIP(ctx, hipGetLastError());
+    return KPB_OK;
+}
+
+const RansacLaunch<RansacArgs> LAUNCH_H{"kpb_find_homography", "ransac_homography", ransac_homography, KPB_ATTR_HOMOGRAPHY, sizeof(float4),
+                                        "kpb_find_homography: at most %d matches per pair"};
+const RansacLaunch<RansacArgs> LAUNCH_F{"kpb_find_fundamental", "ransac_fundamental", ransac_fundamental, KPB_ATTR_FUNDAMENTAL, sizeof(float4),
+                                        "kpb_find_fundamental: at most %d matches per pair"};
+const RansacLaunch<EssArgs> LAUNCH_E{"kpb_find_essential", "ransac_essential", ransac_essential, KPB_ATTR_ESSENTIAL, sizeof(Pt4d),
+                                     "kpb_find_essential: at most %d matches per pair (got %d)"};
+
 }  // namespace
+
+extern "C" __attribute__((visibility("default"))) int kpb_find_homography(
+    kpb_ctx* ctx, const float* m0_dev, int cols0, const float* m1_dev, int cols1, int batch, int max_k, const int32_t* k_dev,
+    const float* scale_dev, const uint32_t* seed_dev, uint32_t seed, const kpb_ransac_params* prm, double* out_h_dev, uint8_t* out_mask_dev,
+    int32_t* out_info_dev)
+{
+    const kpb_ransac_params p = prm ? *prm : kpb_ransac_params{};
+    const RansacArgs a{m0_dev, cols0, m1_dev, cols1, max_k, k_dev, scale_dev, seed_dev, seed, p.threshold, p.confidence, p.max_iters, p.refine,
+                       out_h_dev, out_mask_dev, out_info_dev};
+    return launch_ransac(ctx, LAUNCH_H, a, a, batch, prm != nullptr, p.threshold > 0.0 && p.max_iters >= 1);
+}
 
 extern "C" __attribute__((visibility("default"))) int kpb_find_fundamental(
     kpb_ctx* ctx, const float* m0_dev, int cols0, const float* m1_dev, int cols1, int batch, int max_k, const int32_t* k_dev,
     const float* scale_dev, const uint32_t* seed_dev, uint32_t seed, const kpb_ransac_params* prm, double* out_f_dev, uint8_t* out_mask_dev,
     int32_t* out_info_dev)
 {
-    if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_find_fundamental: null context");
-    if (batch <= 0 || max_k < 0 || cols0 < 2 || cols1 < 2 || !scale_dev || !prm || !out_f_dev || !out_info_dev || (max_k && (!m0_dev || !m1_dev || !out_mask_dev)))
-        return kpb_fail(ctx, KPB_E_INVALID, "kpb_find_fundamental: bad argument");
-    if ((size_t)max_k * sizeof(float4) > 128 * 1024)
-        return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_find_fundamental: at most %d matches per pair", (int)(128 * 1024 / sizeof(float4)));
-    if (!(prm->threshold > 0.0) || prm->max_iters < 1) return kpb_fail(ctx, KPB_E_INVALID, "kpb_find_fundamental: bad parameters");
-    KPB_HIP(ctx, hipSetDevice(ctx->device));
-    FundArgs a{m0_dev, cols0, m1_dev, cols1, max_k, k_dev, scale_dev, seed_dev, seed, prm->threshold, prm->confidence, prm->max_iters,
-               out_f_dev, out_mask_dev, out_info_dev};
-    if (!(ctx->lds_attr_done & KPB_ATTR_FUNDAMENTAL)) {
-        KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(ransac_fundamental), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        ctx->lds_attr_done |= KPB_ATTR_FUNDAMENTAL;
-    }
-    KPB_LAUNCH(ctx, "ransac_fundamental", ransac_fundamental, dim3(batch), dim3(RS_THREADS), (size_t)max_k * sizeof(float4), ctx->stream, a);
-    KPB_HIP(ctx, hipGetLastError());
-    return KPB_OK;
+    const kpb_ransac_params p = prm ? *prm : kpb_ransac_params{};
+    const RansacArgs a{m0_dev, cols0, m1_dev, cols1, max_k, k_dev, scale_dev, seed_dev, seed, p.threshold, p.confidence, p.max_iters, 0,
+                       out_f_dev, out_mask_dev, out_info_dev};
+    return launch_ransac(ctx, LAUNCH_F, a, a, batch, prm != nullptr, p.threshold > 0.0 && p.max_iters >= 1);
 }
 
 extern "C" __attribute__((visibility("default"))) int kpb_find_essential(
@@ -1316,23 +1369,9 @@ extern "C" __attribute__((visibility("default"))) int kpb_find_essential(
     const float* scale_dev, const double* cam_dev, int cam_f32, const double* thr_dev, const uint32_t* seed_dev, uint32_t seed, double prob, int max_iters,
     double* out_e_dev, uint8_t* out_mask_dev, int32_t* out_info_dev, double* out_pts_dev)
 {
-    if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_find_essential: null context");
-    if (batch <= 0 || max_k < 0 || cols0 < 2 || cols1 < 2 || !scale_dev || !cam_dev || !thr_dev || !out_e_dev || !out_info_dev ||
-        (max_k && (!m0_dev || !m1_dev || !out_mask_dev || !out_pts_dev)) || max_iters < 1)
-        return kpb_fail(ctx, KPB_E_INVALID, "kpb_find_essential: bad argument");
-    const size_t lds = (size_t)max_k * 4 * sizeof(double);
-    if (lds > 128 * 1024)      // the matches live in LDS for the whole search (config_vo.yaml's top_k 2000 needs 64 KB)
-        return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_find_essential: at most 4096 matches per pair (got %d)", max_k);
-    KPB_HIP(ctx, hipSetDevice(ctx->device));
-    if (lds > 48 * 1024 && !(ctx->lds_attr_done & KPB_ATTR_ESSENTIAL)) {
-        KPB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(ransac_essential), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        ctx->lds_attr_done |= KPB_ATTR_ESSENTIAL;
-    }
-    EssArgs a{m0_dev, cols0, m1_dev, cols1, max_k, k_dev, scale_dev, cam_dev, cam_f32, thr_dev, seed_dev, seed, prob, max_iters, out_e_dev, out_mask_dev,
-              out_info_dev, out_pts_dev};
-    KPB_LAUNCH(ctx, "ransac_essential", ransac_essential, dim3(batch), dim3(RS_THREADS), lds, ctx->stream, a);
-    KPB_HIP(ctx, hipGetLastError());
-    return KPB_OK;
+    const EssArgs a{{m0_dev, cols0, m1_dev, cols1, max_k, k_dev, scale_dev, seed_dev, seed, 0.0, prob, max_iters, 0, out_e_dev, out_mask_dev, out_info_dev},
+                    cam_dev, cam_f32, thr_dev, out_pts_dev};
+    return launch_ransac(ctx, LAUNCH_E, a, a.r, batch, cam_dev && thr_dev && (!max_k || out_pts_dev) && max_iters >= 1, true);
 }
 
 extern "C" __attribute__((visibility("default"))) int kpb_recover_pose(

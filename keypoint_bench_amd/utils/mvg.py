@@ -14,26 +14,32 @@ import torch
 from .._lib import Context, RansacParams, ptr
 
 
+def _prepare(m0, m1, scale, seeds):
+    """What the three kernels take: the matched rows as contiguous fp32 [B, K, c] (a single pair [K, c] becomes a batch of one), the scale as
+    [B, 4] fp32 on their device (one [4] serves every pair), the per-pair seeds as uint32 bit patterns carried in an int32 tensor (None: the
+    call's one `seed`)."""
+    a = m0.detach().to(torch.float32).contiguous()
+    b = m1.detach().to(torch.float32).contiguous()
+    if a.dim() == 2:
+        a, b = a[None], b[None]
+    if not a.is_cuda:
+        raise RuntimeError("keypoint_bench_amd needs CUDA/HIP tensors; there is no CPU path")
+    dev, B = a.device, a.shape[0]
+    sc = torch.as_tensor(scale, dtype=torch.float32).to(dev).reshape(-1, 4)
+    sc = (sc.expand(B, 4) if sc.shape[0] == 1 else sc).contiguous()
+    sd = None
+    if seeds is not None:
+        sd = torch.from_numpy((np.asarray(seeds, np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32).reshape(B).copy()).to(dev)
+    return a, b, sc, sd
+
+
 def find_homography(m0, m1, scale, k_dev=None, seeds=None, seed=0, threshold=3.0, confidence=0.995, max_iters=2000, refine=True):
     """B independent estimations in one launch.  m0, m1 [B, K, c>=2] (or [K, c]): matched rows, normalised (x, y, ...);
     scale [B, 4] or [4] = (sx0, sy0, sx1, sy1) normalised -> pixels; k_dev int32 [B] valid rows (None: all K);
     seeds: per-pair sampler seeds (int sequence / tensor), default `seed` for every pair.
     Returns (H [B, 3, 3] float64, mask [B, K] uint8, info [B, 4] int32 = found, inliers, hypotheses, 0) on the device."""
-    a = m0.detach().to(torch.float32).contiguous()
-    b = m1.detach().to(torch.float32).contiguous()
-    if a.dim() == 2:
-        a, b = a[None], b[None]
-    dev = a.device
-    if not a.is_cuda:
-        raise RuntimeError("keypoint_bench_amd needs CUDA/HIP tensors; there is no CPU path")
-    B, K = a.shape[0], a.shape[1]
-    sc = torch.as_tensor(scale, dtype=torch.float32).to(dev).reshape(-1, 4)
-    if sc.shape[0] == 1 and B > 1:
-        sc = sc.expand(B, 4)
-    sc = sc.contiguous()
-    sd = None
-    if seeds is not None:       # uint32 bit patterns carried in an int32 tensor
-        sd = torch.from_numpy((np.asarray(seeds, np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32).reshape(B).copy()).to(dev)
+    a, b, sc, sd = _prepare(m0, m1, scale, seeds)
+    dev, B, K = a.device, a.shape[0], a.shape[1]
     H = torch.zeros((B, 3, 3), dtype=torch.float64, device=dev)
     mask = torch.zeros((B, max(K, 1)), dtype=torch.uint8, device=dev)
     info = torch.zeros((B, 4), dtype=torch.int32, device=dev)
@@ -44,12 +50,6 @@ def find_homography(m0, m1, scale, k_dev=None, seeds=None, seed=0, threshold=3.0
     return H, mask[:, :K], info
 
 
-def _seeds(seeds, B, dev):
-    if seeds is None:
-        return None
-    return torch.from_numpy((np.asarray(seeds, np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32).reshape(B).copy()).to(dev)
-
-
 def estimate_pose(m0, m1, scale, K0, K1, thresh=1.0, conf=0.99999, k_dev=None, seeds=None, seed=0, max_iters=1000, recover_all=False, dist=1e9):
     """tasks/AUC.py:40-64 (`estimate_pose`) for B pairs in two launches: cv2.findEssentialMat(RANSAC) + cv2.recoverPose restated
     (PARITY UNPINNED, see the module docstring).  m0, m1 [B, K, c>=2] matched rows, normalised; scale [B, 4] -> pixels;
@@ -57,16 +57,8 @@ def estimate_pose(m0, m1, scale, K0, K1, thresh=1.0, conf=0.99999, k_dev=None, s
     after recoverPose; good [B] int32 = recoverPose's count (0: no pose); info [B, 4] = found, RANSAC inliers, hypotheses, 0).
     recover_all: recoverPose is called WITHOUT the RANSAC mask, on every match (tasks/visual_odometer.py:76-77); dist: its
     distanceThresh (1e9 at AUC.py:60, cv2's default 50 at visual_odometer.py:76)."""
-    a = m0.detach().to(torch.float32).contiguous()
-    b = m1.detach().to(torch.float32).contiguous()
-    if a.dim() == 2:
-        a, b = a[None], b[None]
-    if not a.is_cuda:
-        raise RuntimeError("keypoint_bench_amd needs CUDA/HIP tensors; there is no CPU path")
-    dev = a.device
-    B, K = a.shape[0], a.shape[1]
-    sc = torch.as_tensor(scale, dtype=torch.float32).reshape(-1, 4)
-    sc = (sc.expand(B, 4) if sc.shape[0] == 1 else sc).contiguous().to(dev)
+    a, b, sc, sd = _prepare(m0, m1, scale, seeds)
+    dev, B, K = a.device, a.shape[0], a.shape[1]
     k0 = torch.as_tensor(K0).detach().cpu().numpy()
     k1 = torch.as_tensor(K1).detach().cpu().numpy()
     f32 = k0.dtype == np.float32 and k1.dtype == np.float32         # numpy keeps float32 keypoints / float32 K in float32 (AUC.py:44-48)
@@ -88,7 +80,7 @@ def estimate_pose(m0, m1, scale, K0, K1, thresh=1.0, conf=0.99999, k_dev=None, s
     good = torch.zeros((B,), dtype=torch.int32, device=dev)
     ctx = Context.get(dev)
     ctx.check(ctx.lib.kpb_find_essential(ctx.handle, ptr(a), a.shape[2], ptr(b), b.shape[2], B, K, ptr(k_dev), ptr(sc), ptr(cam_d), 1 if f32 else 0, ptr(thr_d),
-                                         ptr(_seeds(seeds, B, dev)), ctypes.c_uint32(int(seed) & 0xFFFFFFFF), float(conf), int(max_iters), ptr(E),
+                                         ptr(sd), ctypes.c_uint32(int(seed) & 0xFFFFFFFF), float(conf), int(max_iters), ptr(E),
                                          ptr(mask), ptr(info), ptr(pts)))
     if recover_all:
         mask.fill_(1)
@@ -100,22 +92,14 @@ def find_fundamental(m0, m1, scale, k_dev=None, seeds=None, seed=0, threshold=3.
     """cv2.findFundamentalMat(.., cv2.FM_RANSAC) for B pairs in one launch (PARITY UNPINNED, see the module docstring).
     Arguments as find_homography.  Returns (F [B, 3, 3] float64 with F[2,2] = 1, mask [B, K] uint8, info [B, 4] int32 =
     found, inliers, hypotheses, 0) on the device; found = 0 below 8 matches."""
-    a = m0.detach().to(torch.float32).contiguous()
-    b = m1.detach().to(torch.float32).contiguous()
-    if a.dim() == 2:
-        a, b = a[None], b[None]
-    if not a.is_cuda:
-        raise RuntimeError("keypoint_bench_amd needs CUDA/HIP tensors; there is no CPU path")
-    dev = a.device
-    B, K = a.shape[0], a.shape[1]
-    sc = torch.as_tensor(scale, dtype=torch.float32).to(dev).reshape(-1, 4)
-    sc = (sc.expand(B, 4) if sc.shape[0] == 1 else sc).contiguous()
+    a, b, sc, sd = _prepare(m0, m1, scale, seeds)
+    dev, B, K = a.device, a.shape[0], a.shape[1]
     F = torch.zeros((B, 3, 3), dtype=torch.float64, device=dev)
     mask = torch.zeros((B, max(K, 1)), dtype=torch.uint8, device=dev)
     info = torch.zeros((B, 4), dtype=torch.int32, device=dev)
     ctx = Context.get(dev)
     prm = RansacParams(float(threshold), float(confidence), int(max_iters), 0)
-    ctx.check(ctx.lib.kpb_find_fundamental(ctx.handle, ptr(a), a.shape[2], ptr(b), b.shape[2], B, K, ptr(k_dev), ptr(sc), ptr(_seeds(seeds, B, dev)),
+    ctx.check(ctx.lib.kpb_find_fundamental(ctx.handle, ptr(a), a.shape[2], ptr(b), b.shape[2], B, K, ptr(k_dev), ptr(sc), ptr(sd),
                                            ctypes.c_uint32(int(seed) & 0xFFFFFFFF), ctypes.byref(prm), ptr(F), ptr(mask), ptr(info)))
     return F, mask[:, :K], info
 

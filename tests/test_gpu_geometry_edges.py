@@ -19,17 +19,20 @@ mask, which utils/mvg.estimate_pose does not hand out, are fetched for group B b
 
 Why every case terminates (read from csrc/geometry.hip before the first run):
   * gen_round (thread 0) makes 256 subsets per round; a subset costs at most GETSUBSET_ATTEMPTS = 10 000 whole redraws (1 000 in the
-    least-median branch), after which `alive` turns false and the rest of the round, and every later round, draws nothing.  An index
+    least-median branch: the registrator rule's ATTEMPTS), after which `alive` turns false and the rest of the round, and every later round, draws nothing.  An index
     is redrawn `do .. while (dup)` until it differs from the i < M earlier ones: every case has n >= M (asserted on the CPU), so at least
     n - M + 1 of the n residues end the loop, and the draws are cv::RNG's integer stream -- the one the oracle consumes and returns from.
     Worst case here: all 10 000 attempts of the first subset (40 collinear points, 12 / 20 / 50 copies of one point), about 10 000 x (7 draws
     + 30 collinearity tests) operations of one lane: milliseconds.
-  * the round loop advances base by 256 and goes on only while base < niters; niters starts at max_iters and RANSACUpdateNumIters never
+  * the round loop (search for the essential and the fundamental matrix and its least-median branch, ransac_homography's own copy of it)
+    advances base by 256 and goes on only while base < niters; niters starts at max_iters and RANSACUpdateNumIters never
     raises it (it returns at most the value it was given): at most ceil(max_iters / 256) rounds, 8 for the homography (2 000), 4 for the
     other two (1 000), 2 in the least-median branch (300).  scan_round stops earlier at it >= niters or at the first dead subset.
   * a hypothesis is straight-line code: Gauss-Jordan on fixed sizes, 40 Aberth sweeps and 3 Newton steps, a closed-form cubic; the refit
     is at most 10 x 6 Levenberg-Marquardt solves and recoverPose at most 30 Jacobi sweeps.  Every __syncthreads() sits on a branch taken
-    from n, a kernel argument or a value thread 0 left in LDS before the preceding barrier: the same for all 256 threads.
+    from n, a kernel argument or a value thread 0 left in LDS before the preceding barrier: the same for all 256 threads.  The shared
+    helpers keep to it: load_matches ends in its barrier with no return before it, search leaves its loop on ctl, read between two barriers,
+    and returns the same `have` to every thread, and the kernels' early returns (n < M, nothing kept) follow from n and that value.
   * memory: points are read for i < n <= K only (the NaN rows never), s_idx holds indices < n, mask is written for i < K, the dynamic LDS is
     16 or 32 bytes x K <= 13 KB.
 
@@ -54,7 +57,8 @@ Moved from group A to group B after the first run (the reasons, with their figur
     Both have 8 inliers.  The hard scene's max_iters = 1 case (ends_e_1) stays in group A and agrees.
   * e_n5, e_n6: counts, masks and recoverPose's count agree; R, t differ from the oracle's by 5.06e-3 on a sample where one ulp on the input moves the
     oracle's own answer by 7.6e-4 .. 2.9e-2.
-With K0 / K1 swapped in utils/mvg.estimate_pose and sc[0] / sc[2] swapped in ransac_fundamental, test_two_cameras (both) and
+With K0 / K1 swapped in utils/mvg.estimate_pose and sc[0] / sc[2] swapped in ransac_fundamental (the scaling has since moved to load_matches,
+which it shares with ransac_essential), test_two_cameras (both) and
 test_two_image_sizes_homography_and_fundamental fail; with `it > st.niters` in scan_round, 28 of the 41 tests fail, every test_round_ends case but 256 among them.
 """
 import ctypes
