@@ -332,7 +332,8 @@ int kpb_preprocess(kpb_ctx* ctx, const uint8_t* src_dev, int batch, int Hs, int 
 /* ---- N1..: extractor networks (models/ALike.py:136-164 ALNet.forward, ...) ---------------------
  * arch: KPB_ARCH_*.  blob: a .kpbw container (keypoint_bench_amd/weights.py) holding the folded
  * tensors; copied, the caller may free it. */
-#define KPB_ARCH_ALIKE 1        /* models/ALike.py      ALNet (ALIKE-t channel plan), BN folded */
+#define KPB_ARCH_ALIKE 1        /* models/ALike.py      ALNet, BN folded; the plan is read from the blob's tensor shapes: ALIKE-t (c1..c4 = 8,16,32,64, dim 64)
+                                 * or ALIKE-l, the reference's default (32,64,128,128, dim 128); H, W multiples of 32; desc_out_dev NULL = keypoint-only */
 #define KPB_ARCH_SUPERPOINT 2   /* models/SuperPoint.py SuperPointNet, tensors named as its state_dict */
 #define KPB_ARCH_XFEAT 3        /* models/XFeat.py      XFeatModel, BN folded */
 #define KPB_ARCH_DISK 4         /* models/disk.py       DISK (thin U-Net, 5x5), H, W multiples of 16, not 16 x 16 (a 1 x 1 bottleneck has no instance norm) */

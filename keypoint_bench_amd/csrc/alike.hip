@@ -2579,6 +2579,9 @@ void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
 
 int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
+    // the plan is read from the blob: a 129 x 128 head is ALIKE-l's (c1..c4 = 32,64,128,128, dim = 128: alike_l.hip checks the trunk against it); everything else
+    // is held against ALIKE-t here
+    if (bl.get("head.w", {129, 128})) return alike_l_create(ctx, bl, out);
     if (const char* n = first_missing(bl, {{"head.w", {dim + 1, dim}}}))
         return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not ALIKE-t shaped "
                         "(this build supports c1..c4 = 8,16,32,64, dim = 64)", n);

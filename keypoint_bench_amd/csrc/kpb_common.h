@@ -178,7 +178,8 @@ struct kpb_ctx {
     int detect_signed = 0;                          // KPB_OPT_DETECT_SIGNED
     int sfd2_probe = 0;                             // KPB_OPT_SFD2_PROBE
 };
-enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u, KPB_ATTR_NMS_ROUND = 16u, KPB_ATTR_SELECT = 32u };
+enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u, KPB_ATTR_NMS_ROUND = 16u, KPB_ATTR_SELECT = 32u,
+       KPB_ATTR_ALIKE_L_HEAD = 64u };
 
 extern char g_kpb_err[512];
 

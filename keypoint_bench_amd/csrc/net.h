@@ -106,7 +106,8 @@ struct WeightStage {
 // (what the conv_mfma networks lend each other -- Layer, stage_layer, launch_mfma, launch_l2norm_nhwc -- is declared in conv_layer.h)
 
 // factories, one per architecture
-int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
+int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);         // ALIKE-t; hands a blob whose head.w is 129 x 128 to alike_l_create
+int alike_l_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);       // ALIKE-l (alike_l.hip)
 int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);
 int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out);

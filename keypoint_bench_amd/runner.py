@@ -43,8 +43,9 @@ def load_config(path):
 _NOT_SHIPPED = " (it is not shipped with the reference tree either)"
 # model_type -> (module under models/, constructor from (module, its params, dense_descriptors), params key, sub-key of the checkpoint that holds
 # the state dict, what follows "checkpoint %r not found").  No constructor: the checkpoint names its own (model_interface.py:69-73, from_checkpoint).
-# No text: the checkpoint shipped with the package (folded from the reference's weights/alike-t.pth) stands in for a missing file.
-_MODELS = {"Alike": ("ALike", lambda m, p, dense: m.ALNet(p, dense_descriptors=dense), "Alike_params", None, None),
+# No text: the checkpoint shipped with the package (folded from the reference's weights/alike-t.pth) stands in for a missing file -- for ALIKE-t; Alike_params of
+# the reference's default plan (ALIKE-l: c1..c4 = 32,64,128,128, dim 128, or no plan keys at all) build the ALIKE-l net, which needs its checkpoint.
+_MODELS = {"Alike": ("ALike", lambda m, p, dense: m.ALNet(p if "c1" in p else None, dense_descriptors=dense), "Alike_params", None, None),
            "SuperPoint": ("SuperPoint", lambda m, p, dense: m.SuperPointNet(), "SuperPoint_params", None, _NOT_SHIPPED),
            "XFeat": ("XFeat", lambda m, p, dense: m.XFeatModel(), "XFeat_params", None, _NOT_SHIPPED),
            "DISK": ("disk", lambda m, p, dense: m.DISK(), "DISK_params", "extractor", _NOT_SHIPPED),
@@ -89,6 +90,8 @@ def build_model(params, dense_descriptors=True):
         else:
             net.load_state_dict(sd[sub] if sub else sd)
     elif missing is None:
+        if mt == "Alike" and net.dim != 64:      # the packaged checkpoint is ALIKE-t's; the reference ships none for its default plan (ALIKE-l)
+            raise FileNotFoundError("Alike checkpoint %r not found: the packaged checkpoint is ALIKE-t's (dim 64), and ALIKE-l%s" % (w, _NOT_SHIPPED))
         net.load_packed(mod.packaged_blob())
     else:
         raise FileNotFoundError("%s checkpoint %r not found%s" % (mt, w, missing))
