@@ -88,11 +88,16 @@ int kpb_sync(kpb_ctx* ctx);
  *   KPB_OPT_SFD2_PROBE         0 (default).  A test hook: with 1 or 2 an SFD2 forward stops behind the grouped 3 x 3 layer of conv4's first ResBlock and leaves channels
  *                              0..127 (1) or 128..255 (2) of that layer's output [B][H/4][W/4][256] in desc_out_dev, unnormalised; score_out_dev is not written
  *                              (tests/test_gpu_sfd2.py: groups do not leak).  Any other value is invalid.
+ *   KPB_OPT_MATCH_METRIC       KPB_METRIC_EUCLIDEAN (0, default) .. KPB_METRIC_COSINE (4): the distance kpb_match and kpb_match_ratio compute from then on (M2 below).
+ *                              The launches of a call are chosen when it is made: a call already enqueued keeps its metric.  0 is the library of before, launch for
+ *                              launch.  Any other id, a negative one too, is KPB_E_UNSUPPORTED, refused before anything touches the device; the metric stays what it
+ *                              was, and kpb_match_counts has nothing to report until the next match.
  * Returns KPB_E_INVALID for an unknown option or a negative value. */
 #define KPB_OPT_COVIS_STORE_BYTES 1
 #define KPB_OPT_ALIKE_COARSE_FUSED 2
 #define KPB_OPT_DETECT_SIGNED 3
 #define KPB_OPT_SFD2_PROBE 4
+#define KPB_OPT_MATCH_METRIC 5
 int kpb_ctx_set_option(kpb_ctx* ctx, int option, int64_t value);
 
 /* Per-kernel timing for bench.py's roofline leg: when enabled every kernel launch is bracketed by two
@@ -142,7 +147,7 @@ int kpb_sample(kpb_ctx* ctx, const float* desc_dev, int batch, int C, int Hd, in
 /* ---- M2: skimage.feature.match_descriptors as called at utils/matcher.py:227-230 -------------
  * d0_dev [batch][max_n][C], d1_dev [batch][max_m][C] fp32; n_dev/m_dev [batch] or NULL.
  * float64 euclidean distances, argmin with first-index ties, optional cross-check, strict
- * < max_distance.  out_pairs_dev [batch][max_n][2] int32 (i, j) ascending i;
+ * < max_distance (the other cdist metrics the library carries: KPB_OPT_MATCH_METRIC, KPB_METRIC_* below).  out_pairs_dev [batch][max_n][2] int32 (i, j) ascending i;
  * out_dist_dev [batch][max_n] float64 (may be NULL); out_k_dev [batch]. */
 int kpb_match(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch, int C, int max_n,
               int max_m, const int32_t* n_dev, const int32_t* m_dev, const kpb_match_params* params,
@@ -156,6 +161,23 @@ int kpb_match(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch,
 int kpb_match_ratio(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch, int C, int max_n,
                     int max_m, const int32_t* n_dev, const int32_t* m_dev, const kpb_match_params* params, double max_ratio,
                     int32_t* out_pairs_dev, double* out_dist_dev, int32_t* out_k_dev);
+
+/* The metric argument of skimage.feature.match_descriptors (-> scipy.spatial.distance.cdist), by id: the values of KPB_OPT_MATCH_METRIC
+ * (kpb_ctx_set_option).  kpb_match and kpb_match_ratio compute the context's metric; under any but EUCLIDEAN everything after the distance is
+ * applied to the metric's VALUE: order (a NaN first, then the value ascending, then the index ascending), optional cross-check, strict
+ * value < max_distance, the ratio test best / second < max_ratio with second == 0 -> 2^-52; out_dist_dev receives the value.  With x = (double)a_i[k], y = (double)b_j[k],
+ * every operation float64, round to nearest, no FMA:
+ *   EUCLIDEAN    what kpb_match computes: sqrt of the sum below, ordered on the rooted value;
+ *   SQEUCLIDEAN  s = sum_k (x - y)(x - y), one accumulator, ascending k; the value is s (no root: sums one ulp apart that a root merges stay apart);
+ *   CITYBLOCK    s = sum_k |x - y|, one accumulator, ascending k;
+ *   CHEBYSHEV    acc = 0; ascending k: if (|x - y| > acc) acc = |x - y| (a NaN term is skipped, inf wins);
+ *   COSINE       sums in two accumulators (even k, odd k, each ascending, over k < 2 floor(C / 2); e + o; an odd C then adds its last term) of
+ *                x y, x x and y y;  c = dot / (sqrt(|a|^2) sqrt(|b|^2)), c = copysign(1, c) where |c| > 1, value 1 - c; a zero or non-finite row gives NaN. */
+#define KPB_METRIC_EUCLIDEAN 0
+#define KPB_METRIC_SQEUCLIDEAN 1
+#define KPB_METRIC_CITYBLOCK 2
+#define KPB_METRIC_CHEBYSHEV 3
+#define KPB_METRIC_COSINE 4
 
 /* Match counts of the last kpb_match / kpb_match_ratio as host integers: waits for the context's stream, then hands over what match_finalize left in
  * pinned host memory -- the `K` of skimage's `matches` array [K, 2] (utils/matcher.py:227-230) without a device read-back of its own.

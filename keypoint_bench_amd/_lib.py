@@ -35,6 +35,17 @@ class MatchParams(ctypes.Structure):
     _fields_ = [("max_distance", c_double), ("cross_check", ctypes.c_int32)]
 
 
+# brute_force_params.metric -> KPB_METRIC_* of include/kpb.h: the canonical cdist names only (scipy's aliases are not carried)
+METRICS = {"euclidean": 0, "sqeuclidean": 1, "cityblock": 2, "chebyshev": 3, "cosine": 4}
+
+
+def metric_id(metric):
+    """The KPB_METRIC_* id of a brute_force_params metric name; anything but the five canonical names is refused."""
+    if not isinstance(metric, str) or metric not in METRICS:
+        raise NotImplementedError("metric=%r: the supported metrics are %s (config/config_MHA.yaml:83)" % (metric, ", ".join(sorted(METRICS, key=METRICS.get))))
+    return METRICS[metric]
+
+
 # name -> (restype, argtypes); mirrors include/kpb.h one to one (tests check the export list)
 SIGNATURES = {
     "kpb_version": (c_int, []),
@@ -170,12 +181,15 @@ class Context:
     OPT_ALIKE_COARSE_FUSED = 2      # KPB_OPT_ALIKE_COARSE_FUSED
     OPT_DETECT_SIGNED = 3           # KPB_OPT_DETECT_SIGNED
     OPT_SFD2_PROBE = 4              # KPB_OPT_SFD2_PROBE (a test hook)
+    OPT_MATCH_METRIC = 5            # KPB_OPT_MATCH_METRIC (a KPB_METRIC_* id: METRICS above)
 
     def set_option(self, option: int, value: int):
         """kpb_ctx_set_option (include/kpb.h): a limit of this context, e.g. OPT_COVIS_STORE_BYTES."""
         self.check(self.lib.kpb_ctx_set_option(self.handle, int(option), int(value)))
         if int(option) == self.OPT_DETECT_SIGNED:
             self._detect_signed = int(value)
+        if int(option) == self.OPT_MATCH_METRIC:
+            self._match_metric = int(value)
 
     _detect_signed = 0      # what OPT_DETECT_SIGNED was last set to (the library has no getter)
 
@@ -191,6 +205,21 @@ class Context:
         finally:
             if self._detect_signed != before:
                 self.set_option(self.OPT_DETECT_SIGNED, before)
+
+    _match_metric = 0       # what OPT_MATCH_METRIC was last set to
+
+    @contextlib.contextmanager
+    def match_metric(self, metric: int):
+        """OPT_MATCH_METRIC = metric (a KPB_METRIC_* id) for the kpb_match / kpb_match_ratio calls inside the block; what was set before comes back
+        afterwards, also on an exception.  While both are the same -- euclidean under the default -- the option is not touched."""
+        before = self._match_metric
+        if int(metric) != before:
+            self.set_option(self.OPT_MATCH_METRIC, metric)
+        try:
+            yield self
+        finally:
+            if self._match_metric != before:
+                self.set_option(self.OPT_MATCH_METRIC, before)
 
     def prof_enable(self, on: bool):
         self.check(self.lib.kpb_prof_enable(self.handle, 1 if on else 0))

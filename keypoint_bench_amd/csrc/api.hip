@@ -56,6 +56,14 @@ extern "C" __attribute__((visibility("default"))) int kpb_ctx_set_stream(kpb_ctx
 extern "C" __attribute__((visibility("default"))) int kpb_ctx_set_option(kpb_ctx* ctx, int option, int64_t value)
 {
     if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_ctx_set_option: null context");
+    if (option == KPB_OPT_MATCH_METRIC) {       // an id, not a size: an unknown one (a negative one too) is a request the kernels do not carry
+        if (value < KPB_METRIC_EUCLIDEAN || value > KPB_METRIC_COSINE) {
+            ctx->match_counts_valid = 0;        // the refused request leaves no match whose counts could be read
+            return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_ctx_set_option: unknown metric id %lld (KPB_METRIC_EUCLIDEAN .. KPB_METRIC_COSINE)", (long long)value);
+        }
+        ctx->match_metric = (int)value;
+        return KPB_OK;
+    }
     if (value < 0) return kpb_fail(ctx, KPB_E_INVALID, "kpb_ctx_set_option: negative value");
     switch (option) {
     case KPB_OPT_COVIS_STORE_BYTES: ctx->covis_store_bytes = (size_t)value; return KPB_OK;

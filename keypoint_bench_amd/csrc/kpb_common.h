@@ -177,6 +177,7 @@ struct kpb_ctx {
     int alike_coarse_fused = 1;                     // KPB_OPT_ALIKE_COARSE_FUSED
     int detect_signed = 0;                          // KPB_OPT_DETECT_SIGNED
     int sfd2_probe = 0;                             // KPB_OPT_SFD2_PROBE
+    int match_metric = 0;                           // KPB_OPT_MATCH_METRIC: a KPB_METRIC_* id, checked when it is set
 };
 enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u, KPB_ATTR_NMS_ROUND = 16u, KPB_ATTR_SELECT = 32u,
        KPB_ATTR_ALIKE_L_HEAD = 64u };

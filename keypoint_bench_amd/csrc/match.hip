@@ -82,6 +82,37 @@ __device__ __forceinline__ bool precedes(double s1, int i1, double s2, int i2)
     return s1 < s2;
 }
 
+// The metrics of KPB_OPT_MATCH_METRIC (KPB_METRIC_* of kpb.h).  Euclidean keeps its sum in the slots and is ordered on the rooted sum (above);
+// every other metric keeps its VALUE in the slots and is ordered on it: a NaN first, then the value ascending, then the index ascending.
+constexpr int MET_EUCLIDEAN = 0, MET_SQEUCLIDEAN = 1, MET_CITYBLOCK = 2, MET_CHEBYSHEV = 3, MET_COSINE = 4;
+__device__ __forceinline__ bool precedes_value(double s1, int i1, double s2, int i2)
+{
+    if (s1 == s2) return i1 < i2;
+    const bool n1 = s1 != s1, n2 = s2 != s2;
+    if (n1 | n2) return n1 && (!n2 || i1 < i2);
+    return s1 < s2;
+}
+template <bool ROOT>
+__device__ __forceinline__ bool precedes_as(double s1, int i1, double s2, int i2)
+{
+    if (ROOT) return precedes(s1, i1, s2, i2);
+    return precedes_value(s1, i1, s2, i2);
+}
+
+// scipy's cosine sum: even k into one accumulator, odd k into another, each ascending, over k < 2 floor(C / 2); e + o; an odd C adds its last
+// term to that.  The x86-64 wheel's loop runs these two lanes, and a single accumulator differs from it from C = 32 on.
+struct Lanes2 {
+    double e, o;
+};
+// the value of a pair from its three sums: c = dot / (|a| |b|), clipped to [-1, 1] where rounding left it outside, 1 - c; a zero or
+// non-finite row leaves NaN (0 / 0, inf / inf), as scipy has it
+__device__ __forceinline__ double cosine_value(double dot, double a2, double b2)
+{
+    double c = __ddiv_rn(dot, __dmul_rn(sqrt(a2), sqrt(b2)));
+    if (fabs(c) > 1.0) c = copysign(1.0, c);
+    return __dsub_rn(1.0, c);
+}
+
 constexpr int TM = 4, TN = 8;                                 // distances per thread: TM rows x TN columns
 constexpr int MTI = 16 * TM, MTJ = 16 * TN, KC = 16, MATCH_THREADS = 256;
 
@@ -108,9 +139,13 @@ __host__ __device__ constexpr int row_depth(int tiles_j) { return 2 * tiles_j > 
 #define COLJ(c, q) (2 * (c) + 32 * ((q) >> 1) + ((q) & 1))
 // RATIO: the tile hands over its two best (sum, column) per row, in slots 2 tj and 2 tj + 1 (the second one empty -- column INT_MAX -- in a
 // tile of one valid column); the k loop is the same, the extra compares are in the epilogue.
-template <bool RATIO>
+// METRIC: the k loop's three instructions are the metric's own (sqeuclidean: euclidean's; cityblock: subtract, |.|, add; chebyshev: subtract,
+// |.|, fmax, which skips a NaN term).  Cosine accumulates the dot product in two lanes per entry and the squared norms of the thread's
+// TM rows and TN columns beside it, in the same k loop; the epilogue below turns the three sums into the value the slots hold.
+template <bool RATIO, int METRIC = MET_EUCLIDEAN>
 __global__ __launch_bounds__(MATCH_THREADS) void match_tile(MatchArgs a)
 {
+    constexpr bool ROOT = METRIC == MET_EUCLIDEAN, COS = METRIC == MET_COSINE;
     constexpr int PA = MTI + 2, PB = MTJ + 2;                             // padded pitches (doubles)
     constexpr int STAGE = KC * (PA + PB) * 2, RED = 16 * MTJ * 3;         // words: operand tiles / column-minimum exchange
     __shared__ __attribute__((aligned(16))) unsigned smem[STAGE > RED ? STAGE : RED];
@@ -129,6 +164,18 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_tile(MatchArgs a)
     for (int p = 0; p < TM; ++p)
 #pragma unroll
         for (int q = 0; q < TN; ++q) acc[p][q] = 0.0;
+    double acco[COS ? TM : 1][COS ? TN : 1];        // COS: acc is the even lane of the dot product, acco the odd one
+    Lanes2 an[COS ? TM : 1], bn[COS ? TN : 1];      // COS: the squared norms of this thread's rows and columns
+    if (COS) {
+#pragma unroll
+        for (int p = 0; p < TM; ++p) {
+            an[COS ? p : 0] = Lanes2{0.0, 0.0};
+#pragma unroll
+            for (int q = 0; q < TN; ++q) acco[COS ? p : 0][COS ? q : 0] = 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < TN; ++q) bn[COS ? q : 0] = Lanes2{0.0, 0.0};
+    }
 
     const bool vec = (a.C % 4) == 0;
     for (int k0 = 0; k0 < a.C; k0 += KC) {
@@ -154,21 +201,83 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_tile(MatchArgs a)
         }
         __syncthreads();
         const int kend = min(KC, a.C - k0);
-        for (int k = 0; k < kend; ++k) {
-            double av[TM], bv[TN];
+        if (COS) {
+            // k0 and KC are even, so the parity of k is the parity of the channel: k into the even lane, k + 1 into the odd one
+            for (int k = 0; k + 1 < kend; k += 2) {
+                double av[TM], bv[TN], aw[TM], bw[TN];
 #pragma unroll
-            for (int p = 0; p < TM; ++p) av[p] = A[k][TM * r + p];
+                for (int p = 0; p < TM; ++p) { av[p] = A[k][TM * r + p]; aw[p] = A[k + 1][TM * r + p]; }
 #pragma unroll
-            for (int q = 0; q < TN; ++q) bv[q] = Bt[k][COLJ(c, q)];
+                for (int q = 0; q < TN; ++q) { bv[q] = Bt[k][COLJ(c, q)]; bw[q] = Bt[k + 1][COLJ(c, q)]; }
 #pragma unroll
-            for (int p = 0; p < TM; ++p)
+                for (int p = 0; p < TM; ++p) {
+                    an[COS ? p : 0].e = __dadd_rn(an[COS ? p : 0].e, __dmul_rn(av[p], av[p]));
+                    an[COS ? p : 0].o = __dadd_rn(an[COS ? p : 0].o, __dmul_rn(aw[p], aw[p]));
+                }
 #pragma unroll
                 for (int q = 0; q < TN; ++q) {
-                    const double d = __dsub_rn(av[p], bv[q]);
-                    acc[p][q] = __dadd_rn(acc[p][q], __dmul_rn(d, d));   // no FMA: scipy's s += d*d
+                    bn[COS ? q : 0].e = __dadd_rn(bn[COS ? q : 0].e, __dmul_rn(bv[q], bv[q]));
+                    bn[COS ? q : 0].o = __dadd_rn(bn[COS ? q : 0].o, __dmul_rn(bw[q], bw[q]));
                 }
+#pragma unroll
+                for (int p = 0; p < TM; ++p)
+#pragma unroll
+                    for (int q = 0; q < TN; ++q) {
+                        acc[p][q] = __dadd_rn(acc[p][q], __dmul_rn(av[p], bv[q]));       // the product rounded, then added: no FMA
+                        acco[COS ? p : 0][COS ? q : 0] = __dadd_rn(acco[COS ? p : 0][COS ? q : 0], __dmul_rn(aw[p], bw[q]));
+                    }
+            }
+            if (kend & 1) {         // an odd C, in its last chunk: e + o, then the last term (nothing is added after it)
+                const int k = kend - 1;
+                double av[TM], bv[TN];
+#pragma unroll
+                for (int p = 0; p < TM; ++p) av[p] = A[k][TM * r + p];
+#pragma unroll
+                for (int q = 0; q < TN; ++q) bv[q] = Bt[k][COLJ(c, q)];
+#pragma unroll
+                for (int p = 0; p < TM; ++p)
+                    an[COS ? p : 0].e = __dadd_rn(__dadd_rn(an[COS ? p : 0].e, an[COS ? p : 0].o), __dmul_rn(av[p], av[p]));
+#pragma unroll
+                for (int q = 0; q < TN; ++q)
+                    bn[COS ? q : 0].e = __dadd_rn(__dadd_rn(bn[COS ? q : 0].e, bn[COS ? q : 0].o), __dmul_rn(bv[q], bv[q]));
+#pragma unroll
+                for (int p = 0; p < TM; ++p)
+#pragma unroll
+                    for (int q = 0; q < TN; ++q)
+                        acc[p][q] = __dadd_rn(__dadd_rn(acc[p][q], acco[COS ? p : 0][COS ? q : 0]), __dmul_rn(av[p], bv[q]));
+            }
+        } else {
+            for (int k = 0; k < kend; ++k) {
+                double av[TM], bv[TN];
+#pragma unroll
+                for (int p = 0; p < TM; ++p) av[p] = A[k][TM * r + p];
+#pragma unroll
+                for (int q = 0; q < TN; ++q) bv[q] = Bt[k][COLJ(c, q)];
+#pragma unroll
+                for (int p = 0; p < TM; ++p)
+#pragma unroll
+                    for (int q = 0; q < TN; ++q) {
+                        const double d = __dsub_rn(av[p], bv[q]);
+                        if (METRIC == MET_CITYBLOCK) acc[p][q] = __dadd_rn(acc[p][q], fabs(d));
+                        else if (METRIC == MET_CHEBYSHEV) acc[p][q] = fmax(acc[p][q], fabs(d));      // if (|d| > acc) acc = |d|: a NaN term is skipped, inf wins (acc is never NaN) -- one v_max_f64
+                        else acc[p][q] = __dadd_rn(acc[p][q], __dmul_rn(d, d));   // no FMA: scipy's s += d*d
+                    }
+            }
         }
         __syncthreads();
+    }
+    if (COS) {              // the three sums -> the value; an even C still has its two lanes to add
+        const bool odd = a.C & 1;
+        double a2[TM], b2[TN];
+#pragma unroll
+        for (int p = 0; p < TM; ++p) a2[p] = odd ? an[COS ? p : 0].e : __dadd_rn(an[COS ? p : 0].e, an[COS ? p : 0].o);
+#pragma unroll
+        for (int q = 0; q < TN; ++q) b2[q] = odd ? bn[COS ? q : 0].e : __dadd_rn(bn[COS ? q : 0].e, bn[COS ? q : 0].o);
+#pragma unroll
+        for (int p = 0; p < TM; ++p)
+#pragma unroll
+            for (int q = 0; q < TN; ++q)
+                acc[p][q] = cosine_value(odd ? acc[p][q] : __dadd_rn(acc[p][q], acco[COS ? p : 0][COS ? q : 0]), a2[p], b2[q]);
     }
 
     // row minima over this tile's columns: TN local columns, then the 16 lanes that share r
@@ -183,10 +292,10 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_tile(MatchArgs a)
         for (int q = 0; q < TN; ++q) {
             const int j = j0 + COLJ(c, q);
             if (j < m) {
-                if (precedes(acc[p][q], j, bs, bj)) {
+                if (precedes_as<ROOT>(acc[p][q], j, bs, bj)) {
                     if (RATIO) { ss = bs; sj = bj; }
                     bs = acc[p][q]; bj = j;
-                } else if (RATIO && precedes(acc[p][q], j, ss, sj)) { ss = acc[p][q]; sj = j; }
+                } else if (RATIO && precedes_as<ROOT>(acc[p][q], j, ss, sj)) { ss = acc[p][q]; sj = j; }
             }
         }
 #pragma unroll
@@ -196,11 +305,11 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_tile(MatchArgs a)
             if (RATIO) {
                 const double os2 = __shfl_xor(ss, d, 64);
                 const int oj2 = __shfl_xor(sj, d, 64);
-                if (precedes(os, oj, bs, bj)) {           // the other best leads: the runner-up is this best or the other runner-up
-                    if (precedes(os2, oj2, bs, bj)) { ss = os2; sj = oj2; } else { ss = bs; sj = bj; }
+                if (precedes_as<ROOT>(os, oj, bs, bj)) {           // the other best leads: the runner-up is this best or the other runner-up
+                    if (precedes_as<ROOT>(os2, oj2, bs, bj)) { ss = os2; sj = oj2; } else { ss = bs; sj = bj; }
                     bs = os; bj = oj;
-                } else if (precedes(os, oj, ss, sj)) { ss = os; sj = oj; }
-            } else if (precedes(os, oj, bs, bj)) { bs = os; bj = oj; }
+                } else if (precedes_as<ROOT>(os, oj, ss, sj)) { ss = os; sj = oj; }
+            } else if (precedes_as<ROOT>(os, oj, bs, bj)) { bs = os; bj = oj; }
         }
         const int i = i0 + TM * r + p;
         if ((lane & 15) == 0 && i < n) {
@@ -220,7 +329,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_tile(MatchArgs a)
 #pragma unroll
         for (int p = 0; p < TM; ++p) {
             const int i = i0 + TM * r + p;
-            if (i < n && precedes(acc[p][q], i, bs, bi)) { bs = acc[p][q]; bi = i; }
+            if (i < n && precedes_as<ROOT>(acc[p][q], i, bs, bi)) { bs = acc[p][q]; bi = i; }
         }
         cs[r][COLJ(c, q)] = bs; ci[r][COLJ(c, q)] = bi;
     }
@@ -228,7 +337,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_tile(MatchArgs a)
     if (tid < MTJ) {
         double bs = cs[0][tid]; int bi = ci[0][tid];
         for (int g = 1; g < 16; ++g)
-            if (precedes(cs[g][tid], ci[g][tid], bs, bi)) { bs = cs[g][tid]; bi = ci[g][tid]; }
+            if (precedes_as<ROOT>(cs[g][tid], ci[g][tid], bs, bi)) { bs = cs[g][tid]; bi = ci[g][tid]; }
         const int j = j0 + tid;
         if (j < m) {
             const size_t o = ((size_t)b * a.tiles_i + ti) * a.max_m + j;
@@ -254,7 +363,8 @@ struct FinArgs {
 // that precedes all the others once the best is taken out (numpy's argmin after D[i, j*] = inf: the first NaN wins, then the smallest
 // rooted value), 0 becomes eps, and the row is kept when best / second < max_ratio in float64 (a NaN ratio -- inf / inf, a NaN distance --
 // compares false and drops the row; m = 1 leaves second = inf and ratio 0).
-template <bool RATIO>
+// ROOT: the slots hold euclidean's sums (ordered and reported as their roots); otherwise they hold the metric's value itself.
+template <bool RATIO, bool ROOT = true>
 __global__ __launch_bounds__(FIN_THREADS) void match_finalize(FinArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -272,7 +382,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize(FinArgs a)
         for (int t = 0; t < tiles_i; ++t) {
             const size_t o = ((size_t)b * a.tiles_i + t) * a.max_m + j;
             const double s = a.cpart_s[o]; const int i = a.cpart_i[o];
-            if (i != 0x7FFFFFFF && precedes(s, i, bs, bi)) { bs = s; bi = i; }        // INT_MAX: an empty slot of the prefilter path
+            if (i != 0x7FFFFFFF && precedes_as<ROOT>(s, i, bs, bi)) { bs = s; bi = i; }        // INT_MAX: an empty slot of the prefilter path
         }
         colarg[j] = bi;
     }
@@ -290,9 +400,9 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize(FinArgs a)
             for (int t = 0; t < rslots; ++t) {
                 const size_t o = ((size_t)b * a.rdepth + t) * a.max_n + i;
                 const double s = a.rpart_s[o]; const int j = a.rpart_j[o];
-                if (j != 0x7FFFFFFF && precedes(s, j, bs, bj)) { bs = s; bj = j; bt = t; }
+                if (j != 0x7FFFFFFF && precedes_as<ROOT>(s, j, bs, bj)) { bs = s; bj = j; bt = t; }
             }
-            dist = sqrt(bs);
+            dist = ROOT ? sqrt(bs) : bs;
             // skimage filters on distance only `if max_distance < np.inf`: inf / nan distances survive max_distance = inf
             keep = (!a.cross_check || colarg[bj] == i) && (!(a.max_distance < __longlong_as_double(0x7FF0000000000000LL)) || dist < a.max_distance);
             if (RATIO && keep) {
@@ -301,9 +411,9 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize(FinArgs a)
                 for (int t = 0; t < rslots; ++t) {     // every slot holds another column: leaving out the best's slot leaves out the best
                     const size_t o = ((size_t)b * a.rdepth + t) * a.max_n + i;
                     const double s = a.rpart_s[o]; const int j = a.rpart_j[o];
-                    if (t != bt && j != 0x7FFFFFFF && precedes(s, j, ss, sj)) { ss = s; sj = j; }
+                    if (t != bt && j != 0x7FFFFFFF && precedes_as<ROOT>(s, j, ss, sj)) { ss = s; sj = j; }
                 }
-                double second = sqrt(ss);
+                double second = ROOT ? sqrt(ss) : ss;
                 if (second == 0.0) second = 2.220446049250313e-16;      // np.finfo(np.double).eps
                 keep = __ddiv_rn(dist, second) < a.max_ratio;
             }
@@ -354,6 +464,23 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize(FinArgs a)
 // A pair whose descriptors are not finite or reach 2^15 in magnitude (the split would saturate), or that needs more slots than
 // there are tiles (massive exact ties; with the ratio test on: more row candidates than row_depth, eight or two per column tile), raises a flag: match_tile then runs for that pair alone (it returns at once for the others) and overwrites the slots.  Results
 // are bit-identical to match_tile's by construction; tests/test_gpu_match.py checks them on the goldens and the tie / NaN cases.
+//
+// COSINE (KPB_OPT_MATCH_METRIC) runs the same four steps on c~_ij = dot~_ij / (|a_i|~ |b_j|~), D~ = max(1 - c~, 0), with the same split-f16 dot products
+// and match_prep's fp32 norms.  Error bound: an operand component is carried with |r| <= 2^-20 |x| + 2^-24 (the second term: the f16 subnormal
+// grid), the lo.lo products are dropped (<= 2^-20 |a_k b_k|), so by Cauchy-Schwarz |dot~ - dot| <= (3 x 2^-20 + 3 C 2^-24) |a||b| +
+// 2^-24 sqrt(C) (|a| + |b|), the second summand being the fp32 accumulation of 3 C products.  Relative to |a||b| -- c is a ratio -- the main
+// term is an ABSOLUTE constant in C, and the subnormal term becomes 2^-24 sqrt(C) (1/|a| + 1/|b|): it grows as the norms shrink.  The squared
+// norms are fp32 sums of C squares (<= C 2^-24 relative; their roots half of it each, C 2^-24 for the product), v_rsq_f32 is good to an ulp
+// (2 x 2^-23), two multiplies and the subtraction from 1 add 3 x 2^-24 on values <= 2.  A square below fp32's normal range would be lost
+// altogether, so a row whose squared norm is below 2^-80 hands its pair to match_tile (below); at 2^-80 what C underflowing squares can
+// lose is C 2^-46 relative.  In all
+//      |D~ - D| <= 3.4e-6 + 2.4e-7 C + 6.0e-8 sqrt(C) (1/|a| + 1/|b|)  =: delta_ij, used with a quarter to spare (cos_margin_*).
+// The margin is applied per ENTRY, not per row: L_ij = D~_ij - delta_ij <= D_ij <= D~_ij + delta_ij = U_ij.  Pass 0 keeps the minima of U;
+// pass 1 lists (i, j) as a row candidate when L_ij <= min_j' U_ij': the exact arg-minimum j* has L_ij* <= D_ij* <= D_ij' <= U_ij' for every j',
+// and so has every column tied with it.  Columns likewise.  RATIO: pass 0 keeps the second smallest U of a row by rank; the two columns that
+// hold the two smallest U have exact values <= it, so the exact second-smallest value of the row is <= it, and the column holding that
+// value has L <= it.  A row of norm ~1e-6 has a margin of ~1: every column is its candidate, the slots overflow and match_tile takes the pair,
+// as for massive exact ties at 0 (parallel vectors after the clip).
 typedef _Float16 mh8 __attribute__((ext_vector_type(8)));
 typedef float mf4 __attribute__((ext_vector_type(4)));
 constexpr unsigned INF_BITS = 0x7F800000u;
@@ -361,6 +488,10 @@ __device__ __forceinline__ float match_margin(float na, float nb, int C)
 {
     return (7.5e-6f + 6.0e-7f * (float)C) * (na + nb) + 5.0e-6f * (sqrtf(na) + sqrtf(nb));
 }
+
+__device__ __forceinline__ float cos_margin_const(int C) { return 4.3e-6f + 3.0e-7f * (float)C; }
+__device__ __forceinline__ float cos_margin_scale(int C) { return 7.5e-8f * sqrtf((float)C); }      // times 1/|a| + 1/|b|
+constexpr float COS_MIN_NORM2 = 8.271806e-25f;      // 2^-80
 
 struct PreArgs {
     const float* d0; const float* d1; const int* n; const int* m;
@@ -374,6 +505,8 @@ struct PreArgs {
     unsigned* nmax;                  // [B][2] largest squared norm of either side (float bits; zeroed by the host)
 };
 
+// COS: a row whose squared norm is below 2^-80 (a zero row, whose cosine is NaN, among them) raises the pair's flag too.
+template <bool COS>
 __global__ __launch_bounds__(256) void match_prep(PreArgs a)
 {
     // eight lanes per descriptor row: lane q takes the 8-float pieces q, q + 8, ... (coalesced 32-byte loads, 16-byte stores)
@@ -416,7 +549,7 @@ __global__ __launch_bounds__(256) void match_prep(PreArgs a)
     // the whole pair to the exact kernel, like a non-finite one.
     if (row < cnt && big >= 32768.0f) a.flag[b] = 1;
     if (row < cnt && q == 0) {
-        if (!(nn < 3.0e38f)) a.flag[b] = 1;             // NaN / inf / overflow: the exact kernel takes this pair
+        if (!(nn < 3.0e38f) || (COS && nn < COS_MIN_NORM2)) a.flag[b] = 1;             // NaN / inf / overflow: the exact kernel takes this pair
         else atomicMax(&s_max[second ? 1 : 0], __float_as_uint(nn));
     }
     if (q == 0) {
@@ -441,7 +574,9 @@ constexpr int CBUF = 192;       // candidates a wave collects in LDS before it r
 
 // RATIO (PASS 0 only): a.rowmin receives the row's SECOND smallest approximate distance by rank (a tie counts twice; +inf for m = 1), so
 // that PASS 1 -- the same code -- lists the row's candidates against rowmin2_i + mr_i.
-template <int KB, int RT, int PASS, bool RATIO = false>
+// COS: the entry is D~ = max(1 - dot~ / (|a|~ |b|~), 0); pass 0 takes the minima of D~ + delta_ij, pass 1 lists what has D~ - delta_ij at or below
+// them (see above): na holds 1 / |a_i|~ and da the row's share of delta_ij.
+template <int KB, int RT, int PASS, bool RATIO = false, bool COS = false>
 __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
 {
     static_assert(PASS == 0 || !RATIO, "the candidate pass is the same with the ratio test on");
@@ -469,6 +604,8 @@ __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
     const uint4* Bm = a.h1 + (size_t)b * a.max_m * a.P8;
     mh8 ah[RT][KB], al[RT][KB];
     float na[RT][4];
+    float da[COS ? RT : 1][4];
+    const float mconst = COS ? cos_margin_const(a.C) : 0.0f, mscale = COS ? cos_margin_scale(a.C) : 0.0f;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
         const int row = min(i0 + 16 * rt + c16, n - 1);      // A operand: lane (row c16, k-group g)
@@ -481,6 +618,10 @@ __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
         for (int r = 0; r < 4; ++r) {                         // D rows of this lane: 4 g + r
             const int i = i0 + 16 * rt + 4 * g + r;
             na[rt][r] = i < n ? a.nrm0[(size_t)b * a.max_n + i] : __uint_as_float(INF_BITS);
+            if (COS) {          // (an unflagged pair: every squared norm of its rows lies in [2^-80, 3e38))
+                na[rt][r] = i < n ? __builtin_amdgcn_rsqf(na[rt][r]) : 0.0f;
+                da[COS ? rt : 0][r] = i < n ? mconst + mscale * na[rt][r] : __uint_as_float(INF_BITS);
+            }
         }
     }
     const float namax = __uint_as_float(a.nmax[2 * b]), nbmax = __uint_as_float(a.nmax[2 * b + 1]);
@@ -496,7 +637,7 @@ __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) rmin[rt][r] = PASS == 0 ? __uint_as_float(INF_BITS)
-                                                             : (i0 + 16 * rt + 4 * g + r < n ? __uint_as_float(a.rowmin[(size_t)b * a.max_n + i0 + 16 * rt + 4 * g + r]) + match_margin(na[rt][r], nbmax, a.C) : -1.0f);
+                                                             : (i0 + 16 * rt + 4 * g + r < n ? __uint_as_float(a.rowmin[(size_t)b * a.max_n + i0 + 16 * rt + 4 * g + r]) + (COS ? 0.0f : match_margin(na[rt][r], nbmax, a.C)) : -1.0f);
     for (int j0 = 0; j0 < m; j0 += 16) {
         const int j = j0 + c16;
         const int jr = min(j, m - 1);
@@ -506,8 +647,10 @@ __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
             bh[kb] = __builtin_bit_cast(mh8, Bm[(size_t)jr * a.P8 + 4 * kb + g]);
             bl[kb] = __builtin_bit_cast(mh8, Bm[a.lo1 + (size_t)jr * a.P8 + 4 * kb + g]);
         }
-        const float nb = j < m ? a.nrm1[(size_t)b * a.max_m + j] : __uint_as_float(INF_BITS);
-        const float cmin_j = PASS == 1 && j < m ? __uint_as_float(a.colmin[(size_t)b * a.max_m + j]) + match_margin(namax, nb, a.C) : -1.0f;     // colmin_j + mc_j
+        float nb = j < m ? a.nrm1[(size_t)b * a.max_m + j] : __uint_as_float(INF_BITS);
+        const float cmin_j = PASS == 1 && j < m ? __uint_as_float(a.colmin[(size_t)b * a.max_m + j]) + (COS ? 0.0f : match_margin(namax, nb, a.C)) : -1.0f;     // colmin_j + mc_j
+        float db = 0.0f;            // COS: the column's share of delta_ij
+        if (COS) { nb = j < m ? __builtin_amdgcn_rsqf(nb) : 0.0f; db = j < m ? mscale * nb : __uint_as_float(INF_BITS); }
         float cm = __uint_as_float(INF_BITS);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
@@ -521,7 +664,12 @@ __global__ __launch_bounds__(256) void match_approx(ApxArgs a)
             float dd[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r)                       // entry (row 4 g + r of tile rt, column c16); +0 (never -0: the minima are kept as unsigned bit patterns); inf past the end
-                dd[r] = fmaxf(__fadd_rn(__fadd_rn(na[rt][r], nb), -2.0f * acc[r]), 0.0f) + 0.0f;
+                if (COS) {          // U_ij (pass 0) or L_ij (pass 1); +inf past either end
+                    const float dt = da[COS ? rt : 0][r] + db, v = fmaxf(1.0f - acc[r] * na[rt][r] * nb, 0.0f);
+                    dd[r] = dt < __uint_as_float(INF_BITS) ? (PASS == 0 ? v + dt : v - dt) : __uint_as_float(INF_BITS);
+                } else {
+                    dd[r] = fmaxf(__fadd_rn(__fadd_rn(na[rt][r], nb), -2.0f * acc[r]), 0.0f) + 0.0f;
+                }
             if (PASS == 0) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -589,6 +737,9 @@ struct ExactArgs {
 };
 
 // scipy's float64 sum (ascending k, no FMA: the same three instructions as match_tile) for the listed pairs only
+// COS: the three two-lane sums of match_tile<.., MET_COSINE> and cosine_value (C is a multiple of 32 here: no tail).  Sqeuclidean's value
+// is euclidean's sum: the <false> form serves both.
+template <bool COS>
 __global__ __launch_bounds__(256) void match_exact(ExactArgs a)
 {
     const int b = blockIdx.y;
@@ -599,12 +750,27 @@ __global__ __launch_bounds__(256) void match_exact(ExactArgs a)
     const float* pa = a.d0 + ((size_t)b * a.max_n + i) * a.C;
     const float* pb = a.d1 + ((size_t)b * a.max_m + j) * a.C;
     double s = 0.0;
-    for (int k = 0; k < a.C; k += 4) {
-        const float4 u = *reinterpret_cast<const float4*>(pa + k), v = *reinterpret_cast<const float4*>(pb + k);
-        double d = __dsub_rn((double)u.x, (double)v.x); s = __dadd_rn(s, __dmul_rn(d, d));
-        d = __dsub_rn((double)u.y, (double)v.y); s = __dadd_rn(s, __dmul_rn(d, d));
-        d = __dsub_rn((double)u.z, (double)v.z); s = __dadd_rn(s, __dmul_rn(d, d));
-        d = __dsub_rn((double)u.w, (double)v.w); s = __dadd_rn(s, __dmul_rn(d, d));
+    if (COS) {
+        Lanes2 dot{0.0, 0.0}, a2{0.0, 0.0}, b2{0.0, 0.0};
+        for (int k = 0; k < a.C; k += 4) {
+            const float4 u = *reinterpret_cast<const float4*>(pa + k), v = *reinterpret_cast<const float4*>(pb + k);
+            const double x[4] = {(double)u.x, (double)u.y, (double)u.z, (double)u.w}, y[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
+#pragma unroll
+            for (int t = 0; t < 4; t += 2) {
+                dot.e = __dadd_rn(dot.e, __dmul_rn(x[t], y[t])); dot.o = __dadd_rn(dot.o, __dmul_rn(x[t + 1], y[t + 1]));
+                a2.e = __dadd_rn(a2.e, __dmul_rn(x[t], x[t])); a2.o = __dadd_rn(a2.o, __dmul_rn(x[t + 1], x[t + 1]));
+                b2.e = __dadd_rn(b2.e, __dmul_rn(y[t], y[t])); b2.o = __dadd_rn(b2.o, __dmul_rn(y[t + 1], y[t + 1]));
+            }
+        }
+        s = cosine_value(__dadd_rn(dot.e, dot.o), __dadd_rn(a2.e, a2.o), __dadd_rn(b2.e, b2.o));
+    } else {
+        for (int k = 0; k < a.C; k += 4) {
+            const float4 u = *reinterpret_cast<const float4*>(pa + k), v = *reinterpret_cast<const float4*>(pb + k);
+            double d = __dsub_rn((double)u.x, (double)v.x); s = __dadd_rn(s, __dmul_rn(d, d));
+            d = __dsub_rn((double)u.y, (double)v.y); s = __dadd_rn(s, __dmul_rn(d, d));
+            d = __dsub_rn((double)u.z, (double)v.z); s = __dadd_rn(s, __dmul_rn(d, d));
+            d = __dsub_rn((double)u.w, (double)v.w); s = __dadd_rn(s, __dmul_rn(d, d));
+        }
     }
     const int n = a.n ? min(a.n[b], a.max_n) : a.max_n, m = a.m ? min(a.m[b], a.max_m) : a.max_m;
     const int slots_r = a.ratio ? a.rdepth : (m + MTJ - 1) / MTJ, slots_c = (n + MTI - 1) / MTI;      // what match_finalize reads for this pair
@@ -650,10 +816,13 @@ extern "C" __attribute__((visibility("default"))) int kpb_sample(kpb_ctx* ctx, c
     return KPB_OK;
 }
 
-// kpb_match and kpb_match_ratio.  ratio: max_ratio < 1, the ratio test is on; off, every launch, grid and workspace size is what kpb_match
-// has always enqueued (the <false> instantiations are that code).
+// kpb_match and kpb_match_ratio.  ratio: max_ratio < 1, the ratio test is on; off, every launch, grid and workspace size is
+// what kpb_match has always enqueued (the <false> instantiations are that code).  metric: the context's KPB_OPT_MATCH_METRIC, a KPB_METRIC_* id
+// that kpb_ctx_set_option checked; 0, the default, enqueues what these calls have always enqueued.  Sqeuclidean shares euclidean's prefilter (D~ is a squared distance already; match_exact's sum is the value);
+// cosine has a prefilter of its own on the same dot products (match_approx<.., COS>); cityblock and chebyshev have no matrix form and run
+// match_tile alone.
 static int match_impl(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch, int C, int max_n, int max_m, const int32_t* n_dev,
-                      const int32_t* m_dev, const kpb_match_params* prm, double max_ratio, int32_t* out_pairs_dev, double* out_dist_dev, int32_t* out_k_dev)
+                      const int32_t* m_dev, const kpb_match_params* prm, int metric, double max_ratio, int32_t* out_pairs_dev, double* out_dist_dev, int32_t* out_k_dev)
 {
     const bool ratio = max_ratio < 1.0;
     ctx->match_counts_valid = 0;        // set again only when everything of this call has been enqueued
@@ -688,7 +857,8 @@ static int match_impl(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, in
     static const int prefilter = kpb_env_int("KPB_MATCH_PREFILTER", 1);
     // ... and a batch that fills the chip (KPB_MATCH_PREFILTER: 0 never, 1 = default: from 8 pairs, 2 always -- the tests' way to the prefilter with one pair): for a handful of pairs the prefilter's five dependent launches are LATENCY (a single
     // 1000 x 1000 pair: 0.30 ms with it, 0.175 ms on match_tile alone -- profiles/r04_single_pair_latency.txt); both give the same bits
-    const bool pre = prefilter && (batch >= 8 || prefilter == 2) && (C % 32 == 0) && C <= 256 && tiles_i >= 2 && tiles_j >= 2 && (reinterpret_cast<uintptr_t>(d0_dev) % 16 == 0) &&
+    const bool cosine = metric == MET_COSINE;
+    const bool pre = (metric == MET_EUCLIDEAN || metric == MET_SQEUCLIDEAN || cosine) && prefilter && (batch >= 8 || prefilter == 2) && (C % 32 == 0) && C <= 256 && tiles_i >= 2 && tiles_j >= 2 && (reinterpret_cast<uintptr_t>(d0_dev) % 16 == 0) &&
                      (reinterpret_cast<uintptr_t>(d1_dev) % 16 == 0);
     const int* only = nullptr;
     if (pre) {
@@ -711,32 +881,53 @@ static int match_impl(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, in
         PreArgs pa{d0_dev, d1_dev, n_dev, m_dev, C, max_n, max_m, h0, h1, nrm0, nrm1, rowmin, colmin, rcnt, ccnt, flag, ncand, nmax};
         // empty slots are marked by the index INT_MAX (match_finalize skips them): one coalesced 32-bit fill of both index arrays
         KPB_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rj), 0x7FFFFFFF, nr + nc, ctx->stream));
-        KPB_LAUNCH(ctx, "match_prep", match_prep, dim3(cdiv(max_n + max_m, 32), batch), dim3(256), 0, ctx->stream, pa);
+        if (cosine) KPB_LAUNCH(ctx, "match_prep_cos", match_prep<true>, dim3(cdiv(max_n + max_m, 32), batch), dim3(256), 0, ctx->stream, pa);
+        else KPB_LAUNCH(ctx, "match_prep", match_prep<false>, dim3(cdiv(max_n + max_m, 32), batch), dim3(256), 0, ctx->stream, pa);
         ApxArgs xa{h0, h1, nrm0, nrm1, n_dev, m_dev, max_n, max_m, P8, nh0, nh1, rowmin, colmin, cand, ncand, cap, flag, nmax, C};
         const int KB = C / 32;
 #define KPB_APX(KB_, RT_)                                                                                                                   \
         {                                                                                                                                       \
             const dim3 grid(cdiv(max_n, 64 * RT_), batch);                                                                                      \
+            if (cosine) {                                                                                                                       \
+                if (ratio) KPB_LAUNCH(ctx, "match_approx_cos_min2", (match_approx<KB_, RT_, 0, true, true>), grid, dim3(256), 0, ctx->stream, xa); \
+                else KPB_LAUNCH(ctx, "match_approx_cos_min", (match_approx<KB_, RT_, 0, false, true>), grid, dim3(256), 0, ctx->stream, xa);     \
+                KPB_LAUNCH(ctx, "match_approx_cos_cand", (match_approx<KB_, RT_, 1, false, true>), grid, dim3(256), 0, ctx->stream, xa);        \
+            } else {                                                                                                                            \
             if (ratio) KPB_LAUNCH(ctx, "match_approx_min2", (match_approx<KB_, RT_, 0, true>), grid, dim3(256), 0, ctx->stream, xa);            \
             else KPB_LAUNCH(ctx, "match_approx_min", (match_approx<KB_, RT_, 0>), grid, dim3(256), 0, ctx->stream, xa);                         \
             KPB_LAUNCH(ctx, "match_approx_cand", (match_approx<KB_, RT_, 1>), grid, dim3(256), 0, ctx->stream, xa);                             \
+            }                                                                                                                                   \
         }
         if (KB == 1) KPB_APX(1, 4) else if (KB == 2) KPB_APX(2, 4) else if (KB == 3) KPB_APX(3, 2) else if (KB == 4) KPB_APX(4, 2)
         else if (KB == 5) KPB_APX(5, 1) else if (KB == 6) KPB_APX(6, 1) else if (KB == 7) KPB_APX(7, 1) else KPB_APX(8, 1)
 #undef KPB_APX
         ExactArgs ea{d0_dev, d1_dev, cand, ncand, cap, C, max_n, max_m, rcnt, ccnt, rs, rj, cs, ci, tiles_i, rdepth, m_dev, n_dev, flag, ratio ? 1 : 0};
-        KPB_LAUNCH(ctx, "match_exact", match_exact, dim3(cdiv(cap, 256), batch), dim3(256), 0, ctx->stream, ea);
+        if (cosine) KPB_LAUNCH(ctx, "match_exact_cos", match_exact<true>, dim3(cdiv(cap, 256), batch), dim3(256), 0, ctx->stream, ea);
+        else KPB_LAUNCH(ctx, "match_exact", match_exact<false>, dim3(cdiv(cap, 256), batch), dim3(256), 0, ctx->stream, ea);
         only = flag;
     }
     MatchArgs a{only, d0_dev, d1_dev, n_dev, m_dev, rs, rj, cs, ci, C, max_n, max_m, tiles_i, rdepth};
     FinArgs f{rs, rj, cs, ci, n_dev, m_dev, out_pairs_dev, out_dist_dev, out_k_dev, ctx->host_match,
               max_n, max_m, tiles_i, rdepth, prm->cross_check, prm->max_distance, only, max_ratio};
-    if (ratio) {
-        KPB_LAUNCH(ctx, "match_tile2", match_tile<true>, dim3(tiles_j, tiles_i, batch), dim3(MATCH_THREADS), 0, ctx->stream, a);
-        KPB_LAUNCH(ctx, "match_finalize_ratio", match_finalize<true>, dim3(batch), dim3(FIN_THREADS), (size_t)max_m * sizeof(int), ctx->stream, f);
+    const dim3 tgrid(tiles_j, tiles_i, batch);
+    const size_t fin_lds = (size_t)max_m * sizeof(int);
+#define KPB_TILE(MET_, NAME_)                                                                                                               \
+    {                                                                                                                                       \
+        if (ratio) KPB_LAUNCH(ctx, NAME_ "2", (match_tile<true, MET_>), tgrid, dim3(MATCH_THREADS), 0, ctx->stream, a);                     \
+        else KPB_LAUNCH(ctx, NAME_, (match_tile<false, MET_>), tgrid, dim3(MATCH_THREADS), 0, ctx->stream, a);                              \
+    }
+    if (metric == MET_EUCLIDEAN) KPB_TILE(MET_EUCLIDEAN, "match_tile")
+    else if (metric == MET_SQEUCLIDEAN) KPB_TILE(MET_SQEUCLIDEAN, "match_tile_sq")
+    else if (metric == MET_CITYBLOCK) KPB_TILE(MET_CITYBLOCK, "match_tile_l1")
+    else if (metric == MET_CHEBYSHEV) KPB_TILE(MET_CHEBYSHEV, "match_tile_linf")
+    else KPB_TILE(MET_COSINE, "match_tile_cos")
+#undef KPB_TILE
+    if (metric == MET_EUCLIDEAN) {
+        if (ratio) KPB_LAUNCH(ctx, "match_finalize_ratio", match_finalize<true>, dim3(batch), dim3(FIN_THREADS), fin_lds, ctx->stream, f);
+        else KPB_LAUNCH(ctx, "match_finalize", match_finalize<false>, dim3(batch), dim3(FIN_THREADS), fin_lds, ctx->stream, f);
     } else {
-        KPB_LAUNCH(ctx, "match_tile", match_tile<false>, dim3(tiles_j, tiles_i, batch), dim3(MATCH_THREADS), 0, ctx->stream, a);
-        KPB_LAUNCH(ctx, "match_finalize", match_finalize<false>, dim3(batch), dim3(FIN_THREADS), (size_t)max_m * sizeof(int), ctx->stream, f);
+        if (ratio) KPB_LAUNCH(ctx, "match_finalize_value_ratio", (match_finalize<true, false>), dim3(batch), dim3(FIN_THREADS), fin_lds, ctx->stream, f);
+        else KPB_LAUNCH(ctx, "match_finalize_value", (match_finalize<false, false>), dim3(batch), dim3(FIN_THREADS), fin_lds, ctx->stream, f);
     }
     KPB_HIP(ctx, hipGetLastError());
     ctx->match_counts_valid = 1;
@@ -748,7 +939,7 @@ extern "C" __attribute__((visibility("default"))) int kpb_match(kpb_ctx* ctx, co
                          int32_t* out_pairs_dev, double* out_dist_dev, int32_t* out_k_dev)
 {
     if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_match: null context");
-    return match_impl(ctx, d0_dev, d1_dev, batch, C, max_n, max_m, n_dev, m_dev, prm, 1.0, out_pairs_dev, out_dist_dev, out_k_dev);
+    return match_impl(ctx, d0_dev, d1_dev, batch, C, max_n, max_m, n_dev, m_dev, prm, ctx->match_metric, 1.0, out_pairs_dev, out_dist_dev, out_k_dev);
 }
 
 extern "C" __attribute__((visibility("default"))) int kpb_match_ratio(kpb_ctx* ctx, const float* d0_dev, const float* d1_dev, int batch, int C, int max_n,
@@ -760,7 +951,7 @@ extern "C" __attribute__((visibility("default"))) int kpb_match_ratio(kpb_ctx* c
         return kpb_fail(ctx, KPB_E_INVALID, "kpb_match_ratio: max_ratio is NaN");
     }
     if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_match_ratio: null context");
-    return match_impl(ctx, d0_dev, d1_dev, batch, C, max_n, max_m, n_dev, m_dev, prm, max_ratio, out_pairs_dev, out_dist_dev, out_k_dev);
+    return match_impl(ctx, d0_dev, d1_dev, batch, C, max_n, max_m, n_dev, m_dev, prm, ctx->match_metric, max_ratio, out_pairs_dev, out_dist_dev, out_k_dev);
 }
 
 extern "C" __attribute__((visibility("default"))) int kpb_match_counts(kpb_ctx* ctx, int32_t* out_k_host, int batch)

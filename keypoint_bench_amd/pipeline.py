@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from ._lib import Context, DetectParams, LgParams, MatchParams, ptr
+from ._lib import Context, DetectParams, LgParams, MatchParams, metric_id, ptr
 from .utils.matcher import match_ratio_of
 
 
@@ -35,8 +35,7 @@ class _Core:
         self.device = torch.device(device)
         self.ctx = Context.get(self.device)
         ep, bf = extractor_params, brute_force_params
-        if bf.get("metric", "euclidean") != "euclidean":
-            raise NotImplementedError("only metric='euclidean'")
+        self.metric = metric_id(bf.get("metric", "euclidean"))      # LightGlue, where one is attached, does not read it (nor does the reference's)
         self.top_k = min(int(ep["top_k"]), H * W)
         self.dprm = DetectParams(int(ep["nms_dist"]), float(ep["threshold"]), int(ep["border_dist"]), self.top_k,
                                  float(ep["min_score"]))
@@ -94,8 +93,9 @@ class _Core:
                                      ptr(self.desc), ptr(self.desc[second:]), C, Hd, Wd, Hd * Wd * C, 1, Wd * C, C, self.W, self.H,
                                      ctypes.byref(prm), ptr(self.pairs), ptr(self.lg_scores), ptr(self.k), ptr(self.lg_stop)))
         else:
-            ctx.check(L.kpb_match_ratio(ctx.handle, ptr(self.sdesc), ptr(self.sdesc[second:]), count, C, K, K, ptr(n), ptr(n[second:]),
-                                        ctypes.byref(self.mprm), self.max_ratio, ptr(self.pairs), ptr(self.dist), ptr(self.k)))
+            with ctx.match_metric(self.metric):         # KPB_OPT_MATCH_METRIC for this call; euclidean: the option is not touched, the same launches
+                ctx.check(L.kpb_match_ratio(ctx.handle, ptr(self.sdesc), ptr(self.sdesc[second:]), count, C, K, K, ptr(n), ptr(n[second:]),
+                                            ctypes.byref(self.mprm), self.max_ratio, ptr(self.pairs), ptr(self.dist), ptr(self.k)))
         ctx.check(L.kpb_gather_rows(ctx.handle, ptr(pts), count, K, cols, ptr(self.pairs), K, 2, 0, ptr(self.k), ptr(m0)))
         ctx.check(L.kpb_gather_rows(ctx.handle, ptr(pts[second:]), count, K, cols, ptr(self.pairs), K, 2, 1, ptr(self.k), ptr(m1)))
 

@@ -8,7 +8,7 @@ never from oracle/) and routes to it whatever lies outside the library's contrac
   * a score map with negative values -- models/Harris.py:13-22 returns cv2.cornerHarris responses, and the
     reference's NMS lets suppressed zeros win against negative neighbours.  The library finds this with a device-side
     flag raised by the NMS kernels themselves (KPB_E_NEGATIVE), not with a host scan of the map;
-  * arguments the kernels do not carry (fast_nms max_iter / min_value, a non-euclidean metric, nms_dist > 16, more matches
+  * arguments the kernels do not carry (fast_nms max_iter / min_value, a metric other than euclidean / sqeuclidean / cityblock / chebyshev / cosine, nms_dist > 16, more matches
     than a RANSAC kernel holds, ALIKE channel plans other than -t, DISK variants): KPB_E_UNSUPPORTED / NotImplementedError.
 
 One thing is refused instead of routed: a brute-force call whose ``brute_force_params`` carry ``max_ratio`` < 1.  The reference's own
@@ -26,7 +26,7 @@ import warnings
 
 import torch
 
-from ._lib import KpbError
+from ._lib import METRICS, KpbError
 
 KPB_E_INVALID, KPB_E_NEGATIVE, KPB_E_UNSUPPORTED = -1, -4, -7
 FALLBACK_CODES = (KPB_E_NEGATIVE, KPB_E_UNSUPPORTED)       # the whitelist: documented out-of-contract reasons only
@@ -216,7 +216,8 @@ def _c_fast_nms(image_probs, nms_dist=4, max_iter=-1, min_value=0.0):
 def _c_bf(pts0, pts1, desc_map_0, desc_map_1, params=None):
     if not _on_device(pts0, pts1):
         return "keypoints are not on a HIP device"
-    return None if (params or {}).get("metric", "euclidean") == "euclidean" else "metric"
+    metric = (params or {}).get("metric", "euclidean")
+    return None if isinstance(metric, str) and metric in METRICS else "metric"
 
 
 def _c_first(t, *a, **k):

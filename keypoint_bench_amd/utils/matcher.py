@@ -4,7 +4,7 @@ import ctypes
 
 import torch
 
-from .._lib import Context, LkParams, MatchParams, ptr
+from .._lib import Context, LkParams, MatchParams, metric_id, ptr
 
 
 def sample_descriptors(pts: torch.Tensor, desc_map, n=None) -> torch.Tensor:
@@ -37,8 +37,8 @@ def match_ratio_of(params):
     return r
 
 
-def _match32(desc0: torch.Tensor, desc1: torch.Tensor, max_distance, cross_check, want_dist=False, max_ratio=1.0):
-    """kpb_match_ratio (kpb_match itself while max_ratio >= 1) for one pair: (pairs int32 [n, 2] -- the first K rows are the matches --, dist float64 [n] or None, K device
+def _match32(desc0: torch.Tensor, desc1: torch.Tensor, max_distance, cross_check, want_dist=False, max_ratio=1.0, metric=0):
+    """kpb_match_ratio (kpb_match itself while max_ratio >= 1), under KPB_OPT_MATCH_METRIC = metric for a KPB_METRIC_* id other than euclidean's 0, for one pair: (pairs int32 [n, 2] -- the first K rows are the matches --, dist float64 [n] or None, K device
     tensor [1], K as a host integer).  K comes from pinned host memory the kernel wrote (kpb_match_counts): one stream
     synchronisation, no read-back of its own."""
     a = desc0.detach().to(torch.float32).contiguous()
@@ -50,8 +50,9 @@ def _match32(desc0: torch.Tensor, desc1: torch.Tensor, max_distance, cross_check
     dist = torch.empty((n,), dtype=torch.float64, device=dev) if want_dist else None
     k = torch.empty((1,), dtype=torch.int32, device=dev)
     prm = MatchParams(float(max_distance), 1 if cross_check else 0)
-    ctx.check(ctx.lib.kpb_match_ratio(ctx.handle, ptr(a), ptr(b), 1, a.shape[1], n, m, ptr(None), ptr(None),
-                                      ctypes.byref(prm), float(max_ratio), ptr(pairs), ptr(dist), ptr(k)))
+    with ctx.match_metric(metric):
+        ctx.check(ctx.lib.kpb_match_ratio(ctx.handle, ptr(a), ptr(b), 1, a.shape[1], n, m, ptr(None), ptr(None),
+                                          ctypes.byref(prm), float(max_ratio), ptr(pairs), ptr(dist), ptr(k)))
     kk = (ctypes.c_int32 * 1)()
     ctx.check(ctx.lib.kpb_match_counts(ctx.handle, kk, 1))
     return pairs, dist, k, int(kk[0])
@@ -60,16 +61,16 @@ def _match32(desc0: torch.Tensor, desc1: torch.Tensor, max_distance, cross_check
 def match_descriptors(desc0: torch.Tensor, desc1: torch.Tensor, metric="euclidean", max_distance=float("inf"),
                       cross_check=True, return_distance=False, max_ratio=1.0):
     """skimage.feature.match_descriptors as the reference calls it (matcher.py:227-230), on device.
+    metric: "euclidean", "sqeuclidean", "cityblock", "chebyshev" or "cosine", each scipy cdist's float64 value (include/kpb.h, KPB_OPT_MATCH_METRIC).
     Returns int64 [K, 2] (and float64 [K] distances when asked).  max_ratio < 1: skimage's ratio test on the exact float64 second nearest
     (include/kpb.h, kpb_match_ratio); 1.0 and above: off."""
-    if metric != "euclidean":
-        raise NotImplementedError("only metric='euclidean' (config/config_MHA.yaml:83)")
+    metric = metric_id(metric)
     dev = desc0.device
     max_ratio = match_ratio_of({"max_ratio": max_ratio})
     if desc0.shape[0] == 0 or desc1.shape[0] == 0:
         e = torch.zeros((0, 2), dtype=torch.int64, device=dev)
         return (e, torch.zeros((0,), dtype=torch.float64, device=dev)) if return_distance else e
-    pairs, dist, _, kk = _match32(desc0, desc1, max_distance, cross_check, want_dist=True, max_ratio=max_ratio)
+    pairs, dist, _, kk = _match32(desc0, desc1, max_distance, cross_check, want_dist=True, max_ratio=max_ratio, metric=metric)
     pairs = pairs[:kk].to(torch.int64)
     return (pairs, dist[:kk].clone()) if return_distance else pairs
 
@@ -78,15 +79,14 @@ def brute_force_matcher(pts0: torch.Tensor, pts1: torch.Tensor, desc_map_0, desc
     """utils/matcher.py:206-234.  pts0 (n, >=2), pts1 (m, >=2) in [0,1]; returns the matched rows of pts0 and
     pts1 (all columns kept), ordered by ascending index into pts0.  An optional params["max_ratio"] < 1 adds skimage's ratio test (the reference's own
     function does not read that key)."""
-    if params["metric"] != "euclidean":
-        raise NotImplementedError("only metric='euclidean' (config/config_MHA.yaml:83)")
+    metric = metric_id(params["metric"])
     max_ratio = match_ratio_of(params)
     desc0 = sample_descriptors(pts0, desc_map_0)
     desc1 = sample_descriptors(pts1, desc_map_1)
     if desc0.shape[0] == 0 or desc1.shape[0] == 0:
         return pts0[:0], pts1[:0]
     # the int32 pairs and the device count feed the row gather as they are (r03 converted to int64 and back and uploaded K again)
-    m32, _, k_dev, k = _match32(desc0, desc1, params["max_distance"], params["cross_check"], max_ratio=max_ratio)
+    m32, _, k_dev, k = _match32(desc0, desc1, params["max_distance"], params["cross_check"], max_ratio=max_ratio, metric=metric)
     if k == 0:
         return pts0[:0], pts1[:0]
     ctx = Context.get(pts0.device)

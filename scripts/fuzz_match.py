@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Random descriptor sets: kpb_match (drop-in `match_descriptors`, MFMA prefilter + exact refinement) against oracle.match,
-index pairs and float64 distances bit for bit.
-    python scripts/fuzz_match.py [cases] [seed]      (GPU box; the oracle is the checker, never the product)"""
+index pairs and float64 distances bit for bit.  --metric NAME: the same call under KPB_OPT_MATCH_METRIC on sqeuclidean, cityblock, chebyshev or cosine against the numpy
+statement of tests/match_metric_cases.py (pinned on scipy's cdist by tests/test_match_metric_cpu.py); a NaN distance is compared as a NaN.
+    python scripts/fuzz_match.py [cases] [seed] [--metric NAME]      (GPU box; the oracle is the checker, never the product)"""
 import os
 import sys
 
@@ -13,7 +14,10 @@ import torch
 import oracle
 from keypoint_bench_amd.utils.matcher import match_descriptors
 
-def run(n_cases=200, seed=0):
+def run(n_cases=200, seed=0, metric="euclidean"):
+    if metric != "euclidean":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import match_metric_cases
     rng = np.random.default_rng(seed)
     bad = 0
     for case in range(n_cases):
@@ -37,15 +41,22 @@ def run(n_cases=200, seed=0):
             b *= 100.0
         maxd = float(rng.choice([np.inf, 5.0, 0.7, 12.0]))
         cc = bool(rng.integers(0, 2))
-        want_p, want_d = oracle.match(a, b, maxd, cc)
-        got = match_descriptors(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), max_distance=maxd, cross_check=cc, return_distance=True)
+        want_p, want_d = oracle.match(a, b, maxd, cc) if metric == "euclidean" else match_metric_cases.expect(a, b, metric, maxd, cc)[:2]
+        got = match_descriptors(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), metric=metric, max_distance=maxd, cross_check=cc, return_distance=True)
         gp, gd = got[0].cpu().numpy(), got[1].cpu().numpy()
-        if gp.shape != want_p.shape or not np.array_equal(gp, want_p) or not np.array_equal(gd.view(np.uint64), np.asarray(want_d, np.float64).view(np.uint64)):
+        want_d = np.asarray(want_d, np.float64)
+        nan = np.isnan(want_d)
+        if gp.shape != want_p.shape or not np.array_equal(gp, want_p) or not np.array_equal(np.isnan(gd), nan) or not np.array_equal(gd[~nan].view(np.uint64), want_d[~nan].view(np.uint64)):
             bad += 1
-            print("MISMATCH case", case, (n, m, C), maxd, cc, gp.shape, want_p.shape)
-    print("cases", n_cases, "mismatches", bad)
+            print("MISMATCH case", case, metric, (n, m, C), maxd, cc, gp.shape, want_p.shape)
+    print("metric", metric, "cases", n_cases, "mismatches", bad)
     return bad
 
 
 if __name__ == "__main__":
-    sys.exit(1 if run(int(sys.argv[1]) if len(sys.argv) > 1 else 200, int(sys.argv[2]) if len(sys.argv) > 2 else 0) else 0)
+    argv, metric = list(sys.argv[1:]), "euclidean"
+    if "--metric" in argv:
+        at = argv.index("--metric")
+        metric = argv[at + 1]
+        del argv[at: at + 2]
+    sys.exit(1 if run(int(argv[0]) if len(argv) > 0 else 200, int(argv[1]) if len(argv) > 1 else 0, metric) else 0)
