@@ -9,7 +9,7 @@ reference class).  That pins the BatchNorm folding, the tensor layouts and the c
     desc  = convhead2(cat[d1, d2, a3, d4])                    H/8 x W/8, not normalised
 
 Tolerances: the reference's own fp32 forward differs from its fp64 forward by 2.7e-5 (score) and 7.6e-7 (descriptor) at 480 x 640; the chain
-below is the same fp32 arithmetic with the BatchNorm division folded into the weights, so it gets five times that yardstick: 1.4e-4 / 4e-6."""
+(edgepoint_fixtures.chain) is the same fp32 arithmetic with the BatchNorm division folded into the weights, so it gets five times that yardstick: 1.4e-4 / 4e-6."""
 import os
 import re
 
@@ -19,43 +19,10 @@ import torch
 import torch.nn.functional as F
 
 from keypoint_bench_amd import synthetic, weights
-from edgepoint_fixtures import PARAM, SHAPES, checkpoint, load_parts
+from edgepoint_fixtures import PARAM, SHAPES, chain, checkpoint, load_parts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ATOL_SCORE, ATOL_DESC = 1.4e-4, 4e-6
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def chain(t, img):
-    """(score [B,1,H,W], desc [B,64,H/8,W/8]) from the folded tensors `t`."""
-    def conv3(x, n):
-        return F.conv2d(x, _t(t[n + ".w"]), _t(t[n + ".b"]), padding=1)
-
-    def res(x, q):
-        y = conv3(F.relu(conv3(x, q + "c1")), q + "c2")
-        return F.relu(y + F.conv2d(x, _t(t[q + "ds.w"])[:, :, None, None], _t(t[q + "ds.b"])))
-
-    def agg(x, i):
-        return F.relu(F.conv2d(x, _t(t["agg%d.w" % i])[:, :, None, None]))
-
-    x1 = F.relu(conv3(F.relu(conv3(img, "b1c1")), "b1c2"))
-    x2 = res(F.max_pool2d(x1, 2, 2), "b2")
-    x3 = res(F.max_pool2d(x2, 4, 4), "b3")
-    x4 = res(F.max_pool2d(x3, 4, 4), "b4")
-    a1, a2, a3, a4 = agg(x1, 1), agg(x2, 2), agg(x3, 3), agg(x4, 4)
-    score = F.conv2d(a1, _t(t["score.w"])[None, :, None, None], _t(t["score.b"]))
-    d1 = F.conv2d(a1[..., ::8, ::8], _t(t["d8.w"])[:, :, None, None], _t(t["d8.b"]))
-    d2 = F.conv2d(a2[..., ::4, ::4], _t(t["d4.w"])[:, :, None, None], _t(t["d4.b"]))
-    up = a4.repeat_interleave(4, dim=2).repeat_interleave(4, dim=3)                 # a4[y // 4, x // 4]
-    Hc, Wc = up.shape[2:]
-    wct = _t(t["ct4.w"])                                                            # [ci][co][ky][kx]
-    wyx = wct[:, :, torch.arange(Hc) % 4][:, :, :, torch.arange(Wc) % 4]            # [ci][co][Hc][Wc]: the slice (y % 4, x % 4) at every pixel
-    d4 = torch.einsum("bihw,iohw->bohw", up, wyx) + _t(t["ct4.b"])[None, :, None, None]
-    desc = F.conv2d(torch.cat([d1, d2, a3, d4], dim=1), _t(t["head.w"])[:, :, None, None])
-    return score, desc
 
 
 @pytest.fixture(scope="module")
