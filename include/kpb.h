@@ -92,6 +92,8 @@ int kpb_sync(kpb_ctx* ctx);
  *                              The launches of a call are chosen when it is made: a call already enqueued keeps its metric.  0 is the library of before, launch for
  *                              launch.  Any other id, a negative one too, is KPB_E_UNSUPPORTED, refused before anything touches the device; the metric stays what it
  *                              was, and kpb_match_counts has nothing to report until the next match.
+ *   KPB_OPT_LK_PYRLK           0 (default).  1: kpb_lk_track_batch runs the pyramidal tracker behind optical_flow_cv (restated, cv2 parity unpinned) in place of the tensor
+ *                              tracker: its section below defines the option's number and the arguments' meaning under it.  Any other value is invalid.
  * Returns KPB_E_INVALID for an unknown option or a negative value. */
 #define KPB_OPT_COVIS_STORE_BYTES 1
 #define KPB_OPT_ALIKE_COARSE_FUSED 2
@@ -263,6 +265,31 @@ int kpb_lk_track_batch(kpb_ctx* ctx, const float* map1_dev, const float* map2_de
                        const float* pts1_dev, const float* pts2_dev, int pts_stride, const float* unit_dev,
                        int max_n, const int32_t* n_dev, const kpb_lk_params* params,
                        float* out_pts_dev, float* out_err_dev);
+
+/* ---- the pyramidal Lucas-Kanade tracker behind utils/matcher.py:145-185 optical_flow_cv, reached through kpb_lk_track_batch under KPB_OPT_LK_PYRLK = 1
+ * (kpb_ctx_set_option; no export of its own, like the matcher's metrics):
+ *     cv2.calcOpticalFlowPyrLK(img0, img1, pts0, pts1, winSize = (win, win), maxLevel = levels, flags = OPTFLOW_USE_INITIAL_FLOW,
+ *                              criteria = (EPS | COUNT, 10, 0.03))          (minEigThreshold 1e-4, the error output requested)
+ * RESTATED, cv2 PARITY UNPINNED: OpenCV is absent from the reference tree and from this image.  What is computed is "PyrLK-R", the integer / float32 definition
+ * DESIGN.md section 7a writes out from OpenCV 4.x lkpyramid.cpp / pyramids.cpp, and the device agrees BIT FOR BIT with its numpy restatement
+ * (tests/pyrlk_fixtures.py).  In short: the maps become uint8 planes (trunc(x * 255f) & 255, as the reference's astype(np.uint8)); pyrDown (1-4-6-4-1, reflect-101,
+ * (sum + 128) >> 8) up to `levels` times, stopping before a level that is not larger than the window both ways; int16 Scharr derivatives of image 1 per level
+ * (0 outside the image, the image itself reflect-101 outside); per point and level the window of image 1 interpolated with 14-bit integer weights, the 2 x 2
+ * system's sums taken EXACTLY in 64-bit integers and rounded to fp32 once (cv2 adds them in fp32 in an order its SIMD build decides: the exact sum lies
+ * inside that spread), the minimum-eigenvalue test, at most ten Gauss-Newton steps with cv2's two stopping rules, and the range checks that clear the status.
+ * The arguments of kpb_lk_track_batch under the option (the routine is kpb_pyrlk_track in csrc/pyrlk.hip, and its messages carry that name):
+ *   maps, batch, C, H, W, strides, n_dev as above; pts1_dev / pts2_dev [batch][max_n][pts_stride] normalised (x, y, ...): the points in image 1 and their initial
+ *   guesses in image 2 (they may be one buffer); pixel = pt * (W - 1, H - 1).  unit_dev is not read and may be NULL.  params: win_size and levels are read
+ *   (optical_flow_cv's defaults: 15, 3), distance and iterations are not.  out_pts_dev [batch][max_n][2] NORMALISED, as optical_flow_cv returns them
+ *   (pixel / (W - 1, H - 1)); out_err_dev [batch][max_n] receives cv2's STATUS as 1.0f (tracked) or 0.0f.  A row whose point or guess is not finite comes back as
+ *   given with status 0.  Rows past n[j] are not written; max_n == 0 returns KPB_OK without touching a buffer.  Every pair's rows are the same bits alone or in a
+ *   batch, on planar or strided maps.  Asynchronous; the pyramids and the per-point state are carved from the context's workspace.
+ * Refusals: KPB_E_UNSUPPORTED for win_size even or outside 3 .. 31, levels outside 0 .. 4, C other than 1 or 3, H or W <= win_size, more than 65535 pairs, a
+ * pair's map spanning 2^31 elements or more; KPB_E_INVALID for a null map, params, point or output pointer, pts_stride < 2, batch < 1, max_n < 0 or a
+ * stride < 1.  Messages begin "kpb_pyrlk_track:" (a null context is answered by kpb_lk_track_batch itself), and a refused call writes nothing.
+ * KPB_OPT_LK_PYRLK: 0 (default) kpb_lk_track_batch is the tensor tracker above, launch for launch; 1: it is this tracker; any other value is KPB_E_INVALID.
+ * kpb_lk_track does not read the option. */
+#define KPB_OPT_LK_PYRLK 6
 
 /* ---- the tracking error of tasks/VisualizeTrackingError.py:45-46 for `batch` pairs:
  *     kps01_wh = kps01 * tensor([w - 1, h - 1]);  error = torch.norm(kps01_wh - kps1, dim=2)[0];  torch.mean(error)

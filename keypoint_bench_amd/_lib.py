@@ -182,6 +182,7 @@ class Context:
     OPT_DETECT_SIGNED = 3           # KPB_OPT_DETECT_SIGNED
     OPT_SFD2_PROBE = 4              # KPB_OPT_SFD2_PROBE (a test hook)
     OPT_MATCH_METRIC = 5            # KPB_OPT_MATCH_METRIC (a KPB_METRIC_* id: METRICS above)
+    OPT_LK_PYRLK = 6                # KPB_OPT_LK_PYRLK: kpb_lk_track_batch runs the pyramidal tracker behind optical_flow_cv (csrc/pyrlk.hip)
 
     def set_option(self, option: int, value: int):
         """kpb_ctx_set_option (include/kpb.h): a limit of this context, e.g. OPT_COVIS_STORE_BYTES."""
@@ -190,6 +191,8 @@ class Context:
             self._detect_signed = int(value)
         if int(option) == self.OPT_MATCH_METRIC:
             self._match_metric = int(value)
+        if int(option) == self.OPT_LK_PYRLK:
+            self._lk_pyrlk = int(value)
 
     _detect_signed = 0      # what OPT_DETECT_SIGNED was last set to (the library has no getter)
 
@@ -220,6 +223,21 @@ class Context:
         finally:
             if self._match_metric != before:
                 self.set_option(self.OPT_MATCH_METRIC, before)
+
+    _lk_pyrlk = 0           # what OPT_LK_PYRLK was last set to
+
+    @contextlib.contextmanager
+    def lk_pyrlk(self):
+        """OPT_LK_PYRLK = 1 for the kpb_lk_track_batch calls inside the block (they run csrc/pyrlk.hip's tracker: include/kpb.h); what was set before comes back
+        afterwards, also on an exception."""
+        before = self._lk_pyrlk
+        if before != 1:
+            self.set_option(self.OPT_LK_PYRLK, 1)
+        try:
+            yield self
+        finally:
+            if self._lk_pyrlk != before:
+                self.set_option(self.OPT_LK_PYRLK, before)
 
     def prof_enable(self, on: bool):
         self.check(self.lib.kpb_prof_enable(self.handle, 1 if on else 0))

@@ -22,7 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 SO = os.path.join(HERE, "libkpb.so")
-SOURCES = ["api.hip", "detect.hip", "match.hip", "net_api.hip", "alike.hip", "alike_l.hip", "conv_layer.hip", "convnet.hip", "r2d2.hip", "keynet.hip", "harris.hip", "sfd2.hip", "d2net.hip", "lightglue.hip", "covis.hip", "lk.hip",
+SOURCES = ["api.hip", "detect.hip", "match.hip", "net_api.hip", "alike.hip", "alike_l.hip", "conv_layer.hip", "convnet.hip", "r2d2.hip", "keynet.hip", "harris.hip", "sfd2.hip", "d2net.hip", "lightglue.hip", "covis.hip", "lk.hip", "pyrlk.hip",
            "preprocess.hip", "geometry.hip"]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators in ordinary vector registers.  gfx950's register file is unified, so accumulation
 # registers buy no occupancy, and every value that crosses between them and the vector ALUs costs a v_accvgpr_read / _write: 240 of

@@ -79,6 +79,10 @@ extern "C" __attribute__((visibility("default"))) int kpb_ctx_set_option(kpb_ctx
         if (value > 2) return kpb_fail(ctx, KPB_E_INVALID, "kpb_ctx_set_option: KPB_OPT_SFD2_PROBE takes 0, 1 or 2 (got %lld)", (long long)value);
         ctx->sfd2_probe = (int)value;
         return KPB_OK;
+    case KPB_OPT_LK_PYRLK:
+        if (value > 1) return kpb_fail(ctx, KPB_E_INVALID, "kpb_ctx_set_option: KPB_OPT_LK_PYRLK takes 0 or 1 (got %lld)", (long long)value);
+        ctx->lk_pyrlk = (int)value;
+        return KPB_OK;
     default: return kpb_fail(ctx, KPB_E_INVALID, "kpb_ctx_set_option: unknown option %d", option);
     }
 }

@@ -178,6 +178,7 @@ struct kpb_ctx {
     int detect_signed = 0;                          // KPB_OPT_DETECT_SIGNED
     int sfd2_probe = 0;                             // KPB_OPT_SFD2_PROBE
     int match_metric = 0;                           // KPB_OPT_MATCH_METRIC: a KPB_METRIC_* id, checked when it is set
+    int lk_pyrlk = 0;                               // KPB_OPT_LK_PYRLK: kpb_lk_track_batch runs csrc/pyrlk.hip's tracker
 };
 enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u, KPB_ATTR_NMS_ROUND = 16u, KPB_ATTR_SELECT = 32u,
        KPB_ATTR_ALIKE_L_HEAD = 64u };
@@ -271,6 +272,11 @@ template <class List> int kpb_carve(kpb_ctx* ctx, kpb_buf& buf, List&& list)
     list(bind);
     return KPB_OK;
 }
+
+// csrc/pyrlk.hip: what kpb_lk_track_batch runs under KPB_OPT_LK_PYRLK (include/kpb.h); out_status_dev receives 1.0f / 0.0f
+int kpb_pyrlk_track(kpb_ctx* ctx, const float* map1_dev, const float* map2_dev, int batch, int C, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
+                    const float* pts1_dev, const float* pts2_dev, int pts_stride, int max_n, const int32_t* n_dev, int win, int levels, float* out_pts_dev,
+                    float* out_status_dev);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 

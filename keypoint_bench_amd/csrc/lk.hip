@@ -285,6 +285,11 @@ extern "C" __attribute__((visibility("default"))) int kpb_lk_track_batch(
     float* out_pts_dev, float* out_err_dev)
 {
     if (!ctx) return kpb_fail(nullptr, KPB_E_INVALID, "kpb_lk_track_batch: null context");
+    if (ctx->lk_pyrlk) {        // KPB_OPT_LK_PYRLK: the tracker behind optical_flow_cv (csrc/pyrlk.hip); unit_dev, distance and iterations are not read
+        if (!prm) return kpb_fail(ctx, KPB_E_INVALID, "kpb_pyrlk_track: null map or params pointer");
+        return kpb_pyrlk_track(ctx, map1_dev, map2_dev, batch, C, H, W, sb, sc, sh, sw, pts1_dev, pts2_dev, pts_stride, max_n, n_dev, prm->win_size, prm->levels,
+                               out_pts_dev, out_err_dev);
+    }
     return lk_run(ctx, "kpb_lk_track_batch", map1_dev, map2_dev, batch, C, H, W, sb, sc, sh, sw, pts1_dev, pts2_dev, pts_stride, unit_dev, max_n, n_dev, prm,
                   out_pts_dev, out_err_dev);
 }

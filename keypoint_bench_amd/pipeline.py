@@ -285,22 +285,29 @@ class SequencePipeline(_Core):
     slot i against slot i+1 of the same buffers (kpb_match / kpb_gather_rows take the two sides as separate base
     pointers, so the shift is a pointer offset).  Slot 0 carries the last frame of the previous chunk."""
 
-    def __init__(self, net, extractor_params, brute_force_params, frames, H, W, device="cuda:0", track=None):
+    def __init__(self, net, extractor_params, brute_force_params, frames, H, W, device="cuda:0", track=None, pyrlk=None):
         """track = the matcher's optical_flow_params: pair j is TRACKED instead of matched (FundamentalMatrix.py:116-119) -- one kpb_lk_track_batch
         call follows slot j's keypoints from slot j's map into slot j + 1's.  The maps are the net's descriptor maps when net.tracked_maps, the frames
-        themselves otherwise (model_interface.py:262-272); F + 1 of them are kept, slot 0 carried like kps and n.  brute_force_params may be None then."""
-        self.track = track
-        if track is not None and brute_force_params is None:
+        themselves otherwise (model_interface.py:262-272); F + 1 of them are kept, slot 0 carried like kps and n.  brute_force_params may be None then.
+        pyrlk = the optical_flow_params of the visual_odometer task's optical_flow branch (visual_odometer.py:43-47; win_size / levels, {} = 15 / 3), the
+        runner's opt-in: ONE kpb_lk_track_batch call under KPB_OPT_LK_PYRLK (csrc/pyrlk.hip; restated, cv2 parity unpinned) follows slot j's keypoints from slot j's map into slot
+        j + 1's, on the same maps as `track`, and the rows with status 1 are compacted in order into m0 (the keypoint rows) / m1 [F][K][2] (where they were
+        tracked to, normalised) / k -- what the matchers leave there, so relative_motion_batch runs unchanged.  Not together with `track`."""
+        if track is not None and pyrlk is not None:
+            raise ValueError("SequencePipeline: track= and pyrlk= are two different trackers")
+        self.track, self.pyrlk = track, (dict(pyrlk) if pyrlk is not None else None)
+        tracking = track is not None or pyrlk is not None
+        if tracking and brute_force_params is None:
             brute_force_params = dict(metric="euclidean", max_distance=float("inf"), cross_check=True)
         super().__init__(net, extractor_params, brute_force_params, H, W, device)
         self.F = int(frames)
-        if track is None and self.C == 0:
+        if not tracking and self.C == 0:
             raise no_descriptors(net, "SequencePipeline without track=...")
-        if track is not None and net.tracked_maps and not (self.dense and self.div == 1):
+        if tracking and net.tracked_maps and not (self.dense and self.div == 1):
             raise ValueError("a net with tracked_maps writes a full-resolution descriptor map")
         self._buffers(self.F, self.F + 1, self.F, torch.zeros)      # slot 0 is read before it is ever written
         self._last = None       # slot that holds the newest frame of the previous chunk
-        if track is not None:
+        if tracking:
             K, dev = self.top_k, self.device
             if net.tracked_maps:        # the forward writes slots 1 .. F of the map buffer directly; viewed [F+1, C, H, W] over channels-last storage
                 self.maps_store = torch.zeros((self.F + 1, self.H, self.W, self.C), dtype=torch.float32, device=dev)
@@ -309,10 +316,16 @@ class SequencePipeline(_Core):
             else:                       # the frames are tracked (the forward stays the one the single-pair path runs: its score bits are the contract)
                 self.maps_store = self.maps = torch.zeros((self.F + 1, 3, self.H, self.W), dtype=torch.float32, device=dev)
             self.tracked = torch.empty((self.F, K, 2), dtype=torch.float32, device=dev)
-            self.track_err = torch.empty((self.F, K), dtype=torch.float32, device=dev)
+            if track is not None:
+                self.track_err = torch.empty((self.F, K), dtype=torch.float32, device=dev)
+            else:               # the device PyrLK: a status per row, the compaction's row numbers, and m1 as (x, y) rows
+                self.status = torch.empty((self.F, K), dtype=torch.uint8, device=dev)
+                self.order = torch.empty((self.F, K), dtype=torch.int32, device=dev)
+                self.m1 = torch.empty((self.F, K, 2), dtype=torch.float32, device=dev)
+                self._cols = torch.arange(K, dtype=torch.int32, device=dev)[None]
 
     def _carried(self):
-        return (self.kps, self.n, self.maps_store) if self.track is not None else (self.kps, self.n, self.sdesc)
+        return (self.kps, self.n, self.maps_store) if (self.track is not None or self.pyrlk is not None) else (self.kps, self.n, self.sdesc)
 
     def run(self, images, first, angles=None):
         """images [f, 3, H, W], f <= F consecutive frames; first = the chunk starts at frame 0 of the whole sequence
@@ -329,6 +342,26 @@ class SequencePipeline(_Core):
                 for t in self._carried():
                     t[0].copy_(t[self._last])
         self._extract(images, f, self.kps[1:], self.idx[1:], self.n[1:], 1)
+        if self.pyrlk is not None:
+            from .utils.matcher import optical_flow_cv_batch
+            if not self.net.tracked_maps:
+                self.maps[1:f + 1].copy_(images)
+            if first:       # the first frame of a sequence is paired with itself
+                for t in self._carried():
+                    t[0].copy_(t[1])
+            out, status = optical_flow_cv_batch(self.maps[:f], self.maps[1:f + 1], self.kps[:f], self.kps[:f], self.n[:f], self.pyrlk or None)      # both starts are kps0
+            self.tracked[:f].copy_(out)
+            self.status[:f].copy_(status)
+            # visual_odometer.py:46-47: the rows with status 1, in order.  Row numbers and counts are index bookkeeping on [f, K] bytes (rows past n[j] hold
+            # whatever the buffer held: masked); the rows themselves move through kpb_gather_rows, as the matchers' do.
+            keep = (status == 1) & (self._cols < self.n[:f, None])
+            self.order[:f].copy_(torch.sort((~keep).to(torch.uint8), dim=1, stable=True).indices)
+            self.k[:f].copy_(keep.sum(dim=1))
+            ctx, L, K = self.ctx, self.ctx.lib, self.top_k
+            ctx.check(L.kpb_gather_rows(ctx.handle, ptr(self.kps), f, K, 3, ptr(self.order), K, 1, 0, ptr(self.k), ptr(self.m0)))
+            ctx.check(L.kpb_gather_rows(ctx.handle, ptr(self.tracked), f, K, 2, ptr(self.order), K, 1, 0, ptr(self.k), ptr(self.m1)))
+            self._last = f
+            return self
         if self.track is not None:
             from .utils.matcher import optical_flow_batch
             if not self.net.tracked_maps:

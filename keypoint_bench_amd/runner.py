@@ -603,7 +603,9 @@ class PairRunner:
             from .pipeline import no_descriptors
             raise no_descriptors(self.model, "task %r with the %s matcher" % (task_type, mp["type"]))
         if task_type == "visual_odometer":    # 283-298: the per-frame motion; the chain is composed from the gathered rows
-            from .tasks.visual_odometer import relative_motion, step_length
+            from .tasks.visual_odometer import pyrlk_opt_in, relative_motion, step_length
+            if mp["type"] == "optical_flow" and pyrlk_opt_in(self.params) and not getattr(self.model, "tracked_maps", False):
+                d0, d1 = last_img, cur["image0"]        # 284-296: the device tracker (opt-in) follows the two frames, or the maps of a net that makes them for it
             R, t = relative_motion(idx, last_img, cur, s0, s1, d0, d1, self.matcher, self.params)
             r = list(R.reshape(9)) + list(t.reshape(3)) + [step_length(cur)]
             self.results.append(r)
@@ -816,8 +818,10 @@ class PairRunner:
         from .pipeline import SequencePipeline
         from .tasks.FundamentalMatrix import epipolar_error
         mp = self.params["matcher_params"]
-        track = mp["type"] == "optical_flow" and task_type == "FundamentalMatrix"     # (visual_odometer + optical_flow is cv2's tracker: refused per frame)
-        batched = self._can_batch() and (mp["type"] == "brute_force" or (mp["type"] == "light_glue" and self.matcher is None) or track)
+        track = mp["type"] == "optical_flow" and task_type == "FundamentalMatrix"     # (visual_odometer + optical_flow is cv2's tracker: refused per frame ...
+        from .tasks.visual_odometer import pyrlk_opt_in
+        pyrlk = mp["type"] == "optical_flow" and task_type == "visual_odometer" and pyrlk_opt_in(self.params)      # ... unless matcher_params["pyrlk"] == "device")
+        batched = self._can_batch() and (mp["type"] == "brute_force" or (mp["type"] == "light_glue" and self.matcher is None) or track or pyrlk)
         rows = []
         if not indices:
             return rows
@@ -835,7 +839,7 @@ class PairRunner:
         H, W = first.shape[-2:]
         F = min(self.batch, len(indices))
         pipe = SequencePipeline(self.model, self.params["extractor_params"], mp.get("brute_force_params"), F, H, W, device=self.device,
-                                track=mp["optical_flow_params"] if track else None)
+                                track=mp["optical_flow_params"] if track else None, pyrlk=(mp.get("optical_flow_params") or {}) if pyrlk else None)
         images = torch.empty((F, 3, H, W), dtype=torch.float32, device=self.device)
         if indices[0] > 0:
             pipe.prime(as_image(dataset[indices[0] - 1]["image0"], self.device))
@@ -902,7 +906,7 @@ class PairRunner:
 
 
 # ------------------------------------------------------------------------------------------ install shim
-def install():
+def install(optical_flow_cv=False):
     """Swap this package's kernels under an importable reference checkout: see keypoint_bench_amd/shim.py."""
     from . import shim
-    return shim.install()
+    return shim.install(optical_flow_cv=optical_flow_cv)

@@ -17,6 +17,11 @@ One thing is refused instead of routed: a brute-force call whose ``brute_force_p
 Nothing else falls through: KPB_E_INVALID (a malformed call) and every other library error RAISE -- an in-contract call that
 starts failing must not turn into a silent thousandfold slowdown on the reference's CPU code.
 
+``install(optical_flow_cv=True)`` additionally swaps ``utils.matcher.optical_flow_cv`` (cv2.calcOpticalFlowPyrLK, the visual_odometer task's optical_flow
+branch) for csrc/pyrlk.hip's tracker -- OPT-IN because that tracker is RESTATED, cv2 parity unpinned (an integer definition pinned bit for
+bit to a numpy oracle, not to cv2's own bits).  Host tensors and calls beyond the kernel's limits go to the reference's own function; the swapped
+``visual_odometry`` accepts the optical_flow matcher type only while this swap is installed (or when ``matcher_params["pyrlk"] == "device"``).
+
 So the Harris / repeatability configuration keeps running on the reference's code while ALIKE / SuperPoint / XFeat /
 DISK runs go through libkpb.so.  ``uninstall()`` restores every original.
 """
@@ -228,6 +233,32 @@ def _c_lk(pts0, pts1, img0, img1, params=None):
     return None if _on_device(pts0, img0, img1) else "inputs are not on a HIP device"
 
 
+def _c_pyrlk(pts0, pts1, img0, img1, params=None):
+    """The limits of the tracker behind KPB_OPT_LK_PYRLK (include/kpb.h), checked before the call so that nothing out of them reaches the device."""
+    if not _on_device(pts0, pts1, img0, img1):
+        return "inputs are not on a HIP device"
+    p = params or {"win_size": 15, "levels": 3}
+    try:
+        win, levels = p["win_size"], p["levels"]
+        ok = int(win) == win and int(levels) == levels and 3 <= win <= 31 and int(win) % 2 == 1 and 0 <= levels <= 4
+    except (KeyError, TypeError, ValueError):
+        ok = False
+    if not ok:
+        return "win_size / levels beyond the kernel's limits"
+    if img0.dim() != 4 or img0.shape != img1.shape or img0.shape[0] != 1 or img0.shape[1] not in (1, 3) or min(img0.shape[2:]) <= win:
+        return "image shape beyond the kernel's limits"
+    return None
+
+
+def _pyrlk_as_cv2(hip_fn):
+    def optical_flow_cv(pts0, pts1, img0, img1, params=None):
+        """utils/matcher.py:145-185 on the device (restated, cv2 parity unpinned).  The status comes back as cv2 hands it over -- a numpy [n, 1] uint8 array:
+        the reference's task applies np.where to it (visual_odometer.py:46-47)."""
+        pts, status = hip_fn(pts0, pts1, img0, img1, params)
+        return pts, status.cpu().numpy()
+    return optical_flow_cv
+
+
 def _c_vkp(kps0, kps1, warp01, warp10, th=3):
     return None if _on_device(kps0, kps1) else "keypoints are not on a HIP device"
 
@@ -268,13 +299,19 @@ def _table():
     ]
 
 
-def install():
+def install(optical_flow_cv=False):
     """Returns the list of swapped ``module.name`` strings ([] when no reference checkout is importable).
     A reference module that exists but fails to import (a missing third-party package) is reported with a warning and
-    listed in ``installed()['skipped']`` -- it is not silently ignored."""
+    listed in ``installed()['skipped']`` -- it is not silently ignored.
+    optical_flow_cv=True: ``utils.matcher.optical_flow_cv`` is swapped as well (opt-in: restated, cv2 parity unpinned -- the module docstring).  An installed
+    shim is left as it is: uninstall() first to change the set."""
     if _state["swapped"]:
         return list(_state["swapped"])
-    for modname, attr, kind, hip, contract in _table():
+    table = _table()
+    if optical_flow_cv:
+        from .utils import matcher as ma
+        table.append(("utils.matcher", "optical_flow_cv", "fn", _pyrlk_as_cv2(ma.optical_flow_cv), _c_pyrlk))
+    for modname, attr, kind, hip, contract in table:
         try:
             mod = importlib.import_module(modname)
         except ModuleNotFoundError as e:
@@ -304,6 +341,9 @@ def install():
     for m, why in _state["skipped"].items():
         warnings.warn("keypoint_bench_amd.install(): reference module %s not swapped (%s)" % (m, why), RuntimeWarning, stacklevel=2)
     _rebind()
+    if "utils.matcher.optical_flow_cv" in _state["swapped"]:
+        from .tasks import visual_odometer as vo
+        vo.SHIM_PYRLK = True
     return list(_state["swapped"])
 
 
@@ -333,6 +373,8 @@ def uninstall():
             if full.rsplit(".", 1)[1] == attr and modname in sys.modules:
                 setattr(sys.modules[modname], attr, ref)
     _state.update(originals={}, swapped=[], skipped={}, rebound=[])
+    from .tasks import visual_odometer as vo
+    vo.SHIM_PYRLK = False
 
 
 def installed():

@@ -8,8 +8,11 @@ SURVEY 8(e): the chain `r_est[-1]` makes the task sequential, but only in its la
 per frame.  `relative_motion` / `relative_motion_batch` return the per-frame (R, t, scale) rows, `compose` chains them
 (model_interface.py:283-298 + 161-166), so that a sharded run gathers rows and composes once.
 
-The optical-flow branch of the reference calls cv2's pyramidal LK (`optical_flow_cv`, utils/matcher.py); that branch is
-outside this library's contract and is left to the reference (keypoint_bench_amd.shim routes it there)."""
+The optical-flow branch of the reference calls cv2's pyramidal LK (`optical_flow_cv`, utils/matcher.py:145-185).  By default that branch stays
+outside this library's contract and is left to the reference (keypoint_bench_amd.shim routes it there).  It is OPT-IN:
+``matcher_params["pyrlk"] == "device"`` runs it on csrc/pyrlk.hip's tracker (utils.matcher.optical_flow_cv) -- RESTATED, cv2 parity unpinned: the
+tracker is the integer definition of DESIGN.md section 7a, pinned bit for bit to a numpy oracle, not to cv2's own bits.  Without the key, or with any
+other value, everything here answers as before."""
 import numpy as np
 import torch
 
@@ -35,21 +38,36 @@ def _scalar(v):
     return float(torch.as_tensor(v).reshape(-1)[0])
 
 
+PYRLK_KEY, PYRLK_ON = "pyrlk", "device"     # matcher_params["pyrlk"] == "device": the optical_flow branch runs on the device tracker
+SHIM_PYRLK = False      # set while keypoint_bench_amd.shim has optical_flow_cv swapped (install(optical_flow_cv=True)): the swapped visual_odometry then accepts the branch too
+
+
+def pyrlk_opt_in(params):
+    """True when the task parameters ask for the device tracker in the optical_flow branch; a missing key, or any other value, is today's refusal."""
+    return params["matcher_params"].get(PYRLK_KEY) == PYRLK_ON
+
+
 def in_contract(step, pose_R, pose_t, last_img, batch, score_map_0, score_map_1, desc_map_0, desc_map_1, matcher, params):
     if not (torch.is_tensor(score_map_0) and score_map_0.is_cuda):
         return "score maps are not on a HIP device"
-    if params["matcher_params"]["type"] == "optical_flow":
+    if params["matcher_params"]["type"] == "optical_flow" and not (SHIM_PYRLK or pyrlk_opt_in(params)):
         return "optical_flow_cv is cv2's tracker"
     return None
 
 
-def match_branch(kps0, kps1, score_map_0, desc_map_0, desc_map_1, matcher, params):
-    """visual_odometer.py:43-61."""
+def match_branch(kps0, kps1, score_map_0, desc_map_0, desc_map_1, matcher, params, pyrlk=None):
+    """visual_odometer.py:43-61.  pyrlk: run the optical_flow branch on the device tracker (None = what the parameters ask for, pyrlk_opt_in); desc_map_* are the
+    two maps the tracker reads there -- the frames, or the maps of a net that makes them for it (model_interface.py:284-296)."""
     from ..utils.matcher import brute_force_matcher
     mp = params["matcher_params"]
     h, w = score_map_0.shape[2], score_map_0.shape[3]
     if mp["type"] == "optical_flow":
-        raise NotImplementedError("visual_odometry: the optical_flow branch is cv2's tracker (optical_flow_cv); not part of this library")
+        if not (pyrlk_opt_in(params) if pyrlk is None else pyrlk):
+            raise NotImplementedError("visual_odometry: the optical_flow branch is cv2's tracker (optical_flow_cv); not part of this library")
+        from ..utils.matcher import optical_flow_cv
+        k1, status = optical_flow_cv(kps0[:, 0:2], kps0[:, 0:2], desc_map_0, desc_map_1, mp.get("optical_flow_params"))      # 44-45: both starts are kps0
+        keep = torch.nonzero(status[:, 0] == 1)[:, 0]                                                                       # 46-47: np.where(status == 1)[0], in order
+        return kps0[keep], k1[keep]
     if mp["type"] == "brute_force" or (mp["type"] == "light_glue" and matcher is None):
         return brute_force_matcher(kps0, kps1, desc_map_0, desc_map_1, mp["brute_force_params"])
     if mp["type"] == "light_glue":
@@ -62,12 +80,12 @@ def _camera(fx, cx, cy):
     return np.array([[fx, 0.0, cx], [0.0, fx, cy], [0.0, 0.0, 1.0]], np.float64)      # focal= / pp=: one focal length, float64
 
 
-def relative_motion(step, last_img, batch, score_map_0, score_map_1, desc_map_0, desc_map_1, matcher, params, seed=None):
-    """visual_odometer.py:37-78 for one frame pair: (R [3,3], t [3,1]) float64 numpy, as cv2.recoverPose returns them."""
+def relative_motion(step, last_img, batch, score_map_0, score_map_1, desc_map_0, desc_map_1, matcher, params, seed=None, pyrlk=None):
+    """visual_odometer.py:37-78 for one frame pair: (R [3,3], t [3,1]) float64 numpy, as cv2.recoverPose returns them.  pyrlk: as match_branch."""
     from ..utils.extracter import detection
     kps0 = detection(score_map_0, params["extractor_params"])
     kps1 = detection(score_map_1, params["extractor_params"])
-    kps0, kps1 = match_branch(kps0, kps1, score_map_0, desc_map_0, desc_map_1, matcher, params)
+    kps0, kps1 = match_branch(kps0, kps1, score_map_0, desc_map_0, desc_map_1, matcher, params, pyrlk=pyrlk)
     if kps0.shape[0] < 5:
         raise RuntimeError("visual_odometry: fewer than five matches (cv2.findEssentialMat raises there)")
     sc = [score_map_0.shape[3] - 1, score_map_0.shape[2] - 1, last_img.shape[3] - 1, last_img.shape[2] - 1]      # 65-67
@@ -92,7 +110,8 @@ def update(pose_R, pose_t, R, t, scale):
 
 def visual_odometry(step, pose_R, pose_t, last_img, batch, score_map_0, score_map_1, desc_map_0, desc_map_1, matcher, params, seed=None):
     """tasks/visual_odometer.py:10-91.  Returns the reference's dict {'R': R_est, 't': t_est}."""
-    R, t = relative_motion(step, last_img, batch, score_map_0, score_map_1, desc_map_0, desc_map_1, matcher, params, seed)
+    R, t = relative_motion(step, last_img, batch, score_map_0, score_map_1, desc_map_0, desc_map_1, matcher, params, seed,
+                           pyrlk=SHIM_PYRLK or pyrlk_opt_in(params))
     R_est, t_est = update(pose_R, pose_t, R, t, step_length(batch))
     return {"R": R_est, "t": t_est}
 

@@ -1,5 +1,6 @@
 """Drop-in for the brute-force branch of the reference's utils/matcher.py (lines 206-234), computed by
-csrc/match.hip through libkpb.so."""
+csrc/match.hip through libkpb.so; its two trackers: OpticalFlow / optical_flow_tensor (7-142, 188-203: csrc/lk.hip) and
+optical_flow_cv (145-185: csrc/pyrlk.hip -- restated, cv2 parity unpinned)."""
 import ctypes
 
 import torch
@@ -206,3 +207,58 @@ def optical_flow_batch(maps1, maps2, pts1, pts2, n, params, random_angle=None):
         ctx.check(ctx.lib.kpb_lk_track_batch(ctx.handle, ptr(maps1), ptr(maps2), B, C, H, W, sb, sc, sh, sw, ptr(p1), ptr(p2), p1.shape[2], ptr(unit), K,
                                              ptr(n), ctypes.byref(prm), ptr(out), ptr(err)))
     return out, err
+
+
+PYRLK_DEFAULTS = {"win_size": 15, "levels": 3}      # matcher.py:158-162
+
+
+def optical_flow_cv_batch(maps1, maps2, pts1, pts2, n=None, params=None):
+    """The pyramidal tracker behind optical_flow_cv for B pairs in ONE kpb_lk_track_batch call under KPB_OPT_LK_PYRLK (csrc/pyrlk.hip; RESTATED, cv2 parity unpinned: include/kpb.h): pair j
+    follows pts1[j] (normalised rows) from maps1[j] into maps2[j], starting at pts2[j].  maps1 / maps2 [B,C,H,W] fp32 of ANY strides, both with the same ones, C 1 or 3
+    -- planar frames, the channels-last storage behind a net's map, or two shifted views of one buffer; pts1 / pts2 [B,K,>=2] (one tensor is fine); n [B] int32 on
+    the device or None (= K).  Returns (points [B,K,2] NORMALISED, status [B,K] uint8, 1 = tracked); rows past n[j] are left as allocated.  Every pair's rows are the
+    bits of optical_flow_cv on that pair."""
+    if params is None:
+        params = PYRLK_DEFAULTS
+    if not (maps1.is_cuda and maps2.is_cuda and pts1.is_cuda and pts2.is_cuda):
+        raise RuntimeError("keypoint_bench_amd needs CUDA/HIP tensors; there is no CPU path")
+    if maps1.dim() != 4 or maps1.dtype != torch.float32 or maps2.dtype != torch.float32:
+        raise ValueError("maps must be float32 [B,C,H,W]")
+    if maps2.shape != maps1.shape or maps2.stride() != maps1.stride():
+        raise ValueError("maps1 and maps2 must have one shape and one set of strides")
+    B, C, H, W = maps1.shape
+    if pts1.dim() != 3 or pts1.shape[-1] < 2 or pts1.shape != pts2.shape or pts1.stride() != pts2.stride() or pts1.shape[0] != B:
+        raise ValueError("points need (x, y) columns, one [B,K,cols] layout for both arrays")
+    p1, p2 = pts1.detach(), pts2.detach()
+    if p1.dtype != torch.float32 or p2.dtype != torch.float32 or not p1.is_contiguous() or not p2.is_contiguous():
+        p1, p2 = p1.to(torch.float32).contiguous(), p2.to(torch.float32).contiguous()
+    K, dev = p1.shape[1], maps1.device
+    out = torch.empty((B, K, 2), dtype=torch.float32, device=dev)
+    flag = torch.empty((B, K), dtype=torch.float32, device=dev)        # the status as the entry writes it: 1.0 / 0.0 where the tensor tracker's error column stands
+    if B and K:
+        ctx = Context.get(dev)
+        sb, sc, sh, sw = maps1.stride()
+        prm = LkParams(0.0, int(params["win_size"]), int(params["levels"]), 0)         # distance and iterations are not read under the option
+        with ctx.lk_pyrlk():
+            ctx.check(ctx.lib.kpb_lk_track_batch(ctx.handle, ptr(maps1), ptr(maps2), B, C, H, W, max(sb, 1), sc, sh, sw, ptr(p1), ptr(p2), p1.shape[2], ptr(None), K,
+                                                 ptr(n), ctypes.byref(prm), ptr(out), ptr(flag)))
+    status = (flag == 1.0).to(torch.uint8)       # rows past n[j] hold whatever the buffer held
+    return out, status
+
+
+def optical_flow_cv(pts0, pts1, img0, img1, params=None):
+    """utils/matcher.py:145-185 on the device: pts0 (n, >=2) in [0, 1] are followed from img0 into img1 [1,C,H,W], starting at pts1; params: win_size / levels
+    (15 / 3 when None).  Returns (points [n,2] fp32 normalised, status [n,1] uint8) ON THE DEVICE (the reference hands the status back as cv2's numpy array; the
+    shim's wrapper does that conversion).  RESTATED, cv2 parity unpinned: what is computed is the definition in DESIGN.md section 7a, bit for bit."""
+    if not (torch.is_tensor(img0) and img0.is_cuda):
+        raise RuntimeError("keypoint_bench_amd needs CUDA/HIP tensors; there is no CPU path")
+    if img0.dim() != 4 or img0.shape[0] != 1 or pts0.shape[0] != pts1.shape[0]:
+        raise ValueError("one image pair per call, one guess per point (matcher.py:166)")
+    a = img0.detach().to(torch.float32)
+    b = img1.detach().to(torch.float32)
+    if b.stride() != a.stride():
+        a, b = a.contiguous(), b.contiguous()
+    p0 = pts0.detach()[:, :2].to(torch.float32).contiguous()
+    p1 = pts1.detach()[:, :2].to(torch.float32).contiguous()
+    out, status = optical_flow_cv_batch(a, b, p0[None], p1[None], None, params)
+    return out[0], status[0].unsqueeze(1)
