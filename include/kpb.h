@@ -385,7 +385,7 @@ int kpb_preprocess(kpb_ctx* ctx, const uint8_t* src_dev, int batch, int Hs, int 
                                  * or ALIKE-l, the reference's default (32,64,128,128, dim 128); H, W multiples of 32; desc_out_dev NULL = keypoint-only */
 #define KPB_ARCH_SUPERPOINT 2   /* models/SuperPoint.py SuperPointNet, tensors named as its state_dict */
 #define KPB_ARCH_XFEAT 3        /* models/XFeat.py      XFeatModel, BN folded */
-#define KPB_ARCH_DISK 4         /* models/disk.py       DISK (thin U-Net, 5x5), H, W multiples of 16, not 16 x 16 (a 1 x 1 bottleneck has no instance norm) */
+#define KPB_ARCH_DISK 4         /* models/disk.py       DISK (thin U-Net, 5x5), H, W multiples of 16, not 16 x 16 (a 1 x 1 bottleneck has no instance norm); desc_out_dev NULL gives the score only, kpb_net_desc_at the descriptors at keypoints */
 #define KPB_ARCH_R2D2 6         /* models/r2d2.py       Quad_L2Net_ConfCFS (dilated, full resolution), BN folded; any H, W */
 #define KPB_ARCH_EDGEPOINT 7    /* models/EdgePoint.py  EdgePoint (ALIKE-t trunk, plan 8,16,32,64 / 64), BN folded; raw-logit score (KPB_OPT_DETECT_SIGNED), 64-channel map at H/8 x W/8 */
 #define KPB_ARCH_GOODPOINT 8    /* models/GoodPoint.py  GoodPoint (ALIKE-t's block 1, plan c0 = 3, c1 = 8), BN folded; H, W multiples of 32; sigmoid score and a sigmoid 3-channel map at full resolution, not normalised: the map the tracker follows (kpb_lk_track_batch); desc_out_dev 16-byte aligned */
@@ -400,13 +400,17 @@ int kpb_net_desc_dim(const kpb_net* net);   /* descriptor channels C */
 int kpb_net_desc_div(const kpb_net* net);   /* descriptor map is (H/div) x (W/div): 1 for ALIKE, 8 for SuperPoint/XFeat */
 /* img_dev [batch][3][H][W] fp32 RGB in [0,1], H and W multiples of 32 (model_interface.py:192-204).
  * score_out_dev [batch][H][W]; desc_out_dev [batch][H/div][W/div][C] (channels-last storage of the
- * reference's [B,C,H/div,W/div] tensor).  ALIKE only: NULL skips the dense descriptor map (the features
- * needed by kpb_net_desc_at stay resident in the net until the next forward).
+ * reference's [B,C,H/div,W/div] tensor).  ALIKE and DISK: NULL skips the dense descriptor map (the features
+ * needed by kpb_net_desc_at stay resident in the net until the next forward; DISK keeps them after a dense
+ * forward too).  DISK's last layer then runs its score channel alone: score_out_dev holds the dense forward's bits.
  * SuperPoint: H, W multiples of 8; RGB is summed to one channel (SuperPoint.py:42); descriptors L2-normalised. */
 int kpb_net_forward(kpb_net* net, const float* img_dev, int batch, int H, int W,
                     float* score_out_dev, float* desc_out_dev);
-/* Descriptors of the last forward at keypoints, equal to sampling the dense map with kpb_sample
- * (the head and bilinear sampling are both linear): pts/n/out as in kpb_sample. */
+/* Descriptors of the last forward at keypoints (ALIKE, DISK): pts/n/out as in kpb_sample.  ALIKE: equal to
+ * sampling the dense map with kpb_sample (the head and bilinear sampling are both linear).  DISK: its head is NOT
+ * linear (F.normalize per pixel), so the last layer is evaluated at the <= 4 integer taps of every keypoint, each
+ * tap is normalised, and the taps are blended with kpb_sample's coefficients in its order -- kpb_sample on the
+ * dense map up to the rounding of the convolution (the taps' operand scale is per image, the dense layer's per slab). */
 int kpb_net_desc_at(kpb_net* net, const float* pts_dev, int pts_cols, int max_n,
                     const int32_t* n_dev, float* out_dev);
 

@@ -34,6 +34,8 @@ struct MfmaOpt {
     const float2* unfold_mr = nullptr;  // normalised by the per-image (mean, 1 / std) as they are read
     float l2_eps = 0.0f;                // > 0: F.normalize(eps = l2_eps) of every output row in the epilogue (XFeat block_fusion.2, split-f16 form)
     const float* res = nullptr;         // the identity map of a ResBlock [B][H][W][cout], added before the ReLU (SFD2; 1 x 1 layers only)
+    bool last_only = false;             // ntb == 5 layers (DISK up_3): `out` is [B][H][W] and receives the LAST output channel alone (the score logit), with the
+                                        // bits the full layer gives it -- conv_mfma_h<xo> (profile name + "_score"), or the fifth tile by itself on the strict-fp32 path
 };
 
 // L is the net's own Layer (net->L[i]): the stage binds its pointers at the upload.  Profile name = prefix + layer name: "sp_conv1b", "xf_block2.0", "disk_up3"

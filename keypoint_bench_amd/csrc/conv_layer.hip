@@ -29,6 +29,9 @@ int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B
     if (o.unfold_w && !(conv_mfma_use_h16() && L.ks == 1 && S == 1 && CC == 32 && !L.pool_out && !o.xf && L.cin == 64))
         return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: the unfolded input exists for 64-channel 1x1 layers of the split-f16 form only");
     if (o.res && (L.ks != 1 || L.cout % 64)) return kpb_fail(ctx, KPB_E_INVALID, "SFD2 %s: the identity branch joins 1x1 layers of whole 64-channel tiles", L.name.c_str());
+    if (o.last_only && L.ntb != 5) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: %s has no channel beside its tiles to compute alone", L.name.c_str());
+    const std::string last_name = L.prof + "_score";
+    if (o.last_only) name = last_name.c_str();
     hipStream_t st = ctx->stream;
     const bool x = o.xf != nullptr;
     if (conv_mfma_use_h16()) {
@@ -73,6 +76,10 @@ int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B
             // and the score channel on the VALU of the first workgroup
             a.nblk = 2; a.xw = L.xw; a.xb = L.xb; a.xun = L.xun; a.xco = L.cout - 1;
             f.xc = true;
+            if (o.last_only) {      // the same staging and the same VALU channel, no tiles: one workgroup per tile of the image, one float per pixel
+                a.nblk = 1; a.ostride = 1; a.xco = 0;
+                f.xo = true;
+            }
         }
         return launch_conv_mfma_h<
             CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
@@ -80,15 +87,26 @@ int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B
             CmForm{.ks = 3, .s = 2, .cc = 16, .ntb = 1, .mt = 2, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .wn = 2},
             CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2, .up = true},
             CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .xc = true, .wn = 2, .up = true},
+            CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .xc = true, .wn = 2, .up = true, .xo = true},
             CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .dil = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 2, .wn = 2, .dil = 4}>(ctx, name, f, a, B);
+    }
+    int ntb = L.ntb;
+    if (o.last_only) {
+        // strict fp32: channel 4 x 32 of the fifth tile.  An accumulator's chain of v_mfma_f32_32x32x2_f32 does not depend on the tiles beside it, so the tile launched
+        // by itself (its fragments and its bias row, one stored column) gives the logit the five-tile form gives
+        a.wp = L.w + (size_t)4 * L.ks * L.ks * a.NCH * 2 * 32 * (CC / 2);
+        a.bias = L.b + 128;
+        a.COUT = 1; a.nblk = 1; a.ostride = 1;
+        ntb = 1;
     }
     return launch_conv_mfma<
         CmForm{.ks = 1, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1},
         CmForm{.ks = 3, .s = 1, .cc = 32, .pool_out = true}, CmForm{.ks = 3, .s = 2, .cc = 16},
         CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true}, CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 5},
+        CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1},
         CmForm{.ks = 3, .s = 1, .cc = 32, .dil = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .dil = 4},
         CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 4}, CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 8}, CmForm{.ks = 2, .s = 1, .cc = 16, .dil = 16}>(
-        ctx, name, CmForm{.ks = L.ks, .s = S, .cc = CC, .pool_out = L.pool_out, .xf = x, .ntb = L.ntb, .dil = L.dil}, a, B);
+        ctx, name, CmForm{.ks = L.ks, .s = S, .cc = CC, .pool_out = L.pool_out, .xf = x, .ntb = ntb, .dil = L.dil}, a, B);
 }
 
 void stage_layer(WeightStage& ws, Layer& L, const char* prefix, const float* w, const float* b)

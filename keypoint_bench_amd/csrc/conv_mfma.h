@@ -112,6 +112,10 @@ struct CmForm {
     // fmaf chains of conv1x1_relu_body) and, with tail == 2, a third wave pools it.  x3 / x4 are never written: 0.61 MB written and twice read per 480 x 640 image, and
     // three launches.  1: aggregation; 2: aggregation + pool.  One workgroup must own every channel of its pixels (nblk = 1).
     int tail = 0;
+    // DISK's keypoint-only forward: the xc form WITHOUT its MFMA tiles.  The tile is staged exactly as the xc form stages it (the same upsampling mix, the same
+    // per-slab scale e_cur) and only the VALU channel runs, in the same order on the same halves: the extra channel's bits are those of the dense form.  No weight
+    // fragment is loaded and no tile is written; `out` receives the extra channel alone (ostride = 1, xco = 0).
+    bool xo = false;
     constexpr bool operator==(const CmForm&) const = default;
     constexpr int tile_h() const { return 8 * mt / wn; }       // output rows of a workgroup tile
     // conv_mfma_h: waves per SIMD the register allocation is held to: what r02's code reached without being told (accumulators 16 mt ntb) -- left alone, the
@@ -449,7 +453,8 @@ template <CmForm F>
 __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
 {
     constexpr int KS = F.ks, S = F.s, CC = F.cc, NTB = F.ntb, MT = F.mt, PF = F.pf, WN = F.wn, DIL = F.dil;
-    constexpr bool POOL_IN = F.pool_in, POOL_OUT = F.pool_out, XF = F.xf, XC = F.xc, WPRE = F.wpre, PRE = F.pre, GEN = F.gen, UP = F.up;
+    constexpr bool POOL_IN = F.pool_in, POOL_OUT = F.pool_out, XF = F.xf, XC = F.xc, WPRE = F.wpre, PRE = F.pre, GEN = F.gen, UP = F.up, XO = F.xo;
+    static_assert(!XO || (XC && UP && NTB == 1 && F.tail == 0), "conv_mfma_h: the channel-only form is the xc form of the fused upsampling without its tiles");
     static_assert(DIL == 1 || (DIL >= 2 && S == 1 && !WPRE && !PRE && !UP && !XC && !POOL_IN && MT >= 2 && NTB == 1), "conv_mfma_h: the dilated form exists for plain stride-1 layers (R2D2)");
     static_assert(!UP || (S == 1 && !POOL_IN && !PRE && !WPRE && (((F.tile_h() - 1) * S + KS) % 2 == 0) && ((15 * S + KS) % 2 == 0) && KS / 2 % 2 == 0),
                   "conv_mfma_h<UP>: stride-1 layers whose input tile starts on an even row and column");
@@ -782,7 +787,7 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
                     BlA[set][n][kb] = __builtin_bit_cast(cm_h8, bp[n * ntile_stride + (kb * 4 + 2) * 32]);
                 }
         };
-        loadB(0, 0);
+        if constexpr (!XO) loadB(0, 0);
 #pragma unroll (TAPU == 9 ? KS : 1)
         for (int ky = 0; ky < KS; ++ky)
 #pragma unroll (PRE ? 1 : KS)      // (the generated-input form with its columns unrolled: conv1b 1.83 -> 3.3 ms)
@@ -790,7 +795,8 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
             const int tap = ky * KS + kx;
             cm_h8 Ah[MT][NKB], Al[MT][NKB];
             constexpr bool AHEAD = TAPU == 9 || ROW_AHEAD;
-            if constexpr (AHEAD) {
+            if constexpr (XO) {
+            } else if constexpr (AHEAD) {
                 if (tap + 1 < T) loadB(tap + 1, TAPU == 9 ? tap + 1 : (kx + 1) % KS);
                 __builtin_amdgcn_sched_barrier(0);
             } else if (tap > 0) loadB(tap, 0);          // requested where they are used: the scheduler's own order
@@ -816,7 +822,9 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
                 }
                 }
             }
-            if constexpr (MT >= 2 && NTB == 1 && !PRE && !(XC && !UP)) {
+            if constexpr (XO) {
+                // no tile: only the extra channel below reads the staged slab
+            } else if constexpr (MT >= 2 && NTB == 1 && !PRE && !(XC && !UP)) {
                 // r06: the A pieces of a k-block in a pinned order -- the MT lo pieces and the first hi piece in flight together, the next hi piece requested behind
                 // every lo piece's MFMA (whose registers it may take: the allocator decides, the order only makes it possible).  Left alone the scheduler sent the
                 // lo pieces through ONE register quad, a ds_read_b128 and an exposed wait each.  Same MFMAs per accumulator in the same order: bit-identical.
@@ -887,6 +895,7 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
             a.out[(size_t)b * a.H * a.W * a.ostride + a.ooff + ((size_t)gy * a.W + gx) * a.ostride + a.xco] = o;
         }
     }
+    if constexpr (XO) return;
     const float unscale = a.unscale * cm_unscale_of(e_cur);      // weight scale and activation scale, both powers of two
 
     if constexpr (F.tail != 0) {
@@ -1017,8 +1026,8 @@ int cm_launch(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, in
         else KPB_LAUNCH(ctx, tag, conv_mfma<FS>, grid, dim3(256), 0, ctx->stream, a);
         return true;
     }()) || ...);
-    return found ? KPB_OK : kpb_fail(ctx, KPB_E_INVALID, "%s: no instance for %s: ks=%d s=%d cc=%d pool_in=%d pool_out=%d xf=%d ntb=%d mt=%d xc=%d pf=%d wpre=%d pre=%d wn=%d gen=%d up=%d dil=%d tail=%d",
-        H ? "conv_mfma_h" : "conv_mfma", tag, f.ks, f.s, f.cc, f.pool_in, f.pool_out, f.xf, f.ntb, f.mt, f.xc, f.pf, f.wpre, f.pre, f.wn, f.gen, f.up, f.dil, f.tail);
+    return found ? KPB_OK : kpb_fail(ctx, KPB_E_INVALID, "%s: no instance for %s: ks=%d s=%d cc=%d pool_in=%d pool_out=%d xf=%d ntb=%d mt=%d xc=%d pf=%d wpre=%d pre=%d wn=%d gen=%d up=%d dil=%d tail=%d xo=%d",
+        H ? "conv_mfma_h" : "conv_mfma", tag, f.ks, f.s, f.cc, f.pool_in, f.pool_out, f.xf, f.ntb, f.mt, f.xc, f.pf, f.wpre, f.pre, f.wn, f.gen, f.up, f.dil, f.tail, f.xo);
 }
 template <CmForm... FS> int launch_conv_mfma_h(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B) { return cm_launch<true, FS...>(ctx, tag, f, a, B); }
 template <CmForm... FS> int launch_conv_mfma(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B) { return cm_launch<false, FS...>(ctx, tag, f, a, B); }

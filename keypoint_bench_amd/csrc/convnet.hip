@@ -1193,11 +1193,176 @@ __global__ __launch_bounds__(256) void disk_head(const float* __restrict__ feat,
     }
 }
 
+// The keypoint-only forward: up_3 left the score LOGIT in the score map (launch_mfma, last_only); disk_head's sigmoid, the same expression, in place
+__global__ __launch_bounds__(256) void disk_score(float* __restrict__ score, size_t npix)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < npix) score[i] = __fdiv_rn(1.0f, 1.0f + expf(-score[i]));
+}
+
+// ------------------------------------------------------------------------------------------------ DISK descriptors at keypoints
+// up_3's 128 descriptor channels at the <= 4 integer taps of every keypoint instead of at every pixel (disk.py:288, 311; utils/matcher.py:221-226).  DISK's head
+// is NOT linear -- F.normalize acts per pixel -- so each tap pixel is convolved and normalised on its own and the four unit vectors are blended with
+// sample_bilinear's coefficients in its order (match.hip): the result is kpb_sample on the dense map up to the rounding of the convolution.
+// A workgroup takes DA_KP keypoints = 32 tap pixels = ONE M tile; wave w owns n-tile w (32 channels).  Per 16-channel slab the 6 x 6 input patch the four taps of
+// a keypoint share is staged in LDS -- [up2(u2) | f1] through cm_up2_taps / cm_up2_mix (or the materialised c3 on the strict-fp32 path), InstanceNorm + PReLU by
+// (rstd, shift, slope), ZERO outside the image (the padding is of the activated tensor) -- and multiplied by the fragments stage_layer uploaded for the dense layer:
+//   H16: split-f16 triples on v_mfma_f32_32x32x16_f16 (pack_mfma_h), the patch scaled by the power of two of the image's bound of the activated input (xf[..][3]);
+//   else fp32 products on v_mfma_f32_32x32x2_f32 (pack_mfma).
+// The rows then go through LDS as fp32, a wave normalises the eight pixels of two keypoints as disk_head does and blends them.  No atomics, one fixed order.
+constexpr int DA_KP = 8, DA_PATCH = 36, DA_PPITCH = 80, DA_DPITCH = 132;        // keypoints per workgroup, patch pixels, bytes per patch pixel, floats per row
+struct DiskDescAt {
+    const float* u2;        // [B][H / 2][W / 2][64], null with c3
+    const float* f1;        // [B][H][W][16]
+    const float* c3;        // [B][H][W][80]: the materialised [up2(u2) | f1] (strict fp32)
+    const float* xf;        // [B][80][4]
+    const float* wp; const float* bias;
+    const float* pts; const int* n; float* out;
+    int H, W, pts_cols, max_n;
+    float unscale;
+};
+
+template <bool H16>
+__global__ __launch_bounds__(256) void disk_desc_at(DiskDescAt a)
+{
+    constexpr int CIN = 80, CC = 16, NCH = CIN / CC, T = 25, Q = CC / 4;
+    __shared__ __attribute__((aligned(16))) unsigned char patch[DA_KP * DA_PATCH * DA_PPITCH];
+    __shared__ __attribute__((aligned(16))) float rows[4 * DA_KP * DA_DPITCH];
+    __shared__ int s_x0[DA_KP], s_y0[DA_KP];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, p = lane & 31, h = lane >> 5, b = blockIdx.y;
+    const int n = a.n ? min(a.n[b], a.max_n) : a.max_n;
+    const int i0 = blockIdx.x * DA_KP;
+    if (i0 >= n) return;            // workgroup-uniform
+    const int H = a.H, W = a.W;
+    // a keypoint's coordinates as sample_bilinear takes them; the corner is clamped to [-2, size] before the conversion: every value outside has no tap inside either
+    auto corner = [&](int i, float& fx, float& fy, int& x0, int& y0) {
+        const float* pt = a.pts + ((size_t)b * a.max_n + i) * a.pts_cols;
+        const float gx = (pt[0] - 0.5f) * 2.0f, gy = (pt[1] - 0.5f) * 2.0f;
+        const float x = (gx + 1.0f) * ((float)(W - 1) / 2.0f), y = (gy + 1.0f) * ((float)(H - 1) / 2.0f);
+        const float xw = floorf(x), yn = floorf(y);
+        fx = x - xw; fy = y - yn;
+        x0 = (int)fminf(fmaxf(xw, -2.0f), (float)W); y0 = (int)fminf(fmaxf(yn, -2.0f), (float)H);
+    };
+    if (tid < DA_KP) {
+        float fx, fy; int x0, y0;
+        corner(min(i0 + tid, n - 1), fx, fy, x0, y0);
+        s_x0[tid] = x0; s_y0[tid] = y0;
+    }
+    int e = 24;
+    if constexpr (H16) {
+        float bnd = 0.0f;           // workgroup-uniform
+        for (int c = 0; c < CIN; ++c) bnd = fmaxf(bnd, a.xf[((size_t)b * CIN + c) * 4 + 3]);
+        e = cm_exp_of(bnd);
+    }
+    const float sc = cm_scale_of(e);
+    const int Hb = H / 2, Wb = W / 2;
+    // this lane's A row: tap pixel m = p of the M tile = keypoint p >> 2, tap (dy, dx) = (p >> 1 & 1, p & 1); kernel tap (ky, kx) reads patch pixel (dy + ky, dx + kx)
+    const unsigned char* arow = patch + ((p >> 2) * DA_PATCH + ((p >> 1) & 1) * 6 + (p & 1)) * DA_PPITCH + h * (H16 ? 16 : 32);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    for (int ch = 0; ch < NCH; ++ch) {
+        __syncthreads();            // the corners are visible; the previous slab's taps are done with the patch
+        for (int idx = tid; idx < DA_KP * DA_PATCH * Q; idx += 256) {
+            const int kq = idx / (DA_PATCH * Q), rem = idx - kq * (DA_PATCH * Q), px = rem / Q, q = rem - px * Q;
+            const int py = px / 6, gy = s_y0[kq] - 2 + py, gx = s_x0[kq] - 2 + (px - py * 6);
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+                if (a.c3) v = *reinterpret_cast<const float4*>(a.c3 + (((size_t)b * H + gy) * W + gx) * CIN + ch * CC + 4 * q);
+                else if (ch * CC < 64) {
+                    int y0, y1, x0, x1;
+                    float ly, lx;
+                    cm_up2_taps(gy, Hb, y0, y1, ly);
+                    cm_up2_taps(gx, Wb, x0, x1, lx);
+                    const float* s = a.u2 + (size_t)b * Hb * Wb * 64 + ch * CC + 4 * q;
+                    v = cm_up2_mix(*reinterpret_cast<const float4*>(s + ((size_t)y0 * Wb + x0) * 64), *reinterpret_cast<const float4*>(s + ((size_t)y0 * Wb + x1) * 64),
+                                   *reinterpret_cast<const float4*>(s + ((size_t)y1 * Wb + x0) * 64), *reinterpret_cast<const float4*>(s + ((size_t)y1 * Wb + x1) * 64), ly, lx);
+                } else
+                    v = *reinterpret_cast<const float4*>(a.f1 + (((size_t)b * H + gy) * W + gx) * 16 + (ch * CC - 64) + 4 * q);
+                const float4* t4 = reinterpret_cast<const float4*>(a.xf + ((size_t)b * CIN + ch * CC + 4 * q) * 4);
+                const float4 t0 = t4[0], t1 = t4[1], t2 = t4[2], t3 = t4[3];
+                v.x = fmaf(v.x, t0.x, t0.y); v.x = v.x >= 0.0f ? v.x : v.x * t0.z;
+                v.y = fmaf(v.y, t1.x, t1.y); v.y = v.y >= 0.0f ? v.y : v.y * t1.z;
+                v.z = fmaf(v.z, t2.x, t2.y); v.z = v.z >= 0.0f ? v.z : v.z * t2.z;
+                v.w = fmaf(v.w, t3.x, t3.y); v.w = v.w >= 0.0f ? v.w : v.w * t3.z;
+            }
+            unsigned char* d = patch + (kq * DA_PATCH + px) * DA_PPITCH;
+            if constexpr (H16) {        // [hi: 16 halves | lo: 16 halves | pad]
+                uint2 hi, lo;
+                cm_split4(make_float4(v.x * sc, v.y * sc, v.z * sc, v.w * sc), hi, lo);
+                *reinterpret_cast<uint2*>(d + 8 * q) = hi;
+                *reinterpret_cast<uint2*>(d + 32 + 8 * q) = lo;
+            } else
+                *reinterpret_cast<float4*>(d + 16 * q) = v;       // [16 floats | pad]
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int ky = 0; ky < 5; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 5; ++kx) {
+                const int tap = ky * 5 + kx;
+                const unsigned char* ap = arow + (ky * 6 + kx) * DA_PPITCH;
+                if constexpr (H16) {
+                    // pack_mfma_h: [ntile][tap][slab][hi h0 | hi h1 | lo h0 | lo h1][32 lanes] x 8 halves
+                    const uint4* bp = reinterpret_cast<const uint4*>(a.wp) + (((size_t)wv * T + tap) * NCH + ch) * 128 + h * 32 + p;
+                    const cm_h8 Bh = __builtin_bit_cast(cm_h8, bp[0]), Bl = __builtin_bit_cast(cm_h8, bp[64]);
+                    const cm_h8 Ah = __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap)), Al = __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap + 32));
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh, acc, 0, 0, 0);     // small terms first, as conv_mfma_h
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh, acc, 0, 0, 0);
+                } else {
+                    // pack_mfma: [ntile][tap][slab][h][32 lanes][8 floats]
+                    const float4* bp = reinterpret_cast<const float4*>(a.wp + (((((size_t)wv * T + tap) * NCH + ch) * 2 + h) * 32 + p) * 8);
+                    const float4 b0 = bp[0], b1 = bp[1], a0 = *reinterpret_cast<const float4*>(ap), a1 = *reinterpret_cast<const float4*>(ap + 16);
+                    const float A[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w}, Bw[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+                    for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(A[s], Bw[s], acc, 0, 0, 0);
+                }
+            }
+    }
+    {   // D[row = tap pixel i][col = channel]: the lane holds channel 32 wv + p of pixels (r & 3) + 8 (r >> 2) + 4 h
+        const float bias = a.bias[32 * wv + p], un = H16 ? a.unscale * cm_unscale_of(e) : 1.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+            rows[i * DA_DPITCH + 32 * wv + p] = H16 ? fmaf(acc[r], un, bias) : acc[r] + bias;
+        }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int k = 0; k < 2; ++k) {
+        const int kq = 2 * wv + k, i = i0 + kq;
+        if (i >= n) break;          // wave-uniform: rows at or past n[b] are not written
+        float fx, fy; int x0, y0;
+        corner(i, fx, fy, x0, y0);
+        const float w = fx, ee = 1.0f - w, nn = fy, s = 1.0f - nn;
+        const float cf[4] = {s * ee, s * w, nn * ee, nn * w};
+        float da[4], db[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int tx = x0 + (t & 1), ty = y0 + (t >> 1);
+            const bool ok = tx >= 0 && tx < W && ty >= 0 && ty < H;
+            const float va = rows[(4 * kq + t) * DA_DPITCH + lane], vb = rows[(4 * kq + t) * DA_DPITCH + lane + 64];
+            float ss = fmaf(va, va, vb * vb);           // disk_head's sum
+            ss = kpb_wave_sum(ss);
+            const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+            da[t] = ok ? __fdiv_rn(va, nrm) : 0.0f;     // grid_sample's zero padding: a select, never 0 x something
+            db[t] = ok ? __fdiv_rn(vb, nrm) : 0.0f;
+        }
+        float* o = a.out + ((size_t)b * a.max_n + i) * 128;
+        o[lane] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(da[0], cf[0]), __fmul_rn(da[1], cf[1])), __fmul_rn(da[2], cf[2])), __fmul_rn(da[3], cf[3]));
+        o[lane + 64] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(db[0], cf[0]), __fmul_rn(db[1], cf[1])), __fmul_rn(db[2], cf[2])), __fmul_rn(db[3], cf[3]));
+    }
+}
+
 enum { DK_DOWN1, DK_DOWN2, DK_DOWN3, DK_DOWN4, DK_UP0, DK_UP1, DK_UP2, DK_UP3, DK_LAYERS };       // disk_create's plan order; down_0 is a kernel of its own
 
 struct DiskNet : kpb_net {
     Layer L[DK_LAYERS];
     const float *down0_w = nullptr, *down0_b = nullptr;
+    // what up_3 read in the last forward (dense or keypoint-only), for desc_at: u2 [B][H / 2][W / 2][64] and f1 [B][H][W][16], or on the strict-fp32 path the
+    // materialised c3 [B][H][W][80]; up_3's input transform [B][80][4].  Pieces of `act`: valid until the next forward.
+    const float *r_u2 = nullptr, *r_f1 = nullptr, *r_c3 = nullptr, *r_xf = nullptr;
     static constexpr int SUM_BLOCKS = 128;
     int stats_xf(const float* t, size_t P, int C, const float* slope, double* sums, float* xf, int batch)
     {
@@ -1225,7 +1390,6 @@ struct DiskNet : kpb_net {
         // a 16 x 16 image leaves down_4 a single pixel to normalise: the reference's InstanceNorm2d raises there ("Expected more than 1 spatial element"), so there
         // is no value to compute -- refused before anything is launched (16 x 32 and 32 x 16, a two-pixel bottleneck, are the smallest images DISK runs)
         if (H_ == 16 && W_ == 16) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: DISK cannot run a 16x16 image: its 1x1 bottleneck has no instance statistics (the reference's InstanceNorm2d raises on one spatial element)");
-        if (!desc_out) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: DISK writes its 128 x H x W descriptor map; desc_out_dev is required");
         const int H = H_, W = W_;
         const size_t P = (size_t)H * W, B = batch;
         const bool fuse_up = conv_mfma_use_h16();        // r06: the concatenated decoder inputs of up_2 and up_3 are not written (profiles/r06_disk_fused_upsample_ab.txt)
@@ -1242,10 +1406,13 @@ struct DiskNet : kpb_net {
                 c2 = fuse_up ? nullptr : a.take(B * (P / 4) * 96);      // [up(u1) | f2] and [up(u2) | f1]: only the strict-fp32 path materialises them
                 u2 = a.take(B * (P / 4) * 64);
                 c3 = fuse_up ? nullptr : a.take(B * P * 80);
-                lg = a.take(B * P * 129);
+                lg = desc_out ? a.take(B * P * 129) : nullptr;      // the keypoint-only forward (desc_out null) has no feature map: up_3 leaves the logit in score_out
             }))
             return rc;
         this->B = batch; this->H = H; this->W = W;
+        r_u2 = fuse_up ? u2 : nullptr; r_f1 = fuse_up ? f1 : nullptr; r_c3 = c3; r_xf = xf;
+        const bool kp_only = desc_out == nullptr;
+        float* up3_out = kp_only ? score_out : lg;
         hipStream_t st = ctx->stream;
         int rc;
         auto pool = [&](const float* a, float* o, int h, int w, int c) {
@@ -1288,13 +1455,25 @@ struct DiskNet : kpb_net {
         if (fuse_up) {      // r06: [up(u2) | f1] is not written -- up_3 evaluates the upsampling while it stages, the statistics come from u2 and f1
             if ((rc = stats_xf_up(u2, f1, H / 2, W / 2, 64, 16, L[DK_UP3].slope, sums, mm, xf, batch))) return rc;
             const UpSrc up{u2, 64};
-            if ((rc = launch_mfma(ctx, L[DK_UP3], f1, lg, batch, H, W, {.xf = xf, .up = &up}))) return rc;
+            if ((rc = launch_mfma(ctx, L[DK_UP3], f1, up3_out, batch, H, W, {.xf = xf, .up = &up, .last_only = kp_only}))) return rc;
         } else {
             upcat(u2, f1, c3, H / 2, W / 2, 64, 16);
             if ((rc = stats_xf(c3, P, 80, L[DK_UP3].slope, sums, xf, batch))) return rc;
-            if ((rc = launch_mfma(ctx, L[DK_UP3], c3, lg, batch, H, W, {.xf = xf}))) return rc;
+            if ((rc = launch_mfma(ctx, L[DK_UP3], c3, up3_out, batch, H, W, {.xf = xf, .last_only = kp_only}))) return rc;
         }
-        KPB_LAUNCH(ctx, "disk_head", disk_head, dim3((unsigned)((B * P + 15) / 16)), dim3(256), 0, st, lg, desc_out, score_out, B * P);
+        if (kp_only) KPB_LAUNCH(ctx, "disk_score", disk_score, dim3((unsigned)((B * P + 255) / 256)), dim3(256), 0, st, score_out, B * P);
+        else KPB_LAUNCH(ctx, "disk_head", disk_head, dim3((unsigned)((B * P + 15) / 16)), dim3(256), 0, st, lg, desc_out, score_out, B * P);
+        KPB_HIP(ctx, hipGetLastError());
+        return KPB_OK;
+    }
+    int desc_at(const float* pts, int pts_cols, int max_n, const int32_t* n_dev, float* out) override
+    {
+        if (B == 0) return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_desc_at: no forward has run");
+        const Layer& L3 = L[DK_UP3];
+        const DiskDescAt a{r_u2, r_f1, r_c3, r_xf, L3.w, L3.b, pts, n_dev, out, H, W, pts_cols, max_n, L3.unscale};
+        const dim3 grid(cdiv(max_n, DA_KP), B);
+        if (conv_mfma_use_h16()) KPB_LAUNCH(ctx, "disk_desc_at", disk_desc_at<true>, grid, dim3(256), 0, ctx->stream, a);
+        else KPB_LAUNCH(ctx, "disk_desc_at", disk_desc_at<false>, grid, dim3(256), 0, ctx->stream, a);
         KPB_HIP(ctx, hipGetLastError());
         return KPB_OK;
     }

@@ -12,47 +12,18 @@ memory format; ``.shape[2:4]``, ``.detach()`` and ``grid_sample`` all behave).  
 handle is returned instead, which ``brute_force_matcher`` samples at the keypoints (same values: the
 1x1 head and the bilinear sampling are both linear).
 """
-import torch
-
 from .. import weights as _weights
-from .._lib import ptr
-from ._base import HipNet
-
-
-class LazyDescriptors:
-    """Stands where the dense descriptor map would be; only the matcher ever looks inside it
-    (tasks pass desc_map through opaquely: MHA.py:38-39, AUC.py:119-120)."""
-
-    def __init__(self, net, shape, slot, batch_index=0):
-        self._net, self.shape, self._b, self._slot = net, torch.Size(shape), batch_index, slot
-        self._stamp = net._slot_stamp[slot]
-
-    def detach(self):
-        return self
-
-    @property
-    def device(self):
-        return self._net._device
-
-    def sample(self, pts: torch.Tensor) -> torch.Tensor:
-        """Descriptors at pts [N, >=2] (x, y normalised): what grid_sample on the dense map returns."""
-        net = self._net
-        if self._stamp != net._slot_stamp[self._slot]:
-            raise RuntimeError("LazyDescriptors used after %d later forwards of the same net; its features are gone "
-                               "(construct the net with dense_descriptors=True to keep maps alive)" % net.KEEP)
-        return net._desc_at(pts, self._slot, self._b)
+from ._base import KeypointOnlyNet, LazyDescriptors      # noqa: F401 -- LazyDescriptors lived here first and stays importable from here
 
 
 PLANS = ((8, 16, 32, 64, 64), (32, 64, 128, 128, 128))      # (c1, c2, c3, c4, dim): ALIKE-t (csrc/alike.hip) and ALIKE-l, the reference's default (csrc/alike_l.hip)
 
 
-class ALNet(HipNet):
+class ALNet(KeypointOnlyNet):
     """models/ALike.py:84-164.  The native side reads the plan from the weights' shapes; ALIKE-l has no packaged checkpoint (the reference ships none):
     ``ALNet()`` needs ``load_state_dict``, as the reference's does."""
 
     ARCH = _weights.ARCH_ALIKE
-    KEEP = 2    # dense_descriptors=False: the features of the last KEEP forwards stay alive (the reference's pattern is
-                # forward(img0), forward(img1), then the matcher: model_interface.py:205-212 -> tasks/MHA.py:38-39)
 
     def __init__(self, param=None, dense_descriptors=True):
         if param is None:
@@ -61,9 +32,7 @@ class ALNet(HipNet):
         if tuple(self.param[k] for k in ("c1", "c2", "c3", "c4", "dim")) not in PLANS:
             raise NotImplementedError("this build carries kernels for ALIKE-t (c1..c4 = 8,16,32,64, dim = 64) and "
                                       "ALIKE-l (c1..c4 = 32,64,128,128, dim = 128, the default) only")
-        super().__init__()
-        self.dense_descriptors = dense_descriptors
-        self._slot_stamp = [0] * self.KEEP
+        super().__init__(dense_descriptors)
         self.dim, self.desc_div = self.param["dim"], 1
 
     def load_state_dict(self, state_dict, strict=True):
@@ -75,35 +44,6 @@ class ALNet(HipNet):
                 raise ValueError("ALNet.load_state_dict: %s is %s in this state_dict, the plan %s needs %s" % (k, tuple(t[k].shape), self.param, shape))
         self.load_packed(_weights.pack(t, _weights.ARCH_ALIKE))
         return "<All keys matched successfully>"
-
-    def _count(self):       # keypoint-only mode: KEEP native nets, each with its own activations
-        return 1 if self.dense_descriptors else self.KEEP
-
-    def forward(self, image: torch.Tensor):
-        slot = 0 if self.dense_descriptors else self._forward_count % self.KEEP
-        score, desc = self._run(image, self.dense_descriptors, slot)
-        self._slot_stamp[slot] = self._forward_count
-        if desc is not None:
-            return score, desc.permute(0, 3, 1, 2)   # [B, dim, H, W] view, channels-last storage
-        B, _, H, W = image.shape
-        return score, LazyDescriptors(self, (B, self.dim, H, W), slot)
-
-    __call__ = forward
-
-    def _desc_at(self, pts: torch.Tensor, slot: int = 0, batch_index: int = 0):
-        p = pts.detach().to(torch.float32).contiguous()
-        n = p.shape[0]
-        out = torch.empty((n, self.dim), dtype=torch.float32, device=p.device)
-        if n == 0:
-            return out
-        if batch_index != 0 or self._last_batch() != 1:
-            raise NotImplementedError("LazyDescriptors.sample: batch_size 1 only (config/config_MHA.yaml:10); "
-                                      "use keypoint_bench_amd.pipeline for batched pairs")
-        self._ctx.check(self._ctx.lib.kpb_net_desc_at(self._handles[slot], ptr(p), p.shape[1], n, ptr(None), ptr(out)))
-        return out
-
-    def _last_batch(self):
-        return 1
 
 
 def packaged_blob() -> bytes:

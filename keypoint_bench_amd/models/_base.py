@@ -1,6 +1,7 @@
 """What every HIP-backed model object shares: `NativeOwner`, the one owner of a packed blob and the native handle(s) made from it on
 one device (the extractor nets and LightGlue), and `HipNet`, the torch.nn.Module-shaped surface of the extractor nets
-(model_interface.py:43-86 uses load_state_dict / eval / __call__)."""
+(model_interface.py:43-86 uses load_state_dict / eval / __call__).  `KeypointOnlyNet` adds the mode of the nets that can skip their dense
+descriptor map (ALNet, DISK): a `LazyDescriptors` handle stands where the map would be and the matcher samples inside the net."""
 import ctypes
 
 import torch
@@ -61,7 +62,7 @@ class NativeOwner:
 class HipNet(NativeOwner):
     ARCH = 0
     signed_scores = False       # the score map is a raw logit (any sign): detect on it with signed=True (utils/extracter.py), as the pipelines do
-    dense_descriptors = True    # forward writes the descriptor map (ALNet can be built without: the pipelines then sample inside the net)
+    dense_descriptors = True    # forward writes the descriptor map (ALNet and DISK can be built without: the pipelines then sample inside the net)
     tracked_maps = False        # with the optical_flow matcher the tracker follows the net's descriptor maps instead of the frames (model_interface.py:262-272)
 
     def __init__(self):
@@ -113,3 +114,69 @@ class HipNet(NativeOwner):
         return score, desc.permute(0, 3, 1, 2)     # [B, C, H/div, W/div] view, channels-last storage
 
     __call__ = forward
+
+
+class LazyDescriptors:
+    """Stands where the dense descriptor map would be; only the matcher ever looks inside it
+    (tasks pass desc_map through opaquely: MHA.py:38-39, AUC.py:119-120)."""
+
+    def __init__(self, net, shape, slot, batch_index=0):
+        self._net, self.shape, self._b, self._slot = net, torch.Size(shape), batch_index, slot
+        self._stamp = net._slot_stamp[slot]
+
+    def detach(self):
+        return self
+
+    @property
+    def device(self):
+        return self._net._device
+
+    def sample(self, pts: torch.Tensor) -> torch.Tensor:
+        """Descriptors at pts [N, >=2] (x, y normalised): what grid_sample on the dense map returns."""
+        net = self._net
+        if self._stamp != net._slot_stamp[self._slot]:
+            raise RuntimeError("LazyDescriptors used after %d later forwards of the same net; its features are gone "
+                               "(construct the net with dense_descriptors=True to keep maps alive)" % net.KEEP)
+        return net._desc_at(pts, self._slot, self._b)
+
+
+class KeypointOnlyNet(HipNet):
+    """A net whose native side answers kpb_net_forward(desc_out_dev = NULL) and kpb_net_desc_at.  With dense_descriptors=False `forward` returns
+    (score, LazyDescriptors) and KEEP native nets alternate, each with its own activations."""
+
+    KEEP = 2    # dense_descriptors=False: the features of the last KEEP forwards stay alive (the reference's pattern is
+                # forward(img0), forward(img1), then the matcher: model_interface.py:205-212 -> tasks/MHA.py:38-39)
+
+    def __init__(self, dense_descriptors=True):
+        super().__init__()
+        self.dense_descriptors = bool(dense_descriptors)
+        self._slot_stamp = [0] * self.KEEP
+
+    def _count(self):       # keypoint-only mode: KEEP native nets
+        return 1 if self.dense_descriptors else self.KEEP
+
+    def forward(self, image: torch.Tensor):
+        slot = 0 if self.dense_descriptors else self._forward_count % self.KEEP
+        score, desc = self._run(image, self.dense_descriptors, slot)
+        self._slot_stamp[slot] = self._forward_count
+        if desc is not None:
+            return score, desc.permute(0, 3, 1, 2)   # [B, dim, H, W] view, channels-last storage
+        B, _, H, W = image.shape
+        return score, LazyDescriptors(self, (B, self.dim, H, W), slot)
+
+    __call__ = forward
+
+    def _desc_at(self, pts: torch.Tensor, slot: int = 0, batch_index: int = 0):
+        p = pts.detach().to(torch.float32).contiguous()
+        n = p.shape[0]
+        out = torch.empty((n, self.dim), dtype=torch.float32, device=p.device)
+        if n == 0:
+            return out
+        if batch_index != 0 or self._last_batch() != 1:
+            raise NotImplementedError("LazyDescriptors.sample: batch_size 1 only (config/config_MHA.yaml:10); "
+                                      "use keypoint_bench_amd.pipeline for batched pairs")
+        self._ctx.check(self._ctx.lib.kpb_net_desc_at(self._handles[slot], ptr(p), p.shape[1], n, ptr(None), ptr(out)))
+        return out
+
+    def _last_batch(self):
+        return 1

@@ -12,7 +12,7 @@ import torch
 
 from .. import weights as _weights
 from .._lib import LgParams, c_void_p, ptr
-from ._base import NativeOwner
+from ._base import LazyDescriptors, NativeOwner
 
 _FEATURES = {"superpoint": dict(weights="superpoint_lightglue", input_dim=256, desc_scale=8),     # lightglue.py:361-385, 405-408
              "disk": dict(weights="disk_lightglue", input_dim=128, desc_scale=1)}
@@ -64,6 +64,8 @@ class LightGlue(NativeOwner):
 
     def match_indices(self, pts0, pts1, desc_map_0, desc_map_1, params):
         """Returns (pairs [K,2] int64, scores [K] float32, layers_run)."""
+        if isinstance(desc_map_0, LazyDescriptors) or isinstance(desc_map_1, LazyDescriptors):     # a net built with dense_descriptors=False
+            raise ValueError("the LightGlue matcher samples the dense descriptor map")
         if not pts0.is_cuda:
             raise RuntimeError("keypoint_bench_amd.LightGlue needs CUDA/HIP tensors (MI355X); there is no CPU path")
         dev = pts0.device

@@ -48,7 +48,8 @@ _NOT_SHIPPED = " (it is not shipped with the reference tree either)"
 _MODELS = {"Alike": ("ALike", lambda m, p, dense: m.ALNet(p if "c1" in p else None, dense_descriptors=dense), "Alike_params", None, None),
            "SuperPoint": ("SuperPoint", lambda m, p, dense: m.SuperPointNet(), "SuperPoint_params", None, _NOT_SHIPPED),
            "XFeat": ("XFeat", lambda m, p, dense: m.XFeatModel(), "XFeat_params", None, _NOT_SHIPPED),
-           "DISK": ("disk", lambda m, p, dense: m.DISK(), "DISK_params", "extractor", _NOT_SHIPPED),
+           # keypoint-only (no descriptor map) only when DISK_params itself says `dense_descriptors: False`; the caller's `dense` argument is ALIKE's
+           "DISK": ("disk", lambda m, p, dense: m.DISK(dense_descriptors=bool(p.get("dense_descriptors", True))), "DISK_params", "extractor", _NOT_SHIPPED),
            "r2d2": ("r2d2", None, "r2d2_params", None, ""),
            "EdgePoint": ("EdgePoint", lambda m, p, dense: m.EdgePoint(p), "EdgePoint_params", None, ""),
            "GoodPoint": ("GoodPoint", lambda m, p, dense: m.GoodPoint(p), "GoodPoint_params", None, ""),
@@ -75,6 +76,8 @@ def build_model(params, dense_descriptors=True):
         raise NotImplementedError("model_type %r: no MI355X kernels in this build (%s)" % (mt, _MODEL_NAMES))
     mod, make, pkey, sub, missing = _MODELS[mt]
     p = params.get(pkey) or {}
+    if mt == "DISK" and not p.get("dense_descriptors", True) and (params.get("matcher_params") or {}).get("type") == "light_glue":
+        raise ValueError("the LightGlue matcher samples the dense descriptor map")
     if mt in _NO_CHECKPOINT:
         if not p:
             raise NotImplementedError("model_type %r without %s cannot be built (the reference's own constructor call fails there); the model types of this "
