@@ -16,6 +16,7 @@
 //                  as extra K steps; score = sigmoid of row 64
 //   alike_score_lin score-only mode: the score row in its fully linear form
 //   alike_desc_at  descriptors at keypoints only: bilinear taps on f, then one 64x64 mat-vec
+#include "conv_layer.h"     // launch_maxpool_nhwc
 #include "conv_mfma.h"
 
 namespace {
@@ -2230,7 +2231,7 @@ float max_abs(const float* b, int n)
 }
 
 // The conv_mfma_h forms of blocks 3 and 4 (block_h in AlikeNet::forward): C16 / C32 for 16 / 32 input channels, 1T one n-tile per workgroup, LAT the latency
-// forms (CmForm::wpre) for fewer than 16 images, P4_LAT block 4's conv1 max-pooling x3 4 x 4 while it stages it (fewer than 16 images: see maxpool4_nhwc)
+// forms (CmForm::wpre) for fewer than 16 images, P4_LAT block 4's conv1 max-pooling x3 4 x 4 while it stages it (fewer than 16 images: see maxpool4_x3 in AlikeTrunk::trunk)
 constexpr CmForm CM_C16{.ks = 3, .s = 1, .cc = 16, .ntb = 1, .mt = 2, .wn = 2}, CM_C32{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2},
                  CM_C32_1T{.ks = 3, .s = 1, .cc = 32, .ntb = 1}, CM_C16_LAT{.ks = 3, .s = 1, .cc = 16, .wpre = true},
                  CM_C32_LAT{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .wpre = true}, CM_P4_LAT{.ks = 3, .s = 1, .cc = 32, .pool_in = true, .ntb = 1, .pf = 4, .wpre = true};
@@ -2242,29 +2243,6 @@ void launch_conv(kpb_ctx* ctx, const char* name, hipStream_t st, const ConvArgs&
 {
     constexpr int G = COUT / 16, TH = (64 / TW) * (4 / G);
     KPB_LAUNCH(ctx, name, (conv3x3_k<CIN, COUT, POOL, RES, CDS, RPOOL, true, DSOUT, TW>), dim3(cdiv(a.W, TW), cdiv(a.H, TH), B), dim3(256), 0, st, a);
-}
-
-// max_pool2d(x, 4, 4) of an NHWC map (ALike.py:143, block 4's input): one thread per pooled pixel and channel quad.  At batch size block 4's conv1 reads this
-// (19.7 MB per 512 images) instead of max-pooling x3 itself while it stages: sixteen loads per staged value, by four workgroups per tile (r06: 0.26 -> ms).
-__global__ __launch_bounds__(256) void maxpool4_nhwc(const float* __restrict__ in, float* __restrict__ out, int Ho, int Wo, int C)
-{
-    const int C4 = C / 4;
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (i >= (size_t)Ho * Wo * C4) return;
-    const int c = (int)(i % C4) * 4;
-    const size_t pix = i / C4;
-    const int y = (int)(pix / Wo), x = (int)(pix - (size_t)y * Wo);
-    const float* s = in + ((b * 4 * Ho + 4 * y) * (size_t)(4 * Wo) + 4 * x) * C + c;
-    float4 m = *reinterpret_cast<const float4*>(s);
-#pragma unroll
-    for (int py = 0; py < 4; ++py)
-#pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            if (py == 0 && px == 0) continue;
-            const float4 v = *reinterpret_cast<const float4*>(s + ((size_t)py * 4 * Wo + px) * C);
-            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
-        }
-    *reinterpret_cast<float4*>(out + ((b * Ho + y) * (size_t)Wo + x) * C + c) = m;
 }
 
 void AlikeBlock1::block1(const float* img_dev, int batch, int H, int W, const B1Bufs& b)
@@ -2302,7 +2280,7 @@ int AlikeTrunk::trunk(const float* img_dev, int batch, int H, int W, bool dense,
             t3r3 = f16(2 * n_3);        // conv_mfma_h form of blocks 3 / 4: conv1's output and the identity branch side by side per pixel
             t4r4 = f16(2 * n_4);
             p2 = f16(n_3 / 2);          // max_pool2d(x2, 4): [B][H/8][W/8][16]
-            p3 = h16 && batch >= 16 ? a.take(n_4 / 2) : nullptr;        // max_pool2d(x3, 4): [B][H/32][W/32][32] (batches: maxpool4_nhwc)
+            p3 = h16 && batch >= 16 ? a.take(n_4 / 2) : nullptr;        // max_pool2d(x3, 4): [B][H/32][W/32][32] (batches: maxpool4_x3)
             // every group's share of the score logit.  (S4 carried 64 floats of slack: no kernel reads past a map's end -- alike_score_lin, their only
             // reader, clamps its taps to the map.)
             S2 = a.take(B * (P / 4)); S3 = a.take(B * (P / 64)); S4 = a.take(B * (P / 1024));
@@ -2357,8 +2335,8 @@ int AlikeTrunk::trunk(const float* img_dev, int batch, int H, int W, bool dense,
             if (int rc = block_h(blk[4], p3, t4r4, nullptr, 32, 64, H / 8, W / 8, true, 4, a4, S4, E4)) return rc;
         } else if (int rc = block_h(blk[3], p2, t3r3, x3, 16, 32, H / 2, W / 2, true))
             return rc;
-        else if (batch >= 16) {      // block 4's input pooled once, by a kernel of its own (see maxpool4_nhwc); a handful of images keep the fused form (one launch fewer)
-            KPB_LAUNCH(ctx, "maxpool4_x3", maxpool4_nhwc, dim3((unsigned)(((size_t)(H / 32) * (W / 32) * 8 + 255) / 256), batch), dim3(256), 0, st, x3, p3, H / 32, W / 32, 32);
+        else if (batch >= 16) {      // block 4's input pooled once, by a kernel of its own (r06: 0.26 -> ms); a handful of images keep the fused form (one launch fewer)
+            launch_maxpool_nhwc(ctx, "maxpool4_x3", 4, x3, p3, batch, H / 32, W / 32, 32);
             if (int rc = block_h(blk[4], p3, t4r4, x4, 32, 64, H / 8, W / 8, true)) return rc;
         } else if (int rc = block_h(blk[4], x3, t4r4, x4, 32, 64, H / 8, W / 8, false))
             return rc;
@@ -2453,88 +2431,69 @@ int AlikeNet::desc_at(const float* pts_dev, int pts_cols, int max_n, const int32
 
 // this build carries the ALIKE-t channel plan (c1..c4 = 8,16,32,64, dim 64: config/config_MHA.yaml Alike_params, EdgePoint_params)
 constexpr uint32_t c1 = 8, c2 = 16, c3 = 32, c4 = 64, dim = 64;
-struct Need { const char* n; std::vector<uint32_t> d; };
-
-// the first tensor the blob lacks or holds in another shape: the trunk's, then the head's `more`; null when all are there
-const char* first_missing(const KpbwBlob& bl, const std::vector<Need>& more)
-{
-    std::vector<Need> need = {
-        {"b1c1.w", {c1, 3, 3, 3}}, {"b1c1.b", {c1}}, {"b1c2.w", {c1, c1, 3, 3}}, {"b1c2.b", {c1}},
-        {"b2c1.w", {c2, c1, 3, 3}}, {"b2c1.b", {c2}}, {"b2c2.w", {c2, c2, 3, 3}}, {"b2c2.b", {c2}}, {"b2ds.w", {c2, c1}}, {"b2ds.b", {c2}},
-        {"b3c1.w", {c3, c2, 3, 3}}, {"b3c1.b", {c3}}, {"b3c2.w", {c3, c3, 3, 3}}, {"b3c2.b", {c3}}, {"b3ds.w", {c3, c2}}, {"b3ds.b", {c3}},
-        {"b4c1.w", {c4, c3, 3, 3}}, {"b4c1.b", {c4}}, {"b4c2.w", {c4, c4, 3, 3}}, {"b4c2.b", {c4}}, {"b4ds.w", {c4, c3}}, {"b4ds.b", {c4}},
-        {"agg1.w", {dim / 4, c1}}, {"agg2.w", {dim / 4, c2}}, {"agg3.w", {dim / 4, c3}}, {"agg4.w", {dim / 4, c4}}};
-    need.insert(need.end(), more.begin(), more.end());
-    for (auto& nd : need)
-        if (!bl.get(nd.n, nd.d)) return nd.n;
-    return nullptr;
-}
-
 // the profile names of conv1 / conv2 of blocks 2 .. 4 (AlikeTrunk::Res::prof1, prof2)
 constexpr const char* RES_PROF[5][2] = {{}, {}, {"conv3x3_b2c1", "conv3x3_b2c2"}, {"conv3x3_b3c1", "conv3x3_b3c2"}, {"conv3x3_b4c1", "conv3x3_b4c2"}};
 
 // block 1's weights as its two kernels read them, each staged with the member of net->k1 it binds
-void block1_stage(const KpbwBlob& bl, WeightStage& ws, AlikeBlock1* net)
+void block1_stage(const KpbwReader& rd, WeightStage& ws, AlikeBlock1* net)
 {
-    std::vector<float> tmp;
-    {   // block1 conv1: [co][ci][ky][kx] -> [(ci,ky,kx)][co]
-        const float* w = bl.get("b1c1.w", {c1, 3, 3, 3});
-        tmp.assign(27 * 8, 0.f);
-        for (int o = 0; o < 8; ++o) for (int k = 0; k < 27; ++k) tmp[k * 8 + o] = w[o * 27 + k];
-        ws.put(tmp, &net->k1.w1);
-        ws.put_raw(bl.get("b1c1.b", {c1}), 8, &net->k1.b1);
-        repack3x3(bl.get("b1c2.w", {c1, c1, 3, 3}), 8, 8, tmp); ws.put(tmp, &net->k1.w2);
-        {   // split-f16 fragments, each pack scaled to max |w| in [2^12, 2^13), and the constants of conv1's output bound
-            const float* w1 = bl.get("b1c1.w", {c1, 3, 3, 3});
-            const float* w2 = bl.get("b1c2.w", {c1, c1, 3, 3});
-            const float s1 = weight_scale_h(w1, 8 * 27), s2 = weight_scale_h(w2, 8 * 72);
-            ws.put(pack_b1c1_pairs(w1, s1), &net->k1.w1pk);
-            ws.put(pack_win3x4_h16(w2, s2), &net->k1.w2pk);
-            net->k1.inv_ws1 = 1.0f / s1; net->k1.inv_ws2 = 1.0f / s2;
-            net->k1.l1_c1 = l1_rows(w1, 8, 27); net->k1.bmax_c1 = max_abs(bl.get("b1c1.b", {c1}), 8);
-        }
-        ws.put_raw(bl.get("b1c2.b", {c1}), 8, &net->k1.b2);
-    }
+    const float *w1 = rd.need("b1c1.w", {c1, 3, 3, 3}), *b1 = rd.need("b1c1.b", {c1});
+    const float *w2 = rd.need("b1c2.w", {c1, c1, 3, 3}), *b2 = rd.need("b1c2.b", {c1});
+    std::vector<float> tmp(27 * 8);     // conv1: [co][ci][ky][kx] -> [(ci,ky,kx)][co]
+    for (int o = 0; o < 8; ++o) for (int k = 0; k < 27; ++k) tmp[k * 8 + o] = w1[o * 27 + k];
+    ws.put(tmp, &net->k1.w1);
+    ws.put_raw(b1, 8, &net->k1.b1);
+    repack3x3(w2, 8, 8, tmp); ws.put(tmp, &net->k1.w2);
+    // split-f16 fragments, each pack scaled to max |w| in [2^12, 2^13), and the constants of conv1's output bound
+    const float s1 = weight_scale_h(w1, 8 * 27), s2 = weight_scale_h(w2, 8 * 72);
+    ws.put(pack_b1c1_pairs(w1, s1), &net->k1.w1pk);
+    ws.put(pack_win3x4_h16(w2, s2), &net->k1.w2pk);
+    net->k1.inv_ws1 = 1.0f / s1; net->k1.inv_ws2 = 1.0f / s2;
+    net->k1.l1_c1 = l1_rows(w1, 8, 27); net->k1.bmax_c1 = max_abs(b1, 8);
+    ws.put_raw(b2, 8, &net->k1.b2);
 }
 
-// the trunk half of a create: repacks, h16 packs, L1 norms and bias maxima of blocks 1 .. 4 and the four aggregations, each staged with the members of *net it binds
-void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
+// the trunk half of a create: repacks, h16 packs, L1 norms and bias maxima of blocks 1 .. 4 and the four aggregations, each staged with the members of *net it binds.
+// The reads come first and in the order a refusal names them: block by block conv1, conv2, the identity branch (weight, then bias), then agg1 .. agg4
+void trunk_stage(const KpbwReader& rd, WeightStage& ws, AlikeTrunk* net)
 {
     std::vector<float> tmp;
-    block1_stage(bl, ws, net);
+    block1_stage(rd, ws, net);
     const uint32_t ch[5] = {0, c1, c2, c3, c4};
+    struct { const float *w1, *b1, *w2, *b2, *wd, *bd; } t[5];      // [2 .. 4]
+    const float* agg[5];                                            // [1 .. 4]
     for (int i = 2; i <= 4; ++i) {
-        char nm[16];
         const uint32_t ci = ch[i - 1], co = ch[i];
+        const std::string n = "b" + std::to_string(i);
+        t[i] = {rd.need(n + "c1.w", {co, ci, 3, 3}), rd.need(n + "c1.b", {co}), rd.need(n + "c2.w", {co, co, 3, 3}), rd.need(n + "c2.b", {co}),
+                rd.need(n + "ds.w", {co, ci}), rd.need(n + "ds.b", {co})};
+    }
+    for (int i = 1; i <= 4; ++i) agg[i] = rd.need("agg" + std::to_string(i) + ".w", {dim / 4, ch[i]});
+    for (int i = 2; i <= 4; ++i) {
+        const int ci = (int)ch[i - 1], co = (int)ch[i];
         AlikeTrunk::Res& r = net->blk[i];
         r.prof1 = RES_PROF[i][0]; r.prof2 = RES_PROF[i][1];
-        snprintf(nm, 16, "b%dc1.w", i); repack3x3(bl.get(nm, {co, ci, 3, 3}), co, ci, tmp); ws.put(tmp, &r.w1);
-        snprintf(nm, 16, "b%dc1.b", i);
-        if (i == 2) ws.put_raw(bl.get(nm, {co}), co, &r.b1, &net->k2.b1);       // alike_block2 reads conv1's bias as it is
-        else ws.put_raw(bl.get(nm, {co}), co, &r.b1);
-        snprintf(nm, 16, "b%dc2.w", i); repack3x3(bl.get(nm, {co, co, 3, 3}), co, co, tmp); ws.put(tmp, &r.w2);
-        snprintf(nm, 16, "b%dc2.b", i); ws.put_raw(bl.get(nm, {co}), co, &r.b2);
-        snprintf(nm, 16, "b%dds.w", i); transpose(bl.get(nm, {co, ci}), co, ci, tmp); ws.put(tmp, &r.dsw);
-        snprintf(nm, 16, "b%dds.b", i); ws.put_raw(bl.get(nm, {co}), co, &r.dsb);
+        repack3x3(t[i].w1, co, ci, tmp); ws.put(tmp, &r.w1);
+        if (i == 2) ws.put_raw(t[i].b1, co, &r.b1, &net->k2.b1);       // alike_block2 reads conv1's bias as it is
+        else ws.put_raw(t[i].b1, co, &r.b1);
+        repack3x3(t[i].w2, co, co, tmp); ws.put(tmp, &r.w2);
+        ws.put_raw(t[i].b2, co, &r.b2);
+        transpose(t[i].wd, co, ci, tmp); ws.put(tmp, &r.dsw);
+        ws.put_raw(t[i].bd, co, &r.dsb);
     }
     {   // block 2 on the split-f16 MFMA kernel: fragments + combined biases
-        const float* w1 = bl.get("b2c1.w", {c2, c1, 3, 3});
-        const float* w2 = bl.get("b2c2.w", {c2, c2, 3, 3});
-        const float* wd = bl.get("b2ds.w", {c2, c1});
-        const float* wa = bl.get("agg2.w", {dim / 4, c2});
+        const float *w1 = t[2].w1, *w2 = t[2].w2, *wd = t[2].wd, *wa = agg[2];
         const float s1 = weight_scale_h(w1, 16 * 72);
         const float s2 = std::min(weight_scale_h(w2, 16 * 144), weight_scale_h(wd, 16 * 8));     // conv2 and the identity branch share one accumulation
         const float sa = weight_scale_h(wa, 16 * 16);
         ws.put(pack_h16(w1, 8, nullptr, s1), &net->k2.w1pk);
         ws.put(pack_h16(w2, 16, wd, s2), &net->k2.w2pk);
-        const float* b2 = bl.get("b2c2.b", {c2});
-        const float* bd = bl.get("b2ds.b", {c2});
         tmp.assign(16, 0.f);
-        for (int i = 0; i < 16; ++i) tmp[i] = b2[i] + bd[i];
+        for (int i = 0; i < 16; ++i) tmp[i] = t[2].b2[i] + t[2].bd[i];
         ws.put(tmp, &net->k2.bsum);
         ws.put(pack_1x1_h16(wa, sa), &net->k2.wapk);
         net->k2.inv_ws1 = 1.0f / s1; net->k2.inv_ws2 = 1.0f / s2; net->k2.inv_wsa = 1.0f / sa;
-        net->k2.l1_c1 = l1_rows(w1, 16, 72); net->k2.bmax_c1 = max_abs(bl.get("b2c1.b", {c2}), 16);
+        net->k2.l1_c1 = l1_rows(w1, 16, 72); net->k2.bmax_c1 = max_abs(t[2].b1, 16);
         net->k2.l1_c2 = l1_rows(w2, 16, 144); net->k2.l1_ds = l1_rows(wd, 16, 8); net->k2.bmax_sum = max_abs(tmp.data(), 16);
     }
     // both return 1 / the power-of-two scale the split-f16 pack was made with (ConvM::unscale)
@@ -2561,17 +2520,15 @@ void trunk_stage(const KpbwBlob& bl, WeightStage& ws, AlikeTrunk* net)
         r.un1 = 1.0f / sc;
     };
     if (conv_mfma_use_h16()) {
-        put_c1ds(net->blk[3], bl.get("b3c1.w", {c3, c2, 3, 3}), bl.get("b3c1.b", {c3}), bl.get("b3ds.w", {c3, c2}), bl.get("b3ds.b", {c3}), 32, 16);
-        put_c1ds(net->blk[4], bl.get("b4c1.w", {c4, c3, 3, 3}), bl.get("b4c1.b", {c4}), bl.get("b4ds.w", {c4, c3}), bl.get("b4ds.b", {c4}), 64, 32);
+        put_c1ds(net->blk[3], t[3].w1, t[3].b1, t[3].wd, t[3].bd, 32, 16);
+        put_c1ds(net->blk[4], t[4].w1, t[4].b1, t[4].wd, t[4].bd, 64, 32);
     }
-    net->blk[3].un2 = put_mfma(&net->blk[3].w2p, bl.get("b3c2.w", {c3, c3, 3, 3}), 32, 32, 1);
-    ws.put(pad_bias(bl.get("b3c2.b", {c3}), 32, 32), &net->blk[3].b2p);
-    net->blk[4].un2 = put_mfma(&net->blk[4].w2p, bl.get("b4c2.w", {c4, c4, 3, 3}), 64, 64, 2);
-    ws.put(pad_bias(bl.get("b4c2.b", {c4}), 64, 64), &net->blk[4].b2p);
+    net->blk[3].un2 = put_mfma(&net->blk[3].w2p, t[3].w2, 32, 32, 1);
+    ws.put(pad_bias(t[3].b2, 32, 32), &net->blk[3].b2p);
+    net->blk[4].un2 = put_mfma(&net->blk[4].w2p, t[4].w2, 64, 64, 2);
+    ws.put(pad_bias(t[4].b2, 64, 64), &net->blk[4].b2p);
     for (int i = 1; i <= 4; ++i) {
-        char nm[16];
-        snprintf(nm, 16, "agg%d.w", i);
-        transpose(bl.get(nm, {dim / 4, ch[i]}), dim / 4, ch[i], tmp); ws.put(tmp, &net->kh.agg[i]);
+        transpose(agg[i], dim / 4, ch[i], tmp); ws.put(tmp, &net->kh.agg[i]);
     }
 }
 
@@ -2582,21 +2539,18 @@ int alike_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     // the plan is read from the blob: a 129 x 128 head is ALIKE-l's (c1..c4 = 32,64,128,128, dim = 128: alike_l.hip checks the trunk against it); everything else
     // is held against ALIKE-t here
     if (bl.get("head.w", {129, 128})) return alike_l_create(ctx, bl, out);
-    if (const char* n = first_missing(bl, {{"head.w", {dim + 1, dim}}}))
-        return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not ALIKE-t shaped "
-                        "(this build supports c1..c4 = 8,16,32,64, dim = 64)", n);
+    const KpbwReader rd{bl, "kpb_net_create: tensor %s missing or not ALIKE-t shaped (this build supports c1..c4 = 8,16,32,64, dim = 64)"};
     auto net = std::make_unique<AlikeNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_ALIKE; net->dim = dim; net->desc_div = 1;
     WeightStage ws;
     std::vector<float> tmp;
-    trunk_stage(bl, ws, net.get());
-    net->kh.l1_agg1 = l1_rows(bl.get("agg1.w", {dim / 4, c1}), 16, 8);
-    const float* hw = bl.get("head.w", {dim + 1, dim});
+    trunk_stage(rd, ws, net.get());
+    const float *a1w = rd.need("agg1.w", {dim / 4, c1}), *hw = rd.need("head.w", {dim + 1, dim});
+    net->kh.l1_agg1 = l1_rows(a1w, 16, 8);
     transpose(hw, 64, 64, tmp); ws.put(tmp, &net->kh.whT);
     ws.put_raw(hw + 64 * 64, 64, &net->kh.wsc);
     float hmax = 0.0f;      // rows 0..63 x channels 0..31: the part the split-f16 pack carries sets its power-of-two scale
     for (int o = 0; o < 64; ++o) for (int cc = 0; cc < 32; ++cc) hmax = std::max(hmax, std::fabs(hw[o * 64 + cc]));
-    const float* a1w = bl.get("agg1.w", {dim / 4, c1});
     const float sh = weight_scale_h(&hmax, 1), sa1 = weight_scale_h(a1w, 16 * 8);
     net->kh.inv_ws_h = 1.0f / sh; net->kh.inv_wa = 1.0f / sa1;
     ws.put(pack_head_h16(hw, sh), &net->kh.wh16);
@@ -2642,30 +2596,28 @@ int EdgePointNet::forward(const float* img_dev, int batch, int H_, int W_, float
 int edgepoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
     const uint32_t q = dim / 4;
-    if (const char* n = first_missing(bl, {{"head.w", {dim, dim}}, {"score.w", {q}}, {"score.b", {1}}, {"d8.w", {q, q}}, {"d8.b", {q}}, {"d4.w", {q, q}}, {"d4.b", {q}},
-                                           {"ct4.w", {q, q, 4, 4}}, {"ct4.b", {q}}}))
-        return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not EdgePoint shaped "
-                        "(this build supports c1..c4 = 8,16,32,64, dim = 64, single head)", n);
+    const KpbwReader rd{bl, "kpb_net_create: tensor %s missing or not EdgePoint shaped (this build supports c1..c4 = 8,16,32,64, dim = 64, single head)"};
     auto net = std::make_unique<EdgePointNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_EDGEPOINT; net->dim = dim; net->desc_div = 8;
     WeightStage ws;
     std::vector<float> tmp;
-    trunk_stage(bl, ws, net.get());
+    trunk_stage(rd, ws, net.get());
+    const float *w1 = rd.need("agg1.w", {q, c1}), *hw = rd.need("head.w", {dim, dim}), *wsr = rd.need("score.w", {q}), *bsr = rd.need("score.b", {1});
+    const float *w8 = rd.need("d8.w", {q, q}), *b8 = rd.need("d8.b", {q}), *w4 = rd.need("d4.w", {q, q}), *b4 = rd.need("d4.b", {q});      // d8.w, d4.w: [j][c]
+    const float *wt = rd.need("ct4.w", {q, q, 4, 4}), *bt = rd.need("ct4.b", {q});                                                        // ct4.w: [c][j][ky][kx]
     ws.put(std::vector<float>(64, 0.0f), &net->kh.wsc);        // where ALIKE binds its score row: the trunk kernels' score shares come out zero and are not read
-    transpose(bl.get("head.w", {dim, dim}), 64, 64, tmp); ws.put(tmp, &net->kh.whT);
+    transpose(hw, 64, 64, tmp); ws.put(tmp, &net->kh.whT);
     {   // edgepoint_score's weights: rows {conv1.weight[c][0 .. 7], conv_score.weight[c]}, then conv_score.bias
-        const float *w1 = bl.get("agg1.w", {q, c1}), *wsr = bl.get("score.w", {q});
         tmp.assign(EP_WBIAS + 1, 0.0f);
         for (int c = 0; c < 16; ++c) {
             for (int k = 0; k < 8; ++k) tmp[c * EP_WROW + k] = w1[c * 8 + k];
             tmp[c * EP_WROW + 8] = wsr[c];
         }
-        tmp[EP_WBIAS] = bl.get("score.b", {1})[0];
+        tmp[EP_WBIAS] = bsr[0];
         ws.put(tmp, &net->ke.wsc);
     }
     {   // stage-1 table of edgepoint_desc: T[m][c][j] and bias[m][j]
         std::vector<float> tab(19 * 256, 0.0f), tb(19 * 16, 0.0f);
-        const float *w8 = bl.get("d8.w", {q, q}), *w4 = bl.get("d4.w", {q, q}), *wt = bl.get("ct4.w", {q, q, 4, 4});        // [j][c], [j][c], [c][j][ky][kx]
         for (int c = 0; c < 16; ++c)
             for (int j = 0; j < 16; ++j) {
                 tab[0 * 256 + c * 16 + j] = w8[j * 16 + c];
@@ -2674,8 +2626,8 @@ int edgepoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
                 for (int k = 0; k < 16; ++k) tab[(3 + k) * 256 + c * 16 + j] = wt[(c * 16 + j) * 16 + k];
             }
         for (int j = 0; j < 16; ++j) {
-            tb[j] = bl.get("d8.b", {q})[j]; tb[16 + j] = bl.get("d4.b", {q})[j];
-            for (int k = 0; k < 16; ++k) tb[(3 + k) * 16 + j] = bl.get("ct4.b", {q})[j];
+            tb[j] = b8[j]; tb[16 + j] = b4[j];
+            for (int k = 0; k < 16; ++k) tb[(3 + k) * 16 + j] = bt[j];
         }
         ws.put(tab, &net->ke.tab); ws.put(tb, &net->ke.tabb);
     }
@@ -2684,117 +2636,92 @@ int edgepoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     return KPB_OK;
 }
 
-// ================================================================================================ GoodPoint: block 1, its own head
+// ================================================================================================ GoodPoint and LETNet: block 1, then a head of their own
 namespace {
 
-struct GoodPointNet : AlikeBlock1 {
-    struct { const float* w; } kg = {};       // goodpoint_head's weights
-    int forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev) override;
+// What the two share: the shape check, the arena, block 1 and one head kernel over x1 that writes the score map and a 3-channel map.  A net adds its name
+// (for the messages), its head's weights and the launch of its head kernel.
+struct Block1HeadNet : AlikeBlock1 {
+    const char* name = nullptr;
+    const float* head_w = nullptr;
+    virtual void launch_head(float* score, float* desc, dim3 grid) = 0;       // desc null: the score only (the repeatability task)
+    int forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev) override
+    {
+        if ((H_ % 32) || (W_ % 32))     // block 1's contract (its 2 x 2 pooled output and tiles), as for ALIKE and EdgePoint
+            return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: %s needs H and W multiples of 32 (got %dx%d)", name, H_, W_);
+        if (batch > 65535) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_net_forward: %s: at most 65535 images a call (got %d)", name, batch);
+        if (reinterpret_cast<uintptr_t>(desc_out_dev) & 15)     // the head kernels store the map's rows as float4
+            return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: %s: desc_out_dev must be 16-byte aligned", name);
+        const size_t P = (size_t)H_ * W_, B = batch;
+        const bool h16 = conv_mfma_use_h16();
+        B1Bufs b{};
+        if (int rc = kpb_carve(ctx, act, [&](Arena& a) {
+                x1 = a.take(B * P * 8);
+                b.p1 = a.take(B * (P / 4) * 8);
+                b.amax_x1 = h16 ? a.take<unsigned>(B) : nullptr;
+                b.wmax_x1 = h16 ? a.take(B * b1_waves(H_, W_)) : nullptr;
+            }))
+            return rc;
+        this->B = batch; this->H = H_; this->W = W_;
+        block1(img_dev, batch, H_, W_, b);
+        launch_head(score_out_dev, desc_out_dev, dim3(cdiv(W_, GP_TW), cdiv(H_, GP_TH), batch));
+        KPB_HIP(ctx, hipGetLastError());
+        return KPB_OK;
+    }
 };
 
-int GoodPointNet::forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev)
-{
-    if ((H_ % 32) || (W_ % 32))     // block 1's contract (its 2 x 2 pooled output and tiles), as for ALIKE and EdgePoint
-        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: GoodPoint needs H and W multiples of 32 (got %dx%d)", H_, W_);
-    if (batch > 65535) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_net_forward: GoodPoint: at most 65535 images a call (got %d)", batch);
-    if (reinterpret_cast<uintptr_t>(desc_out_dev) & 15)     // goodpoint_head stores the map's rows as float4
-        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: GoodPoint: desc_out_dev must be 16-byte aligned");
-    const size_t P = (size_t)H_ * W_, B = batch;
-    const bool h16 = conv_mfma_use_h16();
-    B1Bufs b{};
-    if (int rc = kpb_carve(ctx, act, [&](Arena& a) {
-            x1 = a.take(B * P * 8);
-            b.p1 = a.take(B * (P / 4) * 8);
-            b.amax_x1 = h16 ? a.take<unsigned>(B) : nullptr;
-            b.wmax_x1 = h16 ? a.take(B * b1_waves(H_, W_)) : nullptr;
-        }))
-        return rc;
-    this->B = batch; this->H = H_; this->W = W_;
-    block1(img_dev, batch, H_, W_, b);
-    GpHeadArgs g{x1, score_out_dev, desc_out_dev, kg.w, H_, W_};      // (a null map: the repeatability task needs the score only)
-    KPB_LAUNCH(ctx, "goodpoint_head", goodpoint_head, dim3(cdiv(W_, GP_TW), cdiv(H_, GP_TH), batch), dim3(256), 0, ctx->stream, g);
-    KPB_HIP(ctx, hipGetLastError());
-    return KPB_OK;
-}
+struct GoodPointNet : Block1HeadNet {
+    void launch_head(float* score, float* desc, dim3 grid) override
+    {
+        const GpHeadArgs g{x1, score, desc, head_w, H, W};
+        KPB_LAUNCH(ctx, "goodpoint_head", goodpoint_head, grid, dim3(256), 0, ctx->stream, g);
+    }
+};
+
+struct LetNet : Block1HeadNet {
+    void launch_head(float* score, float* desc, dim3 grid) override
+    {
+        const LetHeadArgs g{x1, score, desc, head_w, H, W};
+        KPB_LAUNCH(ctx, "letnet_head", letnet_head, grid, dim3(256), 0, ctx->stream, g);
+    }
+};
 
 }  // namespace
 
 int goodpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
-    const std::vector<Need> need = {{"b1c1.w", {c1, 3, 3, 3}}, {"b1c1.b", {c1}}, {"b1c2.w", {c1, c1, 3, 3}}, {"b1c2.b", {c1}}, {"gp.desc.w", {3, c1}},
-                                    {"gp.score.w", {c1, 3, 3}}};
-    for (auto& nd : need)
-        if (!bl.get(nd.n, nd.d))
-            return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not GoodPoint shaped (this build supports c0 = 3, c1 = 8)", nd.n);
+    const KpbwReader rd{bl, "kpb_net_create: tensor %s missing or not GoodPoint shaped (this build supports c0 = 3, c1 = 8)"};
     auto net = std::make_unique<GoodPointNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_GOODPOINT; net->dim = 3; net->desc_div = 1;
+    net->name = "GoodPoint";
     WeightStage ws;
-    block1_stage(bl, ws, net.get());
+    block1_stage(rd, ws, net.get());
     {   // goodpoint_head's weights: conv_head2 [c][ky][kx] -> [ky][kx][c], then conv_head1 [o][c] as it is
-        const float *wsr = bl.get("gp.score.w", {c1, 3, 3}), *wd = bl.get("gp.desc.w", {3, c1});
+        const float *wd = rd.need("gp.desc.w", {3, c1}), *wsr = rd.need("gp.score.w", {c1, 3, 3});
         std::vector<float> tmp(GP_WDESC + 24);
         for (int k = 0; k < 9; ++k)
             for (int c = 0; c < 8; ++c) tmp[k * 8 + c] = wsr[c * 9 + k];
         for (int i = 0; i < 24; ++i) tmp[GP_WDESC + i] = wd[i];
-        ws.put(tmp, &net->kg.w);
+        ws.put(tmp, &net->head_w);
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     *out = net.release();
     return KPB_OK;
 }
 
-// ================================================================================================ LETNet: block 1, its own head
-namespace {
-
-struct LetNet : AlikeBlock1 {
-    struct { const float* w; } kl = {};       // letnet_head's weights
-    int forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev) override;
-};
-
-// GoodPointNet::forward with another head launch
-int LetNet::forward(const float* img_dev, int batch, int H_, int W_, float* score_out_dev, float* desc_out_dev)
-{
-    if ((H_ % 32) || (W_ % 32))     // block 1's contract (its 2 x 2 pooled output and tiles), as for ALIKE, EdgePoint and GoodPoint
-        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: LETNet needs H and W multiples of 32 (got %dx%d)", H_, W_);
-    if (batch > 65535) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_net_forward: LETNet: at most 65535 images a call (got %d)", batch);
-    if (reinterpret_cast<uintptr_t>(desc_out_dev) & 15)     // letnet_head stores the map's rows as float4
-        return kpb_fail(ctx, KPB_E_INVALID, "kpb_net_forward: LETNet: desc_out_dev must be 16-byte aligned");
-    const size_t P = (size_t)H_ * W_, B = batch;
-    const bool h16 = conv_mfma_use_h16();
-    B1Bufs b{};
-    if (int rc = kpb_carve(ctx, act, [&](Arena& a) {
-            x1 = a.take(B * P * 8);
-            b.p1 = a.take(B * (P / 4) * 8);
-            b.amax_x1 = h16 ? a.take<unsigned>(B) : nullptr;
-            b.wmax_x1 = h16 ? a.take(B * b1_waves(H_, W_)) : nullptr;
-        }))
-        return rc;
-    this->B = batch; this->H = H_; this->W = W_;
-    block1(img_dev, batch, H_, W_, b);
-    LetHeadArgs g{x1, score_out_dev, desc_out_dev, kl.w, H_, W_};     // (a null map: the repeatability task needs the score only)
-    KPB_LAUNCH(ctx, "letnet_head", letnet_head, dim3(cdiv(W_, GP_TW), cdiv(H_, GP_TH), batch), dim3(256), 0, ctx->stream, g);
-    KPB_HIP(ctx, hipGetLastError());
-    return KPB_OK;
-}
-
-}  // namespace
-
 int letnet_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
-    const std::vector<Need> need = {{"b1c1.w", {c1, 3, 3, 3}}, {"b1c1.b", {c1}}, {"b1c2.w", {c1, c1, 3, 3}}, {"b1c2.b", {c1}}, {"let.conv1.w", {16, c1}},
-                                    {"let.head.w", {4, 16}}};
-    for (auto& nd : need)
-        if (!bl.get(nd.n, nd.d))
-            return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not LETNet shaped (this build supports c1 = 8, c2 = 16, colour input)", nd.n);
+    const KpbwReader rd{bl, "kpb_net_create: tensor %s missing or not LETNet shaped (this build supports c1 = 8, c2 = 16, colour input)"};
     auto net = std::make_unique<LetNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_LETNET; net->dim = 3; net->desc_div = 1;
+    net->name = "LETNet";
     WeightStage ws;
-    block1_stage(bl, ws, net.get());
+    block1_stage(rd, ws, net.get());
     {   // letnet_head's weights: conv1 [o][c], then conv_head [k][o], both as they are
-        const float *w1 = bl.get("let.conv1.w", {16, c1}), *w2 = bl.get("let.head.w", {4, 16});
+        const float *w1 = rd.need("let.conv1.w", {16, c1}), *w2 = rd.need("let.head.w", {4, 16});
         std::vector<float> tmp(w1, w1 + LET_WHEAD);
         tmp.insert(tmp.end(), w2, w2 + 64);
-        ws.put(tmp, &net->kl.w);
+        ws.put(tmp, &net->head_w);
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     *out = net.release();

@@ -8,10 +8,10 @@
 //     (source coordinate = destination x (in - 1) / (out - 1)); the four concatenated: 128 features per pixel.
 //  4. convhead2, 1 x 1 without bias, 128 -> 129: rows 0 .. 127 are the descriptor map (NOT normalised), row 128 through a sigmoid is the score.
 // Kernels:
-//   alike_l_conv1      block1.conv1 on the vector ALU from the planar image (r2d2_conv0's form: one pixel x 8 output channels per thread)
+//   conv_rgb32         (conv_layer.h, shared with R2D2) block1.conv1 on the vector ALU from the planar image: one pixel x 8 output channels per thread
 //   conv_mfma_h        every other 3 x 3 layer; KPB_FP32_MATRIX=1: conv_mfma
 //   gemm_h             the 1 x 1 layers: downsample as <GE_RES_RELU> with conv2's output as the identity tile (addition commutes), agg2 .. agg4 plain
-//   alike_l_maxpool    max_pool2d(x, K, K) of an NHWC map, K = 2 or 4
+//   maxpool_nhwc       (conv_layer.h, shared with ALIKE-t) max_pool2d(x, K, K) of an NHWC map, K = 2 or 4
 //   alike_l_head_h     the head, split-f16: a wave takes 32 pixels of a row -- builds their 128 features in registers (agg1 as fp32 fmaf chains, the three coarse maps
 //                      gathered bilinearly), splits them at the scale of the tile's own largest magnitude, multiplies by convhead2's fragments (resident in LDS for the
 //                      life of the workgroup) as v_mfma_f32_32x32x16_f16 triples and stores 512-byte descriptor rows; <false> is the keypoint-only form: the score
@@ -29,59 +29,6 @@ namespace {
 constexpr int LQ = 32;          // channels of x1 and of every aggregated map (dim / 4)
 constexpr int LDIM = 128;       // features per pixel = descriptor channels
 constexpr int LWT = 132;        // floats of a row of the transposed head matrix [feature][output]: 128 descriptor rows + score row + pad (float4 aligned)
-
-// block1.conv1 + ReLU: one pixel x 8 output channels per thread, the 27 x 8 weights wave-uniform; reads [B][3][H][W], writes [B][H][W][32]
-__global__ __launch_bounds__(256) void alike_l_conv1(const float* __restrict__ img, float* __restrict__ out, const float* __restrict__ w /*[27][32]*/,
-                                                     const float* __restrict__ bias, int H, int W)
-{
-    const int b = blockIdx.z, cg = blockIdx.y, pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= H * W) return;
-    const int oy = pix / W, ox = pix - oy * W;
-    const float* im = img + (size_t)b * 3 * H * W;
-    float acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = bias[cg * 8 + j];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int iy = oy + ky - 1, ix = ox + kx - 1;
-            const bool in = iy >= 0 && iy < H && ix >= 0 && ix < W;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float v = in ? im[((size_t)c * H + iy) * W + ix] : 0.0f;
-                const float* wt = w + ((ky * 3 + kx) * 3 + c) * 32 + cg * 8;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[j] = fmaf(v, wt[j], acc[j]);
-            }
-        }
-    float4* o = reinterpret_cast<float4*>(out + ((size_t)b * H * W + pix) * 32 + cg * 8);
-    o[0] = make_float4(relu(acc[0]), relu(acc[1]), relu(acc[2]), relu(acc[3]));
-    o[1] = make_float4(relu(acc[4]), relu(acc[5]), relu(acc[6]), relu(acc[7]));
-}
-
-// max_pool2d(x, K, K) of an NHWC map [B][K Ho][K Wo][C] (ALike.py:139, 141, 143): one thread per pooled pixel and channel quad
-template <int K>
-__global__ __launch_bounds__(256) void alike_l_maxpool(const float* __restrict__ in, float* __restrict__ out, int Ho, int Wo, int C)
-{
-    const int C4 = C / 4;
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (i >= (size_t)Ho * Wo * C4) return;
-    const int c = (int)(i % C4) * 4;
-    const size_t pix = i / C4;
-    const int y = (int)(pix / Wo), x = (int)(pix - (size_t)y * Wo);
-    const float* s = in + ((b * K * Ho + K * y) * (size_t)(K * Wo) + K * x) * C + c;
-    float4 m = *reinterpret_cast<const float4*>(s);
-#pragma unroll
-    for (int py = 0; py < K; ++py)
-#pragma unroll
-        for (int px = 0; px < K; ++px) {
-            if (py == 0 && px == 0) continue;
-            const float4 v = *reinterpret_cast<const float4*>(s + ((size_t)py * K * Wo + px) * C);
-            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
-        }
-    *reinterpret_cast<float4*>(out + ((b * Ho + y) * (size_t)Wo + x) * C + c) = m;
-}
 
 // ------------------------------------------------------------------------------------------------ the features of a pixel
 // The four taps of nn.Upsample(scale_factor = H / Hs, 'bilinear', align_corners = True) for destination pixel (y, x): offsets in floats into one image's
@@ -393,18 +340,13 @@ std::vector<float> lh_pack_head(const float* hw, float scale)
 }
 
 struct AlikeLNet : kpb_net {
-    Layer L[AL_LAYERS];         // block1.conv1 (mfma = false) is a kernel of this file: its Layer carries the pointers only
+    Layer L[AL_LAYERS];         // block1.conv1 (mfma = false) is conv_rgb32: its Layer carries the pointers only
     const float* agg1 = nullptr;
     const uint4* wfr = nullptr;
     const float* whT = nullptr;
     float inv_ws = 1.0f;
     bool h16 = true;
     const float *x1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr;       // of the last forward: what desc_at samples
-
-    template <int K> void pool(const char* tag, const float* in, float* out, int batch, int Ho, int Wo, int C)
-    {
-        KPB_LAUNCH(ctx, tag, alike_l_maxpool<K>, dim3((unsigned)(((size_t)Ho * Wo * (C / 4) + 255) / 256), batch), dim3(256), 0, ctx->stream, in, out, Ho, Wo, C);
-    }
 
     // relu(conv2(relu(conv1(x))) + downsample(x)) (ALike.py:65-81): the 1 x 1 layer joins conv2's output as its identity tile
     int res_block(int i, const float* x, float* t, float* u, float* out, int batch, int H, int W)
@@ -440,13 +382,13 @@ struct AlikeLNet : kpb_net {
         x1 = x1m; a2 = a2m; a3 = a3m; a4 = a4m;
         hipStream_t st = ctx->stream;
         int rc;
-        KPB_LAUNCH(ctx, L[AL_B1C1].prof.c_str(), alike_l_conv1, dim3((unsigned)((P + 255) / 256), 4, batch), dim3(256), 0, st, img, c0, L[AL_B1C1].w, L[AL_B1C1].b, H, W);
+        launch_conv_rgb32(ctx, L[AL_B1C1].prof.c_str(), img, c0, L[AL_B1C1].w, L[AL_B1C1].b, batch, H, W);
         if ((rc = launch_mfma(ctx, L[AL_B1C2], c0, x1m, batch, H, W))) return rc;
-        pool<2>("alikel_pool_x1", x1m, p1, batch, H2, W2, 32);
+        launch_maxpool_nhwc(ctx, "alikel_pool_x1", 2, x1m, p1, batch, H2, W2, 32);
         if ((rc = res_block(AL_B2C1, p1, t2, u2, x2, batch, H2, W2))) return rc;
-        pool<4>("alikel_pool_x2", x2, p2, batch, H8, W8, 64);
+        launch_maxpool_nhwc(ctx, "alikel_pool_x2", 4, x2, p2, batch, H8, W8, 64);
         if ((rc = res_block(AL_B3C1, p2, t3, u3, x3, batch, H8, W8))) return rc;
-        pool<4>("alikel_pool_x3", x3, p3, batch, H32, W32, 128);
+        launch_maxpool_nhwc(ctx, "alikel_pool_x3", 4, x3, p3, batch, H32, W32, 128);
         if ((rc = res_block(AL_B4C1, p3, t4, u4, x4, batch, H32, W32))) return rc;
         if ((rc = launch_mfma(ctx, L[AL_AGG2], x2, a2m, batch, H2, W2))) return rc;
         if ((rc = launch_mfma(ctx, L[AL_AGG3], x3, a3m, batch, H8, W8))) return rc;
@@ -482,7 +424,7 @@ struct AlikeLNet : kpb_net {
 
 int alike_l_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
-    // folded tensor name, cin, cout, ks, stride, mfma, relu: block1.conv1 is a kernel of this file; conv2 of a ResBlock gets its ReLU behind the sum, in the
+    // folded tensor name, cin, cout, ks, stride, mfma, relu: block1.conv1 runs on the vector ALU (conv_rgb32); conv2 of a ResBlock gets its ReLU behind the sum, in the
     // downsample layer's epilogue; the aggregations carry no bias
     const Layer plan[] = {
         {"b1c1", 3, 32, 3, 1, false}, {"b1c2", 32, 32, 3, 1, true},
@@ -491,10 +433,8 @@ int alike_l_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         {"b4c1", 128, 128, 3, 1, true}, {"b4c2", 128, 128, 3, 1, true, false}, {"b4ds", 128, 128, 1, 1, true},
         {"agg2", 64, LQ, 1, 1, true}, {"agg3", 128, LQ, 1, 1, true}, {"agg4", 128, LQ, 1, 1, true}};
     static_assert(sizeof(plan) / sizeof(plan[0]) == AL_LAYERS, "one plan entry per AL_* index");
-    auto bad = [&](const std::string& what) {
-        return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: tensor %s missing or not ALIKE shaped (this build supports c1..c4 = 8,16,32,64, dim = 64 "
-                        "and c1..c4 = 32,64,128,128, dim = 128)", what.c_str());
-    };
+    const KpbwReader rd{bl, "kpb_net_create: tensor %s missing or not ALIKE shaped (this build supports c1..c4 = 8,16,32,64, dim = 64 "
+                            "and c1..c4 = 32,64,128,128, dim = 128)"};
     auto net = std::make_unique<AlikeLNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_ALIKE; net->dim = LDIM; net->desc_div = 1;
     net->h16 = conv_mfma_use_h16();
@@ -502,28 +442,13 @@ int alike_l_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     for (int i = 0; i < AL_LAYERS; ++i) {
         Layer& L = net->L[i] = plan[i];
         const uint32_t co = (uint32_t)L.cout, ci = (uint32_t)L.cin;
-        const bool agg = i >= AL_AGG2;
-        const float* w = L.ks == 3 ? bl.get((L.name + ".w").c_str(), {co, ci, 3, 3}) : bl.get((L.name + ".w").c_str(), {co, ci});
-        const float* b = agg ? nullptr : bl.get((L.name + ".b").c_str(), {co});
-        if (!w) return bad(L.name + ".w");
-        if (!b && !agg) return bad(L.name + ".b");
-        if (i == AL_B1C1) {     // [tap][cin][32]
-            L.prof = "alikel_b1c1";
-            std::vector<float> p(27 * 32);
-            for (int o = 0; o < 32; ++o)
-                for (int c = 0; c < 3; ++c)
-                    for (int t = 0; t < 9; ++t) p[(t * 3 + c) * 32 + o] = w[(o * 3 + c) * 9 + t];
-            ws.put(p, &L.w);
-            ws.put_raw(b, 32, &L.b);
-            continue;
-        }
+        const float* w = L.ks == 3 ? rd.need(L.name + ".w", {co, ci, 3, 3}) : rd.need(L.name + ".w", {co, ci});
+        const float* b = i >= AL_AGG2 ? nullptr : rd.need(L.name + ".b", {co});
         L.ntb = (L.ks == 3 && L.cout == 32) ? 1 : 2;        // b1c2 owns one n-tile (r2d2.hip conv1); the 1 x 1 product always reads two (the second of agg2 .. 4 is padding)
-        stage_layer(ws, L, "alikel_", w, b);
+        stage_layer(ws, L, "alikel_", w, b);        // (b1c1, mfma = false: [tap][cin][32], as conv_rgb32 reads it)
     }
-    const float* a1w = bl.get("agg1.w", {(uint32_t)LQ, (uint32_t)LQ});
-    const float* hw = bl.get("head.w", {(uint32_t)LDIM + 1, (uint32_t)LDIM});
-    if (!a1w) return bad("agg1.w");
-    if (!hw) return bad("head.w");
+    const float* a1w = rd.need("agg1.w", {(uint32_t)LQ, (uint32_t)LQ});
+    const float* hw = rd.need("head.w", {(uint32_t)LDIM + 1, (uint32_t)LDIM});
     {
         std::vector<float> t((size_t)LQ * LQ), wt((size_t)LDIM * LWT, 0.0f);
         for (int o = 0; o < LQ; ++o)

@@ -44,6 +44,16 @@ void stage_layer(WeightStage& ws, Layer& L, const char* prefix, const float* w, 
 // One layer with L.mfma on the matrix cores: (Hi, Wi) -> (Hi, Wi) / stride, halved once more with pool_out
 int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const MfmaOpt& o = {});
 
+// The first layer of the trunks that start on the planar RGB image [B][3][H][W]: 3 x 3, padding 1, bias, ReLU on the vector ALU, out [B][H][W][cout].  Weights and
+// bias as stage_layer leaves them for an mfma = false layer: [tap][c][cout].  conv_rgb32 (R2D2 conv0, ALIKE-l block1.conv1): one pixel x 8 output channels per
+// thread.  conv1a_rgb64 (SFD2 conv1a, D2-Net conv1_1): 16 lanes share a pixel and walk down a column; its 64-channel map is written and read back once (2 x 79 MB per
+// 480 x 640 image): generating it inside the next layer's staging, as SuperPoint does, is not built.
+void launch_conv_rgb32(kpb_ctx* ctx, const char* tag, const float* img, float* out, const float* w, const float* bias, int batch, int H, int W);
+void launch_conv1a_rgb64(kpb_ctx* ctx, const char* tag, const float* img, float* out, const float* w, const float* bias, int batch, int H, int W);
+
+// max_pool2d(x, K, K) of an NHWC map [B][K Ho][K Wo][C] -> [B][Ho][Wo][C], K = 2 or 4, C a multiple of 4 (the ALIKE family's pools)
+void launch_maxpool_nhwc(kpb_ctx* ctx, const char* tag, int K, const float* in, float* out, int batch, int Ho, int Wo, int C);
+
 // convnet.hip's l2norm_nhwc for the nets of other translation units: every C-channel row of an NHWC map divided by its L2 norm in place, the norm clamped from
 // below at eps_clamp when that is > 0 (F.normalize)
 void launch_l2norm_nhwc(kpb_ctx* ctx, const char* tag, float* desc, int C, size_t npix, float eps_clamp);

@@ -1,11 +1,110 @@
 // conv_layer.hip -- stage_layer and launch_mfma (conv_layer.h): the one place where the generic forms of conv_mfma_h, conv_mfma and gemm_h that the six
-// networks launch are instantiated.  A network that needs a new form adds it to the lists here.
+// networks launch are instantiated.  A network that needs a new form adds it to the lists here.  Also the small kernels more than one network's unit
+// launches, each defined here once: conv_rgb32, conv1a_rgb64, maxpool_nhwc.
 #include "conv_layer.h"
 #include "conv_mfma.h"
 
 namespace {
 
-// OIHW -> conv_valu's [tap][cin][COUT8] (convnet.hip)
+// 3 -> 32 from the planar image + ReLU: one pixel x 8 output channels per thread, the 27 x 8 weights wave-uniform; reads [B][3][H][W], writes [B][H][W][32]
+__global__ __launch_bounds__(256) void conv_rgb32(const float* __restrict__ img, float* __restrict__ out, const float* __restrict__ w /*[27][32]*/,
+                                                  const float* __restrict__ bias, int H, int W)
+{
+    const int b = blockIdx.z, cg = blockIdx.y, pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= H * W) return;
+    const int oy = pix / W, ox = pix - oy * W;
+    const float* im = img + (size_t)b * 3 * H * W;
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = bias[cg * 8 + j];
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int iy = oy + ky - 1, ix = ox + kx - 1;
+            const bool in = iy >= 0 && iy < H && ix >= 0 && ix < W;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float v = in ? im[((size_t)c * H + iy) * W + ix] : 0.0f;
+                const float* wt = w + ((ky * 3 + kx) * 3 + c) * 32 + cg * 8;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] = fmaf(v, wt[j], acc[j]);
+            }
+        }
+    float4* o = reinterpret_cast<float4*>(out + ((size_t)b * H * W + pix) * 32 + cg * 8);
+    o[0] = make_float4(relu(acc[0]), relu(acc[1]), relu(acc[2]), relu(acc[3]));
+    o[1] = make_float4(relu(acc[4]), relu(acc[5]), relu(acc[6]), relu(acc[7]));
+}
+
+// 3 -> 64 from the planar image + ReLU (27 taps; conv1a_c64's column walk): 16 lanes share a pixel, each keeps the 27 taps of its 4 output channels in registers
+// and walks down a column; a wave store is 4 whole 256-byte pixels.  Every output is bias, then the taps in (kx, channel) order of rows y - 1, y, y + 1
+// interleaved, an fma each; a tap outside the image is zero.
+__global__ __launch_bounds__(256) void conv1a_rgb64(const float* __restrict__ img, float* __restrict__ out, const float* __restrict__ w /*[3 ky][3 kx][3 c][64]*/,
+                                                     const float* __restrict__ bias, int H, int W, int rows_per_block)
+{
+    const int b = blockIdx.z, lane16 = threadIdx.x & 15, c4 = lane16 * 4;
+    const int x = blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (x >= W) return;
+    float wr[27][4], bv[4];
+#pragma unroll
+    for (int t = 0; t < 27; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wr[t][j] = w[t * 64 + c4 + j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bv[j] = bias[c4 + j];
+    const size_t P = (size_t)H * W;
+    const float* im = img + (size_t)b * 3 * P;
+    auto ld = [&](int yy, int k) {      // k = 3 kx + channel
+        const int xx = x - 1 + k / 3;
+        return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? im[(size_t)(k % 3) * P + (size_t)yy * W + xx] : 0.0f;
+    };
+    const int y0 = blockIdx.y * rows_per_block, y1 = min(y0 + rows_per_block, H);
+    float r0[9], r1[9], r2[9], r3[9];       // the row below is requested one iteration before it is used
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { r0[k] = ld(y0 - 1, k); r1[k] = ld(y0, k); r2[k] = ld(y0 + 1, k); }
+    for (int y = y0; y < y1; ++y) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) r3[k] = ld(y + 2, k);
+        float acc[4] = {bv[0], bv[1], bv[2], bv[3]};
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                acc[j] = fmaf(r0[k], wr[k][j], acc[j]);
+                acc[j] = fmaf(r1[k], wr[9 + k][j], acc[j]);
+                acc[j] = fmaf(r2[k], wr[18 + k][j], acc[j]);
+            }
+        *reinterpret_cast<float4*>(out + (((size_t)b * H + y) * W + x) * 64 + c4) = make_float4(relu(acc[0]), relu(acc[1]), relu(acc[2]), relu(acc[3]));
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { r0[k] = r1[k]; r1[k] = r2[k]; r2[k] = r3[k]; }
+    }
+}
+
+// max_pool2d(x, K, K) of an NHWC map [B][K Ho][K Wo][C] (ALike.py:139, 141, 143): one thread per pooled pixel and channel quad.  ALIKE-t at batch size: block 4's
+// conv1 reads the pooled x3 (19.7 MB per 512 images) instead of max-pooling x3 itself while it stages: sixteen loads per staged value, by four workgroups per tile
+template <int K>
+__global__ __launch_bounds__(256) void maxpool_nhwc(const float* __restrict__ in, float* __restrict__ out, int Ho, int Wo, int C)
+{
+    const int C4 = C / 4;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (i >= (size_t)Ho * Wo * C4) return;
+    const int c = (int)(i % C4) * 4;
+    const size_t pix = i / C4;
+    const int y = (int)(pix / Wo), x = (int)(pix - (size_t)y * Wo);
+    const float* s = in + ((b * K * Ho + K * y) * (size_t)(K * Wo) + K * x) * C + c;
+    float4 m = *reinterpret_cast<const float4*>(s);
+#pragma unroll
+    for (int py = 0; py < K; ++py)
+#pragma unroll
+        for (int px = 0; px < K; ++px) {
+            if (py == 0 && px == 0) continue;
+            const float4 v = *reinterpret_cast<const float4*>(s + ((size_t)py * K * Wo + px) * C);
+            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+        }
+    *reinterpret_cast<float4*>(out + ((b * Ho + y) * (size_t)Wo + x) * C + c) = m;
+}
+
+// OIHW -> [tap][cin][COUT8]: conv_valu's weights (convnet.hip), and conv_rgb32's / conv1a_rgb64's with CIN = 3
 std::vector<float> pack_valu(const float* w, int COUT, int CIN, int KS)
 {
     const int T = KS * KS, C8 = ((COUT + 7) / 8) * 8;
@@ -17,6 +116,23 @@ std::vector<float> pack_valu(const float* w, int COUT, int CIN, int KS)
 }
 
 }  // namespace
+
+void launch_conv_rgb32(kpb_ctx* ctx, const char* tag, const float* img, float* out, const float* w, const float* bias, int batch, int H, int W)
+{
+    KPB_LAUNCH(ctx, tag, conv_rgb32, dim3((unsigned)(((size_t)H * W + 255) / 256), 4, batch), dim3(256), 0, ctx->stream, img, out, w, bias, H, W);
+}
+
+void launch_conv1a_rgb64(kpb_ctx* ctx, const char* tag, const float* img, float* out, const float* w, const float* bias, int batch, int H, int W)
+{
+    KPB_LAUNCH(ctx, tag, conv1a_rgb64, dim3(cdiv(W, 16), cdiv(H, 32), batch), dim3(256), 0, ctx->stream, img, out, w, bias, H, W, 32);
+}
+
+void launch_maxpool_nhwc(kpb_ctx* ctx, const char* tag, int K, const float* in, float* out, int batch, int Ho, int Wo, int C)
+{
+    const dim3 grid((unsigned)(((size_t)Ho * Wo * (C / 4) + 255) / 256), batch);
+    if (K == 2) KPB_LAUNCH(ctx, tag, maxpool_nhwc<2>, grid, dim3(256), 0, ctx->stream, in, out, Ho, Wo, C);
+    else KPB_LAUNCH(ctx, tag, maxpool_nhwc<4>, grid, dim3(256), 0, ctx->stream, in, out, Ho, Wo, C);
+}
 
 int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B, int Hi, int Wi, const MfmaOpt& o)
 {

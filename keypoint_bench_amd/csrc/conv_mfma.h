@@ -936,7 +936,7 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
             }
             __syncthreads();
             if (F.tail == 2 && wv == 2) {
-                // max_pool2d(x, 4, 4) of the tile: 2 x 4 pooled pixels x 8 channel quads, one per lane, in maxpool4_nhwc's order
+                // max_pool2d(x, 4, 4) of the tile: 2 x 4 pooled pixels x 8 channel quads, one per lane, in maxpool_nhwc<4>'s order
                 const int pp = lane >> 3, q = lane & 7, py = pp >> 2, px = pp & 3;
                 const int Ho = a.H / 4, Wo = a.W / 4, oy = ty0 / 4 + py, ox = tx0 / 4 + px;
                 const float* s = xt + ((4 * py) * 16 + 4 * px) * XP + 4 * q;
@@ -1308,6 +1308,22 @@ inline float weight_scale_h(const float* w, size_t n)
     int e;
     std::frexp(m, &e);          // m = f * 2^e, f in [0.5, 1)
     return std::ldexp(1.0f, 13 - e);
+}
+
+// The constants of the bound |layer output| <= amax(input) l1 + bmax that a generated or fused intermediate map is split at (ConvM::pre_l1 / pre_bmax,
+// xfeat_block1_23): l1 = the largest L1 norm of the `co` rows of `per` weights, each summed in fp32 in index order, with a hair of slack for that sum's own
+// rounding; bmax = the largest |bias|
+inline void l1_bound(const float* w, const float* b, int co, int per, float* l1, float* bmax)
+{
+    float m = 0.0f, bm = 0.0f;
+    for (int o = 0; o < co; ++o) {
+        float r = 0.0f;
+        for (int k = 0; k < per; ++k) r += std::fabs(w[(size_t)o * per + k]);
+        m = std::max(m, r);
+        bm = std::max(bm, std::fabs(b[o]));
+    }
+    *l1 = m * 1.0001f;
+    *bmax = bm;
 }
 
 // The halves of one split-f16 pack, and the ONE place where the host splits a value for them: hi = f16(v) to nearest even, as the device's

@@ -766,23 +766,13 @@ int superpoint_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     auto net = std::make_unique<SuperPointNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_SUPERPOINT; net->dim = 256; net->desc_div = 8;
     WeightStage ws;
+    const KpbwReader rd{bl, "kpb_net_create: SuperPoint tensor %s missing or mis-shaped"};
     for (int i = 0; i < SP_LAYERS; ++i) {
         Layer& L = net->L[i] = plan[i];
-        const float* w = bl.get((L.name + ".weight").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
-        const float* b = bl.get((L.name + ".bias").c_str(), {(uint32_t)L.cout});
-        if (!w || !b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SuperPoint tensor %s.weight/.bias missing or mis-shaped", L.name.c_str());
+        const float* w = rd.need(L.name + ".weight", {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
+        const float* b = rd.need(L.name + ".bias", {(uint32_t)L.cout});
         stage_layer(ws, L, "sp_", w, b);
-        if (i == SP_1A) {       // |conv1a output| <= amax(gray) l1 + bmax (its channels' largest L1 norm, its largest |bias|)
-            float l1 = 0.0f, bmax = 0.0f;
-            for (int co = 0; co < L.cout; ++co) {
-                float r = 0.0f;
-                for (int k = 0; k < L.cin * 9; ++k) r += std::fabs(w[(size_t)co * L.cin * 9 + k]);
-                l1 = std::max(l1, r);
-                bmax = std::max(bmax, std::fabs(b[co]));
-            }
-            net->l1_1a = l1 * 1.0001f;      // the bound is taken in fp32: a hair of slack for its own rounding
-            net->bmax_1a = bmax;
-        }
+        if (i == SP_1A) l1_bound(w, b, L.cout, L.cin * 9, &net->l1_1a, &net->bmax_1a);      // |conv1a output| <= amax(gray) l1 + bmax
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     *out = net.release();
@@ -922,11 +912,11 @@ int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     auto net = std::make_unique<XFeatNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_XFEAT; net->dim = 64; net->desc_div = 8;
     WeightStage ws;
+    const KpbwReader rd{bl, "kpb_net_create: XFeat tensor %s missing or mis-shaped"};
     for (int i = 0; i < XF_LAYERS; ++i) {
         const XFeatPlan& q = XF[i];
-        const float* w = bl.get((std::string(q.name) + ".w").c_str(), {(uint32_t)q.cout, (uint32_t)q.cin, (uint32_t)q.ks, (uint32_t)q.ks});
-        const float* b = bl.get((std::string(q.name) + ".b").c_str(), {(uint32_t)q.cout});
-        if (!w || !b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat tensor %s.w/.b missing or mis-shaped", q.name);
+        const float* w = rd.need(std::string(q.name) + ".w", {(uint32_t)q.cout, (uint32_t)q.cin, (uint32_t)q.ks, (uint32_t)q.ks});
+        const float* b = rd.need(std::string(q.name) + ".b", {(uint32_t)q.cout});
         // the 24-channel stage (block1.3 out, block2, block3.0 in) is stored with 32 channels, the extra 8 are
         // exact zeros (zero weights, zero bias, ReLU), which puts block2 and block3.0 on the MFMA kernel
         const int cin = q.cin == 24 ? 32 : q.cin, cout = q.cout == 24 ? 32 : q.cout, T = q.ks * q.ks;
@@ -943,34 +933,23 @@ int xfeat_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         stage_layer(ws, L, "xf_", w, b);
     }
     if (conv_mfma_use_h16()) {      // the fused matrix form of block1.2 + block1.3 (xfeat_block1_23)
-        const float* wA = bl.get("block1.2.w", {8, 8, 3, 3});
-        const float* bA = bl.get("block1.2.b", {8});
-        const float* wB = bl.get("block1.3.w", {24, 8, 3, 3});
-        const float* bB = bl.get("block1.3.b", {24});
-        if (!wA || !bA || !wB || !bB || !net->L[XF_B1_2].relu || !net->L[XF_B1_3].relu)
+        const float* wA = rd.need("block1.2.w", {8, 8, 3, 3});
+        const float* bA = rd.need("block1.2.b", {8});
+        const float* wB = rd.need("block1.3.w", {24, 8, 3, 3});
+        const float* bB = rd.need("block1.3.b", {24});
+        if (!net->L[XF_B1_2].relu || !net->L[XF_B1_3].relu)
             return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat block1.2 / block1.3: unexpected layer plan");
         const float scA = weight_scale_h(wA, 8 * 8 * 9), scB = weight_scale_h(wB, 24 * 8 * 9);
         ws.put(pack_win3x4_h16(wA, scA), &net->b23.wA);
         ws.put(pack_xf_s2(wB, 24, scB), &net->b23.wB);
         ws.put(pad_bias(bA, 8, 8), &net->b23.bA);
         ws.put(pad_bias(bB, 24, 32), &net->b23.bB);
-        float l1 = 0.0f, bmax = 0.0f;
-        for (int o = 0; o < 8; ++o) {
-            float s1 = 0.0f;
-            for (int i = 0; i < 8 * 9; ++i) s1 += std::fabs(wA[(size_t)o * 72 + i]);
-            l1 = std::max(l1, s1);
-            bmax = std::max(bmax, std::fabs(bA[o]));
-        }
         net->b23.inv_wsA = 1.0f / scA;
         net->b23.inv_wsB = 1.0f / scB;
-        net->b23.l1A = l1 * 1.0001f;       // the bound is taken in fp32: a hair of slack for its own rounding
-        net->b23.bmaxA = bmax;
+        l1_bound(wA, bA, 8, 8 * 9, &net->b23.l1A, &net->b23.bmaxA);
     }
-    const float* sw = bl.get("skip1.w", {24});
-    const float* sb = bl.get("skip1.b", {24});
-    if (!sw || !sb) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: XFeat skip1 tensors missing");
-    ws.put_raw(sw, 24, &net->skip_w);
-    ws.put_raw(sb, 24, &net->skip_b);
+    ws.put_raw(rd.need("skip1.w", {24}), 24, &net->skip_w);
+    ws.put_raw(rd.need("skip1.b", {24}), 24, &net->skip_b);
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     *out = net.release();
     return KPB_OK;
@@ -1521,11 +1500,10 @@ int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     auto net = std::make_unique<DiskNet>();
     net->ctx = ctx; net->arch = KPB_ARCH_DISK; net->dim = 128; net->desc_div = 1;
     WeightStage ws;
-    auto fail = [&](const char* n) { return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: DISK tensor %s missing or mis-shaped", n); };
+    const KpbwReader rd{bl, "kpb_net_create: DISK tensor %s missing or mis-shaped"};
     {   // down_0
-        const float* w = bl.get("down0.w", {16, 3, 5, 5});
-        const float* b = bl.get("down0.b", {16});
-        if (!w || !b) return fail("down0");
+        const float* w = rd.need("down0.w", {16, 3, 5, 5});
+        const float* b = rd.need("down0.b", {16});
         std::vector<float> t(75 * 16);
         for (int o = 0; o < 16; ++o) for (int k = 0; k < 75; ++k) t[k * 16 + o] = w[o * 75 + k];
         ws.put(t, &net->down0_w);
@@ -1538,18 +1516,16 @@ int disk_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         const auto& q = plan[i];
         Layer& L = net->L[i] = Layer{q.n, q.cin, q.cout, 5, 1, true, false};
         L.cc = (q.cin % 32 == 0) ? 32 : 16;
-        const float* w = bl.get((L.name + ".w").c_str(), {(uint32_t)q.cout, (uint32_t)q.cin, 5, 5});
-        const float* b = bl.get((L.name + ".b").c_str(), {(uint32_t)q.cout});
-        const float* sl = bl.get((L.name + ".slope").c_str(), {(uint32_t)q.cin});
-        if (!w || !b || !sl) return fail(q.n);
+        const float* w = rd.need(L.name + ".w", {(uint32_t)q.cout, (uint32_t)q.cin, 5, 5});
+        const float* b = rd.need(L.name + ".b", {(uint32_t)q.cout});
+        const float* sl = rd.need(L.name + ".slope", {(uint32_t)q.cin});
         stage_layer(ws, L, "disk_", w, b);
         ws.put_raw(sl, q.cin, &L.slope);
     }
     {   // up_3: 80 -> 129 = 128 descriptor channels + the score logit, five 32-wide tiles in one workgroup
-        const float* w = bl.get("up3.w", {129, 80, 5, 5});
-        const float* b = bl.get("up3.b", {129});
-        const float* sl = bl.get("up3.slope", {80});
-        if (!w || !b || !sl) return fail("up3");
+        const float* w = rd.need("up3.w", {129, 80, 5, 5});
+        const float* b = rd.need("up3.b", {129});
+        const float* sl = rd.need("up3.slope", {80});
         Layer& L3 = net->L[DK_UP3] = Layer{"up3", 80, 129, 5, 1, true, false};
         L3.cc = 16; L3.ntb = 5;
         stage_layer(ws, L3, "disk_", w, b);

@@ -9,7 +9,7 @@
 //  4. descriptors = F.normalize(feat, dim = 1, eps 1e-12) of the PRE-ReLU map: 512 channels at 1/8 resolution (desc_div 8), stored channels-last.
 //     H and W must be multiples of 8 (the reference floor-pools other shapes; not built).
 // Kernels:
-//   conv1a_rgb64       (conv1a_rgb.h, shared with SFD2) conv1_1 on the vector ALU from the planar image
+//   conv1a_rgb64       (conv_layer.h, shared with SFD2) conv1_1 on the vector ALU from the planar image
 //   conv_mfma_h        the nine other layers as split-f16 triples (SuperPoint's 16-row form; its pool_out form for conv1_2 / conv2_2 / conv3_3; conv4_3 with
 //                      ConvM::relu = 0); KPB_FP32_MATRIX=1: conv_mfma.  conv4_3 writes the caller's descriptor buffer: the head reads the map there before
 //                      l2norm_nhwc (convnet.hip) normalises it in place, so no second 512-channel map exists.
@@ -22,7 +22,7 @@
 //                      in a batch; no float atomics
 //   d2_upsample        one thread per output pixel: the four taps each divided by the image's sum (a true division), mixed as torch mixes them
 #include "conv_layer.h"
-#include "conv1a_rgb.h"
+#include "conv_mfma.h"
 
 namespace {
 
@@ -217,19 +217,12 @@ int d2net_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     auto net = std::make_unique<D2Net>();
     net->ctx = ctx; net->arch = KPB_ARCH_D2NET; net->dim = D2_C; net->desc_div = 8;
     WeightStage ws;
+    const KpbwReader rd{bl, "kpb_net_create: D2Net tensor %s missing or mis-shaped"};
     for (int i = 0; i < D2_LAYERS; ++i) {
         Layer& L = net->L[i] = plan[i];
-        const float* w = bl.get((L.name + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, 3u, 3u});
-        const float* b = bl.get((L.name + ".b").c_str(), {(uint32_t)L.cout});
-        if (!w) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: D2Net tensor %s.w missing or mis-shaped", L.name.c_str());
-        if (!b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: D2Net tensor %s.b missing or mis-shaped", L.name.c_str());
-        if (i == D2_11) {
-            L.prof = "d2_" + L.name;
-            ws.put(pack_conv1a_rgb64(w), &L.w);
-            ws.put_raw(b, 64, &L.b);
-        } else {
-            stage_layer(ws, L, "d2_", w, b);
-        }
+        const float* w = rd.need(L.name + ".w", {(uint32_t)L.cout, (uint32_t)L.cin, 3u, 3u});
+        const float* b = rd.need(L.name + ".b", {(uint32_t)L.cout});
+        stage_layer(ws, L, "d2_", w, b);        // (conv1_1, mfma = false: [tap][c][64], as conv1a_rgb64 reads it)
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     *out = net.release();

@@ -134,8 +134,7 @@ struct Harris : kpb_net {
 
 int harris_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
 {
-    const float* plan = bl.get("harris.plan", {3});         // [block_size, ksize, k32]
-    if (!plan) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: Harris tensor harris.plan missing or mis-shaped");
+    const float* plan = KpbwReader{bl, "kpb_net_create: Harris tensor %s missing or mis-shaped"}.need("harris.plan", {3});      // [block_size, ksize, k32]
     const float b = plan[0], ks = plan[1], k = plan[2];
     if (ks != 3.0f) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_net_create: Harris ksize %g: this build carries the 3 x 3 Sobel only", (double)ks);
     if (!(b >= 2.0f && b <= 6.0f) || b != std::floor(b))

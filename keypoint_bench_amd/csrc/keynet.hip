@@ -485,15 +485,12 @@ int keynet_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     net->ctx = ctx; net->arch = KPB_ARCH_KEYNET; net->dim = 0; net->desc_div = 1;
     net->h16 = conv_mfma_use_h16();
     WeightStage ws;
-    auto bad = [&](const char* what) { return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: KeyNet tensor %s missing or mis-shaped", what); };
-    static const char* const WN[3] = {"l0.w", "l1.w", "l2.w"};
-    static const char* const BN[3] = {"l0.b", "l1.b", "l2.b"};
+    const KpbwReader rd{bl, "kpb_net_create: KeyNet tensor %s missing or mis-shaped"};
     for (int i = 0; i < 3; ++i) {
         const int cin = i ? 8 : 10;
-        const float* w = bl.get(WN[i], {8, (uint32_t)cin, 5, 5});
-        const float* b = bl.get(BN[i], {8});
-        if (!w) return bad(WN[i]);
-        if (!b) return bad(BN[i]);
+        const std::string name = "l" + std::to_string(i);
+        const float* w = rd.need(name + ".w", {8, (uint32_t)cin, 5, 5});
+        const float* b = rd.need(name + ".b", {8});
         KeyNet::Layer& L = net->lay[i];
         if (net->h16) {
             const float sc = weight_scale_h(w, (size_t)8 * cin * 25);
@@ -504,10 +501,8 @@ int keynet_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
         }
         ws.put_raw(b, 8, &L.b);
     }
-    const float* lw = bl.get("last.w", {1, 24, 5, 5});
-    const float* lb = bl.get("last.b", {1});
-    if (!lw) return bad("last.w");
-    if (!lb) return bad("last.b");
+    const float* lw = rd.need("last.w", {1, 24, 5, 5});
+    const float* lb = rd.need("last.b", {1});
     std::vector<float> hw((size_t)3 * 25 * 8);
     for (int l = 0; l < 3; ++l)
         for (int t = 0; t < 25; ++t)

@@ -4,6 +4,7 @@
 
 #include <map>
 #include <memory>
+#include <stdexcept>
 
 struct kpb_net {
     kpb_ctx* ctx = nullptr;
@@ -22,11 +23,15 @@ struct kpb_net {
     }
 };
 
+// a create's refusal of a weight blob (KpbwReader::need): what() is the whole message, guarded() answers KPB_E_WEIGHTS with it
+struct KpbwMissing : std::runtime_error { using std::runtime_error::runtime_error; };
+
 // runs network and matcher code behind the C API: no C++ exception may cross it
 template <class F> int guarded(kpb_ctx* ctx, const char* what, F&& f)
 {
     try { return f(); }
     catch (const std::bad_alloc&) { return kpb_fail(ctx, KPB_E_NOMEM, "%s: out of host memory", what); }
+    catch (const KpbwMissing& e) { return kpb_fail(ctx, KPB_E_WEIGHTS, "%s", e.what()); }
     catch (const std::exception& e) { return kpb_fail(ctx, KPB_E_INVALID, "%s: %s", what, e.what()); }
 }
 
@@ -64,6 +69,21 @@ struct KpbwBlob {
         auto it = t.find(name);
         if (it == t.end() || it->second.second != dims) return nullptr;
         return it->second.first;
+    }
+};
+
+// The one way a create reads a tensor it cannot do without: need() never returns null -- a tensor that is missing or has other dims ends the create with
+// KpbwMissing, whose text is the create's refusal sentence `fmt` with the tensor's name for its one %s.  A create binds blob and sentence once, reads in the
+// order it wants tensors named, and touches the device only after its last read (WeightStage::upload).  (KpbwBlob::get stays for questions: "is there a ...?")
+struct KpbwReader {
+    const KpbwBlob& bl;
+    const char* fmt;
+    const float* need(const std::string& name, std::vector<uint32_t> dims) const
+    {
+        if (const float* p = bl.get(name.c_str(), std::move(dims))) return p;
+        char msg[384];
+        snprintf(msg, sizeof(msg), fmt, name.c_str());
+        throw KpbwMissing(msg);
     }
 };
 

@@ -1,7 +1,7 @@
 // r2d2.hip -- N6 R2D2 (models/r2d2.py:101-141, Quad_L2Net_ConfCFS) on gfx950.  Nine convolutions at FULL resolution: the reference replaces every
 // stride by a dilation (1, 1, 1, 2, 2, 4 for the 3 x 3 layers, 4, 8, 16 for the closing 2 x 2 ones), BatchNorm(affine = False) folded at pack time
 // (weights.py fold_r2d2), then the confidence head on x^2 and the L2-normalised descriptor -- 483 168 MAC per pixel.
-//   conv0          3 -> 32 on the vector ALU from the planar image (0.2 % of the work)
+//   conv0          conv_rgb32 (conv_layer.h, shared with ALIKE-l): 3 -> 32 on the vector ALU from the planar image (0.2 % of the work)
 //   conv1, conv2   conv_mfma_h, the forms SuperPoint uses
 //   conv3 .. 5     conv_mfma_h with CmForm::dil = 2, 2, 4: the halo tile grows by (ks - 1) dil
 //   conv6 .. 8     gemm_h<.., TAPK = 2>: four taps x 128 channels gathered at (+-d / 2, +-d / 2) -- no halo in LDS
@@ -11,36 +11,6 @@
 #include "conv_mfma.h"      // relu
 
 namespace {
-
-// conv0 + ReLU: one pixel x 8 output channels per thread, the 27 x 8 weights wave-uniform; reads [B][3][H][W], writes [B][H][W][32]
-__global__ __launch_bounds__(256) void r2d2_conv0(const float* __restrict__ img, float* __restrict__ out, const float* __restrict__ w /*[27][32]*/,
-                                                  const float* __restrict__ bias, int H, int W)
-{
-    const int b = blockIdx.z, cg = blockIdx.y, pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= H * W) return;
-    const int oy = pix / W, ox = pix - oy * W;
-    const float* im = img + (size_t)b * 3 * H * W;
-    float acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = bias[cg * 8 + j];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int iy = oy + ky - 1, ix = ox + kx - 1;
-            const bool in = iy >= 0 && iy < H && ix >= 0 && ix < W;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float v = in ? im[((size_t)c * H + iy) * W + ix] : 0.0f;
-                const float* wt = w + ((ky * 3 + kx) * 3 + c) * 32 + cg * 8;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[j] = fmaf(v, wt[j], acc[j]);
-            }
-        }
-    float4* o = reinterpret_cast<float4*>(out + ((size_t)b * H * W + pix) * 32 + cg * 8);
-    o[0] = make_float4(relu(acc[0]), relu(acc[1]), relu(acc[2]), relu(acc[3]));
-    o[1] = make_float4(relu(acc[4]), relu(acc[5]), relu(acc[6]), relu(acc[7]));
-}
 
 // r2d2.py:136-141 on x = conv8's row of 128, IN PLACE on the descriptor map: reliability = softmax(clf(x^2))[1], repeatability = softplus(sal(x^2)) / (1 + softplus),
 // score = their product, desc = x / max(||x||_2, 1e-12).  One wave per pixel, RHW pixels per wave with their loads in flight together; lane l holds channels
@@ -80,7 +50,7 @@ __global__ __launch_bounds__(256) void r2d2_head(float* __restrict__ desc, float
 enum { R2_C0, R2_C1, R2_C2, R2_C3, R2_C4, R2_C5, R2_C6, R2_C7, R2_C8, R2_LAYERS };       // r2d2_create's plan order
 
 struct R2d2Net : kpb_net {
-    Layer L[R2_LAYERS];         // conv0 is a kernel of its own: its Layer carries the pointers only
+    Layer L[R2_LAYERS];         // conv0 (mfma = false) is conv_rgb32: its Layer carries the pointers only
     const float* head_w = nullptr;
     const float* head_b = nullptr;
     int forward(const float* img, int batch, int H, int W, float* score_out, float* desc_out) override
@@ -94,7 +64,7 @@ struct R2d2Net : kpb_net {
         if (int rc = kpb_carve(ctx, act, [&](Arena& a) { for (float*& q : pp) q = a.take(B * P * 128); })) return rc;
         this->B = batch; this->H = H; this->W = W;
         hipStream_t st = ctx->stream;
-        KPB_LAUNCH(ctx, "r2d2_conv0", r2d2_conv0, dim3((unsigned)((P + 255) / 256), 4, batch), dim3(256), 0, st, img, pp[0], L[R2_C0].w, L[R2_C0].b, H, W);
+        launch_conv_rgb32(ctx, "r2d2_conv0", img, pp[0], L[R2_C0].w, L[R2_C0].b, batch, H, W);
         for (int i = R2_C1; i <= R2_C8; ++i)
             if (int rc = launch_mfma(ctx, L[i], pp[(i - 1) & 1], i == R2_C8 ? desc_out : pp[i & 1], batch, H, W)) return rc;
         KPB_LAUNCH(ctx, "r2d2_head", r2d2_head, dim3((unsigned)((B * P + 15) / 16)), dim3(256), 0, st, desc_out, score_out, head_w, head_b, B * P);
@@ -116,31 +86,20 @@ int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     auto net = std::make_unique<R2d2Net>();
     net->ctx = ctx; net->arch = KPB_ARCH_R2D2; net->dim = 128; net->desc_div = 1;
     WeightStage ws;
-    auto bad = [&](const char* what) { return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: R2D2 tensor %s missing or mis-shaped", what); };
+    const KpbwReader rd{bl, "kpb_net_create: R2D2 tensor %s missing or mis-shaped"};
     for (int i = 0; i < R2_LAYERS; ++i) {
         Layer& L = net->L[i] = plan[i];
-        const float* w = bl.get((L.name + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
-        const float* b = bl.get((L.name + ".b").c_str(), {(uint32_t)L.cout});
-        if (!w || !b) return bad(L.name.c_str());
-        if (i == R2_C0) {       // conv0: [tap][cin][32]
-            std::vector<float> p(27 * 32);
-            for (int o = 0; o < 32; ++o)
-                for (int c = 0; c < 3; ++c)
-                    for (int t = 0; t < 9; ++t) p[(t * 3 + c) * 32 + o] = w[(o * 3 + c) * 9 + t];
-            ws.put(p, &L.w);
-            ws.put_raw(b, 32, &L.b);
-            continue;
-        }
+        const float* w = rd.need(L.name + ".w", {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
+        const float* b = rd.need(L.name + ".b", {(uint32_t)L.cout});
         // strict fp32: the 2 x 2, dilation-16 tile fits the LDS window in 16-channel slabs; the tap-gathered split-f16 product reads 32-channel slabs
         L.cc = (L.ks == 2 && !conv_mfma_use_h16()) ? 16 : 32;
         L.ntb = L.cout == 32 ? 1 : 2;       // conv1 owns one n-tile: the packs are n-tile-major, so its fragments sit where a two-tile pack had them and no second tile is fetched
-        stage_layer(ws, L, "", w, b);
+        stage_layer(ws, L, "", w, b);       // (conv0, mfma = false: [tap][cin][32], as conv_rgb32 reads it)
     }
-    const float* cw = bl.get("clf.w", {2, 128});
-    const float* cb = bl.get("clf.b", {2});
-    const float* sw = bl.get("sal.w", {1, 128});
-    const float* sb = bl.get("sal.b", {1});
-    if (!cw || !cb || !sw || !sb) return bad("clf / sal");
+    const float* cw = rd.need("clf.w", {2, 128});
+    const float* cb = rd.need("clf.b", {2});
+    const float* sw = rd.need("sal.w", {1, 128});
+    const float* sb = rd.need("sal.b", {1});
     std::vector<float> hw(cw, cw + 256), hb = {cb[0], cb[1], sb[0]};
     hw.insert(hw.end(), sw, sw + 128);
     ws.put(hw, &net->head_w);

@@ -9,7 +9,7 @@
 //     neighbours clamped at the edge --, argmax over the three (the first maximum wins), classes 0 / 1 / 2 -> 0.1 / 0.5 / 1.0; score = semi_norm x stability.
 //     H and W must be multiples of 8: the reference's own product fails on mismatched shapes otherwise.
 // Kernels:
-//   conv1a_rgb64       (conv1a_rgb.h, shared with D2-Net) 3 -> 64 at full resolution on the vector ALU from the planar image
+//   conv1a_rgb64       (conv_layer.h, shared with D2-Net) 3 -> 64 at full resolution on the vector ALU from the planar image
 //   conv_mfma_h        the 3 x 3 layers at stride 1 and 2 (SuperPoint's forms); KPB_FP32_MATRIX=1: conv_mfma
 //   gemm_h             the 1 x 1 layers; <GE_RES_RELU> adds the ResBlock's identity tile before the ReLU.  KPB_FP32_MATRIX=1: conv_mfma's 1 x 1 form with ConvM::res
 //   sfd2_gconv_f32     the grouped 3 x 3 as strict fp32 fmaf chains: a thread takes one pixel and four groups in turn, the 9 x 8 x 8 weights of a group wave-uniform
@@ -21,7 +21,7 @@
 //   l2norm_nhwc        (convnet.hip) F.normalize of the 128-channel rows in place, eps_clamp 1e-12
 // The dense layers are Layers staged and launched by conv_layer.h's stage_layer / launch_mfma; conv_mfma.h is here for cm_split4 and friends of the grouped kernel.
 #include "conv_layer.h"
-#include "conv1a_rgb.h"
+#include "conv_mfma.h"
 
 namespace {
 
@@ -233,7 +233,7 @@ std::vector<float> sf_pack_gconv_h16(const float* w, float scale)
 }
 
 struct Sfd2Net : kpb_net {
-    Layer L[SF_LAYERS];             // conv1a and the grouped layers (mfma = false) are kernels of this file: their Layers carry the pointers only
+    Layer L[SF_LAYERS];             // conv1a (conv1a_rgb64) and the grouped layers of this file are mfma = false: their Layers carry the pointers only
     const uint4* gw[3] = {};        // split-f16: the grouped layers' fragments (sf_pack_gconv_h16), per ResBlock
     bool h16 = true;
 
@@ -317,31 +317,25 @@ int sfd2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     net->ctx = ctx; net->arch = KPB_ARCH_SFD2; net->dim = 128; net->desc_div = 4;
     net->h16 = conv_mfma_use_h16();
     WeightStage ws;
+    const KpbwReader rd{bl, "kpb_net_create: SFD2 tensor %s missing or mis-shaped"};
     for (int i = 0; i < SF_LAYERS; ++i) {
         Layer& L = net->L[i] = plan[i];
-        const float* w = bl.get((L.name + ".w").c_str(), {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
-        const float* b = bl.get((L.name + ".b").c_str(), {(uint32_t)L.cout});
-        if (!w) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SFD2 tensor %s.w missing or mis-shaped", L.name.c_str());
-        if (!b) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: SFD2 tensor %s.b missing or mis-shaped", L.name.c_str());
-        if (L.mfma) {
+        const float* w = rd.need(L.name + ".w", {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
+        const float* b = rd.need(L.name + ".b", {(uint32_t)L.cout});
+        if (L.mfma || i == SF_1A) {     // (conv1a, mfma = false: [tap][c][64], as conv1a_rgb64 reads it)
             L.cc = L.stride == 2 ? 16 : 32;
             stage_layer(ws, L, "sfd2_", w, b);
             continue;
         }
-        L.prof = "sfd2_" + L.name;
-        if (i == SF_1A) {
-            ws.put(pack_conv1a_rgb64(w), &L.w);
-            ws.put_raw(b, 64, &L.b);
-        } else {        // the grouped 3 x 3 of a ResBlock
-            if (net->h16) {
-                const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * 9);
-                ws.put(sf_pack_gconv_h16(w, sc), &net->gw[(i - SF_R0) / 3]);
-                L.unscale = 1.0f / sc;
-            } else {
-                ws.put(sf_pack_gconv_f32(w), &L.w);
-            }
-            ws.put_raw(b, 256, &L.b);
+        L.prof = "sfd2_" + L.name;      // the grouped 3 x 3 of a ResBlock
+        if (net->h16) {
+            const float sc = weight_scale_h(w, (size_t)L.cout * L.cin * 9);
+            ws.put(sf_pack_gconv_h16(w, sc), &net->gw[(i - SF_R0) / 3]);
+            L.unscale = 1.0f / sc;
+        } else {
+            ws.put(sf_pack_gconv_f32(w), &L.w);
         }
+        ws.put_raw(b, 256, &L.b);
     }
     if (int rc = ws.upload(ctx, &net->wdev)) return rc;
     *out = net.release();

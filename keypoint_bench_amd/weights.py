@@ -58,6 +58,15 @@ def _np(v):
     return v.detach().cpu().numpy().astype(np.float64) if hasattr(v, "detach") else np.asarray(v, np.float64)
 
 
+def _check(sd, need, net, plan):
+    """Every key of `need` is in the state_dict with the shape `need` gives it, or ValueError names the net, the key and what `plan` needs."""
+    for key, shape in need.items():
+        if key not in sd:
+            raise ValueError("%s state_dict: %s is missing" % (net, key))
+        if tuple(sd[key].shape) != shape:
+            raise ValueError("%s state_dict: %s has shape %s, %s needs %s" % (net, key, tuple(sd[key].shape), plan, shape))
+
+
 def _fold(sd, conv, bn, eps=1e-5):
     w = _np(sd[conv + ".weight"])
     g, b = _np(sd[bn + ".weight"]), _np(sd[bn + ".bias"])
@@ -109,12 +118,7 @@ def fold_edgepoint(sd) -> dict:
     need.update({"convhead2.weight": (dim, dim, 1, 1), "conv_score.weight": (1, q, 1, 1), "conv_score.bias": (1,),
                  "conv_8.weight": (q, q, 1, 1), "conv_8.bias": (q,), "conv_4.weight": (q, q, 1, 1), "conv_4.bias": (q,),
                  "conv_transpose_4.weight": (q, q, 4, 4), "conv_transpose_4.bias": (q,)})
-    for key, shape in need.items():
-        if key not in sd:
-            raise ValueError("EdgePoint state_dict: %s is missing" % key)
-        if tuple(sd[key].shape) != shape:
-            raise ValueError("EdgePoint state_dict: %s has shape %s, the supported plan (c1..c4 = 8,16,32,64, dim = 64) needs %s"
-                             % (key, tuple(sd[key].shape), shape))
+    _check(sd, need, "EdgePoint", "the supported plan (c1..c4 = 8,16,32,64, dim = 64)")
     t = fold_alike(sd)
     f32 = lambda k: _np(sd[k]).astype(np.float32)
     t["score.w"], t["score.b"] = f32("conv_score.weight").reshape(q), f32("conv_score.bias")
@@ -136,11 +140,7 @@ def fold_goodpoint(sd) -> dict:
     for bn in ("bn1", "bn2"):
         for leaf in ("weight", "bias", "running_mean", "running_var"):
             need["block.%s.%s" % (bn, leaf)] = (c1,)
-    for key, shape in need.items():
-        if key not in sd:
-            raise ValueError("GoodPoint state_dict: %s is missing" % key)
-        if tuple(sd[key].shape) != shape:
-            raise ValueError("GoodPoint state_dict: %s has shape %s, the supported plan (c0 = 3, c1 = 8) needs %s" % (key, tuple(sd[key].shape), shape))
+    _check(sd, need, "GoodPoint", "the supported plan (c0 = 3, c1 = 8)")
     t = {}
     t["b1c1.w"], t["b1c1.b"] = _fold(sd, "block.conv1", "block.bn1")
     t["b1c2.w"], t["b1c2.b"] = _fold(sd, "block.conv2", "block.bn2")
@@ -161,11 +161,7 @@ def fold_letnet(sd) -> dict:
     for bn in ("bn1", "bn2"):
         for leaf in ("weight", "bias", "running_mean", "running_var"):
             need["block1.%s.%s" % (bn, leaf)] = (c1,)
-    for key, shape in need.items():
-        if key not in sd:
-            raise ValueError("LETNet state_dict: %s is missing" % key)
-        if tuple(sd[key].shape) != shape:
-            raise ValueError("LETNet state_dict: %s has shape %s, the supported plan (c1 = 8, c2 = 16, grayscale = False) needs %s" % (key, tuple(sd[key].shape), shape))
+    _check(sd, need, "LETNet", "the supported plan (c1 = 8, c2 = 16, grayscale = False)")
     t = {}
     t["b1c1.w"], t["b1c1.b"] = _fold(sd, "block1.conv1", "block1.bn1")
     t["b1c2.w"], t["b1c2.b"] = _fold(sd, "block1.conv2", "block1.bn2")
@@ -189,12 +185,7 @@ def fold_keynet(sd, eps=1e-5) -> dict:
         need.update({p + "0.weight": (nf, cin, ks, ks), p + "0.bias": (nf,)})
         for leaf in ("weight", "bias", "running_mean", "running_var"):
             need[p + "1." + leaf] = (nf,)
-    for key, shape in need.items():
-        if key not in sd:
-            raise ValueError("KeyNet state_dict: %s is missing" % key)
-        if tuple(sd[key].shape) != shape:
-            raise ValueError("KeyNet state_dict: %s has shape %s, the supported plan (num_filters = 8, num_levels = 3, kernel_size = 5) needs %s"
-                             % (key, tuple(sd[key].shape), shape))
+    _check(sd, need, "KeyNet", "the supported plan (num_filters = 8, num_levels = 3, kernel_size = 5)")
     t = {}
     for i in range(3):
         p = "feature_extractor.lb_block.conv%d." % i
@@ -268,11 +259,7 @@ def fold_sfd2(sd, eps=1e-5) -> dict:
     b' = (b - mean) g / sqrt(var + eps) + beta per output channel (b = 0 for the ResBlocks' bias-free convolutions).  Keys the forward does not use
     (num_batches_tracked, heads of other variants) are ignored, as the reference's load_state_dict(strict=False) ignores them.  Refused: a missing or
     mis-shaped tensor."""
-    for key, shape in _sfd2_need().items():
-        if key not in sd:
-            raise ValueError("SFD2 state_dict: %s is missing" % key)
-        if tuple(sd[key].shape) != shape:
-            raise ValueError("SFD2 state_dict: %s has shape %s, ResSegNetV2(outdim = 128, require_stability = True) needs %s" % (key, tuple(sd[key].shape), shape))
+    _check(sd, _sfd2_need(), "SFD2", "ResSegNetV2(outdim = 128, require_stability = True)")
     t = {}
     for name, conv, bn, affine, (co, ci, k), bias in _SFD2_LAYERS:
         w = _np(sd[conv + ".weight"])

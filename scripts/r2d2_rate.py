@@ -5,7 +5,8 @@
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python scripts/r2d2_rate.py --steps 3
     python scripts/r2d2_rate.py --trace DIR [--pairs 16]                                per-layer ms and fraction of the split-f16 roof from that trace
 
-The layers share kernels (conv6 .. 8 are one gemm_h instance), so the trace is read by launch order: the ten launches behind every r2d2_conv0."""
+The layers share kernels (conv6 .. 8 are one gemm_h instance), so the trace is read by launch order: the ten launches behind every conv_rgb32 (conv0; ALIKE-l's
+first layer is the same kernel, so a run also has to end in r2d2_head)."""
 import argparse
 import csv
 import glob
@@ -26,7 +27,7 @@ def from_trace(d, pairs):
     f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
     rows = sorted(csv.DictReader(open(f[0])), key=lambda r: int(r["Start_Timestamp"]))
     names = ["conv0"] + [p[0] for p in weights.R2D2_PLAN[1:]] + ["head"]
-    runs = [i for i, r in enumerate(rows) if "r2d2_conv0" in r["Kernel_Name"] and i + 10 < len(rows) and "r2d2_head" in rows[i + 10]["Kernel_Name"]]
+    runs = [i for i, r in enumerate(rows) if "conv_rgb32" in r["Kernel_Name"] and i + 10 < len(rows) and "r2d2_head" in rows[i + 10]["Kernel_Name"]]
     runs = runs[len(runs) // 2:]       # the later half: past allocation and the pipeline's placement probes
     ms = {n: sum((int(rows[i + k]["End_Timestamp"]) - int(rows[i + k]["Start_Timestamp"])) for i in runs) / len(runs) / 1e6 for k, n in enumerate(names)}
     out = {"forwards_read": len(runs), "images_per_forward": 2 * pairs, "kernels_ms": {n: round(v, 4) for n, v in ms.items()},

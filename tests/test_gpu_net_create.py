@@ -1,7 +1,7 @@
 """kpb_net_create and the activation arena, through the C ABI on one native net object per case.
 
 1. A weight blob that lacks a tensor, or carries it with one dimension changed, is refused by kpb_net_create itself with KPB_E_WEIGHTS and a message
-   that names the tensor or its layer -- not by a later forward -- and leaves the context able to create and run the intact net.  A first-layer and a
+   that names the tensor -- not by a later forward -- and leaves the context able to create and run the intact net.  A first-layer and a
    last-layer tensor of each of the five architectures.
    kpb_lg_create likewise: the LightGlue blob without a tensor of its first layer, of its last assignment head or of a token-confidence head, or with one
    weight a column short, is refused with the layer's name before any kernel runs; the context then creates the intact matcher and matches a pair.
@@ -91,14 +91,14 @@ def _image(seed, H, W, B=1):
 REFUSED = [
     ("alike", "b1c1.w", ALIKE_SHAPE % "b1c1.w", (32, 32)),
     ("alike", "head.w", ALIKE_SHAPE % "head.w", (32, 32)),
-    ("superpoint", "conv1a.weight", "kpb_net_create: SuperPoint tensor conv1a.weight/.bias missing or mis-shaped", (8, 8)),
-    ("superpoint", "convDb.bias", "kpb_net_create: SuperPoint tensor convDb.weight/.bias missing or mis-shaped", (8, 8)),
-    ("xfeat", "block1.2.w", "kpb_net_create: XFeat tensor block1.2.w/.b missing or mis-shaped", (32, 32)),
-    ("xfeat", "skip1.b", "kpb_net_create: XFeat skip1 tensors missing", (32, 32)),
-    ("disk", "down0.w", "kpb_net_create: DISK tensor down0 missing or mis-shaped", (16, 32)),
-    ("disk", "up3.slope", "kpb_net_create: DISK tensor up3 missing or mis-shaped", (16, 32)),
-    ("r2d2", "conv8.w", "kpb_net_create: R2D2 tensor conv8 missing or mis-shaped", (24, 40)),
-    ("r2d2", "sal.b", "kpb_net_create: R2D2 tensor clf / sal missing or mis-shaped", (24, 40)),
+    ("superpoint", "conv1a.weight", "kpb_net_create: SuperPoint tensor conv1a.weight missing or mis-shaped", (8, 8)),
+    ("superpoint", "convDb.bias", "kpb_net_create: SuperPoint tensor convDb.bias missing or mis-shaped", (8, 8)),
+    ("xfeat", "block1.2.w", "kpb_net_create: XFeat tensor block1.2.w missing or mis-shaped", (32, 32)),
+    ("xfeat", "skip1.b", "kpb_net_create: XFeat tensor skip1.b missing or mis-shaped", (32, 32)),
+    ("disk", "down0.w", "kpb_net_create: DISK tensor down0.w missing or mis-shaped", (16, 32)),
+    ("disk", "up3.slope", "kpb_net_create: DISK tensor up3.slope missing or mis-shaped", (16, 32)),
+    ("r2d2", "conv8.w", "kpb_net_create: R2D2 tensor conv8.w missing or mis-shaped", (24, 40)),
+    ("r2d2", "sal.b", "kpb_net_create: R2D2 tensor sal.b missing or mis-shaped", (24, 40)),
 ]
 
 
