@@ -94,12 +94,26 @@ int kpb_sync(kpb_ctx* ctx);
  *                              was, and kpb_match_counts has nothing to report until the next match.
  *   KPB_OPT_LK_PYRLK           0 (default).  1: kpb_lk_track_batch runs the pyramidal tracker behind optical_flow_cv (restated, cv2 parity unpinned) in place of the tensor
  *                              tracker: its section below defines the option's number and the arguments' meaning under it.  Any other value is invalid.
+ *   KPB_OPT_DETECT_REFINE      0 (default): kpb_detect returns pixel centres, x = (col + 0.5) / W, y = (row + 0.5) / H, launch for launch the library of before.  1 or 2: one
+ *                              more kernel (refine_kps) behind the selection moves the kept rows to sub-pixel positions, x = ((col + 0.5) + dx) / W, y likewise, from the
+ *                              ORIGINAL score map handed to kpb_detect (the suppressed map is zero around a kept maximum); only columns 0 and 1 of out_kps_dev change --
+ *                              the scores, out_idx_dev (still the pixel the row was selected at), out_n_dev, the row order and kpb_detect_counts are those of mode 0.
+ *                              1, quadratic: one parabola per axis through (a, m, e) = the left / centre / right (upper / centre / lower) pixels:  den = (a - m) + (e - m);
+ *                              dx = 0 on the map's first or last column (row) or unless den < 0 (a plateau, a minimum, a NaN); else dx = (a - e) / (den + den), a NaN
+ *                              becomes 0, clamped to [-0.5, 0.5].  Every operation fp32, rounded on its own: bit-equal to a numpy restatement (tests/detect_refine_cases.py).
+ *                              2, softargmax: the soft-argmax of ALIKE's DKD module, radius 2, temperature 0.1, over the 5 x 5 window's in-map taps in row-major order:
+ *                              mx = their maximum (a NaN never wins), t = (s - mx) / 0.1f, w = expf(t) (0 where s or t is NaN), dx = sum(w ox) / sum(w), dy likewise,
+ *                              clamped to [-2, 2]; a NaN (no tap with weight) becomes 0.  Equal to the restatement up to expf's last bit.
+ *                              Works under KPB_OPT_DETECT_SIGNED and with nms_dist == 0 (the centre need not be a maximum: the rules above define the answer).  A
+ *                              kpb_detect(sync = 0) keeps the mode it was enqueued under; kpb_fast_nms does not read the option.  Any other value is invalid and
+ *                              leaves the mode as it was.
  * Returns KPB_E_INVALID for an unknown option or a negative value. */
 #define KPB_OPT_COVIS_STORE_BYTES 1
 #define KPB_OPT_ALIKE_COARSE_FUSED 2
 #define KPB_OPT_DETECT_SIGNED 3
 #define KPB_OPT_SFD2_PROBE 4
 #define KPB_OPT_MATCH_METRIC 5
+#define KPB_OPT_DETECT_REFINE 7     /* 6 is KPB_OPT_LK_PYRLK, defined with its tracker below */
 int kpb_ctx_set_option(kpb_ctx* ctx, int option, int64_t value);
 
 /* Per-kernel timing for bench.py's roofline leg: when enabled every kernel launch is bracketed by two
@@ -118,7 +132,7 @@ int kpb_fast_nms(kpb_ctx* ctx, const float* score_dev, int batch, int H, int W, 
 /* ---- A5: utils/extracter.py:193-221 detection (A1 nms, A2 border, A3 compaction, A4 top-k) ---
  * score_dev [batch][H][W] fp32 (the reference's [1,1,H,W]); not modified.
  * cap = min(top_k, H*W) rows are reserved per image:
- * out_kps_dev [batch][cap][3] = (x, y, score), x = (col+0.5)/W, y = (row+0.5)/H;
+ * out_kps_dev [batch][cap][3] = (x, y, score), x = (col+0.5)/W, y = (row+0.5)/H (moved to sub-pixel positions under KPB_OPT_DETECT_REFINE);
  * out_idx_dev [batch][cap] flat raster index row*W+col (may be NULL);
  * out_n_dev   [batch] number of valid rows (<= cap).
  * Row order: raster when N <= top_k, descending score (ties: ascending raster index) otherwise.

@@ -46,6 +46,18 @@ def metric_id(metric):
     return METRICS[metric]
 
 
+# extractor_params.refine -> the value of KPB_OPT_DETECT_REFINE (include/kpb.h): sub-pixel refinement of the rows kpb_detect keeps
+REFINE = {None: 0, "none": 0, "quadratic": 1, "softargmax": 2}
+
+
+def refine_id(name):
+    """The KPB_OPT_DETECT_REFINE value of an extractor_params `refine` entry; anything but None, "none", "quadratic" and "softargmax" is a caller's
+    mistake (ValueError), not a reason to route the call elsewhere."""
+    if not (name is None or isinstance(name, str)) or name not in REFINE:
+        raise ValueError("refine=%r: the refinements are %s (or None)" % (name, ", ".join(repr(k) for k in REFINE if k)))
+    return REFINE[name]
+
+
 # name -> (restype, argtypes); mirrors include/kpb.h one to one (tests check the export list)
 SIGNATURES = {
     "kpb_version": (c_int, []),
@@ -183,6 +195,7 @@ class Context:
     OPT_SFD2_PROBE = 4              # KPB_OPT_SFD2_PROBE (a test hook)
     OPT_MATCH_METRIC = 5            # KPB_OPT_MATCH_METRIC (a KPB_METRIC_* id: METRICS above)
     OPT_LK_PYRLK = 6                # KPB_OPT_LK_PYRLK: kpb_lk_track_batch runs the pyramidal tracker behind optical_flow_cv (csrc/pyrlk.hip)
+    OPT_DETECT_REFINE = 7           # KPB_OPT_DETECT_REFINE (a REFINE value above): kpb_detect moves the kept rows to sub-pixel positions
 
     def set_option(self, option: int, value: int):
         """kpb_ctx_set_option (include/kpb.h): a limit of this context, e.g. OPT_COVIS_STORE_BYTES."""
@@ -193,8 +206,10 @@ class Context:
             self._match_metric = int(value)
         if int(option) == self.OPT_LK_PYRLK:
             self._lk_pyrlk = int(value)
+        if int(option) == self.OPT_DETECT_REFINE:
+            self._detect_refine = int(value)
 
-    _detect_signed = 0      # what OPT_DETECT_SIGNED was last set to (the library has no getter)
+    _detect_signed = 0     # what OPT_DETECT_SIGNED was last set to (the library has no getter)
 
     @contextlib.contextmanager
     def detect_signed(self, on: bool):
@@ -238,6 +253,22 @@ class Context:
         finally:
             if self._lk_pyrlk != before:
                 self.set_option(self.OPT_LK_PYRLK, before)
+
+    _detect_refine = 0      # what OPT_DETECT_REFINE was last set to
+
+    @contextlib.contextmanager
+    def detect_refine(self, mode: int):
+        """OPT_DETECT_REFINE = mode (a REFINE value: refine_id) for the kpb_detect calls inside the block; what was set before comes back afterwards, also
+        on an exception.  While both are the same -- no refinement under the default -- the option is not touched.  A pending detection (sync=0) keeps
+        the mode it was enqueued under."""
+        before = self._detect_refine
+        if int(mode) != before:
+            self.set_option(self.OPT_DETECT_REFINE, mode)
+        try:
+            yield self
+        finally:
+            if self._detect_refine != before:
+                self.set_option(self.OPT_DETECT_REFINE, before)
 
     def prof_enable(self, on: bool):
         self.check(self.lib.kpb_prof_enable(self.handle, 1 if on else 0))

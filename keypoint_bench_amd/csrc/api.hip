@@ -34,7 +34,7 @@ extern "C" __attribute__((visibility("default"))) void kpb_ctx_destroy(kpb_ctx* 
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (kpb_buf* b : {&ctx->ws_nms_state, &ctx->ws_nms_map, &ctx->ws_nms_list, &ctx->ws_nms_rounds, &ctx->ws_cand, &ctx->ws_match, &ctx->ws_misc, &ctx->ws_sel})
+    for (kpb_buf* b : {&ctx->ws_nms_state, &ctx->ws_nms_map, &ctx->ws_nms_list, &ctx->ws_nms_rounds, &ctx->ws_cand, &ctx->ws_match, &ctx->ws_misc, &ctx->ws_sel, &ctx->ws_refine})
         if (b->p) (void)hipFree(b->p);
     if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
     if (ctx->host_det) (void)hipHostFree(ctx->host_det);
@@ -82,6 +82,10 @@ extern "C" __attribute__((visibility("default"))) int kpb_ctx_set_option(kpb_ctx
     case KPB_OPT_LK_PYRLK:
         if (value > 1) return kpb_fail(ctx, KPB_E_INVALID, "kpb_ctx_set_option: KPB_OPT_LK_PYRLK takes 0 or 1 (got %lld)", (long long)value);
         ctx->lk_pyrlk = (int)value;
+        return KPB_OK;
+    case KPB_OPT_DETECT_REFINE:
+        if (value > 2) return kpb_fail(ctx, KPB_E_INVALID, "kpb_ctx_set_option: KPB_OPT_DETECT_REFINE takes 0, 1 or 2 (got %lld)", (long long)value);
+        ctx->detect_refine = (int)value;
         return KPB_OK;
     default: return kpb_fail(ctx, KPB_E_INVALID, "kpb_ctx_set_option: unknown option %d", option);
     }

@@ -1577,11 +1577,87 @@ extern "C" __attribute__((visibility("default"))) int kpb_fast_nms(kpb_ctx* ctx,
 }
 
 namespace {
+// ------------------------------------------------------------------------------------------------ sub-pixel refinement (KPB_OPT_DETECT_REFINE)
+// DESIGN.md section 4, "sub-pixel refinement".  Runs behind select_topk on the rows it kept: one lane per row reads the flat index select_topk wrote, gathers
+// <= 5 (quadratic) or <= 25 (soft-argmax) taps of the ORIGINAL score map -- the suppressed one is zero around a kept maximum -- and rewrites columns 0 and 1
+// of the row.  The count is read on the device, so nothing waits for the host.  Every operation is rounded to fp32 on its own (__f*_rn, as emit()).
+constexpr int REFINE_THREADS = 256;
+constexpr int REFINE_RADIUS = 2;            // ALIKE's DKD: radius 2 ...
+constexpr float REFINE_TEMP = 0.1f;         // ... temperature 0.1
+
+struct RefineArgs {
+    const float* score;         // [B][H][W] the map handed to kpb_detect
+    float* kps;                 // [B][top_k][3]
+    const int* idx;             // [B][top_k] flat indices of the kept rows
+    const int* n;               // [B] kept rows
+    int H, W, top_k, mode, blocks;      // blocks: workgroups per image
+};
+
+// one parabola through (a, m, e): the offset of its vertex from the centre tap, 0 where there is none to trust
+__device__ __forceinline__ float refine_parabola(float a, float m, float e)
+{
+    const float den = __fadd_rn(__fsub_rn(a, m), __fsub_rn(e, m));
+    if (!(den < 0.0f)) return 0.0f;         // a plateau, a minimum, a NaN
+    float d = __fdiv_rn(__fsub_rn(a, e), __fadd_rn(den, den));
+    if (d != d) d = 0.0f;
+    return fminf(fmaxf(d, -0.5f), 0.5f);
+}
+
+__global__ __launch_bounds__(REFINE_THREADS) void refine_kps(RefineArgs a)
+{
+    const int img = blockIdx.x / a.blocks;
+    const int i = (blockIdx.x - img * a.blocks) * REFINE_THREADS + threadIdx.x;
+    if (i >= min(max(a.n[img], 0), a.top_k)) return;
+    const unsigned idx = (unsigned)a.idx[(size_t)img * a.top_k + i];
+    if (idx >= (unsigned)(a.H * a.W)) return;       // never for a row select_topk wrote
+    const int r = idx / a.W, c = idx - r * a.W;
+    const float* s = a.score + (size_t)img * a.H * a.W;
+    float dx = 0.0f, dy = 0.0f;
+    if (a.mode == 1) {
+        const float m = s[idx];
+        if (c > 0 && c < a.W - 1) dx = refine_parabola(s[idx - 1], m, s[idx + 1]);
+        if (r > 0 && r < a.H - 1) dy = refine_parabola(s[idx - a.W], m, s[idx + a.W]);
+    } else {
+        float v[2 * REFINE_RADIUS + 1][2 * REFINE_RADIUS + 1];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int oy = -REFINE_RADIUS; oy <= REFINE_RADIUS; ++oy)
+#pragma unroll
+            for (int ox = -REFINE_RADIUS; ox <= REFINE_RADIUS; ++ox) {
+                const bool in = (unsigned)(r + oy) < (unsigned)a.H && (unsigned)(c + ox) < (unsigned)a.W;
+                const float t = in ? s[(r + oy) * a.W + (c + ox)] : NAN;       // an out-of-map tap carries no weight and never wins the maximum: a NaN tap
+                v[oy + REFINE_RADIUS][ox + REFINE_RADIUS] = t;
+                if (t > mx) mx = t;
+            }
+        float sw = 0.0f, sx = 0.0f, sy = 0.0f;
+#pragma unroll
+        for (int oy = -REFINE_RADIUS; oy <= REFINE_RADIUS; ++oy)
+#pragma unroll
+            for (int ox = -REFINE_RADIUS; ox <= REFINE_RADIUS; ++ox) {
+                const float t = __fdiv_rn(__fsub_rn(v[oy + REFINE_RADIUS][ox + REFINE_RADIUS], mx), REFINE_TEMP);
+                if (t != t) continue;           // the tap or its exponent is NaN (inf - inf): weight 0
+                const float w = expf(t);
+                sw = __fadd_rn(sw, w);
+                sx = __fadd_rn(sx, __fmul_rn(w, (float)ox));
+                sy = __fadd_rn(sy, __fmul_rn(w, (float)oy));
+            }
+        dx = __fdiv_rn(sx, sw); dy = __fdiv_rn(sy, sw);
+        if (dx != dx) dx = 0.0f;
+        if (dy != dy) dy = 0.0f;
+        dx = fminf(fmaxf(dx, -(float)REFINE_RADIUS), (float)REFINE_RADIUS);
+        dy = fminf(fmaxf(dy, -(float)REFINE_RADIUS), (float)REFINE_RADIUS);
+    }
+    float* o = a.kps + ((size_t)img * a.top_k + i) * 3;
+    o[0] = __fdiv_rn(__fadd_rn(__fadd_rn((float)c, 0.5f), dx), (float)a.W);
+    o[1] = __fdiv_rn(__fadd_rn(__fadd_rn((float)r, 0.5f), dy), (float)a.H);
+}
+
 struct DetState {
-    NmsRun nms;         // the schedule chosen at the time of the call (KPB_OPT_DETECT_SIGNED may change before kpb_detect_check), its map, batch, H, W
+    NmsRun nms;         // the schedule chosen at the time of the call (KPB_OPT_DETECT_SIGNED may change before kpb_detect_check), its map (nms.src: the caller's score_dev), batch, H, W
     unsigned long long* cand;
     kpb_detect_params prm;
     float* out_kps; int* out_idx; int* out_n;
+    int refine;         // KPB_OPT_DETECT_REFINE at the time of the call, kept like the schedule; with it out_idx is never null (the caller's, or one carved from ws_refine)
 };
 
 DetState& det_state(kpb_ctx* ctx)
@@ -1622,6 +1698,10 @@ int det_select(kpb_ctx* ctx, const DetState& d)
     }
     if (s.cbits && !s.chunk_cnt) KPB_LAUNCH(ctx, "select_topk", select_topk<true>, dim3(batch), dim3(SEL_THREADS), lds, ctx->stream, s);
     else KPB_LAUNCH(ctx, "select_topk", select_topk<false>, dim3(batch), dim3(SEL_THREADS), lds, ctx->stream, s);
+    if (d.refine) {     // the rows just written, moved to sub-pixel positions: on every re-run too, select_topk has put the pixel centres back
+        RefineArgs ra{d.nms.src, d.out_kps, d.out_idx, d.out_n, H, W, d.prm.top_k, d.refine, cdiv(d.prm.top_k, REFINE_THREADS)};
+        KPB_LAUNCH(ctx, "refine_kps", refine_kps, dim3((unsigned)batch * ra.blocks), dim3(REFINE_THREADS), 0, ctx->stream, ra);
+    }
     KPB_HIP(ctx, hipGetLastError());
     return KPB_OK;
 }
@@ -1650,6 +1730,9 @@ extern "C" __attribute__((visibility("default"))) int kpb_detect(kpb_ctx* ctx, c
     d.prm = *prm;
     if (d.prm.top_k > H * W) d.prm.top_k = H * W;   // N can never exceed H*W: same rows, smaller buffers
     d.out_kps = out_kps_dev; d.out_idx = out_idx_dev; d.out_n = out_n_dev;
+    d.refine = ctx->detect_refine;
+    if (d.refine && !d.out_idx)     // refine_kps takes (row, col) from the flat index: select_topk writes it into a buffer of the library's own
+        if (int rc = kpb_carve(ctx, ctx->ws_refine, [&](Arena& a) { d.out_idx = a.take<int>((size_t)batch * d.prm.top_k); })) return rc;
     if (int rc = kpb_carve(ctx, ctx->ws_cand, [&](Arena& a) { d.cand = a.take<unsigned long long>((size_t)batch * H * W); })) return rc;
     // tiled sweeps enqueued before the first look at the status: an ALIKE map is at its fixed point after 3-4 of them; a sweep
     // with nothing to do still costs its launch (5 us each on the single map of the drop-in path), an early look costs a

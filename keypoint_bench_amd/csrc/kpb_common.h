@@ -156,6 +156,7 @@ struct kpb_ctx {
     kpb_buf ws_misc;        // shared by the match prefilter, covisibility and LK: each carves it anew from offset 0 at every call, so nothing may be
                             // kept in it across calls (one allocation for the three keeps the footprint down)
     kpb_buf ws_sel;         // [batch][chunks] candidate counts of the two-phase selection (small batches)
+    kpb_buf ws_refine;      // [batch][top_k] flat indices for refine_kps when the caller of kpb_detect passed no out_idx_dev (KPB_OPT_DETECT_REFINE)
     // kpb_detect: select_topk leaves (last sweep that changed, negative flag, keypoint count) of every image HERE -- pinned host
     // memory the kernel writes directly -- so that completing a detection is one stream synchronisation, not two copies back
     int* host_det = nullptr;
@@ -179,6 +180,7 @@ struct kpb_ctx {
     int sfd2_probe = 0;                             // KPB_OPT_SFD2_PROBE
     int match_metric = 0;                           // KPB_OPT_MATCH_METRIC: a KPB_METRIC_* id, checked when it is set
     int lk_pyrlk = 0;                               // KPB_OPT_LK_PYRLK: kpb_lk_track_batch runs csrc/pyrlk.hip's tracker
+    int detect_refine = 0;                          // KPB_OPT_DETECT_REFINE: 0 off, 1 quadratic, 2 soft-argmax (refine_kps behind select_topk)
 };
 enum { KPB_ATTR_NMS = 1u, KPB_ATTR_HOMOGRAPHY = 2u, KPB_ATTR_ESSENTIAL = 4u, KPB_ATTR_FUNDAMENTAL = 8u, KPB_ATTR_NMS_ROUND = 16u, KPB_ATTR_SELECT = 32u,
        KPB_ATTR_ALIKE_L_HEAD = 64u };

@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from ._lib import Context, DetectParams, LgParams, MatchParams, metric_id, ptr
+from ._lib import Context, DetectParams, LgParams, MatchParams, metric_id, ptr, refine_id
 from .utils.matcher import match_ratio_of
 
 
@@ -39,6 +39,7 @@ class _Core:
         self.top_k = min(int(ep["top_k"]), H * W)
         self.dprm = DetectParams(int(ep["nms_dist"]), float(ep["threshold"]), int(ep["border_dist"]), self.top_k,
                                  float(ep["min_score"]))
+        self.refine = refine_id(ep.get("refine"))                   # extractor_params.refine: sub-pixel keypoints (KPB_OPT_DETECT_REFINE); absent = off, today's launches
         self.mprm = MatchParams(float(bf["max_distance"]), 1 if bf["cross_check"] else 0)
         self.max_ratio = match_ratio_of(bf)         # the optional max_ratio key: absent = 1.0 = off (the call is then kpb_match, launch for launch)
         net._ensure(self.device)
@@ -67,7 +68,7 @@ class _Core:
         ctx, L, net = self.ctx, self.ctx.lib, self.net
         ctx.check(L.kpb_net_forward(net._handle, ptr(images), count, self.H, self.W, ptr(self.score), ptr(self.desc)))
         net._forward_count += 1
-        with ctx.detect_signed(net.signed_scores):      # a pending detection (sync=0) keeps the setting until kpb_detect_check
+        with ctx.detect_signed(net.signed_scores), ctx.detect_refine(self.refine):      # a pending detection (sync=0) keeps both settings until kpb_detect_check
             ctx.check(L.kpb_detect(ctx.handle, ptr(self.score), count, self.H, self.W, ctypes.byref(self.dprm), ptr(kps), ptr(idx), ptr(n), sync))
 
     def _describe(self, count, pts, cols, n, sdesc):

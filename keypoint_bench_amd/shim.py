@@ -11,8 +11,9 @@ never from oracle/) and routes to it whatever lies outside the library's contrac
   * arguments the kernels do not carry (fast_nms max_iter / min_value, a metric other than euclidean / sqeuclidean / cityblock / chebyshev / cosine, nms_dist > 16, more matches
     than a RANSAC kernel holds, ALIKE channel plans other than -t, DISK variants): KPB_E_UNSUPPORTED / NotImplementedError.
 
-One thing is refused instead of routed: a brute-force call whose ``brute_force_params`` carry ``max_ratio`` < 1.  The reference's own
-``brute_force_matcher`` does not read that key, so handing it the call would drop the filter without a word: ValueError.
+Two things are refused instead of routed: a brute-force call whose ``brute_force_params`` carry ``max_ratio`` < 1, and a ``detection`` call whose
+``extractor_params`` carry ``refine`` (sub-pixel keypoints, KPB_OPT_DETECT_REFINE).  The reference's own ``brute_force_matcher`` / ``detection`` do not
+read those keys, so handing them the call would drop the filter / the refinement without a word: ValueError.  On the device ``detection`` honours ``refine``.
 
 Nothing else falls through: KPB_E_INVALID (a malformed call) and every other library error RAISE -- an in-contract call that
 starts failing must not turn into a silent thousandfold slowdown on the reference's CPU code.
@@ -60,6 +61,12 @@ def ratio_refusal(*a, **k):
         if isinstance(d, dict) and d.get("max_ratio") is not None and not float(d["max_ratio"]) >= 1.0:
             return "max_ratio = %r: the reference's brute_force_matcher ignores the key" % (d["max_ratio"],)
     return None
+
+
+def refine_refusal(score_map, params=None, *a, **k):
+    """Why the reference's own detection cannot take this call: an extractor_params `refine` it would ignore, returning pixel centres without a word."""
+    mode = params.get("refine") if isinstance(params, dict) else None
+    return None if mode in (None, "none") else "refine = %r: the reference's detection ignores the key" % (mode,)
 
 
 def guarded(name, hip_fn, ref_fn, in_contract, refuse=None):
@@ -329,7 +336,7 @@ def install(optical_flow_cv=False):
         ref = getattr(mod, attr)
         _state["originals"][full] = ref
         if kind == "fn":
-            new = guarded(full, hip, ref, contract, refuse=ratio_refusal if attr in RATIO_ROUTES else None)
+            new = guarded(full, hip, ref, contract, refuse=ratio_refusal if attr in RATIO_ROUTES else refine_refusal if attr == "detection" else None)
         elif kind == "lk":
             new = _lk_factory(hip, ref)
         elif kind == "matcher":

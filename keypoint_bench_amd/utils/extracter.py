@@ -7,7 +7,7 @@ import ctypes
 
 import torch
 
-from .._lib import Context, DetectParams, ptr
+from .._lib import Context, DetectParams, ptr, refine_id
 
 
 def _as_maps(t: torch.Tensor):
@@ -40,10 +40,13 @@ def fast_nms(image_probs: torch.Tensor, nms_dist: int = 4, max_iter: int = -1, m
 def detection_batch(score_map: torch.Tensor, params: dict = None, sync: bool = True, signed: bool = False):
     """All batch elements at once: returns (kps [B, top_k, 3], flat_idx [B, top_k], n [B]) device tensors.
     signed=True: signed score maps, every image by the reference's rounds (KPB_OPT_DETECT_SIGNED); a sync=False call keeps that choice until
-    kpb_detect_check completes it."""
+    kpb_detect_check completes it.
+    params["refine"] (absent or None: off; "quadratic" or "softargmax"): the kept rows moved to sub-pixel positions (KPB_OPT_DETECT_REFINE, include/kpb.h) -- the same
+    rows in the same order, columns 0 and 1 refined; a key of extractor_params, so a YAML config carries it.  A sync=False call keeps the mode likewise."""
     if params is None:  # utils/extracter.py:200-205
         params = dict(nms_dist=4, threshold=0.0, border_dist=8, top_k=300, min_score=0.0)
     x = _as_maps(score_map)
+    refine = refine_id(params.get("refine"))
     B, _, H, W = x.shape
     ctx = Context.get(x.device)
     top_k = min(int(params["top_k"]), H * W)
@@ -52,14 +55,14 @@ def detection_batch(score_map: torch.Tensor, params: dict = None, sync: bool = T
     kps = torch.empty((B, top_k, 3), dtype=torch.float32, device=x.device)
     idx = torch.empty((B, top_k), dtype=torch.int32, device=x.device)
     n = torch.empty((B,), dtype=torch.int32, device=x.device)
-    with ctx.detect_signed(signed):
+    with ctx.detect_signed(signed), ctx.detect_refine(refine):
         ctx.check(ctx.lib.kpb_detect(ctx.handle, ptr(x), B, H, W, ctypes.byref(prm), ptr(kps), ptr(idx), ptr(n),
                                      1 if sync else 0))
     return kps, idx, n
 
 
 def detection(score_map: torch.Tensor, params: dict = None, signed: bool = False):
-    """utils/extracter.py:193-221.  score_map Bx1xHxW -> Nx3 (x, y, prob) of batch element 0.  signed: see detection_batch."""
+    """utils/extracter.py:193-221.  score_map Bx1xHxW -> Nx3 (x, y, prob) of batch element 0.  signed, params["refine"]: see detection_batch."""
     kps, _, _ = detection_batch(score_map[:1], params, sync=True, signed=signed)
     ctx = Context.get(kps.device)
     n = (ctypes.c_int32 * 1)()
