@@ -400,7 +400,10 @@ int kpb_preprocess(kpb_ctx* ctx, const uint8_t* src_dev, int batch, int Hs, int 
 #define KPB_ARCH_SUPERPOINT 2   /* models/SuperPoint.py SuperPointNet, tensors named as its state_dict */
 #define KPB_ARCH_XFEAT 3        /* models/XFeat.py      XFeatModel, BN folded */
 #define KPB_ARCH_DISK 4         /* models/disk.py       DISK (thin U-Net, 5x5), H, W multiples of 16, not 16 x 16 (a 1 x 1 bottleneck has no instance norm); desc_out_dev NULL gives the score only, kpb_net_desc_at the descriptors at keypoints */
-#define KPB_ARCH_R2D2 6         /* models/r2d2.py       Quad_L2Net_ConfCFS (dilated, full resolution), BN folded; any H, W */
+#define KPB_ARCH_R2D2 6         /* models/r2d2.py       Quad_L2Net_ConfCFS (dilated, full resolution), BN folded; any H, W.  Optional tensor matrix.mode {1}: absent or 0 = split-f16 products
+                                 * (three MFMAs each, fp32-class results); 1 = the single-f16 matrix mode on conv1 .. conv8 (one MFMA a_hi b_hi per product: operands rounded to f16 at the same
+                                 * power-of-two scales, fp32 accumulation -- TF32-class, score / descriptor errors of the order 1e-3); any other value, or 1 under KPB_FP32_MATRIX=1, is
+                                 * KPB_E_UNSUPPORTED ("kpb_net_create: R2D2 ...").  A blob of any OTHER arch with matrix.mode != 0 is KPB_E_UNSUPPORTED too, before anything is built */
 #define KPB_ARCH_EDGEPOINT 7    /* models/EdgePoint.py  EdgePoint (ALIKE-t trunk, plan 8,16,32,64 / 64), BN folded; raw-logit score (KPB_OPT_DETECT_SIGNED), 64-channel map at H/8 x W/8 */
 #define KPB_ARCH_GOODPOINT 8    /* models/GoodPoint.py  GoodPoint (ALIKE-t's block 1, plan c0 = 3, c1 = 8), BN folded; H, W multiples of 32; sigmoid score and a sigmoid 3-channel map at full resolution, not normalised: the map the tracker follows (kpb_lk_track_batch); desc_out_dev 16-byte aligned */
 #define KPB_ARCH_LETNET 9       /* models/LETNet.py     LETNet(c1 = 8, c2 = 16, grayscale = False) (ALIKE-t's block 1, then two 1 x 1 convolutions, 8 -> 16 -> 4), BN folded; H, W multiples of 32; the sigmoid of channels 0..2 is the 3-channel map at full resolution the tracker follows, that of channel 3 the score; desc_out_dev 16-byte aligned, NULL gives the score only */

@@ -20,6 +20,9 @@ struct Layer {      // one convolution of a network plan
     const float *w = nullptr, *b = nullptr, *xw = nullptr;
     const float* slope = nullptr;       // DISK: the PReLU slopes of the layer's input
     std::string prof;                   // profile name of its launch
+    // the single-f16 matrix mode (CmForm::h1), set by the net's create BEFORE stage_layer: one MFMA a_hi * b_hi per product on the same pack and LDS layout;
+    // profile name + "_h1".  launch_mfma refuses it (KPB_E_INVALID) on a layer whose form has no such instance, and on the strict-fp32 path
+    bool h1 = false;
 };
 
 struct UpSrc { const float* src; int c; };      // ConvM::up_src, up_c

@@ -150,9 +150,11 @@ int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B
     if (o.last_only) name = last_name.c_str();
     hipStream_t st = ctx->stream;
     const bool x = o.xf != nullptr;
+    if (L.h1 && !conv_mfma_use_h16()) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: %s: the single-f16 mode has no strict-fp32 form (KPB_FP32_MATRIX is set)", L.name.c_str());
     if (conv_mfma_use_h16()) {
         a.unscale = L.unscale;
         if (L.ks == 1 && S == 1 && CC == 32 && !L.pool_out && !x && !o.pre) {     // 1x1: gemm_h
+            if (L.h1) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: no single-f16 instance of the 1x1 product for %s", L.name.c_str());
             const dim3 grid(cdiv(a.H * a.W, 128), 1, B * a.nblk), block(256);
             if (o.l2_eps > 0.0f) {
                 if (L.cout != 64 || L.ntb != 2) return kpb_fail(ctx, KPB_E_INVALID, "launch_mfma: the fused L2 norm needs a 64-channel layer");
@@ -166,12 +168,13 @@ int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B
         }
         if (L.ks == 2) {        // tap-gathered product (R2D2's dilated 2 x 2 layers): K = 4 taps x cin, 128 pixels x 64 output channels per workgroup
             a.NCH = 4 * (L.cin / 32); a.tap_dil = L.dil;
-            KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_PLAIN, false, 2>), dim3(cdiv(a.H * a.W, 128), 1, B * a.nblk), dim3(256), 0, st, a);
+            if (L.h1) KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_PLAIN, false, 2, true>), dim3(cdiv(a.H * a.W, 128), 1, B * a.nblk), dim3(256), 0, st, a);
+            else KPB_LAUNCH(ctx, name, (gemm_h<2, 1, GE_PLAIN, false, 2>), dim3(cdiv(a.H * a.W, 128), 1, B * a.nblk), dim3(256), 0, st, a);
             return KPB_OK;
         }
         // split-f16 form: stride-1 layers on 16-row workgroup tiles; with two n-tiles per workgroup the waves form 2 row groups x 2 n-tiles
         // (four M tiles and one n-tile per wave)
-        CmForm f{.ks = L.ks, .s = S, .cc = CC, .pool_out = L.pool_out, .xf = x, .ntb = 1, .mt = 4, .wn = 2, .dil = L.dil};
+        CmForm f{.ks = L.ks, .s = S, .cc = CC, .pool_out = L.pool_out, .xf = x, .ntb = 1, .mt = 4, .wn = 2, .dil = L.dil, .h1 = L.h1};
         // one-tile layers (cout <= 32) are bound by per-workgroup latency: 8-row tiles (one M tile per wave, 28 KB of LDS, five
         // workgroups per CU) measured 8-16 % faster; layers with two output tiles lose the fragment reuse that way (+8 % time)
         if (L.ntb == 1) f.mt = f.wn = 1;
@@ -204,7 +207,10 @@ int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B
             CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2}, CmForm{.ks = 5, .s = 1, .cc = 32, .xf = true, .ntb = 1, .mt = 4, .wn = 2, .up = true},
             CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .xc = true, .wn = 2, .up = true},
             CmForm{.ks = 5, .s = 1, .cc = 16, .xf = true, .ntb = 1, .mt = 4, .xc = true, .wn = 2, .up = true, .xo = true},
-            CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .dil = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 2, .wn = 2, .dil = 4}>(ctx, name, f, a, B);
+            CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .dil = 2}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 2, .wn = 2, .dil = 4},
+            // the single-f16 mode (CmForm::h1): R2D2's conv1, conv2, conv3 / conv4, conv5
+            CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .h1 = true}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .h1 = true},
+            CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 4, .wn = 2, .dil = 2, .h1 = true}, CmForm{.ks = 3, .s = 1, .cc = 32, .ntb = 1, .mt = 2, .wn = 2, .dil = 4, .h1 = true}>(ctx, name, f, a, B);
     }
     int ntb = L.ntb;
     if (o.last_only) {
@@ -227,7 +233,7 @@ int launch_mfma(kpb_ctx* ctx, const Layer& L, const float* in, float* out, int B
 
 void stage_layer(WeightStage& ws, Layer& L, const char* prefix, const float* w, const float* b)
 {
-    L.prof = prefix + L.name;
+    L.prof = prefix + L.name + (L.h1 ? "_h1" : "");
     if (L.mfma) {
         if (conv_mfma_use_h16() && L.ntb == 5) {       // cout = 4 x 32 + 1: the last channel goes to the VALU side of conv_mfma_h<XC>
             const int T = L.ks * L.ks, co = L.cout - 1;

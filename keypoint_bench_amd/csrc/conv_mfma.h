@@ -116,6 +116,10 @@ struct CmForm {
     // per-slab scale e_cur) and only the VALU channel runs, in the same order on the same halves: the extra channel's bits are those of the dense form.  No weight
     // fragment is loaded and no tile is written; `out` receives the extra channel alone (ostride = 1, xco = 0).
     bool xo = false;
+    // The single-f16 matrix mode (opt-in per net: R2D2's `matrix.mode`): each product is the ONE MFMA a_hi * b_hi -- operands of 11 significant bits, fp32
+    // accumulation, what the reference's convolutions are on its own GPU (TF32).  Scales, slabs, the rescale and the epilogue are those of the split form; only the
+    // hi halves are formed, staged, read and multiplied -- the lo half of an LDS pixel and the lo fragments of the weight pack are never touched.
+    bool h1 = false;
     constexpr bool operator==(const CmForm&) const = default;
     constexpr int tile_h() const { return 8 * mt / wn; }       // output rows of a workgroup tile
     // conv_mfma_h: waves per SIMD the register allocation is held to: what r02's code reached without being told (accumulators 16 mt ntb) -- left alone, the
@@ -454,7 +458,9 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
 {
     constexpr int KS = F.ks, S = F.s, CC = F.cc, NTB = F.ntb, MT = F.mt, PF = F.pf, WN = F.wn, DIL = F.dil;
     constexpr bool POOL_IN = F.pool_in, POOL_OUT = F.pool_out, XF = F.xf, XC = F.xc, WPRE = F.wpre, PRE = F.pre, GEN = F.gen, UP = F.up, XO = F.xo;
+    constexpr bool H1 = F.h1;
     static_assert(!XO || (XC && UP && NTB == 1 && F.tail == 0), "conv_mfma_h: the channel-only form is the xc form of the fused upsampling without its tiles");
+    static_assert(!H1 || (S == 1 && !POOL_IN && !POOL_OUT && !XF && !XC && !WPRE && !PRE && !UP && F.tail == 0), "conv_mfma_h: the single-f16 mode exists for plain stride-1 layers (R2D2)");
     static_assert(DIL == 1 || (DIL >= 2 && S == 1 && !WPRE && !PRE && !UP && !XC && !POOL_IN && MT >= 2 && NTB == 1), "conv_mfma_h: the dilated form exists for plain stride-1 layers (R2D2)");
     static_assert(!UP || (S == 1 && !POOL_IN && !PRE && !WPRE && (((F.tile_h() - 1) * S + KS) % 2 == 0) && ((15 * S + KS) % 2 == 0) && KS / 2 % 2 == 0),
                   "conv_mfma_h<UP>: stride-1 layers whose input tile starts on an even row and column");
@@ -735,10 +741,14 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
                 const int pix = idx / Q, q = idx - pix * Q;
                 if (idx < IH * IW * Q) {
                     const int y = pix / IW, x = pix - y * IW;
+                    if constexpr (H1) {     // the hi halves alone: cm_split4's first conversion, to nearest
+                        *reinterpret_cast<uint2*>(&tile[y * ROWP + x * PITCH + 8 * q]) = make_uint2(cm_cvt_pk_rtn(buf[k].x * sc, buf[k].y * sc), cm_cvt_pk_rtn(buf[k].z * sc, buf[k].w * sc));
+                    } else {
                     uint2 hi, lo;
                     cm_split4(make_float4(buf[k].x * sc, buf[k].y * sc, buf[k].z * sc, buf[k].w * sc), hi, lo);
                     *reinterpret_cast<uint2*>(&tile[y * ROWP + x * PITCH + 8 * q]) = hi;
                     *reinterpret_cast<uint2*>(&tile[y * ROWP + x * PITCH + LO + 8 * q]) = lo;
+                    }
                 }
             }
         }
@@ -784,7 +794,7 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
 #pragma unroll
                 for (int kb = 0; kb < NKB; ++kb) {
                     BhA[set][n][kb] = __builtin_bit_cast(cm_h8, bp[n * ntile_stride + (kb * 4 + 0) * 32]);
-                    BlA[set][n][kb] = __builtin_bit_cast(cm_h8, bp[n * ntile_stride + (kb * 4 + 2) * 32]);
+                    if constexpr (!H1) BlA[set][n][kb] = __builtin_bit_cast(cm_h8, bp[n * ntile_stride + (kb * 4 + 2) * 32]);
                 }
         };
         if constexpr (!XO) loadB(0, 0);
@@ -802,8 +812,10 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
             } else if (tap > 0) loadB(tap, 0);          // requested where they are used: the scheduler's own order
             auto& Bh = BhA[TAPU == 9 ? tap : (ROW_AHEAD ? kx : 0)];
             auto& Bl = BlA[TAPU == 9 ? tap : (ROW_AHEAD ? kx : 0)];
+            // the pinned order below interleaves the lo pieces with the hi ones: the single-f16 mode has none and takes the plain loop
+            constexpr bool PINNED = !H1 && MT >= 2 && NTB == 1 && !PRE && !(XC && !UP);
 #pragma unroll
-            for (int m = 0; m < ((MT >= 2 && NTB == 1 && !PRE && !(XC && !UP)) ? 0 : MT); ++m) {
+            for (int m = 0; m < (PINNED ? 0 : MT); ++m) {
                 const int orow = 2 * (wm * MT + m) + (p >> 4);
                 if constexpr (PRE) {
                     const int t = (orow + ky) * IW + ocol + kx, key = ((ocol + kx) >> 1) & 7;
@@ -818,13 +830,13 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
 #pragma unroll
                 for (int kb = 0; kb < NKB; ++kb) {
                     Ah[m][kb] = __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap + 16 * kb));
-                    Al[m][kb] = __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap + LO + 16 * kb));
+                    if constexpr (!H1) Al[m][kb] = __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap + LO + 16 * kb));
                 }
                 }
             }
             if constexpr (XO) {
                 // no tile: only the extra channel below reads the staged slab
-            } else if constexpr (MT >= 2 && NTB == 1 && !PRE && !(XC && !UP)) {
+            } else if constexpr (PINNED) {
                 // r06: the A pieces of a k-block in a pinned order -- the MT lo pieces and the first hi piece in flight together, the next hi piece requested behind
                 // every lo piece's MFMA (whose registers it may take: the allocator decides, the order only makes it possible).  Left alone the scheduler sent the
                 // lo pieces through ONE register quad, a ds_read_b128 and an exposed wait each.  Same MFMAs per accumulator in the same order: bit-identical.
@@ -859,8 +871,10 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
                 for (int m = 0; m < MT; ++m)
 #pragma unroll
                     for (int n = 0; n < NTB; ++n) {
+                        if constexpr (!H1) {
                         acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al[m][kb], Bh[n][kb], acc[m][n], 0, 0, 0);
                         acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[m][kb], Bl[n][kb], acc[m][n], 0, 0, 0);
+                        }
                         acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[m][kb], Bh[n][kb], acc[m][n], 0, 0, 0);
                     }
             if (XC && nb == 0) {       // the extra channel at pixel (tid / 16, tid % 16): hi + lo restores the staged activation, weights are wave-uniform
@@ -1026,8 +1040,8 @@ int cm_launch(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, in
         else KPB_LAUNCH(ctx, tag, conv_mfma<FS>, grid, dim3(256), 0, ctx->stream, a);
         return true;
     }()) || ...);
-    return found ? KPB_OK : kpb_fail(ctx, KPB_E_INVALID, "%s: no instance for %s: ks=%d s=%d cc=%d pool_in=%d pool_out=%d xf=%d ntb=%d mt=%d xc=%d pf=%d wpre=%d pre=%d wn=%d gen=%d up=%d dil=%d tail=%d xo=%d",
-        H ? "conv_mfma_h" : "conv_mfma", tag, f.ks, f.s, f.cc, f.pool_in, f.pool_out, f.xf, f.ntb, f.mt, f.xc, f.pf, f.wpre, f.pre, f.wn, f.gen, f.up, f.dil, f.tail, f.xo);
+    return found ? KPB_OK : kpb_fail(ctx, KPB_E_INVALID, "%s: no instance for %s: ks=%d s=%d cc=%d pool_in=%d pool_out=%d xf=%d ntb=%d mt=%d xc=%d pf=%d wpre=%d pre=%d wn=%d gen=%d up=%d dil=%d tail=%d xo=%d h1=%d",
+        H ? "conv_mfma_h" : "conv_mfma", tag, f.ks, f.s, f.cc, f.pool_in, f.pool_out, f.xf, f.ntb, f.mt, f.xc, f.pf, f.wpre, f.pre, f.wn, f.gen, f.up, f.dil, f.tail, f.xo, f.h1);
 }
 template <CmForm... FS> int launch_conv_mfma_h(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B) { return cm_launch<true, FS...>(ctx, tag, f, a, B); }
 template <CmForm... FS> int launch_conv_mfma(kpb_ctx* ctx, const char* tag, const CmForm& f, const ConvM& a, int B) { return cm_launch<false, FS...>(ctx, tag, f, a, B); }
@@ -1043,7 +1057,8 @@ template <CmForm... FS> int launch_conv_mfma(kpb_ctx* ctx, const char* tag, cons
 // (NCHI = CIN / 32; ConvM::NCH = TAPK^2 NCHI, pack_mfma_h's tap-major order as it stands) is the 1 x 1 row staging read at the pixel offset of its tap,
 // (ky, kx) tap_dil - (TAPK - 1) tap_dil / 2; a row whose tap falls outside the image is staged as zeros, like a row past rowcnt.  Nothing but the wave's own rows is
 // ever in LDS -- a halo tile of the 2 x 2, dilation-16 layer would be 32 x 32 x 144 B = 147 KB per slab -- and the operand scale is measured per wave and slab as in the 1 x 1 form.
-template <int NTB, int MT = 2, int EPI = GE_PLAIN, bool UNFOLD = false, int TAPK = 0>
+// H1: the single-f16 mode (CmForm::h1): the hi halves alone are staged, read and multiplied, one MFMA per product.
+template <int NTB, int MT = 2, int EPI = GE_PLAIN, bool UNFOLD = false, int TAPK = 0, bool H1 = false>
 // (at four waves per SIMD the one-tile GE_RESIDUAL / GE_ROTARY forms spill 2 / 11 registers to scratch -- their epilogue operands
 // xv sit beside the accumulators in the last slab.  r05 measured the alternative it named, three waves per SIMD for those two (132 / 144
 // registers, no scratch): ffn3 + residual 0.915 -> 1.09 ms per 18 launches, three interleaved runs -- the spill is the cheaper evil; loading
@@ -1145,10 +1160,14 @@ __global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY || EPI == GE_RES_R
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
             const int idx = lane + k * 64, row = idx / Q, q = idx - row * Q;
+            if constexpr (H1) {
+                *reinterpret_cast<uint2*>(&t[row * PITCH + 8 * q]) = make_uint2(cm_cvt_pk_rtn(buf[k].x * sc, buf[k].y * sc), cm_cvt_pk_rtn(buf[k].z * sc, buf[k].w * sc));
+            } else {
             uint2 hi, lo;
             cm_split4(make_float4(buf[k].x * sc, buf[k].y * sc, buf[k].z * sc, buf[k].w * sc), hi, lo);
             *reinterpret_cast<uint2*>(&t[row * PITCH + 8 * q]) = hi;
             *reinterpret_cast<uint2*>(&t[row * PITCH + LO + 8 * q]) = lo;
+            }
         }
     };
     fetch(0);
@@ -1206,7 +1225,7 @@ __global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY || EPI == GE_RES_R
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
                 Bh[n][kb] = __builtin_bit_cast(cm_h8, bp[n * ntile_stride + (kb * 4 + 0) * 32]);
-                Bl[n][kb] = __builtin_bit_cast(cm_h8, bp[n * ntile_stride + (kb * 4 + 2) * 32]);
+                if constexpr (!H1) Bl[n][kb] = __builtin_bit_cast(cm_h8, bp[n * ntile_stride + (kb * 4 + 2) * 32]);
             }
         const unsigned char* t = wt + (ch & 1) * 4 * WBUF;
 #pragma unroll
@@ -1215,7 +1234,7 @@ __global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY || EPI == GE_RES_R
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
                 Ah[m][kb] = __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap + 16 * kb));
-                Al[m][kb] = __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap + LO + 16 * kb));
+                if constexpr (!H1) Al[m][kb] = __builtin_bit_cast(cm_h8, *reinterpret_cast<const uint4*>(ap + LO + 16 * kb));
             }
         }
 #pragma unroll
@@ -1224,8 +1243,10 @@ __global__ __launch_bounds__(256, MT == 1 ? (EPI == GE_ROTARY || EPI == GE_RES_R
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int n = 0; n < NTB; ++n) {
+                    if constexpr (!H1) {
                     acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al[m][kb], Bh[n][kb], acc[m][n], 0, 0, 0);
                     acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[m][kb], Bl[n][kb], acc[m][n], 0, 0, 0);
+                    }
                     acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[m][kb], Bh[n][kb], acc[m][n], 0, 0, 0);
                 }
         if constexpr (more) stage((ch + 1) & 1, false);      // the wave's other buffer

@@ -10,6 +10,16 @@ KPB_API int kpb_net_create(kpb_ctx* ctx, int arch, const void* blob, size_t len,
     return guarded(ctx, "kpb_net_create", [&] {
         KpbwBlob bl;
         if (!bl.parse(blob, len) || (int)bl.arch != arch) return kpb_fail(ctx, KPB_E_WEIGHTS, "kpb_net_create: malformed .kpbw blob");
+        // matrix.mode (the single-f16 matrix mode) is R2D2's: a blob of another arch that asks for it is refused, never built as if it had not asked
+        if (arch != KPB_ARCH_R2D2) {
+            const auto it = bl.t.find("matrix.mode");
+            if (it != bl.t.end()) {
+                size_t cnt = 1;
+                for (uint32_t v : it->second.second) cnt *= v;
+                for (size_t i = 0; i < cnt; ++i)
+                    if (it->second.first[i] != 0.0f) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_net_create: arch %d has no single-f16 matrix mode (matrix.mode is R2D2's)", arch);
+            }
+        }
         switch (arch) {
         case KPB_ARCH_ALIKE: return alike_create(ctx, bl, out);
         case KPB_ARCH_SUPERPOINT: return superpoint_create(ctx, bl, out);

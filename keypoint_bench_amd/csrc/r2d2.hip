@@ -7,6 +7,8 @@
 //   conv6 .. 8     gemm_h<.., TAPK = 2>: four taps x 128 channels gathered at (+-d / 2, +-d / 2) -- no halo in LDS
 //   r2d2_head      one pass over the 128-channel map: score and the normalised descriptor row
 // KPB_FP32_MATRIX=1: conv1 .. 8 on conv_mfma (fp32 MFMA) with the same dilation field.
+// matrix.mode = 1 in the blob (Quad_L2Net_ConfCFS(matrix="f16")): conv1 .. 8 in the single-f16 mode (Layer::h1, profile names r2d2_conv1_h1 ..): one MFMA a_hi b_hi
+// per product -- TF32-class operands, what the reference's convolutions are on its own GPU.  conv0 and the head stay fp32.
 #include "conv_layer.h"
 #include "conv_mfma.h"      // relu
 
@@ -87,14 +89,26 @@ int r2d2_create(kpb_ctx* ctx, const KpbwBlob& bl, kpb_net** out)
     net->ctx = ctx; net->arch = KPB_ARCH_R2D2; net->dim = 128; net->desc_div = 1;
     WeightStage ws;
     const KpbwReader rd{bl, "kpb_net_create: R2D2 tensor %s missing or mis-shaped"};
+    // the matrix mode travels in the blob (as harris.plan does): the optional tensor matrix.mode {1}; absent or 0 = split-f16, 1 = single f16 on conv1 .. conv8
+    bool h1 = false;
+    if (bl.t.count("matrix.mode")) {
+        const float m = rd.need("matrix.mode", {1})[0];
+        if (m != 0.0f && m != 1.0f) return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_net_create: R2D2 matrix.mode %g: 0 (split-f16) or 1 (single f16)", (double)m);
+        if (m == 1.0f && !conv_mfma_use_h16())
+            return kpb_fail(ctx, KPB_E_UNSUPPORTED, "kpb_net_create: R2D2 matrix.mode 1: the single-f16 mode needs the matrix-pipe build of the convolutions (KPB_FP32_MATRIX is set)");
+        h1 = m == 1.0f;
+    }
     for (int i = 0; i < R2_LAYERS; ++i) {
         Layer& L = net->L[i] = plan[i];
+        L.h1 = h1 && L.mfma;
         const float* w = rd.need(L.name + ".w", {(uint32_t)L.cout, (uint32_t)L.cin, (uint32_t)L.ks, (uint32_t)L.ks});
         const float* b = rd.need(L.name + ".b", {(uint32_t)L.cout});
         // strict fp32: the 2 x 2, dilation-16 tile fits the LDS window in 16-channel slabs; the tap-gathered split-f16 product reads 32-channel slabs
         L.cc = (L.ks == 2 && !conv_mfma_use_h16()) ? 16 : 32;
         L.ntb = L.cout == 32 ? 1 : 2;       // conv1 owns one n-tile: the packs are n-tile-major, so its fragments sit where a two-tile pack had them and no second tile is fetched
-        stage_layer(ws, L, "", w, b);       // (conv0, mfma = false: [tap][cin][32], as conv_rgb32 reads it)
+        // (conv0, mfma = false: [tap][cin][32], as conv_rgb32 reads it.)  Profile names: the split net's layers are conv1 .. conv8 as they always were; the
+        // single-f16 layers are r2d2_conv1_h1 .. r2d2_conv8_h1, so a report or a trace that holds both nets tells them apart
+        stage_layer(ws, L, L.h1 ? "r2d2_" : "", w, b);
     }
     const float* cw = rd.need("clf.w", {2, 128});
     const float* cb = rd.need("clf.b", {2});

@@ -85,11 +85,16 @@ def build_model(params, dense_descriptors=True):
         return make(importlib.import_module("keypoint_bench_amd.models." + mod), p, dense_descriptors).eval()
     mod = importlib.import_module("keypoint_bench_amd.models." + mod)
     net = make(mod, p, dense_descriptors) if make else None
+    ckw = {}
+    if mt == "r2d2":        # r2d2_params: {weight: ..., matrix: f16}: the single-f16 matrix mode; absent = split.  Checked before the file is read
+        from . import weights as _weights
+        ckw["matrix"] = p.get("matrix", "split")
+        _weights.matrix_mode(ckw["matrix"])
     w = p.get("weight")
     if w and os.path.exists(w):
         sd = torch.load(w, map_location="cpu")
         if net is None:
-            net = mod.from_checkpoint(sd)
+            net = mod.from_checkpoint(sd, **ckw)
         else:
             net.load_state_dict(sd[sub] if sub else sd)
     elif missing is None:

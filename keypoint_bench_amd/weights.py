@@ -492,6 +492,26 @@ def fold_r2d2(sd, eps=1e-5) -> dict:
     return t
 
 
+MATRIX_MODES = {"split": 0, "f16": 1}       # the values of the optional tensor matrix.mode (include/kpb.h, KPB_ARCH_R2D2)
+
+
+def matrix_mode(matrix) -> int:
+    """The matrix.mode value of a net's `matrix` keyword: "split" (three split-f16 MFMAs per product, fp32-class results) or "f16" (one MFMA on the
+    f16-rounded operands, fp32 accumulation: TF32-class).  Anything else is a ValueError."""
+    if not isinstance(matrix, str) or matrix not in MATRIX_MODES:
+        raise ValueError("matrix must be 'split' or 'f16', not %r" % (matrix,))
+    return MATRIX_MODES[matrix]
+
+
+def with_matrix_mode(tensors: dict, matrix) -> dict:
+    """`tensors` for pack(), with the tensor matrix.mode = [1.0] added for matrix = "f16".  "split" adds nothing: its blob is the blob of a build without the
+    mode, byte for byte.  The tensors themselves must not carry the name already."""
+    mode = matrix_mode(matrix)
+    if "matrix.mode" in tensors:
+        raise ValueError("the tensor set already carries matrix.mode")
+    return dict(tensors, **{"matrix.mode": np.array([mode], np.float32)}) if mode else dict(tensors)
+
+
 LG_LAYERS = 9
 
 

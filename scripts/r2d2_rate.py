@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """R2D2 (real checkpoint, tests/golden/r2d2_state_dict*.npz) under the batched PairPipeline: 640 x 480 pairs, nms_dist 6, top_k 1000, 16 pairs per step.
 
-    python scripts/r2d2_rate.py [--pairs 16] [--steps 10] [--warmup 3]                  one JSON line: pairs/s from HIP events around the timed steps
+    python scripts/r2d2_rate.py [--pairs 16] [--steps 10] [--warmup 3] [--matrix split|f16]     one JSON line: pairs/s from HIP events around the timed steps,
+                                                                                        the net's forward alone (ms per 2 x pairs images) and, with --prof, the
+                                                                                        per-kernel ms of one forward under kpb_prof_enable
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python scripts/r2d2_rate.py --steps 3
     python scripts/r2d2_rate.py --trace DIR [--pairs 16]                                per-layer ms and fraction of the split-f16 roof from that trace
 
@@ -48,6 +50,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--trace", default=None)
+    ap.add_argument("--matrix", choices=("split", "f16"), default="split", help="the net's matrix mode (Quad_L2Net_ConfCFS(matrix=...))")
+    ap.add_argument("--prof", action="store_true", help="per-kernel ms of one forward (kpb_prof_enable) after the timed steps")
     args = ap.parse_args()
     if args.trace:
         print(json.dumps(from_trace(args.trace, args.pairs)))
@@ -63,7 +67,8 @@ def main():
     bf = dict(metric="euclidean", max_distance=5, cross_check=True)
     v = [synthetic.image_pair(5000 + i, H, W) for i in range(args.pairs)]
     images = torch.from_numpy(np.concatenate([np.stack([a for a, _ in v]), np.stack([b for _, b in v])])).to(dev)
-    pipe = PairPipeline(from_checkpoint(checkpoint()), ep, bf, args.pairs, H, W, device=dev)
+    net = from_checkpoint(checkpoint(), matrix=args.matrix) if args.matrix != "split" else from_checkpoint(checkpoint())
+    pipe = PairPipeline(net, ep, bf, args.pairs, H, W, device=dev)
     for _ in range(args.warmup):
         pipe.run(images)
     torch.cuda.synchronize()
@@ -74,7 +79,26 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / args.steps
-    print(json.dumps({"workload": "R2D2 real checkpoint, %d pairs of %dx%d per step, nms_dist 6, top_k 1000, brute-force matcher" % (args.pairs, W, H),
+    fwd = []        # the forward alone, on a net of its own (the pipeline keeps its net's outputs)
+    solo = from_checkpoint(checkpoint(), matrix=args.matrix) if args.matrix != "split" else from_checkpoint(checkpoint())
+    for i in range(args.warmup + args.steps):
+        e0.record()
+        solo(images)
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= args.warmup:
+            fwd.append(e0.elapsed_time(e1))
+    kernels = None
+    if args.prof:
+        ctx = _lib.Context.get(torch.device(dev))
+        ctx.prof_enable(True)
+        ctx.prof_report()
+        solo(images)
+        torch.cuda.synchronize()
+        kernels = {k: round(v[1], 4) for k, v in sorted(ctx.prof_report().items()) if k.startswith(("r2d2_", "conv"))}
+        ctx.prof_enable(False)
+    print(json.dumps({"matrix": args.matrix, "forward_ms": round(sum(fwd) / len(fwd), 3), "forward_ms_min_max": [round(min(fwd), 3), round(max(fwd), 3)],
+                      "kernels_ms": kernels, "workload": "R2D2 real checkpoint, %d pairs of %dx%d per step, nms_dist 6, top_k 1000, brute-force matcher" % (args.pairs, W, H),
                       "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "pairs_per_s": round(args.pairs / ms * 1e3, 2),
                       "mean_matches": float(pipe.k.float().mean()), "lib_sha256": hashlib.sha256(open(_lib.SO_PATH, "rb").read()).hexdigest()[:12],
                       "lib_path_override": os.environ.get("KPB_LIB_PATH")}))
