@@ -1037,22 +1037,16 @@ struct HeadArgs {
 // 8 channels [c0, c0+8) of an align_corners=True bilinear upsample (nn.Upsample, ALike.py:126-129) at (y, x)
 __device__ __forceinline__ void up8ch(const float* m, int Hs, int Ws, float sy, float sx, int y, int x, int c0, float* f)
 {
-    const float fy = sy * (float)y, fx = sx * (float)x;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < Hs - 1 ? 1 : 0), x1 = x0 + (x0 < Ws - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.0f - ly, hx = 1.0f - lx;
-    const float* p00 = m + ((size_t)y0 * Ws + x0) * 16 + c0;
-    const float* p01 = m + ((size_t)y0 * Ws + x1) * 16 + c0;
-    const float* p10 = m + ((size_t)y1 * Ws + x0) * 16 + c0;
-    const float* p11 = m + ((size_t)y1 * Ws + x1) * 16 + c0;
+    const kpb_lin ty = kpb_tap_ac(y, Hs, sy), tx = kpb_tap_ac(x, Ws, sx);
+    const float* p00 = m + ((size_t)ty.i0 * Ws + tx.i0) * 16 + c0;
+    const float* p01 = m + ((size_t)ty.i0 * Ws + tx.i1) * 16 + c0;
+    const float* p10 = m + ((size_t)ty.i1 * Ws + tx.i0) * 16 + c0;
+    const float* p11 = m + ((size_t)ty.i1 * Ws + tx.i1) * 16 + c0;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        const float4 a = *reinterpret_cast<const float4*>(p00 + 4 * q), b = *reinterpret_cast<const float4*>(p01 + 4 * q);
-        const float4 c = *reinterpret_cast<const float4*>(p10 + 4 * q), d = *reinterpret_cast<const float4*>(p11 + 4 * q);
-        f[4 * q + 0] = hy * (hx * a.x + lx * b.x) + ly * (hx * c.x + lx * d.x);
-        f[4 * q + 1] = hy * (hx * a.y + lx * b.y) + ly * (hx * c.y + lx * d.y);
-        f[4 * q + 2] = hy * (hx * a.z + lx * b.z) + ly * (hx * c.z + lx * d.z);
-        f[4 * q + 3] = hy * (hx * a.w + lx * b.w) + ly * (hx * c.w + lx * d.w);
+        const float4 v = kpb_mix4(*reinterpret_cast<const float4*>(p00 + 4 * q), *reinterpret_cast<const float4*>(p01 + 4 * q),
+                                  *reinterpret_cast<const float4*>(p10 + 4 * q), *reinterpret_cast<const float4*>(p11 + 4 * q), ty.l, tx.l);
+        f[4 * q + 0] = v.x; f[4 * q + 1] = v.y; f[4 * q + 2] = v.z; f[4 * q + 3] = v.w;
     }
 }
 
@@ -1060,7 +1054,7 @@ __device__ __forceinline__ void up8ch(const float* m, int Hs, int Ws, float sy, 
 struct Up8Taps { float4 t[8]; float ly, lx; };
 // The bilinear interpolation of up8ch from taps already in registers, as four weighted taps: the four weights once per pixel, then a
 // multiply and three FMAs per channel (36 vector instructions per pixel; r03's hy (hx a + lx b) + ly (hx c + lx d), unfused, took 56 and
-// differs in the last bit).  `sc` (a power of two) scales the result exactly: it rides on the two y weights.
+// differs in the last bit: interp.h's kpb_mix; this fused form is deliberate).  `sc` (a power of two) scales the result exactly: it rides on the two y weights.
 // (History: this form went in at 775c39f and out again a day later, because from that commit on ~0.5 % of the dense maps differed RUN TO
 // RUN in 16-pixel groups.  r05 found why -- not this arithmetic but ONE encoding hipcc chose for it: it splats the two lower weights with
 // `v_pk_mul_f32 w, ly, {hx, lx} op_sel:[0,1] op_sel_hi:[0,1]`, and gfx950 drops src1's high dword from the LOW lane of a packed-fp32
@@ -1126,24 +1120,21 @@ struct StripRegs { float4 u[(NT * (ESTRIDE / 4) + 63) / 64], d[(NT * (ESTRIDE / 
 template <int NT>
 __device__ __forceinline__ void strip_load(StripRegs<NT>& r, const float* E, int Hs, int Ws, float sy, int y, int tb, int lane)
 {
-    const float fy = sy * (float)y;
-    const int y0 = (int)fy, y1 = y0 + (y0 < Hs - 1 ? 1 : 0);
+    const kpb_lin ty = kpb_tap_ac(y, Hs, sy);
 #pragma unroll
     for (int k = 0; k < (NT * (ESTRIDE / 4) + 63) / 64; ++k) {
         const int i = min(lane + 64 * k, NT * (ESTRIDE / 4) - 1);
         const int t = i / (ESTRIDE / 4), q = i - t * (ESTRIDE / 4);
         const int xt = min(tb + t, Ws - 1);
-        r.u[k] = *reinterpret_cast<const float4*>(E + ((size_t)y0 * Ws + xt) * ESTRIDE + 4 * q);
-        r.d[k] = *reinterpret_cast<const float4*>(E + ((size_t)y1 * Ws + xt) * ESTRIDE + 4 * q);
+        r.u[k] = *reinterpret_cast<const float4*>(E + ((size_t)ty.i0 * Ws + xt) * ESTRIDE + 4 * q);
+        r.d[k] = *reinterpret_cast<const float4*>(E + ((size_t)ty.i1 * Ws + xt) * ESTRIDE + 4 * q);
     }
 }
 
 template <int NT>
 __device__ __forceinline__ void strip_store(const StripRegs<NT>& r, float* V, int Hs, float sy, int y, int lane, float c)
 {
-    const float fy = sy * (float)y;
-    const int y0 = (int)fy;
-    const float ly = fy - (float)y0, hy = 1.0f - ly;
+    const float ly = kpb_tap_ac(y, Hs, sy).l, hy = 1.0f - ly;
 #pragma unroll
     for (int k = 0; k < (NT * (ESTRIDE / 4) + 63) / 64; ++k) {
         const int i = lane + 64 * k;
@@ -1197,9 +1188,9 @@ __global__ __launch_bounds__(256) void alike_head_hyb(HybArgs a)
     const float* a2 = a.a2 + (size_t)b * H2 * W2 * 16;
     const float* E3 = a.E3 + (size_t)b * H8 * W8 * ESTRIDE;
     const float* E4 = a.E4 + (size_t)b * H32 * W32 * ESTRIDE;
-    const float sy2 = (float)(H2 - 1) / (float)(a.H - 1), sx2 = (float)(W2 - 1) / (float)(a.W - 1);
-    const float sy8 = (float)(H8 - 1) / (float)(a.H - 1), sx8 = (float)(W8 - 1) / (float)(a.W - 1);
-    const float sy32 = (float)(H32 - 1) / (float)(a.H - 1), sx32 = (float)(W32 - 1) / (float)(a.W - 1);
+    const float sy2 = kpb_ac_scale_gt1(H2, a.H), sx2 = kpb_ac_scale_gt1(W2, a.W);
+    const float sy8 = kpb_ac_scale_gt1(H8, a.H), sx8 = kpb_ac_scale_gt1(W8, a.W);
+    const float sy32 = kpb_ac_scale_gt1(H32, a.H), sx32 = kpb_ac_scale_gt1(W32, a.W);
     const int tiles_per_row = a.W / 32, segs_per_row = (tiles_per_row + SEG_TILES - 1) / SEG_TILES;
     int y, xs;
     bool live;
@@ -1212,7 +1203,7 @@ __global__ __launch_bounds__(256) void alike_head_hyb(HybArgs a)
     const int ntile = live ? min(SEG_TILES, tiles_per_row - xs / 32) : 0;
     // a 128-pixel segment spans < 16 source columns of the up8 map and < 4 of the up32 map (scale < 1/8, 1/32), a tile
     // starts at most 12 (3) columns into the strip and uses 6 (4) rows from there: NT3 = 12 + 6, NT4 = 3 + 4
-    const int tb3 = (int)(sx8 * (float)xs), tb4 = (int)(sx32 * (float)xs);
+    const int tb3 = kpb_tap_ac(xs, W8, sx8).i0, tb4 = kpb_tap_ac(xs, W32, sx32).i0;
     if (live) {
         build_strip<NT3>(V3[wv], E3, H8, W8, sy8, y, tb3, lane);
         build_strip<NT4>(V4[wv], E4, H32, W32, sy32, y, tb4, lane);
@@ -1242,7 +1233,7 @@ __global__ __launch_bounds__(256) void alike_head_hyb(HybArgs a)
         }
         up8ch(a2, H2, W2, sy2, sx2, y, x, 8 * h, f + 8);      // ALike.py:151
 
-        // x interpolation of the two coarse groups: source column and weight of this lane's pixel, relative to the tile
+        // x interpolation of the two coarse groups: source column and weight of this lane's pixel, relative to the tile (kpb_tap_ac's arithmetic (interp.h) written out: this kernel's assembly is held identical to its parent's, and calling the header reorders it)
         const float fx3 = sx8 * (float)x, fx4 = sx32 * (float)x;
         const int rb3 = (int)(sx8 * (float)x0) - tb3, rb4 = (int)(sx32 * (float)x0) - tb4;     // tile's first strip row
         const int t3 = (int)fx3 - tb3 - rb3, t4 = (int)fx4 - tb4 - rb4;
@@ -1358,13 +1349,10 @@ constexpr int HP_LA = 2;                                                      //
 // rows of a source map (height Hs) live at once while the head walks an image of height H: lo(g) .. hi(g + HP_LA) over all groups g
 inline bool hp_ring_rows_ok(int H, int Hs, int ring_rows)
 {
-    const float s = (float)(Hs - 1) / (float)(H - 1);
+    const float s = kpb_ac_scale(Hs, H);
     for (int g = 0; g < H / 4; ++g) {
-        const int lo = (int)(s * (float)(4 * g));
         const int last = std::min(H / 4 - 1, g + HP_LA);
-        const int r = (int)(s * (float)(4 * last + 3));
-        const int hi = r + (r < Hs - 1 ? 1 : 0);
-        if (hi - lo + 1 > ring_rows) return false;
+        if (kpb_tap_ac(4 * last + 3, Hs, s).i1 - kpb_tap_ac(4 * g, Hs, s).i0 + 1 > ring_rows) return false;
     }
     return true;
 }
@@ -1445,19 +1433,20 @@ __global__ __launch_bounds__(256, 3) void alike_head_f16p(HybArgs a, const uint4
     const float* a2 = a.a2 + (size_t)b * H2 * W2 * 16;
     const float* E3 = a.E3 + (size_t)b * H8 * W8 * ESTRIDE;
     const float* E4 = a.E4 + (size_t)b * H32 * W32 * ESTRIDE;
-    const float sy2 = uf((float)(H2 - 1) / (float)(a.H - 1)), sx2 = uf((float)(W2 - 1) / (float)(a.W - 1));
-    const float sy8 = uf((float)(H8 - 1) / (float)(a.H - 1)), sx8 = uf((float)(W8 - 1) / (float)(a.W - 1));
-    const float sy32 = uf((float)(H32 - 1) / (float)(a.H - 1)), sx32 = uf((float)(W32 - 1) / (float)(a.W - 1));
+    const float sy2 = uf(kpb_ac_scale_gt1(H2, a.H)), sx2 = uf(kpb_ac_scale_gt1(W2, a.W));
+    const float sy8 = uf(kpb_ac_scale_gt1(H8, a.H)), sx8 = uf(kpb_ac_scale_gt1(W8, a.W));
+    const float sy32 = uf(kpb_ac_scale_gt1(H32, a.H)), sx32 = uf(kpb_ac_scale_gt1(W32, a.W));
     const int tiles_per_row = a.W / 32, bands = (tiles_per_row + HP_TILES - 1) / HP_TILES, ngroups = a.H / 4;
     const int band = (int)blockIdx.x % bands, seg = (int)blockIdx.x / bands;
     const int g0 = seg * groups_per_wg, g1 = min(g0 + groups_per_wg, ngroups);
     const int xs = band * HP_BW;
     const int ntile = min(HP_TILES, tiles_per_row - xs / 32);
-    const int c_lo = ui((int)(sx2 * (float)xs)), tb3 = ui((int)(sx8 * (float)xs)), tb4 = ui((int)(sx32 * (float)xs));
+    const int c_lo = ui(kpb_tap_ac(xs, W2, sx2).i0), tb3 = ui(kpb_tap_ac(xs, W8, sx8).i0), tb4 = ui(kpb_tap_ac(xs, W32, sx32).i0);
 
-    // rows [lo(G), hi(G)] of a source map that row group G reads (align_corners taps of its rows 4 G .. 4 G + 3)
+    // rows [lo(G), hi(G)] of a source map that row group G reads (align_corners taps of its rows 4 G .. 4 G + 3;
+    // kpb_tap_ac's arithmetic (interp.h) written out: this kernel's assembly is held identical to its parent's, and calling the header reorders it, here and at the three sites marked `written out` below)
     auto hi_row = [&](float s, int G, int Hs) { const int r = ui((int)(s * (float)(4 * G + 3))); return r + (r < Hs - 1 ? 1 : 0); };
-    int a2next = ui((int)(sy2 * (float)(4 * g0))), e3next = ui((int)(sy8 * (float)(4 * g0))), e4next = ui((int)(sy32 * (float)(4 * g0)));
+    int a2next = ui(kpb_tap_ac(4 * g0, H2, sy2).i0), e3next = ui(kpb_tap_ac(4 * g0, H8, sy8).i0), e4next = ui(kpb_tap_ac(4 * g0, H32, sy32).i0);
     // per-lane byte offsets of the 1 KB request units inside a source row, once per walk (8 registers): LDS position q = 64 j + lane of
     // an a2 ring row holds slot (q & 3) ^ swizzle of pixel q >> 2 (bank spread, see above); of an E ring row, 16-byte piece q % 17 of
     // band column q / 17 (clamped to the map's last column)
@@ -1527,12 +1516,12 @@ __global__ __launch_bounds__(256, 3) void alike_head_f16p(HybArgs a, const uint4
     const bool stamp_wg = (blockIdx.x % 61) == 7 && (blockIdx.y % 16) == 3 && ntile == 2;
 #endif
 
-    // per group and wave: the y taps of the raw coarse rows (strip_store's arithmetic, applied where the value is read)
+    // per group and wave: the y taps of the raw coarse rows (strip_store's arithmetic, applied where the value is read; kpb_tap_ac written out in the walk below)
     int U3 = 0, D3 = 0, U4 = 0, D4 = 0;        // float offsets of the two tapped ring rows inside E3r / E4r (offsets, not pointers: the reads stay ds_read)
     float hy3 = 0.f, ly3 = 0.f, hy4 = 0.f, ly4 = 0.f, hy3c = 0.f, ly3c = 0.f, hy4c = 0.f, ly4c = 0.f;
 
     // The x taps of the coarse maps depend on the tile position only, not on the row group: the hat weights and their fractions are
-    // taken once per walk for both tiles (14 registers; the a2 tap offsets and the rest stay per tile -- hoisting everything spilled)
+    // taken once per walk for both tiles (14 registers; the a2 tap offsets and the rest stay per tile -- hoisting everything spilled).  kpb_tap_ac written out
     float w3t[HP_TILES][3], w4t[HP_TILES][2], lx3t[HP_TILES], lx4t[HP_TILES];
 #pragma unroll
     for (int t = 0; t < HP_TILES; ++t) {
@@ -1565,7 +1554,7 @@ __global__ __launch_bounds__(256, 3) void alike_head_f16p(HybArgs a, const uint4
         ++ktile;
         KPB_STAMP(5 + 8 * t);
         Up8Taps taps;
-        {
+        {   // kpb_tap_ac of both axes, written out
             const float fy = sy2 * (float)y, fx = sx2 * (float)x;
             const int gy0 = (int)fy, gx0 = (int)fx;
             const int gy1 = gy0 + (gy0 < H2 - 1 ? 1 : 0);
@@ -1759,11 +1748,8 @@ struct LinArgs {
 
 __device__ __forceinline__ float lerp_scalar(const float* m, int Hs, int Ws, float sy, float sx, int y, int x)
 {
-    const float fy = sy * (float)y, fx = sx * (float)x;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < Hs - 1 ? 1 : 0), x1 = x0 + (x0 < Ws - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.0f - ly, hx = 1.0f - lx;
-    return hy * (hx * m[(size_t)y0 * Ws + x0] + lx * m[(size_t)y0 * Ws + x1]) + ly * (hx * m[(size_t)y1 * Ws + x0] + lx * m[(size_t)y1 * Ws + x1]);
+    const kpb_lin ty = kpb_tap_ac(y, Hs, sy), tx = kpb_tap_ac(x, Ws, sx);
+    return kpb_mix_at(ty, tx, [&](int yy, int xx) { return m[(size_t)yy * Ws + xx]; });
 }
 
 // one thread per pixel
@@ -1836,12 +1822,9 @@ __global__ __launch_bounds__(256) void alike_desc_at(DescAtArgs a)
         const int i = i0 + kk;
         if (i >= n) break;                                   // wave-uniform
         const float* pt = a.pts + ((size_t)b * a.max_n + i) * a.pts_cols;
-        const float gx = (pt[0] - 0.5f) * 2.0f, gy = (pt[1] - 0.5f) * 2.0f;   // matcher.py:221-222
-        const float x = (gx + 1.0f) * ((float)(W - 1) / 2.0f), y = (gy + 1.0f) * ((float)(H - 1) / 2.0f);
-        const float xw = floorf(x), yn = floorf(y);
-        const float w = x - xw, e = 1.0f - w, nn = y - yn, s = 1.0f - nn;
-        const float cw[4] = {s * e, s * w, nn * e, nn * w};
-        const int x0 = (int)xw, y0 = (int)yn;
+        const kpb_grid gt = kpb_grid_taps((pt[0] - 0.5f) * 2.0f, (pt[1] - 0.5f) * 2.0f, W, H);   // matcher.py:221-222
+        const float* cw = gt.w;         // summed below as one fused chain, not kpb_grid_blend: the head's mat-vec that follows re-associates anyway
+        const int x0 = (int)gt.x0, y0 = (int)gt.y0;
         float acc = 0.0f;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -1858,12 +1841,8 @@ __global__ __launch_bounds__(256) void alike_desc_at(DescAtArgs a)
                 const int sh = g == 1 ? 2 : (g == 2 ? 8 : 32);
                 const int Hs = H / sh, Ws = W / sh;
                 const float* m = (g == 1 ? a.h.a2 : (g == 2 ? a.h.a3 : a.h.a4)) + (size_t)b * Hs * Ws * 16;
-                const float fy = ((float)(Hs - 1) / (float)(H - 1)) * (float)ty, fx = ((float)(Ws - 1) / (float)(W - 1)) * (float)tx;
-                const int sy0 = (int)fy, sx0 = (int)fx;
-                const int sy1 = sy0 + (sy0 < Hs - 1 ? 1 : 0), sx1 = sx0 + (sx0 < Ws - 1 ? 1 : 0);
-                const float ly = fy - (float)sy0, lx = fx - (float)sx0, hy = 1.0f - ly, hx = 1.0f - lx;
-                v = hy * (hx * m[((size_t)sy0 * Ws + sx0) * 16 + j] + lx * m[((size_t)sy0 * Ws + sx1) * 16 + j]) +
-                    ly * (hx * m[((size_t)sy1 * Ws + sx0) * 16 + j] + lx * m[((size_t)sy1 * Ws + sx1) * 16 + j]);
+                const kpb_lin ry = kpb_tap_ac(ty, Hs, kpb_ac_scale_gt1(Hs, H)), rx = kpb_tap_ac(tx, Ws, kpb_ac_scale_gt1(Ws, W));
+                v = kpb_mix_at(ry, rx, [&](int yy, int xx) { return m[((size_t)yy * Ws + xx) * 16 + j]; });
             }
             acc = fmaf(cw[t], v, acc);
         }
@@ -2411,8 +2390,7 @@ int AlikeNet::forward(const float* img_dev, int batch, int H_, int W_, float* sc
             KPB_LAUNCH(ctx, "alike_head_dense", alike_head_hyb, dim3(work4, batch), dim3(256), 0, st, hy);
     } else {
         LinArgs la{x1, S2, S3, S4, kh.agg[1], kh.wsc, score_out_dev, H, W,
-                   (float)(H / 2 - 1) / (float)(H - 1), (float)(W / 2 - 1) / (float)(W - 1), (float)(H / 8 - 1) / (float)(H - 1), (float)(W / 8 - 1) / (float)(W - 1),
-                   (float)(H / 32 - 1) / (float)(H - 1), (float)(W / 32 - 1) / (float)(W - 1)};
+                   kpb_ac_scale(H / 2, H), kpb_ac_scale(W / 2, W), kpb_ac_scale(H / 8, H), kpb_ac_scale(W / 8, W), kpb_ac_scale(H / 32, H), kpb_ac_scale(W / 32, W)};
         KPB_LAUNCH(ctx, "alike_head_score", alike_score_lin, dim3(cdiv(H * W, 256), batch), dim3(256), 0, st, la);
     }
     KPB_HIP(ctx, hipGetLastError());

@@ -36,22 +36,20 @@ constexpr int LWT = 132;        // floats of a row of the transposed head matrix
 struct LTap { int o00, o01, o10, o11; float ly, lx; };
 __device__ __forceinline__ LTap lh_taps(int y, int x, int H, int W, int Hs, int Ws)
 {
-    const float fy = ((float)(Hs - 1) / (float)(H - 1)) * (float)y, fx = ((float)(Ws - 1) / (float)(W - 1)) * (float)x;
-    const int y0 = min((int)fy, Hs - 1), x0 = min((int)fx, Ws - 1);
+    const float sy = kpb_ac_scale_gt1(Hs, H), sx = kpb_ac_scale_gt1(Ws, W);
+    const kpb_lin ty = kpb_tap_ac(y, Hs, sy), tx = kpb_tap_ac(x, Ws, sx);
+    // the first index stays clamped here, a guard that never acts (scale * o < n); the weights are those of the UNclamped index, the same wherever it does not act
+    const int y0 = min(ty.i0, Hs - 1), x0 = min(tx.i0, Ws - 1);
     const int y1 = y0 + (y0 < Hs - 1 ? 1 : 0), x1 = x0 + (x0 < Ws - 1 ? 1 : 0);
-    return LTap{(y0 * Ws + x0) * LQ, (y0 * Ws + x1) * LQ, (y1 * Ws + x0) * LQ, (y1 * Ws + x1) * LQ, fy - (float)y0, fx - (float)x0};
+    return LTap{(y0 * Ws + x0) * LQ, (y0 * Ws + x1) * LQ, (y1 * Ws + x0) * LQ, (y1 * Ws + x1) * LQ, ty.l, tx.l};
 }
 __device__ __forceinline__ float4 lh_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 // channels c .. c + 3 of the upsampled map at the taps t
 __device__ __forceinline__ float4 lh_mix4(const float* m, const LTap& t, int c)
 {
-    return cm_up2_mix(lh_ld4(m + t.o00 + c), lh_ld4(m + t.o01 + c), lh_ld4(m + t.o10 + c), lh_ld4(m + t.o11 + c), t.ly, t.lx);
+    return kpb_mix4(lh_ld4(m + t.o00 + c), lh_ld4(m + t.o01 + c), lh_ld4(m + t.o10 + c), lh_ld4(m + t.o11 + c), t.ly, t.lx);
 }
-__device__ __forceinline__ float lh_mix1(const float* m, const LTap& t, int c)
-{
-    const float hy = 1.0f - t.ly, hx = 1.0f - t.lx;
-    return hy * (hx * m[t.o00 + c] + t.lx * m[t.o01 + c]) + t.ly * (hx * m[t.o10 + c] + t.lx * m[t.o11 + c]);
-}
+__device__ __forceinline__ float lh_mix1(const float* m, const LTap& t, int c) { return kpb_mix(m[t.o00 + c], m[t.o01 + c], m[t.o10 + c], m[t.o11 + c], t.ly, t.lx); }
 
 struct LHeadArgs {
     const float *x1, *a2, *a3, *a4;     // [B][H][W][32], [B][H/2][W/2][32], [B][H/8][W/8][32], [B][H/32][W/32][32]
@@ -270,12 +268,9 @@ __global__ __launch_bounds__(256) void alike_l_desc_at(LDescAtArgs a)
             float v0 = 0.0f, v1 = 0.0f;
             if (i < n) {
                 const float* pt = a.pts + ((size_t)b * a.max_n + i) * a.pts_cols;
-                const float gx = (pt[0] - 0.5f) * 2.0f, gy = (pt[1] - 0.5f) * 2.0f;   // matcher.py:221-222
-                const float x = (gx + 1.0f) * ((float)(W - 1) / 2.0f), y = (gy + 1.0f) * ((float)(H - 1) / 2.0f);
-                const float xw = floorf(x), yn = floorf(y);
-                const float w = x - xw, e = 1.0f - w, nn = y - yn, s = 1.0f - nn;
-                const float cw[4] = {s * e, s * w, nn * e, nn * w};
-                const int x0 = (int)xw, y0 = (int)yn;
+                const kpb_grid gt = kpb_grid_taps((pt[0] - 0.5f) * 2.0f, (pt[1] - 0.5f) * 2.0f, W, H);   // matcher.py:221-222
+                const float* cw = gt.w;         // blended below as one fused chain per feature, not kpb_grid_blend: the head that follows re-associates anyway
+                const int x0 = (int)gt.x0, y0 = (int)gt.y0;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const int tx = x0 + (t & 1), ty = y0 + (t >> 1);

@@ -2,6 +2,7 @@
 // nets (convnet.hip) and the LightGlue matcher (lightglue.hip, where a Linear over tokens is a 1x1 convolution).
 #pragma once
 #include <type_traits>
+#include "interp.h"
 #include "net.h"
 
 #include <algorithm>
@@ -351,22 +352,8 @@ __device__ __forceinline__ float cm_wave_max(float v)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-// The taps of the 2 x bilinear upsampling torch's F.interpolate(scale_factor = 2, mode = 'bilinear', align_corners = False) reads for output coordinate o of
-// a source of n samples: source indices i0 <= i1, weight l of i1 (1 - l of i0).  Shared by upsample2_concat (the materialised form the strict-fp32 path keeps),
-// up_chan_sums (its statistics) and conv_mfma_h<UP> (the staging that evaluates it in place): the three compute the same floats.
-__device__ __forceinline__ void cm_up2_taps(int o, int n, int& i0, int& i1, float& l)
-{
-    const float f = fmaxf(((float)o + 0.5f) * 0.5f - 0.5f, 0.0f);
-    i0 = (int)f;
-    i1 = i0 + (i0 < n - 1 ? 1 : 0);
-    l = f - (float)i0;
-}
-__device__ __forceinline__ float4 cm_up2_mix(const float4 p00, const float4 p01, const float4 p10, const float4 p11, float ly, float lx)
-{
-    const float hy = 1.0f - ly, hx = 1.0f - lx;
-    return make_float4(hy * (hx * p00.x + lx * p01.x) + ly * (hx * p10.x + lx * p11.x), hy * (hx * p00.y + lx * p01.y) + ly * (hx * p10.y + lx * p11.y),
-                       hy * (hx * p00.z + lx * p01.z) + ly * (hx * p10.z + lx * p11.z), hy * (hx * p00.w + lx * p01.w) + ly * (hx * p10.w + lx * p11.w));
-}
+// The 2 x bilinear upsampling F.interpolate(scale_factor = 2, mode = 'bilinear', align_corners = False) is kpb_tap_hp(o, n, 0.5f) and kpb_mix4 of interp.h in upsample2_concat
+// (the materialised form the strict-fp32 path keeps) and conv_mfma_h<UP> (the staging that evaluates it in place); up_chan_sums (its statistics) has its own association.
 
 // CmForm::tail, the part of one wave: conv1x1_relu_body (alike.hip) on 64 pixels of the block's output that sit in LDS (`x`: this lane's pixel, CT floats) instead of
 // HBM -- the same fmaf chains in the same order, so the same bits.  The wave's pixels are four rows of a 16-wide tile: row g (lanes 16 g ..) starts at pixel
@@ -628,13 +615,10 @@ __global__ __launch_bounds__(256, F.waves()) void conv_mfma_h(ConvM a)
             live = idx < IH * IW * Q;
             if (live && gy >= 0 && gy < Hc && gx >= 0 && gx < Wc) {
                 if (upslab) {
-                    int y0, y1, x0, x1;
-                    float ly, lx;
-                    cm_up2_taps(gy, a.Hi / 2, y0, y1, ly);
-                    cm_up2_taps(gx, a.Wi / 2, x0, x1, lx);
-                    const float4* r0 = rawbuf + ((y0 - ry0) * RWD - rx0) * Q + q;
-                    const float4* r1 = rawbuf + ((y1 - ry0) * RWD - rx0) * Q + q;
-                    v = cm_up2_mix(r0[x0 * Q], r0[x1 * Q], r1[x0 * Q], r1[x1 * Q], ly, lx);
+                    const kpb_lin ty = kpb_tap_hp(gy, a.Hi / 2, 0.5f), tx = kpb_tap_hp(gx, a.Wi / 2, 0.5f);
+                    const float4* r0 = rawbuf + ((ty.i0 - ry0) * RWD - rx0) * Q + q;
+                    const float4* r1 = rawbuf + ((ty.i1 - ry0) * RWD - rx0) * Q + q;
+                    v = kpb_mix4(r0[tx.i0 * Q], r0[tx.i1 * Q], r1[tx.i0 * Q], r1[tx.i1 * Q], ty.l, tx.l);
                 } else
                     v = *reinterpret_cast<const float4*>(in + ((size_t)gy * a.Wi + gx) * a.istride + (ch * CC - a.up_c) + 4 * q);
                 const float4* t4 = reinterpret_cast<const float4*>(a.xf + ((size_t)b * a.CIN + ch * CC + 4 * q) * 4);

@@ -623,16 +623,9 @@ __global__ void instnorm_params(const double* stats, size_t P, float2* mr, int B
 __device__ __forceinline__ float4 bilerp4(const float* m, int Hs, int Ws, int Hd, int Wd, int y, int x, int c4)
 {
     const float sy = (float)Hs / (float)Hd, sx = (float)Ws / (float)Wd;
-    const float fy = fmaxf(((float)y + 0.5f) * sy - 0.5f, 0.0f), fx = fmaxf(((float)x + 0.5f) * sx - 0.5f, 0.0f);
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < Hs - 1 ? 1 : 0), x1 = x0 + (x0 < Ws - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.0f - ly, hx = 1.0f - lx;
-    const float4 a = *reinterpret_cast<const float4*>(m + ((size_t)y0 * Ws + x0) * 64 + c4);
-    const float4 b = *reinterpret_cast<const float4*>(m + ((size_t)y0 * Ws + x1) * 64 + c4);
-    const float4 c = *reinterpret_cast<const float4*>(m + ((size_t)y1 * Ws + x0) * 64 + c4);
-    const float4 d = *reinterpret_cast<const float4*>(m + ((size_t)y1 * Ws + x1) * 64 + c4);
-    return make_float4(hy * (hx * a.x + lx * b.x) + ly * (hx * c.x + lx * d.x), hy * (hx * a.y + lx * b.y) + ly * (hx * c.y + lx * d.y),
-                       hy * (hx * a.z + lx * b.z) + ly * (hx * c.z + lx * d.z), hy * (hx * a.w + lx * b.w) + ly * (hx * c.w + lx * d.w));
+    const kpb_lin ty = kpb_tap_hp(y, Hs, sy), tx = kpb_tap_hp(x, Ws, sx);
+    auto at = [&](int yy, int xx) { return *reinterpret_cast<const float4*>(m + ((size_t)yy * Ws + xx) * 64 + c4); };
+    return kpb_mix4(at(ty.i0, tx.i0), at(ty.i0, tx.i1), at(ty.i1, tx.i0), at(ty.i1, tx.i1), ty.l, tx.l);
 }
 
 __global__ void pyramid_sum(const float* x3, const float* x4, const float* x5, float* out, int H8, int W8, int H16, int W16, int H32, int W32)
@@ -988,14 +981,10 @@ __global__ void upsample2_concat(const float* bot, const float* hor, float* out,
     const int y = (int)(pix / W), x = (int)(pix - (size_t)y * W);
     float4 v;
     if (c < Cb) {
-        int y0, y1, x0, x1;
-        float ly, lx;
-        cm_up2_taps(y, Hb, y0, y1, ly);
-        cm_up2_taps(x, Wb, x0, x1, lx);
+        const kpb_lin ty = kpb_tap_hp(y, Hb, 0.5f), tx = kpb_tap_hp(x, Wb, 0.5f);
         const float* m = bot + (size_t)b * Hb * Wb * Cb + c;
-        const float4 p00 = *reinterpret_cast<const float4*>(m + ((size_t)y0 * Wb + x0) * Cb), p01 = *reinterpret_cast<const float4*>(m + ((size_t)y0 * Wb + x1) * Cb);
-        const float4 p10 = *reinterpret_cast<const float4*>(m + ((size_t)y1 * Wb + x0) * Cb), p11 = *reinterpret_cast<const float4*>(m + ((size_t)y1 * Wb + x1) * Cb);
-        v = cm_up2_mix(p00, p01, p10, p11, ly, lx);
+        auto at = [&](int yy, int xx) { return *reinterpret_cast<const float4*>(m + ((size_t)yy * Wb + xx) * Cb); };
+        v = kpb_mix4(at(ty.i0, tx.i0), at(ty.i0, tx.i1), at(ty.i1, tx.i0), at(ty.i1, tx.i1), ty.l, tx.l);
     } else {
         v = *reinterpret_cast<const float4*>(hor + (((size_t)b * H + y) * W + x) * Ch + (c - Cb));
     }
@@ -1048,7 +1037,7 @@ __global__ void chan_sums(const float* in, double* part, size_t P, int C, int Ct
 // while it stages.  A thread owns four channels and walks source cells (i, j): the cell's 3 x 3 neighbourhood (edge-replicated: at the frame the interpolation's
 // clamped taps coincide) gives its four output pixels (2 i + dy, 2 j + dx) separably -- 1/4 : 3/4 mixes down the columns, then along the rows.  These are sums of
 // fp64 over 1.2 M values for a mean and a variance that are rounded to float: they need the map's values to a few ulp, not to the bit (the staging evaluates
-// torch's own expression, cm_up2_mix).  Fixed order: the same bits every run.  blockDim = (Cb / 4, 256 / (Cb / 4)).
+// torch's own expression, kpb_mix4).  Fixed order: the same bits every run.  blockDim = (Cb / 4, 256 / (Cb / 4)).
 __global__ __launch_bounds__(256) void up_chan_sums(const float* __restrict__ bot, double* __restrict__ part, int Hb, int Wb, int Cb, int Ctot, int coff, float* __restrict__ mm)
 {
     extern __shared__ double sh[];   // [R][Cb / 4][8]
@@ -1184,7 +1173,7 @@ __global__ __launch_bounds__(256) void disk_score(float* __restrict__ score, siz
 // is NOT linear -- F.normalize acts per pixel -- so each tap pixel is convolved and normalised on its own and the four unit vectors are blended with
 // sample_bilinear's coefficients in its order (match.hip): the result is kpb_sample on the dense map up to the rounding of the convolution.
 // A workgroup takes DA_KP keypoints = 32 tap pixels = ONE M tile; wave w owns n-tile w (32 channels).  Per 16-channel slab the 6 x 6 input patch the four taps of
-// a keypoint share is staged in LDS -- [up2(u2) | f1] through cm_up2_taps / cm_up2_mix (or the materialised c3 on the strict-fp32 path), InstanceNorm + PReLU by
+// a keypoint share is staged in LDS -- [up2(u2) | f1] through kpb_tap_hp / kpb_mix4 (or the materialised c3 on the strict-fp32 path), InstanceNorm + PReLU by
 // (rstd, shift, slope), ZERO outside the image (the padding is of the activated tensor) -- and multiplied by the fragments stage_layer uploaded for the dense layer:
 //   H16: split-f16 triples on v_mfma_f32_32x32x16_f16 (pack_mfma_h), the patch scaled by the power of two of the image's bound of the activated input (xf[..][3]);
 //   else fp32 products on v_mfma_f32_32x32x2_f32 (pack_mfma).
@@ -1213,20 +1202,14 @@ __global__ __launch_bounds__(256) void disk_desc_at(DiskDescAt a)
     const int i0 = blockIdx.x * DA_KP;
     if (i0 >= n) return;            // workgroup-uniform
     const int H = a.H, W = a.W;
-    // a keypoint's coordinates as sample_bilinear takes them; the corner is clamped to [-2, size] before the conversion: every value outside has no tap inside either
-    auto corner = [&](int i, float& fx, float& fy, int& x0, int& y0) {
+    // a keypoint's taps as sample_bilinear takes them; the corner is clamped to [-2, size] before the conversion: every value outside has no tap inside either
+    auto corner = [&](int i, int& x0, int& y0) {
         const float* pt = a.pts + ((size_t)b * a.max_n + i) * a.pts_cols;
-        const float gx = (pt[0] - 0.5f) * 2.0f, gy = (pt[1] - 0.5f) * 2.0f;
-        const float x = (gx + 1.0f) * ((float)(W - 1) / 2.0f), y = (gy + 1.0f) * ((float)(H - 1) / 2.0f);
-        const float xw = floorf(x), yn = floorf(y);
-        fx = x - xw; fy = y - yn;
-        x0 = (int)fminf(fmaxf(xw, -2.0f), (float)W); y0 = (int)fminf(fmaxf(yn, -2.0f), (float)H);
+        const kpb_grid g = kpb_grid_taps((pt[0] - 0.5f) * 2.0f, (pt[1] - 0.5f) * 2.0f, W, H);     // matcher.py:221-222, then interp.h
+        x0 = (int)fminf(fmaxf(g.x0, -2.0f), (float)W); y0 = (int)fminf(fmaxf(g.y0, -2.0f), (float)H);
+        return g;
     };
-    if (tid < DA_KP) {
-        float fx, fy; int x0, y0;
-        corner(min(i0 + tid, n - 1), fx, fy, x0, y0);
-        s_x0[tid] = x0; s_y0[tid] = y0;
-    }
+    if (tid < DA_KP) corner(min(i0 + tid, n - 1), s_x0[tid], s_y0[tid]);
     int e = 24;
     if constexpr (H16) {
         float bnd = 0.0f;           // workgroup-uniform
@@ -1249,13 +1232,10 @@ __global__ __launch_bounds__(256) void disk_desc_at(DiskDescAt a)
             if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
                 if (a.c3) v = *reinterpret_cast<const float4*>(a.c3 + (((size_t)b * H + gy) * W + gx) * CIN + ch * CC + 4 * q);
                 else if (ch * CC < 64) {
-                    int y0, y1, x0, x1;
-                    float ly, lx;
-                    cm_up2_taps(gy, Hb, y0, y1, ly);
-                    cm_up2_taps(gx, Wb, x0, x1, lx);
+                    const kpb_lin ty = kpb_tap_hp(gy, Hb, 0.5f), tx = kpb_tap_hp(gx, Wb, 0.5f);
                     const float* s = a.u2 + (size_t)b * Hb * Wb * 64 + ch * CC + 4 * q;
-                    v = cm_up2_mix(*reinterpret_cast<const float4*>(s + ((size_t)y0 * Wb + x0) * 64), *reinterpret_cast<const float4*>(s + ((size_t)y0 * Wb + x1) * 64),
-                                   *reinterpret_cast<const float4*>(s + ((size_t)y1 * Wb + x0) * 64), *reinterpret_cast<const float4*>(s + ((size_t)y1 * Wb + x1) * 64), ly, lx);
+                    auto at = [&](int yy, int xx) { return *reinterpret_cast<const float4*>(s + ((size_t)yy * Wb + xx) * 64); };
+                    v = kpb_mix4(at(ty.i0, tx.i0), at(ty.i0, tx.i1), at(ty.i1, tx.i0), at(ty.i1, tx.i1), ty.l, tx.l);
                 } else
                     v = *reinterpret_cast<const float4*>(a.f1 + (((size_t)b * H + gy) * W + gx) * 16 + (ch * CC - 64) + 4 * q);
                 const float4* t4 = reinterpret_cast<const float4*>(a.xf + ((size_t)b * CIN + ch * CC + 4 * q) * 4);
@@ -1312,10 +1292,8 @@ __global__ __launch_bounds__(256) void disk_desc_at(DiskDescAt a)
     for (int k = 0; k < 2; ++k) {
         const int kq = 2 * wv + k, i = i0 + kq;
         if (i >= n) break;          // wave-uniform: rows at or past n[b] are not written
-        float fx, fy; int x0, y0;
-        corner(i, fx, fy, x0, y0);
-        const float w = fx, ee = 1.0f - w, nn = fy, s = 1.0f - nn;
-        const float cf[4] = {s * ee, s * w, nn * ee, nn * w};
+        int x0, y0;
+        const kpb_grid gt = corner(i, x0, y0);
         float da[4], db[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -1329,8 +1307,8 @@ __global__ __launch_bounds__(256) void disk_desc_at(DiskDescAt a)
             db[t] = ok ? __fdiv_rn(vb, nrm) : 0.0f;
         }
         float* o = a.out + ((size_t)b * a.max_n + i) * 128;
-        o[lane] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(da[0], cf[0]), __fmul_rn(da[1], cf[1])), __fmul_rn(da[2], cf[2])), __fmul_rn(da[3], cf[3]));
-        o[lane + 64] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(db[0], cf[0]), __fmul_rn(db[1], cf[1])), __fmul_rn(db[2], cf[2])), __fmul_rn(db[3], cf[3]));
+        o[lane] = kpb_grid_blend(da[0], da[1], da[2], da[3], gt.w);
+        o[lane + 64] = kpb_grid_blend(db[0], db[1], db[2], db[3], gt.w);
     }
 }
 

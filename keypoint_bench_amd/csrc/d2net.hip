@@ -146,15 +146,15 @@ __global__ __launch_bounds__(256) void d2_upsample(const float* __restrict__ s, 
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
     if (x >= W || y >= H) return;
-    const float sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.0f, sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.0f;
-    const float fy = sy * (float)y, fx = sx * (float)x;
-    const int y0 = min((int)fy, h - 1), x0 = min((int)fx, w - 1), y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-    const float ly = fminf(fmaxf(fy - (float)y0, 0.0f), 1.0f), lx = fminf(fmaxf(fx - (float)x0, 0.0f), 1.0f), hy = 1.0f - ly, hx = 1.0f - lx;
+    const kpb_lin ty = kpb_tap_ac(y, h, kpb_ac_scale(h, H)), tx = kpb_tap_ac(x, w, kpb_ac_scale(w, W));
+    // the source can be one sample: index and weight stay clamped here.  Both are guards that never act (scale * o < n); the weight is that of the UNclamped index
+    const int y0 = min(ty.i0, h - 1), x0 = min(tx.i0, w - 1), y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
+    const float ly = fminf(fmaxf(ty.l, 0.0f), 1.0f), lx = fminf(fmaxf(tx.l, 0.0f), 1.0f);
     const float* p = s + (size_t)b * h * w;
     const float t = sum[b];
     const float a = __fdiv_rn(p[(size_t)y0 * w + x0], t), c = __fdiv_rn(p[(size_t)y0 * w + x1], t);
     const float d = __fdiv_rn(p[(size_t)y1 * w + x0], t), e = __fdiv_rn(p[(size_t)y1 * w + x1], t);
-    out[((size_t)b * H + y) * W + x] = hy * (hx * a + lx * c) + ly * (hx * d + lx * e);
+    out[((size_t)b * H + y) * W + x] = kpb_mix(a, c, d, e, ly, lx);
 }
 
 // ------------------------------------------------------------------------------------------------ host

@@ -5,7 +5,7 @@
 //     from 8 to 8192: tests/test_keynet_cpu.py), computed on the host.  Level 2 is a pyrdown of LEVEL 1's gray, not of level 0 (the reference overwrites x).
 //  3. custom_pyrdown: 5 x 5 binomial blur [1,4,6,4,1]^T [1,4,6,4,1] / 256 over torch's `reflect` padding (the edge pixel is not repeated: index -1 maps to 1),
 //     then F.interpolate(size, 'bilinear', align_corners = False): scale = in / out, src = max((dst + 0.5) scale - 0.5, 0), i0 = floor(src),
-//     i1 = min(i0 + 1, in - 1), weight of i1 = src - i0 (kn_lin_taps).
+//     i1 = min(i0 + 1, in - 1), weight of i1 = src - floor(src) (kpb_tap_hp of interp.h; kn_lin_taps adds its clamps).
 //  4. handcrafted block: spatial_gradient = the 3 x 3 Sobel pair / 8 (x kernel [[-1,0,1],[-2,0,2],[-1,0,1]], y its transpose) as correlation over REPLICATE
 //     padding; dx, dy = grad(x), dxx, dxy = grad(dx), dyy = grad(dy)[1].  The second gradients replicate the border of dx and dy THEMSELVES, so the outermost
 //     ring is not a 5 x 5 stencil on a replicated image: kn_hc_stage keeps, for every position of the tile, the gradient AT THE CLAMPED pixel.
@@ -42,10 +42,10 @@ constexpr int KN_IH = KN_TH + 4;            // with the 5 x 5 halo
 // source taps of output index o under F.interpolate(mode = 'bilinear', align_corners = False) with scale = in / out (point 3)
 __device__ __forceinline__ void kn_lin_taps(int o, int n_in, float scale, int& i0, int& i1, float& l)
 {
-    const float f = fmaxf(scale * ((float)o + 0.5f) - 0.5f, 0.0f);
-    i0 = min((int)f, n_in - 1);
+    const kpb_lin t = kpb_tap_hp(o, n_in, scale);
+    i0 = min(t.i0, n_in - 1);           // Key.Net's scales are no powers of two: index and weight stay clamped here -- guards that never act (src < in at every scale)
     i1 = min(i0 + 1, n_in - 1);
-    l = fminf(fmaxf(f - (float)i0, 0.0f), 1.0f);
+    l = fminf(fmaxf(t.l, 0.0f), 1.0f);   // the weight of the UNclamped index: the same value wherever the index clamp does not act
 }
 
 // the gray value of pixel `at` of one image: the channel sum of a planar 3-channel image (level 0), or the level's own one-channel map
@@ -101,8 +101,7 @@ __global__ __launch_bounds__(256) void keynet_pyrdown(KnPyrArgs a)
         return acc;
     };
     const float p00 = blur(y0, x0), p01 = blur(y0, x1), p10 = blur(y1, x0), p11 = blur(y1, x1);
-    const float hy = 1.0f - ly, hx = 1.0f - lx;
-    a.dst[((size_t)b * a.ho + oy) * a.wo + ox] = hy * (hx * p00 + lx * p01) + ly * (hx * p10 + lx * p11);
+    a.dst[((size_t)b * a.ho + oy) * a.wo + ox] = kpb_mix(p00, p01, p10, p11, ly, lx);
 }
 
 // ------------------------------------------------------------------------------------------------ the handcrafted block, on chip
@@ -367,8 +366,8 @@ __global__ __launch_bounds__(256) void keynet_head(KnHeadArgs a)
                     const float4* p01 = reinterpret_cast<const float4*>(src + ((size_t)y0 * wl + x1) * 8);
                     const float4* p10 = reinterpret_cast<const float4*>(src + ((size_t)y1 * wl + x0) * 8);
                     const float4* p11 = reinterpret_cast<const float4*>(src + ((size_t)y1 * wl + x1) * 8);
-                    q0 = cm_up2_mix(p00[0], p01[0], p10[0], p11[0], ly, lx);
-                    q1 = cm_up2_mix(p00[1], p01[1], p10[1], p11[1], ly, lx);
+                    q0 = kpb_mix4(p00[0], p01[0], p10[0], p11[0], ly, lx);
+                    q1 = kpb_mix4(p00[1], p01[1], p10[1], p11[1], ly, lx);
                 }
             }
             sf[i] = q0; sf[NPOS + i] = q1;

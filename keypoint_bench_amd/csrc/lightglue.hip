@@ -83,11 +83,8 @@ __global__ __launch_bounds__(256) void lg_sample(SampleArgs a)
     float kx = (a.kpx[((size_t)s * a.MP + t) * 2] - half) + 0.5f, ky = (a.kpx[((size_t)s * a.MP + t) * 2 + 1] - half) + 0.5f;
     kx = __fdiv_rn(kx, (float)((double)a.Wd * a.ds - a.ds / 2.0 - 0.5)); ky = __fdiv_rn(ky, (float)((double)a.Hd * a.ds - a.ds / 2.0 - 0.5));
     const float gx = kx * 2.0f - 1.0f, gy = ky * 2.0f - 1.0f;
-    const float x = (gx + 1.0f) * ((float)(a.Wd - 1) / 2.0f), y = (gy + 1.0f) * ((float)(a.Hd - 1) / 2.0f);
-    const float xw = floorf(x), yn = floorf(y);
-    const float w = x - xw, e = 1.0f - w, nn = y - yn, so = 1.0f - nn;
-    const float c_nw = so * e, c_ne = so * w, c_sw = nn * e, c_se = nn * w;
-    const long long x0 = (long long)xw, y0 = (long long)yn, x1 = x0 + 1, y1 = y0 + 1;
+    const kpb_grid gt = kpb_grid_taps(gx, gy, a.Wd, a.Hd);
+    const long long x0 = (long long)gt.x0, y0 = (long long)gt.y0, x1 = x0 + 1, y1 = y0 + 1;
     const bool vx0 = x0 >= 0 && x0 < a.Wd, vx1 = x1 >= 0 && x1 < a.Wd, vy0 = y0 >= 0 && y0 < a.Hd, vy1 = y1 >= 0 && y1 < a.Hd;
     float v[4];
     float ss = 0.0f;
@@ -99,7 +96,7 @@ __global__ __launch_bounds__(256) void lg_sample(SampleArgs a)
             const float* p = map + (size_t)ch * a.sc;
             const float nw = (vx0 && vy0) ? p[y0 * a.sh + x0 * a.sw] : 0.0f, ne = (vx1 && vy0) ? p[y0 * a.sh + x1 * a.sw] : 0.0f;
             const float sw = (vx0 && vy1) ? p[y1 * a.sh + x0 * a.sw] : 0.0f, se = (vx1 && vy1) ? p[y1 * a.sh + x1 * a.sw] : 0.0f;
-            v[q] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(nw, c_nw), __fmul_rn(ne, c_ne)), __fmul_rn(sw, c_sw)), __fmul_rn(se, c_se));
+            v[q] = kpb_grid_blend(nw, ne, sw, se, gt.w);
             ss = fmaf(v[q], v[q], ss);
         }
     }

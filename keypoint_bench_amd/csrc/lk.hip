@@ -11,22 +11,18 @@
 // reductions per iteration.  fp32 throughout, the reference's formulas kept as they are -- including its update
 // einsum 'bik,bk->bk', which sums the inverse over its second index instead of applying it.
 #include "kpb_common.h"
+#include "interp.h"
 
 namespace {
 
 struct Taps { int x0, y0; float w[4]; bool ok[4]; };
 
 // grid_sample(align_corners=True, bilinear, zeros) taps of pixel position (px, py), through the reference's normalise
-// (matcher.py:109, 115) and ATen's unnormalise
+// (matcher.py:109, 115) and kpb_grid_taps (interp.h); ok[k]: tap k lies inside the image
 __device__ __forceinline__ Taps make_taps(float px, float py, int H, int W)
 {
-    Taps t;
-    const float gx = px / (float)(W - 1) * 2.0f - 1.0f, gy = py / (float)(H - 1) * 2.0f - 1.0f;
-    const float ix = (gx + 1.0f) * ((float)(W - 1) / 2.0f), iy = (gy + 1.0f) * ((float)(H - 1) / 2.0f);
-    const float fx = floorf(ix), fy = floorf(iy);
-    const float wx = ix - fx, wy = iy - fy, ex = 1.0f - wx, sy = 1.0f - wy;
-    t.x0 = (int)fx; t.y0 = (int)fy;
-    t.w[0] = sy * ex; t.w[1] = sy * wx; t.w[2] = wy * ex; t.w[3] = wy * wx;
+    const kpb_grid g = kpb_grid_taps(px / (float)(W - 1) * 2.0f - 1.0f, py / (float)(H - 1) * 2.0f - 1.0f, W, H);
+    Taps t{(int)g.x0, (int)g.y0, {g.w[0], g.w[1], g.w[2], g.w[3]}, {}};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int xt = t.x0 + (k & 1), yt = t.y0 + (k >> 1);

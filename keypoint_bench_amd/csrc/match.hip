@@ -8,6 +8,7 @@
 // 1000x1000x64 pair), LDS-tiled 64x64 with 4x4 register blocking; it is not reshaped into an MFMA
 // GEMM because the |a|^2+|b|^2-2ab expansion changes the rounding and flips near-tie argmins.
 #include "kpb_common.h"
+#include "interp.h"
 
 namespace {
 
@@ -32,13 +33,9 @@ __global__ __launch_bounds__(256) void sample_bilinear(SampleArgs a)
     for (int k = 0; k < SAMPLE_KPW; ++k) {
         const int i = min(i0 + k, n - 1);
         const float* p = a.pts + ((size_t)b * a.max_n + i) * a.pts_cols;
-        // matcher.py:221-222 then ATen's align_corners=True un-normalisation (g + 1) * ((size - 1) / 2)
-        const float gx = (p[0] - 0.5f) * 2.0f, gy = (p[1] - 0.5f) * 2.0f;
-        const float x = (gx + 1.0f) * ((float)(a.Wd - 1) / 2.0f), y = (gy + 1.0f) * ((float)(a.Hd - 1) / 2.0f);
-        const float xw = floorf(x), yn = floorf(y);
-        const float w = x - xw, e = 1.0f - w, nn = y - yn, s = 1.0f - nn;
-        cf[k][0] = s * e; cf[k][1] = s * w; cf[k][2] = nn * e; cf[k][3] = nn * w;
-        const long long x0 = (long long)xw, y0 = (long long)yn, x1 = x0 + 1, y1 = y0 + 1;
+        const kpb_grid gt = kpb_grid_taps((p[0] - 0.5f) * 2.0f, (p[1] - 0.5f) * 2.0f, a.Wd, a.Hd);       // matcher.py:221-222, then grid_sample's taps (interp.h)
+        cf[k][0] = gt.w[0]; cf[k][1] = gt.w[1]; cf[k][2] = gt.w[2]; cf[k][3] = gt.w[3];
+        const long long x0 = (long long)gt.x0, y0 = (long long)gt.y0, x1 = x0 + 1, y1 = y0 + 1;
         const bool vx0 = x0 >= 0 && x0 < a.Wd, vx1 = x1 >= 0 && x1 < a.Wd;
         const bool vy0 = y0 >= 0 && y0 < a.Hd, vy1 = y1 >= 0 && y1 < a.Hd;
         ok[k][0] = vx0 && vy0; ok[k][1] = vx1 && vy0; ok[k][2] = vx0 && vy1; ok[k][3] = vx1 && vy1;
@@ -58,8 +55,7 @@ __global__ __launch_bounds__(256) void sample_bilinear(SampleArgs a)
             const float nw = ok[k][0] ? t[k][0] : 0.0f, ne = ok[k][1] ? t[k][1] : 0.0f;      // zero padding
             const float sw = ok[k][2] ? t[k][2] : 0.0f, se = ok[k][3] ? t[k][3] : 0.0f;
             if (i0 + k < n)
-                a.out[((size_t)b * a.max_n + i0 + k) * a.C + ch] =
-                    __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(nw, cf[k][0]), __fmul_rn(ne, cf[k][1])), __fmul_rn(sw, cf[k][2])), __fmul_rn(se, cf[k][3]));
+                a.out[((size_t)b * a.max_n + i0 + k) * a.C + ch] = kpb_grid_blend(nw, ne, sw, se, cf[k]);
         }
     }
 }

@@ -178,16 +178,14 @@ __global__ __launch_bounds__(256) void sfd2_score(const float* __restrict__ semi
         if (cell >= ncell) break;       // wave-uniform
         const int cy = cell / Wc, cx = cell - cy * Wc, py = cy * 8 + (lane >> 3), px = cx * 8 + (lane & 7);
         // stability class of pixel (py, px): the three logits upsampled x 4 (point 5), first maximum
-        const float fy = fmaxf(((float)py + 0.5f) * 0.25f - 0.5f, 0.0f), fx = fmaxf(((float)px + 0.5f) * 0.25f - 0.5f, 0.0f);
-        const int y0 = min((int)fy, H4 - 1), x0 = min((int)fx, W4 - 1), y1 = min(y0 + 1, H4 - 1), x1 = min(x0 + 1, W4 - 1);
-        const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.0f - ly, hx = 1.0f - lx;
-        const float* p00 = st + ((size_t)y0 * W4 + x0) * 3;
-        const float* p01 = st + ((size_t)y0 * W4 + x1) * 3;
-        const float* p10 = st + ((size_t)y1 * W4 + x0) * 3;
-        const float* p11 = st + ((size_t)y1 * W4 + x1) * 3;
+        const kpb_lin ty = kpb_tap_hp(py, H4, 0.25f), tx = kpb_tap_hp(px, W4, 0.25f);
+        const float* p00 = st + ((size_t)ty.i0 * W4 + tx.i0) * 3;
+        const float* p01 = st + ((size_t)ty.i0 * W4 + tx.i1) * 3;
+        const float* p10 = st + ((size_t)ty.i1 * W4 + tx.i0) * 3;
+        const float* p11 = st + ((size_t)ty.i1 * W4 + tx.i1) * 3;
         float l[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) l[c] = hy * (hx * p00[c] + lx * p01[c]) + ly * (hx * p10[c] + lx * p11[c]);
+        for (int c = 0; c < 3; ++c) l[c] = kpb_mix(p00[c], p01[c], p10[c], p11[c], ty.l, tx.l);
         float stab = 0.1f, best = l[0];
         if (l[1] > best) { best = l[1]; stab = 0.5f; }
         if (l[2] > best) stab = 1.0f;
